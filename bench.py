@@ -10,15 +10,23 @@ and off-haplotype flags to rank 0 that north_star names.  `--total-windows T` sw
 (BASELINE.json configs[3]: one job of T windows, rank r takes the r-th contiguous block, in sub-batches
 that fit the int32 read-base offsets of a batch).
 
-`value` is the kernel path on HBM-resident inputs.  At N=1 the line also carries what SURVEY §8(d) defines
+`value` is the kernel path on HBM-resident inputs.  A plain run does only what that figure needs: it sets up, warms up, times the
+--steps steps and prints the line (`ms_per_step`: one timed step; `roofline` / `valu_fp64` from the same launches' HIP events).
+`--full` adds the legs beside the headline figure, each of which takes runs of its own.  At N=1 these carry what SURVEY §8(d) defines
 windows/s on: `windows_per_s_incl_copies` (dd_compute_likelihoods with host pointers: H2D + kernels + D2H)
 and `windows_per_s_end_to_end` (dindel::LikelihoodEngine::computeLikelihoodsBatch on the reference's own
 C++ objects: pack + H2D + kernels + D2H + per-window status scan, records delivered as lazy views), with
 the split and the eager-record rate under `end_to_end`, and `window_loop`: the batched window loop of the diploid analysis (BAM ->
 read selection -> kernels -> diploidGLF -> .glf.txt, host/dindel_gpu) on a synthetic 100,000-window sample the leg writes itself
-(`windows_per_s` by the driver's own clock from set-up to the last line written, `steady_windows_per_s` once the pipeline is full).
+(`windows_per_s` by the driver's own clock from set-up to the last line written, `steady_windows_per_s` once the pipeline is full),
+the real-shaped `ragged` batch and `cpu_baseline` (the oracle on a bounded sample).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--windows 10000] [--total-windows T]
+`--dump-outputs DIR` writes, after the timed steps, what the last step handed its caller: every dd_result array as DIR/<name>.npy
+(float64 for the doubles and int32, float32 for the narrower integers), per-pair records at a seeded sample of pairs and the
+per-window arrays (hpos, var_covered, var_fcov, onHap) over a seeded sample of windows, 64 MB at most.  The inputs are generated from
+fixed seeds, so two builds given the same arguments can be compared output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--windows 10000] [--total-windows T] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 Launched plainly with `--gpus N` (N > 1, no WORLD_SIZE in the environment) the script starts the second form itself: the
@@ -26,7 +34,7 @@ parent touches no GPU, runs `python -m torch.distributed.run --nproc-per-node N`
 with the child's code (`self_launch`).  Inside a rank, WORLD_SIZE must equal --gpus: anything else is an error, never a silent
 single-GPU run.
 
-At N > 1 the line carries three figures: `value` — every rank runs --windows windows per step and gathers ll + flags to rank 0
+At N > 1 the line carries `value` and, with --full, two more figures.  `value` — every rank runs --windows windows per step and gathers ll + flags to rank 0
 over RCCL (weak; what the driver's scaling table is computed from: the per-GPU work is the N = 1 workload); `configs3` — ONE pass
 over one job of --configs3-windows (default 1,000,000 = BASELINE.json configs[3]) windows split into contiguous blocks per rank
 (strong; a single pass because 25 driver steps of a 41 GPU-second job would not "finish within minutes"); `in_process` — the same
@@ -96,6 +104,29 @@ def algorithmic_bytes_per_pair(L, Hs, R):
     """L bases + L quals + 16 (mapQual, start, flags) + Hs/R + 32 (ll, llOn, llOff, packed
     flags/counters) + 2L (hpos int16) = 4L + 48 + Hs/R."""
     return 4.0 * L + 48.0 + float(Hs) / R
+
+
+def dump_outputs(dev, out_dir, seed=0x0D0D):
+    """--dump-outputs: the dd_result arrays of `dev`'s last launch as out_dir/<name>.npy.  Per-pair records at 2^18 pairs, the per-window
+    arrays over up to 32 windows cut to 2^21 elements each, both drawn from `seed`: 21 + 4 x 8 MB at most.  Integers become float32
+    (int16 / uint8) or float64 (int32), both exact."""
+    pb = dev.pb
+    rng = np.random.default_rng(seed)
+    pairs = np.sort(rng.choice(pb.n_pairs, min(pb.n_pairs, 1 << 18), replace=False))
+    wins = np.sort(rng.choice(pb.n_windows, min(pb.n_windows, 32), replace=False))
+    win_off = {"hpos": pb.win_hpos_off, "var_covered": pb.win_varcov_off, "var_fcov": pb.win_varcov_off, "onHap": pb.a["win_read_off"]}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, _ in capi.RESULT_FIELDS:
+        idx = pairs
+        if k in win_off:
+            o, idx, room = win_off[k], [], 1 << 21
+            for w in wins:
+                n = min(int(o[w + 1]) - int(o[w]), room)
+                idx.append(np.arange(int(o[w]), int(o[w]) + n))
+                room -= n
+            idx = np.concatenate(idx)
+        a = dev.out[k][torch.from_numpy(idx).to(dev.device)].cpu().numpy()
+        np.save(os.path.join(out_dir, k + ".npy"), a.astype(np.float64 if a.dtype.itemsize >= 4 else np.float32))
 
 
 def measured_traffic(n_pairs, kernel_sub="dd_hmm_kernel"):
@@ -340,6 +371,12 @@ def main():
     ap.add_argument("--read-len", type=int, default=100)
     ap.add_argument("--hap-len", type=int, default=120)
     ap.add_argument("--max-length-del", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: at N=1 the host API (copies included), the C++ adapter end to end, "
+                         "the window loop, the ragged batch and the CPU baseline; at N>1 the CPU baseline, the configs[3] pass and the "
+                         "one-process leg (the --no-* options and --kernel-only leave some of them out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a seeded sample of what the last step computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-window-loop", action="store_true", help="skip the BAM -> .glf.txt window-loop leg (N=1)")
     ap.add_argument("--no-ragged", action="store_true", help="skip the real-shaped (ragged) batch leg (N=1)")
@@ -377,7 +414,7 @@ def main():
         local_rank = 0
     host_group = None
     cpu_base = None
-    if world > 1 and rank == 0 and not args.no_cpu_baseline and not args.rehearse and args.total_windows == 0:
+    if world > 1 and rank == 0 and args.full and not args.no_cpu_baseline and not args.rehearse and args.total_windows == 0:
         # the CPU baseline belongs in the N > 1 line too (a SCALE record without it is incomplete): rank 0 times it BEFORE the process
         # group exists — the other ranks wait in the rendezvous meanwhile, no collective kernel spins on their GPUs
         p0 = capi.params_cli_defaults()
@@ -487,9 +524,12 @@ def main():
         # the gathered block of rank 0 is its own result (sanity of the collective's layout)
         assert torch.equal(gather_bufs["ll"][0][:n_pairs].cpu(), dev.out["ll"][:n_pairs].cpu())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(dev, args.dump_outputs)
+
     # ---- N > 1: ONE pass over the configs[3] job (strong scaling), every rank its contiguous block ----
     configs3 = None
-    if world > 1 and not strong and not args.kernel_only and args.configs3_windows > 0:
+    if world > 1 and not strong and args.full and not args.kernel_only and args.configs3_windows > 0:
         del gather_bufs
         plan3, mine3 = build_plan(args.configs3_windows, rank, world, args, params, device, seed=0xC0F1C53)
         gather3, _bufs3 = make_gather(plan3[0][0])
@@ -506,7 +546,7 @@ def main():
 
     # ---- N > 1: the same devices from ONE process (dd_compute_likelihoods_multi), run by rank 0 while the others wait on the host ----
     in_process = None
-    if world > 1 and not strong and not args.kernel_only:
+    if world > 1 and not strong and args.full and not args.kernel_only:
         (dist.barrier(group=host_group) if host_group is not None else dist.barrier())
         if rank == 0:
             in_process = in_process_leg(pb, params, world, [0] * world if args.rehearse else list(range(world)), dev, args)
@@ -556,7 +596,7 @@ def main():
             out["configs3"] = configs3
         if in_process is not None:
             out["in_process"] = in_process
-        if world == 1 and not strong and not args.kernel_only:
+        if world == 1 and not strong and args.full and not args.kernel_only:
             import ctypes as C
             from dindel_tgi_amd.batch import alloc_result
             lib = capi.load()
@@ -591,9 +631,9 @@ def main():
                 "frac_of_kernel_only": (args.windows / lazy["seconds"]) / (total_windows / elapsed)}
             if not args.no_window_loop:
                 out["window_loop"] = window_loop_leg(args.faster)
-        if world == 1 and not strong and not args.no_ragged and not args.faster:
+        if world == 1 and not strong and args.full and not args.no_ragged and not args.faster:
             out["ragged"] = ragged_leg(params, device, windows=args.ragged_windows)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(pb, params, faster=args.faster)
         elif cpu_base is not None:                        # N > 1: timed by rank 0 before the ranks met (see above)
             out["cpu_baseline"] = cpu_base

@@ -63,7 +63,7 @@ def test_world_size_must_equal_gpus():
 
 @pytest.mark.gpu
 def test_plain_launch_two_ranks_one_gpu():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse", "--windows", "300", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--rehearse", "--windows", "300", "--steps", "2", "--warmup", "1",
                         "--configs3-windows", "1500", "--max-batch-windows", "400"],
                        capture_output=True, text=True, timeout=900, env=_env(), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -75,3 +75,31 @@ def test_plain_launch_two_ranks_one_gpu():
     ip = row["in_process"]
     assert "error" not in ip, ip
     assert ip["devices"] == [0, 0] and ip["equals_resident_launch"] is True and ip["cells_per_s"] > 1e9
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_step(tmp_path):
+    """A plain N = 1 run times its steps and leaves the legs beside the headline to --full; --dump-outputs writes every dd_result
+    array of the last step as float32 / float64 .npy, the same in two runs with the same arguments."""
+    import numpy as np
+    from dindel_tgi_amd import capi
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--windows", "300", "--steps", "3", "--warmup", "1"]
+    rows = []
+    for k in range(2):
+        r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / str(k))], capture_output=True, text=True, timeout=600, env=_env(), cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rows.append(_json_line(r.stdout))
+    row = rows[0]
+    assert row["steps"] == 3 and row["warmup"] == 1 and row["ms_per_step"] > 0 and row["value"] > 1e9
+    assert row["metric"] == "read-haplotype HMM cells/s" and row["unit"] == "cells/s" and row["higher_is_better"] is True and row["dtype"] == "f64"
+    assert not {"host_api", "end_to_end", "window_loop", "ragged", "cpu_baseline"} & set(row), sorted(row)
+    total = 0
+    for name, _ in capi.RESULT_FIELDS:
+        a, b = np.load(tmp_path / "0" / (name + ".npy")), np.load(tmp_path / "1" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and a.size > 0, name
+        assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert (np.load(tmp_path / "0" / "status.npy") == 0).all()
+    ll = np.load(tmp_path / "0" / "ll.npy")
+    assert ll.dtype == np.float64 and np.isfinite(ll).all() and (ll <= 0).all()

@@ -11,7 +11,7 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp
 export TMPDIR=/tmp
-python3 $R/bench.py --steps 5 --warmup 1 $BENCH_EXTRA "$@" > $OUT/bench.json      # BENCH_EXTRA=--host-api: un-profiled line only
+python3 $R/bench.py --full --steps 5 --warmup 1 $BENCH_EXTRA "$@" > $OUT/bench.json      # BENCH_EXTRA=--host-api: un-profiled line only
 echo "bench done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --kernel-only --no-ragged "$@" > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
 cp $(find $OUT/trace -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv
