@@ -21,12 +21,16 @@ c_f64p = C.POINTER(C.c_double)
 DD_TABLE_DOUBLES = 32 + 4 * 256 + 4 * 256 + 2 * 64 + 2 * 256 + 2 * 256 + 64
 DD_READ_UNMAPPED, DD_READ_PAIRED, DD_READ_MATE_UNMAPPED, DD_READ_MATE_REVERSE, DD_READ_MATE_SAME_TID = 1, 2, 4, 8, 16
 
-ABI_VERSION = 12           # DD_ABI_VERSION of include/dindel_hmm.h
+ABI_VERSION = 13           # DD_ABI_VERSION of include/dindel_hmm.h
 DD_HPOS_INS, DD_HPOS_LO, DD_HPOS_RO, DD_HPOS_INS_KEY0 = -1, -3, -4, -16
 
 DD_SUCCESS, DD_ERR_NO_DEVICE, DD_ERR_INVALID, DD_ERR_UNSUPPORTED, DD_ERR_HIP = 0, -1, -2, -3, -4
 DD_PAIR_OK, DD_PAIR_HAPSIZE, DD_PAIR_NAN, DD_PAIR_LLPOS, DD_PAIR_UNSUPPORTED = 0, 1, 2, 3, 4
 DD_MAX_HAP_LEN, DD_MAX_READ_LEN = 766, 1024
+DD_LONG_MAX_HAP_LEN, DD_LONG_MAX_READ_LEN = 4094, 4096      # the long-window path (opt-in)
+DD_OPT_LONG_WINDOWS = 1
+DD_WIN_MAIN, DD_WIN_UNSUPPORTED, DD_WIN_LONG = 0, 1, 2
+DD_LONG_WS_BUDGET = 512 << 20
 
 
 class dd_params(C.Structure):
@@ -98,7 +102,8 @@ class dd_device_batch(C.Structure):
                 ("n_qual", C.c_int32), ("n_mapq", C.c_int32), ("hap_var_flank", C.c_void_p), ("sym_lut", C.c_void_p),
                 ("read_mate_pos", C.c_void_p), ("read_mate_len", C.c_void_p), ("read_lib", C.c_void_p),
                 ("lib_off", C.c_void_p), ("lib_logprob", C.c_void_p), ("lib_log95", C.c_void_p),
-                ("hap_class_list", C.c_void_p), ("classes", C.c_void_p), ("win_skip", C.c_void_p)]
+                ("hap_class_list", C.c_void_p), ("classes", C.c_void_p), ("win_skip", C.c_void_p),
+                ("long_max_hap_len", C.c_int32), ("long_max_read_len", C.c_int32)]
 
 
 # haplotype-length classes of a ragged batch, one per lane tiling (capi.cpp kHapClasses): longest haplotype, pairs per wavefront, positions per lane
@@ -127,7 +132,8 @@ class dd_device_result(C.Structure):
 EXPORTS = ["dd_params_struct_defaults", "dd_params_cli_defaults", "dd_batch_sizes", "dd_batch_offsets", "dd_screen_windows",
            "dd_compute_likelihoods", "dd_compute_likelihoods_faster", "dd_compute_likelihoods_multi", "dd_compute_likelihoods_faster_multi", "dd_partition_windows", "dd_launch_device_faster", "dd_release_cache", "dd_reserve_cache", "dd_host_alloc", "dd_host_free", "dd_build_tables", "dd_build_symbol_lut", "dd_build_library_tables", "dd_build_length_classes", "dd_plan_info", "dd_build_index", "dd_workspace_bytes",
            "dd_launch_device", "dd_kernel_name", "dd_last_launch", "dd_launch_log", "dd_last_direct_outputs", "dd_pair_sum_offsets", "dd_pair_sums_device",
-           "dd_pair_sums", "dd_map_pairs_device", "dd_map_pairs", "dd_last_error", "dd_abi_version", "dd_device_count"]
+           "dd_pair_sums", "dd_map_pairs_device", "dd_map_pairs", "dd_last_error", "dd_abi_version", "dd_device_count",
+           "dd_screen_windows_ex", "dd_compute_likelihoods_ex", "dd_workspace_bytes_long", "dd_launch_device_long", "dd_long_launch_log"]
 
 _lib = None
 
@@ -181,6 +187,13 @@ def load():
     lib.dd_pair_sums.argtypes = [C.POINTER(dd_batch), c_f64p, c_f64p, C.c_int]
     lib.dd_map_pairs_device.argtypes = [C.POINTER(dd_device_batch)] + [C.c_void_p] * 9
     lib.dd_map_pairs.argtypes = [C.POINTER(dd_batch), c_f64p, c_f64p, C.POINTER(C.c_uint8), c_i32p, c_f64p, c_f64p, c_i32p, c_f64p, C.c_int]
+    lib.dd_screen_windows_ex.argtypes = [C.POINTER(dd_params), C.POINTER(dd_batch), C.c_uint32, c_u8p, C.POINTER(C.c_int32 * 4)]
+    lib.dd_compute_likelihoods_ex.argtypes = [C.POINTER(dd_params), C.POINTER(dd_batch), C.POINTER(dd_result), C.c_int, C.c_uint32]
+    lib.dd_workspace_bytes_long.argtypes = [C.POINTER(dd_params), C.POINTER(dd_device_batch)]
+    lib.dd_workspace_bytes_long.restype = C.c_size_t
+    lib.dd_launch_device_long.argtypes = [C.POINTER(dd_params), C.POINTER(dd_device_batch), C.POINTER(dd_device_result),
+                                          C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.dd_long_launch_log.argtypes = [c_i64p, C.c_int]
     lib.dd_last_launch.argtypes = [C.POINTER(C.c_int32 * 8)]
     lib.dd_last_launch.restype = None
     lib.dd_launch_log.argtypes = [c_i32p, C.c_int]
@@ -211,6 +224,30 @@ def launch_log():
     buf = np.zeros((64, len(LAUNCH_LOG_FIELDS)), np.int32)
     n = load().dd_launch_log(buf.ctypes.data_as(c_i32p), 64)
     return [dict(zip(LAUNCH_LOG_FIELDS, [int(v) for v in buf[i]])) for i in range(min(n, 64))]
+
+
+LONG_LOG_FIELDS = ["grid", "pairs", "max_pairs_per_wg", "ws_bytes", "K", "max_hap", "max_read", "lds_block"]
+
+
+def long_launch_log():
+    """Every long-window launch of the last dd_launch_device_long / dd_compute_likelihoods_ex call of this thread (dd_long_launch_log)."""
+    import numpy as np
+    buf = np.zeros((64, len(LONG_LOG_FIELDS)), np.int64)
+    n = load().dd_long_launch_log(buf.ctypes.data_as(c_i64p), 64)
+    return [dict(zip(LONG_LOG_FIELDS, [int(v) for v in buf[i]])) for i in range(min(n, 64))]
+
+
+def screen_windows_ex(params, pb, options=DD_OPT_LONG_WINDOWS):
+    """dd_screen_windows_ex: (class per window, [main max hap, main max read, long max hap, long max read], unsupported count)."""
+    import numpy as np
+    cls = np.zeros(max(pb.n_windows, 1), np.uint8)
+    mx = (C.c_int32 * 4)()
+    b = pb.ctypes_batch()
+    n = load().dd_screen_windows_ex(C.byref(params) if params is not None else None, C.byref(b), options, cls.ctypes.data_as(c_u8p),
+                                    C.byref(mx))
+    if n < 0:
+        raise RuntimeError("dd_screen_windows_ex rc=%d: %s" % (n, last_error()))
+    return cls[:pb.n_windows], list(mx), n
 
 
 def last_error():

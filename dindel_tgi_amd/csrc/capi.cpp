@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 #include "hmm_kernel.h"
+#include "long_kernel.h"
 
 namespace {
 
@@ -563,6 +564,69 @@ int dd_screen_windows(const dd_batch *b, uint8_t *win_skip, int32_t max_len_out[
     const int left = assign_symbols(b, lut);
     if (left < 0) return left;
     return screen_windows(b, win_skip, max_len_out, lut, left > 0);
+}
+
+// Classes of the long-window option (dd_screen_windows_ex): 0 main kernels, 1 unsupported, 2 long path.  Without the option exactly
+// screen_windows.  With it a window the main kernels cannot take — a haplotype > DD_MAX_HAP_LEN, a read > DD_MAX_READ_LEN, or on the D = 32
+// build (maxLengthDel >= 12) a haplotype > 574 bp, which make_plan cannot place — goes to the long path when it is within the long limits.
+static int screen_windows_ex(const dd_params *p, const dd_batch *b, uint32_t options, uint8_t *win_class, int32_t max_len_out[4],
+                             const uint8_t *sym_lut, bool with_symbols)
+{
+    if (!(options & DD_OPT_LONG_WINDOWS)) {
+        int32_t m2[2] = {0, 0};
+        const int n = screen_windows(b, win_class, m2, sym_lut, with_symbols);
+        if (max_len_out) { max_len_out[0] = m2[0]; max_len_out[1] = m2[1]; max_len_out[2] = 0; max_len_out[3] = 0; }
+        return n;
+    }
+    const int main_hap_cap = pick_Dt(p->maxLengthDel + 1) > 12 ? kHapClasses[12].bound : DD_MAX_HAP_LEN;   // D = 32 build: K <= 9 (574 bp)
+    int n_bad = 0, mh = 0, mr = 0, lh = 0, lr = 0;
+    for (int w = 0; w < b->n_windows; w++) {
+        int wh = 0, wr = 0;
+        bool bad = false;
+        for (int h = b->win_hap_off[w]; h < b->win_hap_off[w + 1]; h++) {
+            const int len = b->hap_seq_off[h + 1] - b->hap_seq_off[h];
+            if (len < 1) bad = true;
+            if (len > wh) wh = len;
+        }
+        for (int q = b->win_read_off[w]; q < b->win_read_off[w + 1]; q++) {
+            const int len = b->read_seq_off[q + 1] - b->read_seq_off[q];
+            if (len < 1) bad = true;
+            if (len > wr) wr = len;
+        }
+        if (wh > DD_LONG_MAX_HAP_LEN || wr > DD_LONG_MAX_READ_LEN) bad = true;
+        if (with_symbols && !bad) {
+            const int64_t from = b->hap_seq_off[b->win_hap_off[w]], to = b->hap_seq_off[b->win_hap_off[w + 1]];
+            for (int64_t i = from; i < to && !bad; i++)
+                if (sym_lut[(unsigned char)b->hap_seq[i]] == 31) bad = true;
+        }
+        const bool with_pairs = b->win_hap_off[w + 1] > b->win_hap_off[w] && b->win_read_off[w + 1] > b->win_read_off[w];
+        if (bad) { win_class[w] = DD_WIN_UNSUPPORTED; n_bad++; continue; }
+        if (wh > main_hap_cap || wr > DD_MAX_READ_LEN) {
+            win_class[w] = DD_WIN_LONG;
+            if (with_pairs) { lh = std::max(lh, wh); lr = std::max(lr, wr); }
+        } else {
+            win_class[w] = DD_WIN_MAIN;
+            if (with_pairs) { mh = std::max(mh, wh); mr = std::max(mr, wr); }
+        }
+    }
+    if (max_len_out) { max_len_out[0] = mh; max_len_out[1] = mr; max_len_out[2] = lh; max_len_out[3] = lr; }
+    return n_bad;
+}
+
+int dd_screen_windows_ex(const dd_params *p, const dd_batch *b, uint32_t options, uint8_t *win_class, int32_t max_len_out[4])
+{
+    if (!b || !win_class) return fail(DD_ERR_INVALID, "null argument");
+    if (b->n_windows < 0 || !b->win_hap_off || !b->win_read_off || !b->hap_seq_off || !b->read_seq_off)
+        return fail(DD_ERR_INVALID, "null offset array");
+    if (options & ~DD_OPT_LONG_WINDOWS) return fail(DD_ERR_INVALID, "unknown option bits");
+    if (options) {
+        const int rc = check_params(p);
+        if (rc) return rc;
+    }
+    uint8_t lut[256];
+    const int left = assign_symbols(b, lut);
+    if (left < 0) return left;
+    return screen_windows_ex(p, b, options, win_class, max_len_out, lut, left > 0);
 }
 
 int dd_batch_offsets(const dd_batch *b, int64_t *win_pair_off, int64_t *win_hpos_off, int64_t *win_varcov_off)
@@ -1203,6 +1267,126 @@ static int launch_range(Model model, const dd_params *p, const dd_device_batch *
     return DD_SUCCESS;
 }
 
+// ---------------- long windows (long_kernel.hip) ----------------
+// Plan of a long launch: K states per thread (numS <= 256 K, K = 1, 2, 4, 8, 16), LDS, and the persistent grid: the chip's resident
+// workgroups (LDS- and register-limited: 2 per CU, 1 at K = 16), shrunk so that header + lists + one back-pointer tile per workgroup stay
+// within DD_LONG_WS_BUDGET.
+struct LongPlan { int K; size_t lds; unsigned grid; uint64_t off_lpoff, off_tiles, stash_off, tile_bytes, ws_bytes; };
+static int long_plan(int n_windows, int max_hap_len, int max_read_len, int n_qual, LongPlan &lp, ddl::LongArgs &A)
+{
+    if (max_hap_len < 1 || max_hap_len > DD_LONG_MAX_HAP_LEN) return fail(DD_ERR_UNSUPPORTED, "long path: haplotype length outside [1,4094]");
+    if (max_read_len < 1 || max_read_len > DD_LONG_MAX_READ_LEN) return fail(DD_ERR_UNSUPPORTED, "long path: read length outside [1,4096]");
+    const int numS = max_hap_len + 2;
+    lp.K = 1;
+    while (DD_LONG_THREADS * lp.K < numS) lp.K *= 2;
+    A.n_qual = n_qual;
+    lp.lds = ddl::long_lds_layout(lp.K, max_read_len, A);
+    if (lp.lds + 64 > 160u * 1024u) return fail(DD_ERR_UNSUPPORTED, "long path: LDS layout too large");
+    const unsigned per_cu = std::max(1u, std::min(lp.K >= 16 ? 1u : 2u, (unsigned)((160u * 1024u) / (lp.lds + 64))));
+    auto al = [](uint64_t v) { return (v + 255u) & ~(uint64_t)255u; };
+    lp.off_lpoff = al(DD_LONG_WS_HEADER + 4 * (uint64_t)std::max(n_windows, 1));
+    lp.off_tiles = al(lp.off_lpoff + 8 * (uint64_t)(n_windows + 1));
+    lp.stash_off = al((uint64_t)max_read_len * DD_LONG_THREADS * lp.K);
+    lp.tile_bytes = lp.stash_off + 16 * (uint64_t)DD_LONG_THREADS * lp.K;
+    uint64_t grid = 256u * per_cu;
+    const uint64_t fit = DD_LONG_WS_BUDGET > lp.off_tiles ? (DD_LONG_WS_BUDGET - lp.off_tiles) / lp.tile_bytes : 0;
+    if (grid > fit) grid = fit;
+    if (grid < 1) grid = 1;
+    lp.grid = (unsigned)grid;
+    lp.ws_bytes = lp.off_tiles + grid * lp.tile_bytes;
+    return DD_SUCCESS;
+}
+
+struct LongRec {
+    int64_t v[DD_LONG_LOG_FIELDS];
+    const unsigned long long *stats;     // device: {pairs, most pairs of one workgroup}
+    hipStream_t stream;
+};
+static thread_local std::vector<LongRec> g_long_log;
+
+// one long launch over the windows [w_begin, w_end) (their reads: [read_begin, read_end)); stats: device words the kernel counts into
+static int launch_long_range(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes,
+                             void *stream, int w_begin, int w_end, int read_begin, int read_end, unsigned long long *stats)
+{
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (!b || !r || !r->ll || !r->status) return fail(DD_ERR_INVALID, "ll and status outputs are required");
+    if (b->long_max_hap_len <= 0 || b->long_max_read_len <= 0 || b->n_haps <= 0 || b->n_reads <= 0 || w_end <= w_begin) return DD_SUCCESS;
+    if (!b->win_skip) return fail(DD_ERR_INVALID, "long path: win_skip must hold dd_screen_windows_ex's classes");
+    ddl::LongArgs A;
+    memset(&A, 0, sizeof(A));
+    LongPlan lp;
+    if ((rc = long_plan(b->n_windows, b->long_max_hap_len, b->long_max_read_len, b->n_qual, lp, A))) return rc;
+    if (!workspace || workspace_bytes < lp.ws_bytes)
+        return fail(DD_ERR_INVALID, "workspace too small for the long path: allocate dd_workspace_bytes_long() bytes");
+    A.n_windows = b->n_windows; A.w_begin = w_begin; A.w_end = w_end; A.read_begin = read_begin; A.read_end = read_end;
+    A.win_hap_off = b->win_hap_off; A.win_read_off = b->win_read_off; A.win_hap_start = b->win_hap_start;
+    A.hap_seq_off = b->hap_seq_off; A.hap_seq = b->hap_seq; A.hap_var_off = b->hap_var_off; A.hap_var = b->hap_var; A.hap_var_flank = b->hap_var_flank;
+    A.read_seq_off = b->read_seq_off; A.read_seq = b->read_seq; A.read_qidx = b->read_qidx; A.read_mqidx = b->read_mqidx;
+    A.read_start = b->read_start; A.read_flags = b->read_flags;
+    A.win_pair_off = b->win_pair_off; A.win_hpos_off = b->win_hpos_off; A.win_varcov_off = b->win_varcov_off;
+    A.tables = b->tables; A.sym_lut = b->sym_lut; A.win_class = b->win_skip;
+    if (p->mapUnmappedReads) {
+        if (!b->read_mate_pos || !b->read_mate_len || !b->read_lib || !b->lib_off || !b->lib_logprob || !b->lib_log95)
+            return fail(DD_ERR_INVALID, "mapUnmappedReads needs the mate arrays and the library log tables");
+        A.read_mate_pos = b->read_mate_pos; A.read_mate_len = b->read_mate_len; A.read_lib = b->read_lib;
+        A.lib_off = b->lib_off; A.lib_logprob = b->lib_logprob; A.lib_log95 = b->lib_log95;
+    }
+    A.out = *r;
+    A.D = p->maxLengthDel + 1; A.maxLengthDel = p->maxLengthDel; A.padCover = p->padCover; A.bMid = p->bMid; A.maxMismatch = p->maxMismatch;
+    A.max_read_len = b->long_max_read_len;
+    A.ws = static_cast<unsigned char *>(workspace);
+    A.stats = stats ? stats : reinterpret_cast<unsigned long long *>(A.ws + DD_LONG_HDR_STATS);
+    A.off_lpoff = lp.off_lpoff; A.off_tiles = lp.off_tiles; A.tile_bytes = lp.tile_bytes; A.stash_off = lp.stash_off;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool onhap = r->onHap && r->offHapHMQ;
+    HIP_TRY(ddl::launch_long(lp.K, A, lp.grid, lp.lds, onhap, st));
+    LongRec rec;
+    const int64_t v[DD_LONG_LOG_FIELDS] = {(int64_t)lp.grid, -1, -1, (int64_t)lp.ws_bytes, lp.K, b->long_max_hap_len, b->long_max_read_len, (int64_t)lp.lds};
+    memcpy(rec.v, v, sizeof(v));
+    rec.stats = A.stats;
+    rec.stream = st;
+    g_long_log.push_back(rec);
+    return DD_SUCCESS;
+}
+
+size_t dd_workspace_bytes_long(const dd_params *p, const dd_device_batch *b)
+{
+    (void)p;
+    if (!b || b->long_max_hap_len <= 0 || b->long_max_read_len <= 0) return 0;
+    ddl::LongArgs A;
+    memset(&A, 0, sizeof(A));
+    LongPlan lp;
+    if (long_plan(b->n_windows, b->long_max_hap_len, b->long_max_read_len, b->n_qual, lp, A)) return 0;
+    return (size_t)lp.ws_bytes;
+}
+
+int dd_launch_device_long(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes, void *stream)
+{
+    g_long_log.clear();
+    if (!b) return fail(DD_ERR_INVALID, "null batch");
+    return launch_long_range(p, b, r, workspace, workspace_bytes, stream, 0, b->n_windows, 0, b->n_reads, nullptr);
+}
+
+int dd_long_launch_log(int64_t *out, int max_records)
+{   // see include/dindel_hmm.h
+    const int n = (int)g_long_log.size();
+    for (int i = 0; i < n && i < max_records && out; i++) {
+        LongRec &r = g_long_log[(size_t)i];
+        if (r.stats && r.v[1] < 0) {
+            unsigned long long st[2] = {0, 0};
+            if (hipStreamSynchronize(r.stream) == hipSuccess && hipMemcpy(st, r.stats, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess) {
+                r.v[1] = (int64_t)st[0];
+                r.v[2] = (int64_t)st[1];
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+        memcpy(out + (size_t)i * DD_LONG_LOG_FIELDS, r.v, sizeof(r.v));
+    }
+    return n;
+}
+
 int dd_plan_info(const dd_params *p, int max_hap_len, int max_read_len, int n_qual, int avg_reads, int n_haps, int32_t out[10])
 {
     int rc = check_params(p);
@@ -1389,11 +1573,17 @@ int dd_pair_sums(const dd_batch *b, const double *ll_host, double *out_host, int
     return DD_SUCCESS;
 }
 
-static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b, dd_result *r, int device);
+static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options = 0);
 
 int dd_compute_likelihoods(const dd_params *p, const dd_batch *b, dd_result *r, int device)
 {
     return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device);
+}
+
+int dd_compute_likelihoods_ex(const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options)
+{
+    if (options & ~DD_OPT_LONG_WINDOWS) return fail(DD_ERR_INVALID, "unknown option bits");
+    return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device, options);
 }
 
 int dd_compute_likelihoods_faster(const dd_params *p, const dd_batch *b, dd_result *r, int device)
@@ -1442,10 +1632,11 @@ struct StageClock {
 };
 }
 
-static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b, dd_result *r, int device)
+static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options)
 {
     StageClock clk;
     launch_log_clear();
+    g_long_log.clear();
     int rc = check_params(p);
     if (rc) return rc;
     if (!r || !r->ll || !r->status) return fail(DD_ERR_INVALID, "ll and status outputs are required");
@@ -1470,7 +1661,18 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
     const int sym_left = assign_symbols(b, sym_lut);     // > 0: more than 26 distinct non-ACGTN haplotype bytes in the batch
     if (sym_left < 0) return sym_left;
     clk.mark("symbols");
-    const int n_skip = screen_windows(b, win_skip.data(), ok_max, sym_lut, sym_left > 0 && model == MODEL_FBMAXERR);
+    // long windows (DD_OPT_LONG_WINDOWS): win_skip holds the classes; the main kernels skip both non-zero classes, the long launch that
+    // follows each block's main launches computes class 2
+    const bool long_on = model == MODEL_FBMAXERR && (options & DD_OPT_LONG_WINDOWS);
+    int32_t long_max[4] = {0, 0, 0, 0};
+    int n_skip;
+    if (long_on) {
+        n_skip = screen_windows_ex(p, b, options, win_skip.data(), long_max, sym_lut, sym_left > 0);
+        ok_max[0] = long_max[0]; ok_max[1] = long_max[1];
+        for (int w = 0; w < b->n_windows; w++) if (win_skip[(size_t)w] == DD_WIN_LONG) n_skip++;   // (counts every window the main kernels skip)
+    } else {
+        n_skip = screen_windows(b, win_skip.data(), ok_max, sym_lut, sym_left > 0 && model == MODEL_FBMAXERR);
+    }
     sz.max_hap_len = ok_max[0] > 0 ? ok_max[0] : 1;      // planning maxima: the windows that are computed
     sz.max_read_len = ok_max[1] > 0 ? ok_max[1] : 1;
     clk.mark("screen");
@@ -1535,6 +1737,13 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
         db.classes = nullptr; db.hap_class_list = nullptr;
     }
 
+    size_t lws_bytes = 0;                                   // long path: its own workspace per stream
+    if (long_on && long_max[2] > 0) {
+        db.long_max_hap_len = long_max[2]; db.long_max_read_len = long_max[3];
+        lws_bytes = dd_workspace_bytes_long(p, &db);
+        if (!lws_bytes) return fail(DD_ERR_UNSUPPORTED, "long path: no plan for this shape");
+    }
+
     clk.mark("plan");
     // ---- device arena (cached per host thread) ----
     const size_t np = (size_t)sz.n_pairs;
@@ -1546,7 +1755,8 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
     const size_t out_bytes = np * (4 * 8 + 2 + 8 * 2 + 4) + (size_t)sz.hpos_len * 2 + 2 * (size_t)sz.var_cov_len + (size_t)sz.n_reads + 24 * 256;
     const bool staged = in_bytes + out_bytes <= (size_t)64 << 20;    // small batch: one H2D, one D2H through the pinned mirror
     DeviceCtx &ctx = g_ctx.c;
-    if ((rc = ctx.reserve(device, in_bytes + out_bytes + 2 * (ws_bytes + 256), staged ? in_bytes + out_bytes : 0))) return rc;
+    const size_t long_bytes = lws_bytes ? 2 * (lws_bytes + 256) + 16 * 64 + 256 : 0;
+    if ((rc = ctx.reserve(device, in_bytes + out_bytes + 2 * (ws_bytes + 256) + long_bytes, staged ? in_bytes + out_bytes : 0))) return rc;
     clk.mark("reserve");
     DevBuf dev(ctx);
     dev.staged = staged;
@@ -1652,6 +1862,13 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
     for (int i = 0; i < 2; i++)
         if (ws_bytes && (rc = dev.alloc(&ws[i], ws_bytes))) return rc;
     struct { hipStream_t s[2]; } streams = {{ctx.s[0], ctx.s[1]}};
+    unsigned char *lws[2] = {nullptr, nullptr};
+    unsigned long long *long_stats = nullptr;               // 2 words per window block's long launch
+    if (lws_bytes) {
+        for (int i = 0; i < 2; i++)
+            if ((rc = dev.alloc(&lws[i], lws_bytes))) return rc;
+        if ((rc = dev.alloc(&long_stats, (size_t)2 * 64))) return rc;
+    }
 
     // Chunked, double-buffered execution: contiguous window blocks alternate between two streams, and the D2H
     // of block c is issued after the kernel of block c+1 has been enqueued, so the copy engine drains results
@@ -1713,6 +1930,11 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
                 rc = launch_range(model, p, &db, &dr, ws[c & 1], ws_bytes, streams.s[c & 1], g0, g1, q0, q1, &lc);
                 if (rc) return rc;
             }
+        }
+        if (lws_bytes) {
+            bool any = false;
+            for (int w = w0; w < w1 && !any; w++) any = win_skip[(size_t)w] == DD_WIN_LONG;
+            if (any && (rc = launch_long_range(p, &db, &dr, lws[c & 1], lws_bytes, streams.s[c & 1], w0, w1, q0, q1, long_stats + 2 * c))) return rc;
         }
         if (!staged && c > 0 && (rc = download(c - 1))) return rc;
     }

@@ -28,9 +28,13 @@ def _to_dev(arr, device):
 class DeviceBatch:
     """A PackedBatch resident in HBM + the dd_device_batch that points at it."""
 
-    def __init__(self, pb: PackedBatch, params: capi.dd_params, device="cuda:0"):
+    def __init__(self, pb: PackedBatch, params: capi.dd_params, device="cuda:0", long_windows=False):
+        """long_windows: windows beyond the main kernels' limits (haplotypes up to 4,094 bp, reads up to 4,096 bp, and with maxLengthDel
+        12..31 haplotypes over 574 bp) are computed by the long-window kernel after the main launch (dd_launch_device_long) instead of
+        being marked DD_PAIR_UNSUPPORTED.  Off by default."""
         lib = capi.load()
         self.pb, self.params, self.device = pb, params, torch.device(device)
+        self.long_windows = bool(long_windows)
         a = pb.a
         t = {}
         for k in ["win_hap_off", "win_read_off", "win_hap_start", "hap_seq_off", "hap_seq", "hap_var_off", "hap_var",
@@ -70,10 +74,20 @@ class DeviceBatch:
         # ragged batches: per-class launch plans (haplotype length x read length), as the host-pointer path does by itself
         # windows outside the kernel limits are marked (DD_PAIR_UNSUPPORTED), not computed: flags + the maxima of the rest
         skip = np.zeros(max(pb.n_windows, 1), np.uint8)
-        ok_max = (C.c_int32 * 2)()
-        self.n_skipped = lib.dd_screen_windows(C.byref(hb), skip.ctypes.data_as(capi.c_u8p), C.byref(ok_max))
-        if self.n_skipped < 0:
-            raise RuntimeError("dd_screen_windows: " + capi.last_error())
+        self.n_long = 0
+        if self.long_windows:          # classes: 0 main kernels, 1 unsupported, 2 long path (the main kernels skip every non-zero value)
+            ok_max = (C.c_int32 * 4)()
+            n_bad = lib.dd_screen_windows_ex(C.byref(params), C.byref(hb), capi.DD_OPT_LONG_WINDOWS, skip.ctypes.data_as(capi.c_u8p),
+                                             C.byref(ok_max))
+            if n_bad < 0:
+                raise RuntimeError("dd_screen_windows_ex: " + capi.last_error())
+            self.n_long = int((skip[:pb.n_windows] == capi.DD_WIN_LONG).sum())
+            self.n_skipped = n_bad + self.n_long
+        else:
+            ok_max = (C.c_int32 * 2)()
+            self.n_skipped = lib.dd_screen_windows(C.byref(hb), skip.ctypes.data_as(capi.c_u8p), C.byref(ok_max))
+            if self.n_skipped < 0:
+                raise RuntimeError("dd_screen_windows: " + capi.last_error())
         if self.n_skipped:
             t["win_skip"] = _to_dev(skip, self.device)
         self.classes = capi.dd_length_classes()
@@ -92,6 +106,8 @@ class DeviceBatch:
             setattr(db, k, v.data_ptr())
         db.n_qual, db.n_mapq = hb.n_qual, hb.n_mapq
         db.classes = C.addressof(self.classes)
+        if self.n_long:
+            db.long_max_hap_len, db.long_max_read_len = int(ok_max[2]), int(ok_max[3])
         self.db = db
         # results
         n = result_lengths(pb)
@@ -105,6 +121,8 @@ class DeviceBatch:
         # device scratch the launch needs for this shape (back-pointer tiles in HBM for long reads); 0 if none
         self.ws_bytes = int(lib.dd_workspace_bytes(C.byref(params), C.byref(db)))
         self.ws = torch.empty(max(self.ws_bytes, 8), dtype=torch.uint8, device=self.device)
+        self.long_ws_bytes = int(lib.dd_workspace_bytes_long(C.byref(params), C.byref(db))) if self.n_long else 0
+        self.long_ws = torch.empty(max(self.long_ws_bytes, 8), dtype=torch.uint8, device=self.device) if self.n_long else None
 
     def launch(self, stream=None):
         """Enqueue the path on `stream` (default: torch's current stream on this device). Asynchronous."""
@@ -115,6 +133,11 @@ class DeviceBatch:
                                   C.c_void_p(self.ws.data_ptr()), self.ws_bytes, C.c_void_p(stream.cuda_stream))
         if rc != 0:
             raise RuntimeError("dd_launch_device rc=%d: %s" % (rc, capi.last_error()))
+        if self.n_long:                # after the main launch and its onHap pass, on the same stream
+            rc = lib.dd_launch_device_long(C.byref(self.params), C.byref(self.db), C.byref(self.dr), C.c_void_p(self.long_ws.data_ptr()),
+                                           self.long_ws_bytes, C.c_void_p(stream.cuda_stream))
+            if rc != 0:
+                raise RuntimeError("dd_launch_device_long rc=%d: %s" % (rc, capi.last_error()))
 
     def launch_faster(self, stream=None):
         """The --faster model (ObservationModelS) on the same resident batch. Asynchronous."""

@@ -749,8 +749,9 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
         fprintf(stderr, "pack_timing: windows=%d pass1=%.2fms pass2+alloc=%.2fms\n", W, std::chrono::duration<double, std::milli>(t_pass1 - t_start).count(),
                 std::chrono::duration<double, std::milli>(t_packed - t_pass1).count());
     if (sz.n_pairs > 0) {
-        const int rc = faster ? dd_compute_likelihoods_faster(&P, &Bt, &Rz, device_) : dd_compute_likelihoods(&P, &Bt, &Rz, device_);
-        if (rc != DD_SUCCESS) throw std::string(faster ? "dd_compute_likelihoods_faster: " : "dd_compute_likelihoods: ") + dd_last_error();
+        const int rc = faster ? dd_compute_likelihoods_faster(&P, &Bt, &Rz, device_)
+                     : longWindows_ ? dd_compute_likelihoods_ex(&P, &Bt, &Rz, device_, DD_OPT_LONG_WINDOWS) : dd_compute_likelihoods(&P, &Bt, &Rz, device_);
+        if (rc != DD_SUCCESS) throw std::string(faster ? "dd_compute_likelihoods_faster: " : longWindows_ ? "dd_compute_likelihoods_ex: " : "dd_compute_likelihoods: ") + dd_last_error();
     }
 
     const std::chrono::steady_clock::time_point t_device = std::chrono::steady_clock::now();
@@ -769,7 +770,9 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
                 const int st = B.status[size_t(p)];
                 if (st == DD_PAIR_HAPSIZE) { J.error = "hapSize error."; break; }   // ObservationModelFB.cpp:47, Faster.cpp:47
                 if (st == DD_PAIR_UNSUPPORTED) {      // this window only; the caller skips it like a window that threw (DInDel.cpp:1369-1374)
-                    J.error = "window outside the GPU kernel limits (haplotype > 766 bp, read > 1024 bp or an empty sequence)";
+                    J.error = (longWindows_ && !faster)
+                                  ? "window outside the GPU kernel limits (haplotype > 4094 bp, read > 4096 bp, an empty sequence or a haplotype byte without a symbol id)"
+                                  : "window outside the GPU kernel limits (haplotype > 766 bp, read > 1024 bp or an empty sequence)";
                     break;
                 }
                 if (faster && st != DD_PAIR_OK) { J.error = "HapHash string too short"; break; }   // Haplotype.hpp:341

@@ -9,8 +9,9 @@
 //   * NaN / Inf log-likelihood             -> throws std::string("Nan detected")     (DInDel.cpp:1732-1735)
 //   * log-likelihood > 0.1                 -> "Likelihood>0" on stderr, exit(1)      (DInDel.cpp:1722-1731)
 //                                             (setThrowOnPositiveLikelihood(true) turns the exit into a throw)
-//   * window shape outside the kernel limits (haplotype > 766 bp, read > 1024 bp, empty sequence; no reference
-//     counterpart) -> throws std::string("window outside the GPU kernel limits ...") for THAT window only
+//   * window shape outside the kernel limits (haplotype > 766 bp, read > 1024 bp, empty sequence — with setLongWindows(true) in the main
+//     model: haplotype > 4,094 bp, read > 4,096 bp, empty sequence, a haplotype byte without a symbol id; no reference counterpart)
+//     -> throws std::string("window outside the GPU kernel limits ...") for THAT window only
 // All arithmetic runs on the GPU through the C ABI (include/dindel_hmm.h); this class only packs the
 // windows, calls dd_compute_likelihoods and hands the records back.
 //
@@ -138,6 +139,11 @@ public:
     // false: the per-base alignments (hpos, 45 % of the result bytes) stay on the device side of the call; lazy views
     // recompute a window on the first get().  Scalars, covered flags and onHap are always delivered.
     void setKeepAlignments(bool v) { keepAlignments_ = v; }
+    // true: windows beyond the main kernels' limits (haplotypes up to 4,094 bp, reads up to 4,096 bp; with maxLengthIndel >= 12 haplotypes
+    // over 574 bp) are computed by the long-window kernel (dd_compute_likelihoods_ex, DD_OPT_LONG_WINDOWS) instead of being reported as
+    // windows that threw.  Main model only; default off.
+    void setLongWindows(bool v) { longWindows_ = v; }
+    bool longWindows() const { return longWindows_; }
     // optional: have the calling thread's device cache (arena, staging mirror, streams) of this engine's device made now, for batches of
     // about `pairs` (haplotype, read) pairs — e.g. while the first batch is still being prepared.  Throws like the batch calls.
     void warmUp(size_t pairs);
@@ -162,6 +168,7 @@ private:
     bool throwOnPositive_;
     int hostThreads_;
     bool keepAlignments_;
+    bool longWindows_ = false;
     std::vector<std::shared_ptr<BatchBlock> > spare_;   // result blocks of earlier calls; one nobody references any more is reused (warm pages)
     unsigned spareNext_ = 0;
     std::shared_ptr<PackScratch> scratch_;   // the packed inputs' buffers, reused between calls

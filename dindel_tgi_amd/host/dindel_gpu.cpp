@@ -39,6 +39,9 @@
 //   [--prepareOnly]   stop after the prepare stage (no likelihoods, no calls: profiling the read selection on a GPU-less host)
 //   [--windowByWindow] tests: the writer re-does every window one after the other with a read buffer of its own (the reference's loop as it stands)
 //   [--windowByWindow] tests: the writer re-does every window one after the other with a read buffer of its own (the reference's loop as it stands)
+//   [--longWindows]   windows beyond the main kernels' limits (a haplotype > 766 bp, a read > 1024 bp, or with --maxLengthIndel >= 12 a
+//                     haplotype > 574 bp) are computed by the long-window kernel (haplotypes up to 4,094 bp, reads up to 4,096 bp) instead
+//                     of being written as skipped windows; no effect with --faster
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -189,6 +192,8 @@ int main(int argc, char **argv)
             "dindel_gpu: the --analysis indels --doDiploid window loop with the likelihood step on the GPU\n"
             "  required: --bamFile F --varFile F --hapFile F --outputFile PREFIX          (writes PREFIX.glf.txt)\n"
             "  model:    [--faster] [--libFile F] [--filterHaplotypes] [--outputRealignedBAM] [--varFileIsOneBased]\n"
+            "            [--longWindows]  compute windows with a haplotype > 766 bp or a read > 1024 bp (up to 4,094 / 4,096; with --maxLengthIndel >= 12\n"
+            "                             also haplotypes > 574 bp) instead of skipping them; main model only: no effect with --faster\n"
             "            [--maxRead N] [--maxReadLength N] [--minReadOverlap N] [--mapQualThreshold X] [--filterReadAux STR] [--pError X] [--pMut X] [--maxLengthIndel N]\n"
             "            [--flankRefSeq N] [--flankMaxMismatch N] [--priorSNP X] [--priorIndel X] [--capMapQualThreshold X] [--capMapQualFast X] [--maxHapReadProd N]\n"
             "  running:  [--batchWindows N] [--mergeBatches N] [--device D | --devices D0,D1,...] [--prepareThreads N] [--computeThreads N] [--packThreads N] [--reduceThreads N]\n"
@@ -201,7 +206,7 @@ int main(int argc, char **argv)
         if (a.compare(0, 2, "--") != 0) { std::cerr << "Unknown argument " << a << "\n"; return 2; }
         a = a.substr(2);
         if (a == "varFileIsOneBased" || a == "faster" || a == "filterHaplotypes" || a == "quiet" || a == "doDiploid" || a == "timing" || a == "outputRealignedBAM" ||
-            a == "prepareOnly" || a == "noLookBack" || a == "lateSkipsKnown" || a == "windowByWindow") opt[a] = "1";
+            a == "prepareOnly" || a == "noLookBack" || a == "lateSkipsKnown" || a == "windowByWindow" || a == "longWindows") opt[a] = "1";
         else if (i + 1 < argc) opt[a] = argv[++i];
         else { std::cerr << "Option --" << a << " needs a value\n"; return 2; }
     }
@@ -228,6 +233,7 @@ int main(int argc, char **argv)
         dip.filterHaplotypes = has("filterHaplotypes"); dip.quiet = has("quiet");
         const double maxHapReadProd = num("maxHapReadProd", 10000000.0);
         const int batchWindows = std::max(1, int(num("batchWindows", 256)));
+        const bool longWindows = has("longWindows");
         const bool faster = has("faster"), oneBased = has("varFileIsOneBased"), prepareOnly = has("prepareOnly");
         const bool realignedBAM = has("outputRealignedBAM") && !faster;                  // `params.outputRealignedBAM && params.slower`, :589
         rsp.keepRecords = realignedBAM;
@@ -417,6 +423,7 @@ int main(int argc, char **argv)
                 engine.setThrowOnPositiveLikelihood(false);
                 // diploidGLF reads scalars and covered flags only; the --faster model's indel count (DInDel.cpp:3529) needs hpos
                 engine.setKeepAlignments(faster || realignedBAM);
+                engine.setLongWindows(longWindows);
                 if (packThreads > 0) engine.setHostThreads(packThreads);
                 if (!prepareOnly) engine.warmUp(size_t(batchWindows) * size_t(mergeBatches) * 8 * 200);     // while the first batches are being prepared
                 t_ready_of[size_t(ct)] = seconds_since(t_start);
@@ -534,6 +541,7 @@ int main(int argc, char **argv)
                         redo.engine.reset(new LikelihoodEngine(obs, devices[0]));
                         redo.engine->setThrowOnPositiveLikelihood(false);
                         redo.engine->setKeepAlignments(faster || realignedBAM);
+                        redo.engine->setLongWindows(longWindows);
                     }
                     WindowJob J;
                     J.haps = T.haps; J.reads = &T.reads; J.leftPos = T.leftPos; J.rightPos = T.rightPos;

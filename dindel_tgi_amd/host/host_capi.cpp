@@ -92,7 +92,7 @@ int ddh_rebuild_json(const char *hap, const char *read, const double *qual, cons
 static int compute_window_json(bool faster, const char *haps_nl, const char *reads_nl, const double *quals, const double *mapq,
                                const double *pos_first, const int *unmapped, unsigned leftPos, const double *pd, const int *pi,
                                int device, char *out, int cap, const int *mate = NULL, const double *lib_counts = NULL,
-                               const int *lib_sizes = NULL, int n_libs = 0)
+                               const int *lib_sizes = NULL, int n_libs = 0, bool long_windows = false)
 {
     try {
         std::vector<Haplotype> haps;
@@ -128,6 +128,7 @@ static int compute_window_json(bool faster, const char *haps_nl, const char *rea
         prm.mapUnmappedReads = mate != NULL;
         LikelihoodEngine eng(prm, device);
         eng.setThrowOnPositiveLikelihood(true);
+        eng.setLongWindows(long_windows);
         std::vector<std::vector<MLAlignment> > liks;
         std::vector<int> onHap;
         if (faster) eng.computeLikelihoodsFaster(haps, reads, liks, leftPos, leftPos + 1, onHap);
@@ -153,6 +154,14 @@ int ddh_compute_window_json(const char *haps_nl, const char *reads_nl, const dou
                             int device, char *out, int cap)
 {
     return compute_window_json(false, haps_nl, reads_nl, quals, mapq, pos_first, unmapped, leftPos, pd, pi, device, out, cap);
+}
+
+// the same with LikelihoodEngine::setLongWindows(true): windows beyond the main kernels' limits go to the long-window kernel
+int ddh_compute_window_long_json(const char *haps_nl, const char *reads_nl, const double *quals, const double *mapq,
+                                 const double *pos_first, const int *unmapped, unsigned leftPos, const double *pd, const int *pi,
+                                 int device, char *out, int cap)
+{
+    return compute_window_json(false, haps_nl, reads_nl, quals, mapq, pos_first, unmapped, leftPos, pd, pi, device, out, cap, NULL, NULL, NULL, 0, true);
 }
 
 // computeLikelihoods with the insert-size prior (mapUnmappedReads; the reference's --libFile run)
@@ -344,7 +353,7 @@ void parse_windows(int W, const int *n_haps, const int *n_reads, const char *hap
 // Runs the windows twice through computeLikelihoodsBatch — once eager (the reference's containers), once lazy (views; with
 // flags bit1 also without alignments kept) — and reports, per window, the error string and the lazy view's scalars, plus the
 // number of pairs whose lazy view (every scalar accessor and the full record from get()) differs from the eager record.
-// flags: bit0 = --faster model, bit1 = setKeepAlignments(false) for the lazy run.
+// flags: bit0 = --faster model, bit1 = setKeepAlignments(false) for the lazy run, bit2 = setLongWindows(true) for both runs.
 int ddh_batch_json(int W, const int *n_haps, const int *n_reads, const char *haps_nl, const char *reads_nl, const double *quals,
                    const double *mapq, const double *pos_first, const int *unmapped, const unsigned *leftPos, const double *pd,
                    const int *pi, int flags, int device, char *out, int cap)
@@ -355,6 +364,7 @@ int ddh_batch_json(int W, const int *n_haps, const int *n_reads, const char *hap
         const bool faster = (flags & 1) != 0;
         LikelihoodEngine eng(make_params(pd, pi), device);
         eng.setThrowOnPositiveLikelihood(true);
+        eng.setLongWindows((flags & 4) != 0);
         std::vector<std::vector<std::vector<MLAlignment> > > liks(static_cast<size_t>(W));
         std::vector<std::vector<int> > onHap(static_cast<size_t>(W));
         std::vector<WindowJob> eager(static_cast<size_t>(W)), lazy(static_cast<size_t>(W));

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DD_ABI_VERSION 12
+#define DD_ABI_VERSION 13
 
 /* hpos[] sentinel values — reference: MLAlignment.hpp:31-34 */
 #define DD_HPOS_INS (-1)
@@ -75,6 +75,9 @@ extern "C" {
 #define DD_MAX_READ_LEN    1024
 #define DD_MAX_LENGTH_DEL    31   /* D = maxLengthDel + 1 <= 32.  0..11 run the specialised D = 6 / 11 / 12 builds; 12..31 one D = 32 build (correct, not tuned;
                                      haplotypes up to 574 bp there) */
+/* limits of the long-window path (opt-in: DD_OPT_LONG_WINDOWS); numS = Hs+2 <= 4,096 states */
+#define DD_LONG_MAX_HAP_LEN  4094
+#define DD_LONG_MAX_READ_LEN 4096
 #define DD_MAX_QUAL_TABLE   256
 #define DD_HP_TABLE          64   /* homopolymer run lengths >= 52 are all capped at 0.99            */
 
@@ -299,7 +302,10 @@ typedef struct dd_device_batch {   /* all DEVICE pointers; same meaning as dd_ba
     const int32_t *hap_class_list;          /* DEVICE copy of dd_build_length_classes' list */
     const dd_length_classes *classes;       /* HOST pointer */
     const uint8_t *win_skip;                /* optional: DEVICE copy of dd_screen_windows' flags [n_windows]; NULL = every window is
-                                               within the limits (max_hap_len / max_read_len then cover the whole batch) */
+                                               within the limits (max_hap_len / max_read_len then cover the whole batch).  May be
+                                               dd_screen_windows_ex's classes: the main kernels skip every non-zero value */
+    int32_t long_max_hap_len, long_max_read_len;   /* long path only (dd_workspace_bytes_long / dd_launch_device_long): the maxima over
+                                                      its windows, dd_screen_windows_ex's max_len_out[2..3]; 0 = none */
 } dd_device_batch;
 
 /* bytes of device scratch dd_launch_device needs for this shape: the back-pointer tiles of the HBM-scratch builds behind a 256-byte header whose
@@ -311,6 +317,41 @@ size_t dd_workspace_bytes(const dd_params *p, const dd_device_batch *b);
  * Result pointers are DEVICE pointers.  Asynchronous; no allocation, no synchronisation. */
 int dd_launch_device(const dd_params *p, const dd_device_batch *b, const dd_result *r,
                      void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- long windows (opt-in) ----------------------------------------------------------------- */
+/* The main kernels cover haplotypes up to DD_MAX_HAP_LEN, reads up to DD_MAX_READ_LEN, and with maxLengthDel >= 12 haplotypes up to 574 bp.
+ * With DD_OPT_LONG_WINDOWS a window outside those limits but inside DD_LONG_MAX_HAP_LEN / DD_LONG_MAX_READ_LEN (any maxLengthDel 0..31) is
+ * computed by a kernel of its own (one workgroup per pair), launched after the main launch: the same outputs, bit for bit, as the main
+ * kernels would give (main model only; the --faster model keeps skipping such windows).  Without the option nothing changes. */
+#define DD_OPT_LONG_WINDOWS 1u
+#define DD_WIN_MAIN 0          /* dd_screen_windows_ex classes */
+#define DD_WIN_UNSUPPORTED 1
+#define DD_WIN_LONG 2
+/* win_class[w]: DD_WIN_MAIN, DD_WIN_UNSUPPORTED (DD_PAIR_UNSUPPORTED, as dd_screen_windows flags it) or, with DD_OPT_LONG_WINDOWS,
+ * DD_WIN_LONG — a haplotype > DD_MAX_HAP_LEN, a read > DD_MAX_READ_LEN, or (p->maxLengthDel >= 12) a haplotype > 574 bp, within the long
+ * limits.  Empty reads / haplotypes and haplotype bytes without a symbol id stay DD_WIN_UNSUPPORTED.  max_len_out[4] (may be NULL): longest
+ * haplotype / read of the DD_WIN_MAIN windows with pairs, then of the DD_WIN_LONG ones.  Returns the number of DD_WIN_UNSUPPORTED windows.
+ * options = 0: win_class and max_len_out[0..1] are dd_screen_windows' (p may then be NULL). */
+int dd_screen_windows_ex(const dd_params *p, const dd_batch *b, uint32_t options, uint8_t *win_class, int32_t max_len_out[4]);
+/* dd_compute_likelihoods with options; options = 0 is dd_compute_likelihoods. */
+int dd_compute_likelihoods_ex(const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options);
+/* Device-pointer path: b->win_skip = DEVICE copy of dd_screen_windows_ex's classes, b->long_max_hap_len / long_max_read_len its maxima.
+ * Workspace: a 256-byte header (item counter, pair count, stats), the long windows' list, then one back-pointer tile of
+ * long_max_read_len x 256 K bytes (K = 1, 2, 4, 8, 16: numS <= 256 K) per workgroup of the persistent grid.  The grid is the chip's
+ * resident workgroups, shrunk so that the workspace stays within DD_LONG_WS_BUDGET (at least one workgroup: the maximum shape needs 16 MiB).
+ * Never shared by two launches that may run at the same time. */
+#define DD_LONG_WS_BUDGET ((size_t)512 << 20)
+size_t dd_workspace_bytes_long(const dd_params *p, const dd_device_batch *b);
+/* Enqueue the long kernel for the DD_WIN_LONG windows on `stream`, AFTER dd_launch_device on the same batch and stream: it overwrites its
+ * windows' placeholder outputs and (when r->onHap and r->offHapHMQ are given) their reads' onHap.  No-op without long windows. */
+int dd_launch_device_long(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes, void *stream);
+/* Every long launch of the last dd_launch_device_long / dd_compute_likelihoods_ex call on this host thread: records of DD_LONG_LOG_FIELDS
+ * int64 {grid, pairs computed, most pairs one workgroup took, workspace bytes, K (states per thread / 256), long windows' longest
+ * haplotype, longest read, LDS bytes per workgroup}.  The two counters are read from device memory (the workspace header, or the
+ * host path's own copy): this synchronises the launch's stream, and for dd_launch_device_long the workspace must still be allocated.
+ * Returns the number of launches. */
+#define DD_LONG_LOG_FIELDS 8
+int dd_long_launch_log(int64_t *out, int max_records);
 
 /* ---- row A13: the --faster model ---------------------------------------------------------- */
 /* Same batch in, same result layout out, but each pair is scored by ObservationModelS(hap, read, hapStart,
