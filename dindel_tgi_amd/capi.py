@@ -29,6 +29,8 @@ DD_PAIR_OK, DD_PAIR_HAPSIZE, DD_PAIR_NAN, DD_PAIR_LLPOS, DD_PAIR_UNSUPPORTED = 0
 DD_MAX_HAP_LEN, DD_MAX_READ_LEN = 766, 1024
 DD_LONG_MAX_HAP_LEN, DD_LONG_MAX_READ_LEN = 4094, 4096      # the long-window path (opt-in)
 DD_OPT_LONG_WINDOWS = 1
+DD_OPT_LONG_WINDOWS_FASTER = 2     # the --faster model's own long-window option
+DD_FASTER_LONG_WS_BUDGET = 512 << 20
 DD_WIN_MAIN, DD_WIN_UNSUPPORTED, DD_WIN_LONG = 0, 1, 2
 DD_LONG_WS_BUDGET = 512 << 20
 
@@ -133,7 +135,8 @@ EXPORTS = ["dd_params_struct_defaults", "dd_params_cli_defaults", "dd_batch_size
            "dd_compute_likelihoods", "dd_compute_likelihoods_faster", "dd_compute_likelihoods_multi", "dd_compute_likelihoods_faster_multi", "dd_partition_windows", "dd_launch_device_faster", "dd_release_cache", "dd_reserve_cache", "dd_host_alloc", "dd_host_free", "dd_build_tables", "dd_build_symbol_lut", "dd_build_library_tables", "dd_build_length_classes", "dd_plan_info", "dd_build_index", "dd_workspace_bytes",
            "dd_launch_device", "dd_kernel_name", "dd_last_launch", "dd_launch_log", "dd_last_direct_outputs", "dd_pair_sum_offsets", "dd_pair_sums_device",
            "dd_pair_sums", "dd_map_pairs_device", "dd_map_pairs", "dd_last_error", "dd_abi_version", "dd_device_count",
-           "dd_screen_windows_ex", "dd_compute_likelihoods_ex", "dd_workspace_bytes_long", "dd_launch_device_long", "dd_long_launch_log"]
+           "dd_screen_windows_ex", "dd_compute_likelihoods_ex", "dd_workspace_bytes_long", "dd_launch_device_long", "dd_long_launch_log",
+           "dd_compute_likelihoods_faster_ex", "dd_workspace_bytes_faster_long", "dd_launch_device_faster_long", "dd_faster_long_launch_log"]
 
 _lib = None
 
@@ -194,6 +197,11 @@ def load():
     lib.dd_launch_device_long.argtypes = [C.POINTER(dd_params), C.POINTER(dd_device_batch), C.POINTER(dd_device_result),
                                           C.c_void_p, C.c_size_t, C.c_void_p]
     lib.dd_long_launch_log.argtypes = [c_i64p, C.c_int]
+    lib.dd_compute_likelihoods_faster_ex.argtypes = lib.dd_compute_likelihoods_ex.argtypes
+    lib.dd_workspace_bytes_faster_long.argtypes = [C.POINTER(dd_params), C.POINTER(dd_device_batch)]
+    lib.dd_workspace_bytes_faster_long.restype = C.c_size_t
+    lib.dd_launch_device_faster_long.argtypes = lib.dd_launch_device_long.argtypes
+    lib.dd_faster_long_launch_log.argtypes = [c_i64p, C.c_int]
     lib.dd_last_launch.argtypes = [C.POINTER(C.c_int32 * 8)]
     lib.dd_last_launch.restype = None
     lib.dd_launch_log.argtypes = [c_i32p, C.c_int]
@@ -235,6 +243,18 @@ def long_launch_log():
     buf = np.zeros((64, len(LONG_LOG_FIELDS)), np.int64)
     n = load().dd_long_launch_log(buf.ctypes.data_as(c_i64p), 64)
     return [dict(zip(LONG_LOG_FIELDS, [int(v) for v in buf[i]])) for i in range(min(n, 64))]
+
+
+FASTER_LONG_LOG_FIELDS = ["grid", "pairs", "max_pairs_per_wg", "ws_bytes", "max_items_per_wg", "max_hap", "max_read", "lds_block"]
+
+
+def faster_long_launch_log():
+    """Every long-window launch of the --faster model in the last dd_launch_device_faster_long / dd_compute_likelihoods_faster_ex call of
+    this thread (dd_faster_long_launch_log)."""
+    import numpy as np
+    buf = np.zeros((64, len(FASTER_LONG_LOG_FIELDS)), np.int64)
+    n = load().dd_faster_long_launch_log(buf.ctypes.data_as(c_i64p), 64)
+    return [dict(zip(FASTER_LONG_LOG_FIELDS, [int(v) for v in buf[i]])) for i in range(min(n, 64))]
 
 
 def screen_windows_ex(params, pb, options=DD_OPT_LONG_WINDOWS):

@@ -19,6 +19,7 @@
 #include <vector>
 #include "hmm_kernel.h"
 #include "long_kernel.h"
+#include "faster_long_kernel.h"
 
 namespace {
 
@@ -572,6 +573,36 @@ int dd_screen_windows(const dd_batch *b, uint8_t *win_skip, int32_t max_len_out[
 static int screen_windows_ex(const dd_params *p, const dd_batch *b, uint32_t options, uint8_t *win_class, int32_t max_len_out[4],
                              const uint8_t *sym_lut, bool with_symbols)
 {
+    if (options & DD_OPT_LONG_WINDOWS_FASTER) {
+        // classes for the --faster model: lengths only (it compares haplotype bytes, and maxLengthDel is only a size check there)
+        int n_bad = 0, mh = 0, mr = 0, lh = 0, lr = 0;
+        for (int w = 0; w < b->n_windows; w++) {
+            int wh = 0, wr = 0;
+            bool bad = false;
+            for (int h = b->win_hap_off[w]; h < b->win_hap_off[w + 1]; h++) {
+                const int len = b->hap_seq_off[h + 1] - b->hap_seq_off[h];
+                if (len < 1) bad = true;
+                if (len > wh) wh = len;
+            }
+            for (int q = b->win_read_off[w]; q < b->win_read_off[w + 1]; q++) {
+                const int len = b->read_seq_off[q + 1] - b->read_seq_off[q];
+                if (len < 1) bad = true;
+                if (len > wr) wr = len;
+            }
+            if (wh > DD_LONG_MAX_HAP_LEN || wr > DD_LONG_MAX_READ_LEN) bad = true;
+            const bool with_pairs = b->win_hap_off[w + 1] > b->win_hap_off[w] && b->win_read_off[w + 1] > b->win_read_off[w];
+            if (bad) { win_class[w] = DD_WIN_UNSUPPORTED; n_bad++; continue; }
+            if (wh > DD_MAX_HAP_LEN || wr > DD_MAX_READ_LEN) {
+                win_class[w] = DD_WIN_LONG;
+                if (with_pairs) { lh = std::max(lh, wh); lr = std::max(lr, wr); }
+            } else {
+                win_class[w] = DD_WIN_MAIN;
+                if (with_pairs) { mh = std::max(mh, wh); mr = std::max(mr, wr); }
+            }
+        }
+        if (max_len_out) { max_len_out[0] = mh; max_len_out[1] = mr; max_len_out[2] = lh; max_len_out[3] = lr; }
+        return n_bad;
+    }
     if (!(options & DD_OPT_LONG_WINDOWS)) {
         int32_t m2[2] = {0, 0};
         const int n = screen_windows(b, win_class, m2, sym_lut, with_symbols);
@@ -618,7 +649,9 @@ int dd_screen_windows_ex(const dd_params *p, const dd_batch *b, uint32_t options
     if (!b || !win_class) return fail(DD_ERR_INVALID, "null argument");
     if (b->n_windows < 0 || !b->win_hap_off || !b->win_read_off || !b->hap_seq_off || !b->read_seq_off)
         return fail(DD_ERR_INVALID, "null offset array");
-    if (options & ~DD_OPT_LONG_WINDOWS) return fail(DD_ERR_INVALID, "unknown option bits");
+    if (options & ~(DD_OPT_LONG_WINDOWS | DD_OPT_LONG_WINDOWS_FASTER)) return fail(DD_ERR_INVALID, "unknown option bits");
+    if ((options & DD_OPT_LONG_WINDOWS) && (options & DD_OPT_LONG_WINDOWS_FASTER))
+        return fail(DD_ERR_INVALID, "DD_OPT_LONG_WINDOWS and DD_OPT_LONG_WINDOWS_FASTER class the windows for different models: one at a time");
     if (options) {
         const int rc = check_params(p);
         if (rc) return rc;
@@ -1387,6 +1420,119 @@ int dd_long_launch_log(int64_t *out, int max_records)
     return n;
 }
 
+// ---------------- long windows of the --faster model (faster_long_kernel.hip) ----------------
+// Plan of a launch: LDS for the shape, and the persistent grid: the chip's resident workgroups (LDS-limited, at most 2 per CU: the kernel is
+// built for 2 waves per SIMD), no more than the batch can have 16-pair items, shrunk so that header + lists + 16 tiles per workgroup stay
+// within DD_FASTER_LONG_WS_BUDGET.
+struct FLPlan { size_t lds; unsigned grid; uint64_t off_ioff, off_tiles, ws_bytes; };
+static int fl_plan(const dd_device_batch *b, FLPlan &fp, ddf::FLArgs &A)
+{
+    const int mh = b->long_max_hap_len, mr = b->long_max_read_len;
+    if (mh < 1 || mh > DD_LONG_MAX_HAP_LEN) return fail(DD_ERR_UNSUPPORTED, "--faster long path: haplotype length outside [1,4094]");
+    if (mr < 1 || mr > DD_LONG_MAX_READ_LEN) return fail(DD_ERR_UNSUPPORTED, "--faster long path: read length outside [1,4096]");
+    A.n_qual = b->n_qual;
+    A.max_hap_len = mh; A.max_read_len = mr;
+    fp.lds = ddf::fl_lds_layout(mh, mr, A);
+    if (fp.lds + 64 > 160u * 1024u) return fail(DD_ERR_UNSUPPORTED, "--faster long path: LDS layout too large");
+    const unsigned per_cu = std::max(1u, std::min(2u, (unsigned)((160u * 1024u) / (fp.lds + 64))));
+    auto al = [](uint64_t v) { return (v + 255u) & ~(uint64_t)255u; };
+    fp.off_ioff = al(DD_FL_WS_HEADER + 4 * (uint64_t)std::max(b->n_windows, 1));
+    fp.off_tiles = al(fp.off_ioff + 8 * (uint64_t)(std::max(b->n_windows, 0) + 1));
+    const uint64_t wg_bytes = DD_FL_PAIRS * ddf::fl_tile_layout(mh, mr, A);
+    uint64_t grid = 256u * per_cu;
+    const uint64_t items = (uint64_t)std::max(b->n_haps, 0) * (((uint64_t)std::max(b->n_reads, 0) + DD_FL_PAIRS - 1) / DD_FL_PAIRS);
+    if (grid > items) grid = items;
+    const uint64_t fit = DD_FASTER_LONG_WS_BUDGET > fp.off_tiles ? (DD_FASTER_LONG_WS_BUDGET - fp.off_tiles) / wg_bytes : 0;
+    if (grid > fit) grid = fit;
+    if (grid < 1) grid = 1;
+    fp.grid = (unsigned)grid;
+    fp.ws_bytes = fp.off_tiles + grid * wg_bytes;
+    A.off_ioff = fp.off_ioff; A.off_tiles = fp.off_tiles; A.grid = (int32_t)grid;
+    return DD_SUCCESS;
+}
+
+struct FLRec {
+    int64_t v[DD_FASTER_LONG_LOG_FIELDS];
+    const unsigned long long *stats;     // device: {pairs, most pairs of one workgroup, most items of one workgroup, 0}
+    hipStream_t stream;
+};
+static thread_local std::vector<FLRec> g_fl_log;
+
+// one launch over the windows [w_begin, w_end) (their reads: [read_begin, read_end)); stats: 4 device words the kernel counts into
+static int launch_faster_long_range(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes,
+                                    void *stream, int w_begin, int w_end, int read_begin, int read_end, unsigned long long *stats)
+{
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (!b || !r || !r->ll || !r->status) return fail(DD_ERR_INVALID, "ll and status outputs are required");
+    if (b->long_max_hap_len <= 0 || b->long_max_read_len <= 0 || b->n_haps <= 0 || b->n_reads <= 0 || w_end <= w_begin) return DD_SUCCESS;
+    if (!b->win_skip) return fail(DD_ERR_INVALID, "--faster long path: win_skip must hold dd_screen_windows_ex's classes");
+    ddf::FLArgs A;
+    memset(&A, 0, sizeof(A));
+    FLPlan fp;
+    if ((rc = fl_plan(b, fp, A))) return rc;
+    if (!workspace || workspace_bytes < fp.ws_bytes)
+        return fail(DD_ERR_INVALID, "workspace too small for the --faster long path: allocate dd_workspace_bytes_faster_long() bytes");
+    A.n_windows = b->n_windows; A.w_begin = w_begin; A.w_end = w_end; A.read_begin = read_begin; A.read_end = read_end;
+    A.win_hap_off = b->win_hap_off; A.win_read_off = b->win_read_off; A.win_hap_start = b->win_hap_start;
+    A.hap_seq_off = b->hap_seq_off; A.hap_seq = b->hap_seq; A.hap_var_off = b->hap_var_off; A.hap_var = b->hap_var; A.hap_var_flank = b->hap_var_flank;
+    A.read_seq_off = b->read_seq_off; A.read_seq = b->read_seq; A.read_qidx = b->read_qidx; A.read_mqidx = b->read_mqidx;
+    A.read_start = b->read_start;
+    A.win_pair_off = b->win_pair_off; A.win_hpos_off = b->win_hpos_off; A.win_varcov_off = b->win_varcov_off;
+    A.tables = b->tables; A.win_class = b->win_skip;
+    A.out = *r;
+    A.maxLengthDel = p->maxLengthDel; A.padCover = p->padCover; A.maxMismatch = p->maxMismatch;
+    A.ws = static_cast<unsigned char *>(workspace);
+    A.stats = stats ? stats : reinterpret_cast<unsigned long long *>(A.ws + DD_FL_HDR_STATS);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    HIP_TRY(ddf::launch_faster_long(A, fp.grid, fp.lds, r->onHap && r->offHapHMQ, st));
+    FLRec rec;
+    const int64_t v[DD_FASTER_LONG_LOG_FIELDS] = {(int64_t)fp.grid, -1, -1, (int64_t)fp.ws_bytes, -1, b->long_max_hap_len, b->long_max_read_len, (int64_t)fp.lds};
+    memcpy(rec.v, v, sizeof(v));
+    rec.stats = A.stats;
+    rec.stream = st;
+    g_fl_log.push_back(rec);
+    return DD_SUCCESS;
+}
+
+size_t dd_workspace_bytes_faster_long(const dd_params *p, const dd_device_batch *b)
+{
+    (void)p;
+    if (!b || b->long_max_hap_len <= 0 || b->long_max_read_len <= 0) return 0;
+    ddf::FLArgs A;
+    memset(&A, 0, sizeof(A));
+    FLPlan fp;
+    if (fl_plan(b, fp, A)) return 0;
+    return (size_t)fp.ws_bytes;
+}
+
+int dd_launch_device_faster_long(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes, void *stream)
+{
+    g_fl_log.clear();
+    if (!b) return fail(DD_ERR_INVALID, "null batch");
+    return launch_faster_long_range(p, b, r, workspace, workspace_bytes, stream, 0, b->n_windows, 0, b->n_reads, nullptr);
+}
+
+int dd_faster_long_launch_log(int64_t *out, int max_records)
+{   // see include/dindel_hmm.h
+    const int n = (int)g_fl_log.size();
+    for (int i = 0; i < n && i < max_records && out; i++) {
+        FLRec &r = g_fl_log[(size_t)i];
+        if (r.stats && r.v[1] < 0) {
+            unsigned long long st[4] = {0, 0, 0, 0};
+            if (hipStreamSynchronize(r.stream) == hipSuccess && hipMemcpy(st, r.stats, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess) {
+                r.v[1] = (int64_t)st[0];
+                r.v[2] = (int64_t)st[1];
+                r.v[4] = (int64_t)st[2];
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+        memcpy(out + (size_t)i * DD_FASTER_LONG_LOG_FIELDS, r.v, sizeof(r.v));
+    }
+    return n;
+}
+
 int dd_plan_info(const dd_params *p, int max_hap_len, int max_read_len, int n_qual, int avg_reads, int n_haps, int32_t out[10])
 {
     int rc = check_params(p);
@@ -1591,6 +1737,12 @@ int dd_compute_likelihoods_faster(const dd_params *p, const dd_batch *b, dd_resu
     return compute_likelihoods_impl(MODEL_S, p, b, r, device);
 }
 
+int dd_compute_likelihoods_faster_ex(const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options)
+{
+    if (options & ~DD_OPT_LONG_WINDOWS_FASTER) return fail(DD_ERR_INVALID, "unknown option bits");
+    return compute_likelihoods_impl(MODEL_S, p, b, r, device, options);
+}
+
 namespace {
 // true iff some p[i] >= limit.  The arrays checked this way hold one byte per read base (2e8 for configs[1]): a branch-free
 // pass the compiler vectorises, cut into pieces for a few threads when it is long.
@@ -1637,6 +1789,7 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
     StageClock clk;
     launch_log_clear();
     g_long_log.clear();
+    g_fl_log.clear();
     int rc = check_params(p);
     if (rc) return rc;
     if (!r || !r->ll || !r->status) return fail(DD_ERR_INVALID, "ll and status outputs are required");
@@ -1663,7 +1816,9 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
     clk.mark("symbols");
     // long windows (DD_OPT_LONG_WINDOWS): win_skip holds the classes; the main kernels skip both non-zero classes, the long launch that
     // follows each block's main launches computes class 2
-    const bool long_on = model == MODEL_FBMAXERR && (options & DD_OPT_LONG_WINDOWS);
+    // (DD_OPT_LONG_WINDOWS_FASTER: the same for the --faster model, with its own classes and its own kernel)
+    const bool fl_on = model == MODEL_S && (options & DD_OPT_LONG_WINDOWS_FASTER);
+    const bool long_on = (model == MODEL_FBMAXERR && (options & DD_OPT_LONG_WINDOWS)) || fl_on;
     int32_t long_max[4] = {0, 0, 0, 0};
     int n_skip;
     if (long_on) {
@@ -1740,7 +1895,7 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
     size_t lws_bytes = 0;                                   // long path: its own workspace per stream
     if (long_on && long_max[2] > 0) {
         db.long_max_hap_len = long_max[2]; db.long_max_read_len = long_max[3];
-        lws_bytes = dd_workspace_bytes_long(p, &db);
+        lws_bytes = fl_on ? dd_workspace_bytes_faster_long(p, &db) : dd_workspace_bytes_long(p, &db);
         if (!lws_bytes) return fail(DD_ERR_UNSUPPORTED, "long path: no plan for this shape");
     }
 
@@ -1755,7 +1910,7 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
     const size_t out_bytes = np * (4 * 8 + 2 + 8 * 2 + 4) + (size_t)sz.hpos_len * 2 + 2 * (size_t)sz.var_cov_len + (size_t)sz.n_reads + 24 * 256;
     const bool staged = in_bytes + out_bytes <= (size_t)64 << 20;    // small batch: one H2D, one D2H through the pinned mirror
     DeviceCtx &ctx = g_ctx.c;
-    const size_t long_bytes = lws_bytes ? 2 * (lws_bytes + 256) + 16 * 64 + 256 : 0;
+    const size_t long_bytes = lws_bytes ? 2 * (lws_bytes + 256) + 32 * 64 + 256 : 0;
     if ((rc = ctx.reserve(device, in_bytes + out_bytes + 2 * (ws_bytes + 256) + long_bytes, staged ? in_bytes + out_bytes : 0))) return rc;
     clk.mark("reserve");
     DevBuf dev(ctx);
@@ -1867,7 +2022,7 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
     if (lws_bytes) {
         for (int i = 0; i < 2; i++)
             if ((rc = dev.alloc(&lws[i], lws_bytes))) return rc;
-        if ((rc = dev.alloc(&long_stats, (size_t)2 * 64))) return rc;
+        if ((rc = dev.alloc(&long_stats, (size_t)4 * 64))) return rc;      // (4 words per block for the --faster model's launch)
     }
 
     // Chunked, double-buffered execution: contiguous window blocks alternate between two streams, and the D2H
@@ -1934,7 +2089,9 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
         if (lws_bytes) {
             bool any = false;
             for (int w = w0; w < w1 && !any; w++) any = win_skip[(size_t)w] == DD_WIN_LONG;
-            if (any && (rc = launch_long_range(p, &db, &dr, lws[c & 1], lws_bytes, streams.s[c & 1], w0, w1, q0, q1, long_stats + 2 * c))) return rc;
+            if (any && fl_on) {
+                if ((rc = launch_faster_long_range(p, &db, &dr, lws[c & 1], lws_bytes, streams.s[c & 1], w0, w1, q0, q1, long_stats + 4 * c))) return rc;
+            } else if (any && (rc = launch_long_range(p, &db, &dr, lws[c & 1], lws_bytes, streams.s[c & 1], w0, w1, q0, q1, long_stats + 2 * c))) return rc;
         }
         if (!staged && c > 0 && (rc = download(c - 1))) return rc;
     }

@@ -28,13 +28,19 @@ def _to_dev(arr, device):
 class DeviceBatch:
     """A PackedBatch resident in HBM + the dd_device_batch that points at it."""
 
-    def __init__(self, pb: PackedBatch, params: capi.dd_params, device="cuda:0", long_windows=False):
+    def __init__(self, pb: PackedBatch, params: capi.dd_params, device="cuda:0", long_windows=False, long_windows_faster=False):
         """long_windows: windows beyond the main kernels' limits (haplotypes up to 4,094 bp, reads up to 4,096 bp, and with maxLengthDel
         12..31 haplotypes over 574 bp) are computed by the long-window kernel after the main launch (dd_launch_device_long) instead of
-        being marked DD_PAIR_UNSUPPORTED.  Off by default."""
+        being marked DD_PAIR_UNSUPPORTED.  Off by default.
+        long_windows_faster: the same for the --faster model: the batch is screened for that model (haplotypes over 766 bp or reads over
+        1,024 bp, within the same long limits), and launch_faster() follows its main launch with dd_launch_device_faster_long.  A resident
+        batch is screened once, for one model: both flags together raise ValueError, and launch() on such a batch raises."""
+        if long_windows and long_windows_faster:
+            raise ValueError("long_windows and long_windows_faster screen the batch for different models: one resident batch, one screening")
         lib = capi.load()
         self.pb, self.params, self.device = pb, params, torch.device(device)
         self.long_windows = bool(long_windows)
+        self.long_windows_faster = bool(long_windows_faster)
         a = pb.a
         t = {}
         for k in ["win_hap_off", "win_read_off", "win_hap_start", "hap_seq_off", "hap_seq", "hap_var_off", "hap_var",
@@ -75,9 +81,10 @@ class DeviceBatch:
         # windows outside the kernel limits are marked (DD_PAIR_UNSUPPORTED), not computed: flags + the maxima of the rest
         skip = np.zeros(max(pb.n_windows, 1), np.uint8)
         self.n_long = 0
-        if self.long_windows:          # classes: 0 main kernels, 1 unsupported, 2 long path (the main kernels skip every non-zero value)
+        if self.long_windows or self.long_windows_faster:   # classes: 0 main kernels, 1 unsupported, 2 long path (the main kernels skip every non-zero value)
             ok_max = (C.c_int32 * 4)()
-            n_bad = lib.dd_screen_windows_ex(C.byref(params), C.byref(hb), capi.DD_OPT_LONG_WINDOWS, skip.ctypes.data_as(capi.c_u8p),
+            opt = capi.DD_OPT_LONG_WINDOWS_FASTER if self.long_windows_faster else capi.DD_OPT_LONG_WINDOWS
+            n_bad = lib.dd_screen_windows_ex(C.byref(params), C.byref(hb), opt, skip.ctypes.data_as(capi.c_u8p),
                                              C.byref(ok_max))
             if n_bad < 0:
                 raise RuntimeError("dd_screen_windows_ex: " + capi.last_error())
@@ -121,11 +128,14 @@ class DeviceBatch:
         # device scratch the launch needs for this shape (back-pointer tiles in HBM for long reads); 0 if none
         self.ws_bytes = int(lib.dd_workspace_bytes(C.byref(params), C.byref(db)))
         self.ws = torch.empty(max(self.ws_bytes, 8), dtype=torch.uint8, device=self.device)
-        self.long_ws_bytes = int(lib.dd_workspace_bytes_long(C.byref(params), C.byref(db))) if self.n_long else 0
+        ws_long = lib.dd_workspace_bytes_faster_long if self.long_windows_faster else lib.dd_workspace_bytes_long
+        self.long_ws_bytes = int(ws_long(C.byref(params), C.byref(db))) if self.n_long else 0
         self.long_ws = torch.empty(max(self.long_ws_bytes, 8), dtype=torch.uint8, device=self.device) if self.n_long else None
 
     def launch(self, stream=None):
         """Enqueue the path on `stream` (default: torch's current stream on this device). Asynchronous."""
+        if self.long_windows_faster:
+            raise RuntimeError("this batch was screened for the --faster model (long_windows_faster=True): use launch_faster()")
         lib = capi.load()
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
@@ -147,6 +157,11 @@ class DeviceBatch:
         rc = lib.dd_launch_device_faster(C.byref(self.params), C.byref(self.db), C.byref(self.dr), C.c_void_p(stream.cuda_stream))
         if rc != 0:
             raise RuntimeError("dd_launch_device_faster rc=%d: %s" % (rc, capi.last_error()))
+        if self.long_windows_faster and self.n_long:   # after the main launch and its onHap pass, on the same stream
+            rc = lib.dd_launch_device_faster_long(C.byref(self.params), C.byref(self.db), C.byref(self.dr), C.c_void_p(self.long_ws.data_ptr()),
+                                                  self.long_ws_bytes, C.c_void_p(stream.cuda_stream))
+            if rc != 0:
+                raise RuntimeError("dd_launch_device_faster_long rc=%d: %s" % (rc, capi.last_error()))
 
     def results(self):
         """Host copies (numpy) of the outputs, trimmed to their logical lengths."""

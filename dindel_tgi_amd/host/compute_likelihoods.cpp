@@ -749,9 +749,10 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
         fprintf(stderr, "pack_timing: windows=%d pass1=%.2fms pass2+alloc=%.2fms\n", W, std::chrono::duration<double, std::milli>(t_pass1 - t_start).count(),
                 std::chrono::duration<double, std::milli>(t_packed - t_pass1).count());
     if (sz.n_pairs > 0) {
-        const int rc = faster ? dd_compute_likelihoods_faster(&P, &Bt, &Rz, device_)
+        const int rc = faster ? (longWindowsFaster_ ? dd_compute_likelihoods_faster_ex(&P, &Bt, &Rz, device_, DD_OPT_LONG_WINDOWS_FASTER)
+                                                    : dd_compute_likelihoods_faster(&P, &Bt, &Rz, device_))
                      : longWindows_ ? dd_compute_likelihoods_ex(&P, &Bt, &Rz, device_, DD_OPT_LONG_WINDOWS) : dd_compute_likelihoods(&P, &Bt, &Rz, device_);
-        if (rc != DD_SUCCESS) throw std::string(faster ? "dd_compute_likelihoods_faster: " : longWindows_ ? "dd_compute_likelihoods_ex: " : "dd_compute_likelihoods: ") + dd_last_error();
+        if (rc != DD_SUCCESS) throw std::string(faster ? (longWindowsFaster_ ? "dd_compute_likelihoods_faster_ex: " : "dd_compute_likelihoods_faster: ") : longWindows_ ? "dd_compute_likelihoods_ex: " : "dd_compute_likelihoods: ") + dd_last_error();
     }
 
     const std::chrono::steady_clock::time_point t_device = std::chrono::steady_clock::now();

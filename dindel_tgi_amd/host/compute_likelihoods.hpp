@@ -144,6 +144,11 @@ public:
     // windows that threw.  Main model only; default off.
     void setLongWindows(bool v) { longWindows_ = v; }
     bool longWindows() const { return longWindows_; }
+    // true: the same for the --faster model, which setLongWindows does not touch: windows with a haplotype of 767..4,094 bp or a read of
+    // 1,025..4,096 bp are computed by that model's long-window kernel (dd_compute_likelihoods_faster_ex, DD_OPT_LONG_WINDOWS_FASTER).
+    // No effect on the main model; default off.
+    void setLongWindowsFaster(bool v) { longWindowsFaster_ = v; }
+    bool longWindowsFaster() const { return longWindowsFaster_; }
     // optional: have the calling thread's device cache (arena, staging mirror, streams) of this engine's device made now, for batches of
     // about `pairs` (haplotype, read) pairs — e.g. while the first batch is still being prepared.  Throws like the batch calls.
     void warmUp(size_t pairs);
@@ -169,6 +174,7 @@ private:
     int hostThreads_;
     bool keepAlignments_;
     bool longWindows_ = false;
+    bool longWindowsFaster_ = false;
     std::vector<std::shared_ptr<BatchBlock> > spare_;   // result blocks of earlier calls; one nobody references any more is reused (warm pages)
     unsigned spareNext_ = 0;
     std::shared_ptr<PackScratch> scratch_;   // the packed inputs' buffers, reused between calls

@@ -38,10 +38,11 @@
 //   [--timing]        one "timing:" line on stdout with the busy time of each stage
 //   [--prepareOnly]   stop after the prepare stage (no likelihoods, no calls: profiling the read selection on a GPU-less host)
 //   [--windowByWindow] tests: the writer re-does every window one after the other with a read buffer of its own (the reference's loop as it stands)
-//   [--windowByWindow] tests: the writer re-does every window one after the other with a read buffer of its own (the reference's loop as it stands)
 //   [--longWindows]   windows beyond the main kernels' limits (a haplotype > 766 bp, a read > 1024 bp, or with --maxLengthIndel >= 12 a
 //                     haplotype > 574 bp) are computed by the long-window kernel (haplotypes up to 4,094 bp, reads up to 4,096 bp) instead
 //                     of being written as skipped windows; no effect with --faster
+//   [--longWindowsFaster]  the same for the --faster model (its own kernel): windows with a haplotype of 767..4,094 bp or a read of
+//                     1,025..4,096 bp are computed instead of being written as skipped windows; effective only with --faster
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -194,6 +195,8 @@ int main(int argc, char **argv)
             "  model:    [--faster] [--libFile F] [--filterHaplotypes] [--outputRealignedBAM] [--varFileIsOneBased]\n"
             "            [--longWindows]  compute windows with a haplotype > 766 bp or a read > 1024 bp (up to 4,094 / 4,096; with --maxLengthIndel >= 12\n"
             "                             also haplotypes > 574 bp) instead of skipping them; main model only: no effect with --faster\n"
+            "            [--longWindowsFaster]  with --faster: compute windows with a haplotype > 766 bp or a read > 1024 bp (up to 4,094 / 4,096) instead of\n"
+            "                             skipping them; no effect without --faster\n"
             "            [--maxRead N] [--maxReadLength N] [--minReadOverlap N] [--mapQualThreshold X] [--filterReadAux STR] [--pError X] [--pMut X] [--maxLengthIndel N]\n"
             "            [--flankRefSeq N] [--flankMaxMismatch N] [--priorSNP X] [--priorIndel X] [--capMapQualThreshold X] [--capMapQualFast X] [--maxHapReadProd N]\n"
             "  running:  [--batchWindows N] [--mergeBatches N] [--device D | --devices D0,D1,...] [--prepareThreads N] [--computeThreads N] [--packThreads N] [--reduceThreads N]\n"
@@ -206,7 +209,7 @@ int main(int argc, char **argv)
         if (a.compare(0, 2, "--") != 0) { std::cerr << "Unknown argument " << a << "\n"; return 2; }
         a = a.substr(2);
         if (a == "varFileIsOneBased" || a == "faster" || a == "filterHaplotypes" || a == "quiet" || a == "doDiploid" || a == "timing" || a == "outputRealignedBAM" ||
-            a == "prepareOnly" || a == "noLookBack" || a == "lateSkipsKnown" || a == "windowByWindow" || a == "longWindows") opt[a] = "1";
+            a == "prepareOnly" || a == "noLookBack" || a == "lateSkipsKnown" || a == "windowByWindow" || a == "longWindows" || a == "longWindowsFaster") opt[a] = "1";
         else if (i + 1 < argc) opt[a] = argv[++i];
         else { std::cerr << "Option --" << a << " needs a value\n"; return 2; }
     }
@@ -234,6 +237,7 @@ int main(int argc, char **argv)
         const double maxHapReadProd = num("maxHapReadProd", 10000000.0);
         const int batchWindows = std::max(1, int(num("batchWindows", 256)));
         const bool longWindows = has("longWindows");
+        const bool longWindowsFaster = has("longWindowsFaster");
         const bool faster = has("faster"), oneBased = has("varFileIsOneBased"), prepareOnly = has("prepareOnly");
         const bool realignedBAM = has("outputRealignedBAM") && !faster;                  // `params.outputRealignedBAM && params.slower`, :589
         rsp.keepRecords = realignedBAM;
@@ -424,6 +428,7 @@ int main(int argc, char **argv)
                 // diploidGLF reads scalars and covered flags only; the --faster model's indel count (DInDel.cpp:3529) needs hpos
                 engine.setKeepAlignments(faster || realignedBAM);
                 engine.setLongWindows(longWindows);
+                engine.setLongWindowsFaster(longWindowsFaster);
                 if (packThreads > 0) engine.setHostThreads(packThreads);
                 if (!prepareOnly) engine.warmUp(size_t(batchWindows) * size_t(mergeBatches) * 8 * 200);     // while the first batches are being prepared
                 t_ready_of[size_t(ct)] = seconds_since(t_start);
@@ -542,6 +547,7 @@ int main(int argc, char **argv)
                         redo.engine->setThrowOnPositiveLikelihood(false);
                         redo.engine->setKeepAlignments(faster || realignedBAM);
                         redo.engine->setLongWindows(longWindows);
+                        redo.engine->setLongWindowsFaster(longWindowsFaster);
                     }
                     WindowJob J;
                     J.haps = T.haps; J.reads = &T.reads; J.leftPos = T.leftPos; J.rightPos = T.rightPos;

@@ -92,7 +92,7 @@ int ddh_rebuild_json(const char *hap, const char *read, const double *qual, cons
 static int compute_window_json(bool faster, const char *haps_nl, const char *reads_nl, const double *quals, const double *mapq,
                                const double *pos_first, const int *unmapped, unsigned leftPos, const double *pd, const int *pi,
                                int device, char *out, int cap, const int *mate = NULL, const double *lib_counts = NULL,
-                               const int *lib_sizes = NULL, int n_libs = 0, bool long_windows = false)
+                               const int *lib_sizes = NULL, int n_libs = 0, bool long_windows = false, bool long_windows_faster = false)
 {
     try {
         std::vector<Haplotype> haps;
@@ -129,6 +129,7 @@ static int compute_window_json(bool faster, const char *haps_nl, const char *rea
         LikelihoodEngine eng(prm, device);
         eng.setThrowOnPositiveLikelihood(true);
         eng.setLongWindows(long_windows);
+        eng.setLongWindowsFaster(long_windows_faster);
         std::vector<std::vector<MLAlignment> > liks;
         std::vector<int> onHap;
         if (faster) eng.computeLikelihoodsFaster(haps, reads, liks, leftPos, leftPos + 1, onHap);
@@ -162,6 +163,14 @@ int ddh_compute_window_long_json(const char *haps_nl, const char *reads_nl, cons
                                  int device, char *out, int cap)
 {
     return compute_window_json(false, haps_nl, reads_nl, quals, mapq, pos_first, unmapped, leftPos, pd, pi, device, out, cap, NULL, NULL, NULL, 0, true);
+}
+
+// computeLikelihoodsFaster with LikelihoodEngine::setLongWindowsFaster(true): the --faster model's long-window kernel
+int ddh_compute_window_faster_long_json(const char *haps_nl, const char *reads_nl, const double *quals, const double *mapq,
+                                        const double *pos_first, const int *unmapped, unsigned leftPos, const double *pd, const int *pi,
+                                        int device, char *out, int cap)
+{
+    return compute_window_json(true, haps_nl, reads_nl, quals, mapq, pos_first, unmapped, leftPos, pd, pi, device, out, cap, NULL, NULL, NULL, 0, false, true);
 }
 
 // computeLikelihoods with the insert-size prior (mapUnmappedReads; the reference's --libFile run)
@@ -353,7 +362,8 @@ void parse_windows(int W, const int *n_haps, const int *n_reads, const char *hap
 // Runs the windows twice through computeLikelihoodsBatch — once eager (the reference's containers), once lazy (views; with
 // flags bit1 also without alignments kept) — and reports, per window, the error string and the lazy view's scalars, plus the
 // number of pairs whose lazy view (every scalar accessor and the full record from get()) differs from the eager record.
-// flags: bit0 = --faster model, bit1 = setKeepAlignments(false) for the lazy run, bit2 = setLongWindows(true) for both runs.
+// flags: bit0 = --faster model, bit1 = setKeepAlignments(false) for the lazy run, bit2 = setLongWindows(true) for both runs,
+// bit3 = setLongWindowsFaster(true) for both runs.
 int ddh_batch_json(int W, const int *n_haps, const int *n_reads, const char *haps_nl, const char *reads_nl, const double *quals,
                    const double *mapq, const double *pos_first, const int *unmapped, const unsigned *leftPos, const double *pd,
                    const int *pi, int flags, int device, char *out, int cap)
@@ -365,6 +375,7 @@ int ddh_batch_json(int W, const int *n_haps, const int *n_reads, const char *hap
         LikelihoodEngine eng(make_params(pd, pi), device);
         eng.setThrowOnPositiveLikelihood(true);
         eng.setLongWindows((flags & 4) != 0);
+        eng.setLongWindowsFaster((flags & 8) != 0);
         std::vector<std::vector<std::vector<MLAlignment> > > liks(static_cast<size_t>(W));
         std::vector<std::vector<int> > onHap(static_cast<size_t>(W));
         std::vector<WindowJob> eager(static_cast<size_t>(W)), lazy(static_cast<size_t>(W));

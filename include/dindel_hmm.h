@@ -322,7 +322,8 @@ int dd_launch_device(const dd_params *p, const dd_device_batch *b, const dd_resu
 /* The main kernels cover haplotypes up to DD_MAX_HAP_LEN, reads up to DD_MAX_READ_LEN, and with maxLengthDel >= 12 haplotypes up to 574 bp.
  * With DD_OPT_LONG_WINDOWS a window outside those limits but inside DD_LONG_MAX_HAP_LEN / DD_LONG_MAX_READ_LEN (any maxLengthDel 0..31) is
  * computed by a kernel of its own (one workgroup per pair), launched after the main launch: the same outputs, bit for bit, as the main
- * kernels would give (main model only; the --faster model keeps skipping such windows).  Without the option nothing changes. */
+ * kernels would give (main model only; the --faster model has an option of its own, DD_OPT_LONG_WINDOWS_FASTER below).  Without the option
+ * nothing changes. */
 #define DD_OPT_LONG_WINDOWS 1u
 #define DD_WIN_MAIN 0          /* dd_screen_windows_ex classes */
 #define DD_WIN_UNSUPPORTED 1
@@ -365,6 +366,43 @@ int dd_long_launch_log(int64_t *out, int max_records);
 int dd_compute_likelihoods_faster(const dd_params *p, const dd_batch *b, dd_result *r, int device);
 int dd_compute_likelihoods_faster_multi(const dd_params *p, const dd_batch *b, dd_result *r, const int *devices, int n_devices);
 int dd_launch_device_faster(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *stream);
+
+/* ---- long windows of the --faster model (opt-in, separate from DD_OPT_LONG_WINDOWS) ------- */
+/* dd_faster_kernel covers haplotypes up to DD_MAX_HAP_LEN and reads up to DD_MAX_READ_LEN (its per-pair LDS area); the reference's model has
+ * no such limit.  With DD_OPT_LONG_WINDOWS_FASTER a window with a haplotype of 767..DD_LONG_MAX_HAP_LEN bp or a read of
+ * 1,025..DD_LONG_MAX_READ_LEN bp is computed by a kernel of its own (faster_long_kernel.hip: back-pointers and vote histogram in an HBM
+ * workspace), launched after the --faster main launch: the same outputs, bit for bit, as dd_faster_kernel's arithmetic gives.  Without the
+ * option nothing changes, and DD_OPT_LONG_WINDOWS has no effect on the --faster model.
+ *
+ * dd_screen_windows_ex with this bit classes the windows for the --faster model: DD_WIN_LONG as above, whatever maxLengthDel is (the
+ * 574-bp cap of the D = 32 build is a main-model matter) and whatever bytes the haplotypes hold (this model compares bytes); max_len_out[2..3]
+ * the long windows' maxima.  The classes are per model: both option bits together are DD_ERR_INVALID.
+ * Out of scope: dd_compute_likelihoods_faster_multi (long windows stay skipped there); mapUnmappedReads (this model has no insert-size prior). */
+#define DD_OPT_LONG_WINDOWS_FASTER 2u
+/* dd_compute_likelihoods_faster with options: 0 is dd_compute_likelihoods_faster; DD_OPT_LONG_WINDOWS_FASTER computes the long windows
+ * too; any other bit is DD_ERR_INVALID. */
+int dd_compute_likelihoods_faster_ex(const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options);
+/* Device-pointer path: b->win_skip = DEVICE copy of the classes dd_screen_windows_ex gave with DD_OPT_LONG_WINDOWS_FASTER,
+ * b->long_max_hap_len / long_max_read_len its max_len_out[2..3] (a dd_device_batch is screened for one model at a time).
+ * Workspace: a 256-byte header (item counter, counts, stats), the long windows' list and item offsets, then per workgroup of the persistent
+ * grid 16 tiles (one per pair in flight) of 16 B per read base + 2 B per diagonal.  The grid is the chip's resident workgroups (LDS-limited,
+ * at most 2 per CU) and no more than the batch can have items (n_haps x ceil(n_reads / 16)), shrunk so that the workspace stays within
+ * DD_FASTER_LONG_WS_BUDGET — never below one workgroup (the maximum shape needs 1.3 MiB per workgroup).  0 when there is no long window
+ * or a shape is beyond the limits.  Never shared by two launches that may run at the same time. */
+#define DD_FASTER_LONG_WS_BUDGET ((size_t)512 << 20)
+size_t dd_workspace_bytes_faster_long(const dd_params *p, const dd_device_batch *b);
+/* Enqueue the kernel for the DD_WIN_LONG windows on `stream`, AFTER dd_launch_device_faster on the same batch and stream: it overwrites
+ * its windows' placeholder outputs and (when r->onHap and r->offHapHMQ are given) their reads' onHap.  No-op without long windows; a
+ * workspace that is too small is DD_ERR_INVALID. */
+int dd_launch_device_faster_long(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+/* Every such launch of the last dd_launch_device_faster_long / dd_compute_likelihoods_faster_ex call on this host thread: records of
+ * DD_FASTER_LONG_LOG_FIELDS int64 {grid, pairs handled, most pairs one workgroup took, workspace bytes, most items one workgroup took,
+ * long windows' longest haplotype, longest read, LDS bytes per workgroup}.  The three counters are read from device memory (the workspace
+ * header, or the host path's own copy): this synchronises the launch's stream, and for dd_launch_device_faster_long the workspace must
+ * still be allocated.  Returns the number of launches. */
+#define DD_FASTER_LONG_LOG_FIELDS 8
+int dd_faster_long_launch_log(int64_t *out, int max_records);
 
 /* ---- N1 (next row): read sums of the diploid genotype reduction --------------------------- */
 /* S[w][h1*H_w+h2] (h1<=h2) = sum over the window's reads, in order, of log(0.5)+addLogs(ll[h1][r], ll[h2][r])
