@@ -235,26 +235,26 @@ def launch_log():
 
 
 LONG_LOG_FIELDS = ["grid", "pairs", "max_pairs_per_wg", "ws_bytes", "K", "max_hap", "max_read", "lds_block"]
+FASTER_LONG_LOG_FIELDS = ["grid", "pairs", "max_pairs_per_wg", "ws_bytes", "max_items_per_wg", "max_hap", "max_read", "lds_block"]
+
+
+def _launch_log(fn, fields):
+    """The records of one of the library's int64 launch logs as dicts."""
+    import numpy as np
+    buf = np.zeros((64, len(fields)), np.int64)
+    n = fn(buf.ctypes.data_as(c_i64p), 64)
+    return [dict(zip(fields, [int(v) for v in buf[i]])) for i in range(min(n, 64))]
 
 
 def long_launch_log():
     """Every long-window launch of the last dd_launch_device_long / dd_compute_likelihoods_ex call of this thread (dd_long_launch_log)."""
-    import numpy as np
-    buf = np.zeros((64, len(LONG_LOG_FIELDS)), np.int64)
-    n = load().dd_long_launch_log(buf.ctypes.data_as(c_i64p), 64)
-    return [dict(zip(LONG_LOG_FIELDS, [int(v) for v in buf[i]])) for i in range(min(n, 64))]
-
-
-FASTER_LONG_LOG_FIELDS = ["grid", "pairs", "max_pairs_per_wg", "ws_bytes", "max_items_per_wg", "max_hap", "max_read", "lds_block"]
+    return _launch_log(load().dd_long_launch_log, LONG_LOG_FIELDS)
 
 
 def faster_long_launch_log():
     """Every long-window launch of the --faster model in the last dd_launch_device_faster_long / dd_compute_likelihoods_faster_ex call of
     this thread (dd_faster_long_launch_log)."""
-    import numpy as np
-    buf = np.zeros((64, len(FASTER_LONG_LOG_FIELDS)), np.int64)
-    n = load().dd_faster_long_launch_log(buf.ctypes.data_as(c_i64p), 64)
-    return [dict(zip(FASTER_LONG_LOG_FIELDS, [int(v) for v in buf[i]])) for i in range(min(n, 64))]
+    return _launch_log(load().dd_faster_long_launch_log, FASTER_LONG_LOG_FIELDS)
 
 
 def screen_windows_ex(params, pb, options=DD_OPT_LONG_WINDOWS):
@@ -288,7 +288,8 @@ def kernel_source_id(kernel="dd_hmm_kernel"):
     bench.py quotes a file's HBM-traffic counters only for the kernel they were measured on."""
     import hashlib
     import re
-    files = ["hmm_kernel.h", "faster_kernel.hip" if "faster" in kernel else "hmm_kernel.hip"]
+    faster = ["faster_model.h", "faster_sstate.inc", "faster_pair_end.inc", "faster_kernel.hip"]
+    files = ["hmm_kernel.h"] + (faster if "faster" in kernel else ["hmm_kernel.hip"])
     h = hashlib.sha1()
     for f in files:                                # the code, not its comments or layout
         text = open(os.path.join(_HERE, "csrc", f), "r", errors="replace").read()

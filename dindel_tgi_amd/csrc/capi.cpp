@@ -1300,7 +1300,115 @@ static int launch_range(Model model, const dd_params *p, const dd_device_batch *
     return DD_SUCCESS;
 }
 
-// ---------------- long windows (long_kernel.hip) ----------------
+// The device address of [host, host + bytes) if that is page-locked host memory this device can address (dd_host_alloc, hipHostMalloc)
+// and its last byte belongs to the same registered range; else NULL.
+static void *mapped_device_ptr(const void *host, size_t bytes)
+{
+    if (!host || !bytes) return nullptr;
+    hipPointerAttribute_t a, e;
+    if (hipPointerGetAttributes(&a, host) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (a.type != hipMemoryTypeHost || !a.devicePointer) return nullptr;
+    if (hipPointerGetAttributes(&e, static_cast<const unsigned char *>(host) + bytes - 1) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (e.type != hipMemoryTypeHost || !e.devicePointer ||
+        static_cast<unsigned char *>(e.devicePointer) - static_cast<unsigned char *>(a.devicePointer) != (ptrdiff_t)(bytes - 1)) return nullptr;
+    return a.devicePointer;
+}
+
+// ---------------- long windows: what the two long paths share (long_kernel.hip for the main model, faster_long_kernel.hip for --faster) ----------------
+static_assert(DD_LONG_LOG_FIELDS == DD_FASTER_LONG_LOG_FIELDS, "one record type serves both logs");
+struct LongRec {
+    int64_t v[DD_LONG_LOG_FIELDS];
+    const unsigned long long *stats;     // device words the launch counts into
+    hipStream_t stream;
+};
+// One long path: its name in the error texts, its stats words and the log fields they fill, and this thread's launch log.
+struct LongPath {
+    const char *name, *ws_fn;
+    int n_stats, stat_field[4];          // stats word i -> log field stat_field[i] (-1: none); also the stride of compute_likelihoods' stats words per window block
+    int (*launch_range)(const dd_params *, const dd_device_batch *, const dd_result *, void *, size_t, void *, int, int, int, int, unsigned long long *);
+    size_t (*workspace_bytes)(const dd_params *, const dd_device_batch *);
+    std::vector<LongRec> log;
+};
+
+// header + window list + prefix list of a long workspace (kernel_common.h): where the prefix list and the tiles start
+static uint64_t al256(uint64_t v) { return (v + 255u) & ~(uint64_t)255u; }
+static void long_list_layout(int n_windows, uint64_t &off_prefix, uint64_t &off_tiles)
+{
+    off_prefix = al256(DD_LWS_HEADER + 4 * (uint64_t)std::max(n_windows, 1));
+    off_tiles = al256(off_prefix + 8 * (uint64_t)(std::max(n_windows, 0) + 1));
+}
+
+// The front checks of a long launch.  1: nothing to do (empty batch or range), 0: go on, < 0: error.
+static int long_front_checks(const LongPath &lp, const dd_params *p, const dd_device_batch *b, const dd_result *r, int w_begin, int w_end)
+{
+    int rc = check_params(p);
+    if (rc) return rc;
+    if (!b || !r || !r->ll || !r->status) return fail(DD_ERR_INVALID, "ll and status outputs are required");
+    if (b->long_max_hap_len <= 0 || b->long_max_read_len <= 0 || b->n_haps <= 0 || b->n_reads <= 0 || w_end <= w_begin) return 1;
+    if (!b->win_skip) return fail(DD_ERR_INVALID, std::string(lp.name) + ": win_skip must hold dd_screen_windows_ex's classes");
+    return 0;
+}
+
+// The fields LongArgs and FLArgs name alike, from the batch; the model's own (read_flags, sym_lut, mate / library arrays, D, bMid) stay with the caller.
+// ws_bytes: what the plan needs.  stats: the caller's device words, or NULL for the ones in the workspace header.
+extern "C++" template <class Args>
+static int long_fill_args(const LongPath &lp, Args &A, const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace,
+                          size_t workspace_bytes, uint64_t ws_bytes, int w_begin, int w_end, int read_begin, int read_end, unsigned long long *stats)
+{
+    if (!workspace || workspace_bytes < ws_bytes)
+        return fail(DD_ERR_INVALID, std::string("workspace too small for the ") + lp.name + ": allocate " + lp.ws_fn + "() bytes");
+    A.n_windows = b->n_windows; A.w_begin = w_begin; A.w_end = w_end; A.read_begin = read_begin; A.read_end = read_end;
+    A.win_hap_off = b->win_hap_off; A.win_read_off = b->win_read_off; A.win_hap_start = b->win_hap_start;
+    A.hap_seq_off = b->hap_seq_off; A.hap_seq = b->hap_seq; A.hap_var_off = b->hap_var_off; A.hap_var = b->hap_var; A.hap_var_flank = b->hap_var_flank;
+    A.read_seq_off = b->read_seq_off; A.read_seq = b->read_seq; A.read_qidx = b->read_qidx; A.read_mqidx = b->read_mqidx;
+    A.read_start = b->read_start;
+    A.win_pair_off = b->win_pair_off; A.win_hpos_off = b->win_hpos_off; A.win_varcov_off = b->win_varcov_off;
+    A.tables = b->tables; A.win_class = b->win_skip;
+    A.out = *r;
+    A.maxLengthDel = p->maxLengthDel; A.padCover = p->padCover; A.maxMismatch = p->maxMismatch;
+    A.ws = static_cast<unsigned char *>(workspace);
+    A.stats = stats ? stats : reinterpret_cast<unsigned long long *>(A.ws + DD_LWS_HDR_STATS);
+    return DD_SUCCESS;
+}
+
+// v: the record's fields, those of the stats words still -1
+static void long_log_push(LongPath &lp, const int64_t (&v)[DD_LONG_LOG_FIELDS], const unsigned long long *stats, hipStream_t st)
+{
+    LongRec rec;
+    memcpy(rec.v, v, sizeof(v));
+    rec.stats = stats;
+    rec.stream = st;
+    lp.log.push_back(rec);
+}
+
+// the records of a path's log; the stats words of a launch are read back (after its stream has drained) the first time they are asked for
+static int long_read_log(LongPath &lp, int64_t *out, int max_records)
+{
+    const int n = (int)lp.log.size();
+    for (int i = 0; i < n && i < max_records && out; i++) {
+        LongRec &r = lp.log[(size_t)i];
+        if (r.stats && r.v[1] < 0) {
+            unsigned long long st[4] = {0, 0, 0, 0};
+            if (hipStreamSynchronize(r.stream) == hipSuccess && hipMemcpy(st, r.stats, (size_t)lp.n_stats * sizeof(st[0]), hipMemcpyDeviceToHost) == hipSuccess) {
+                for (int k = 0; k < lp.n_stats; k++)
+                    if (lp.stat_field[k] >= 0) r.v[lp.stat_field[k]] = (int64_t)st[k];
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+        memcpy(out + (size_t)i * DD_LONG_LOG_FIELDS, r.v, sizeof(r.v));
+    }
+    return n;
+}
+
+static int launch_long_range(const dd_params *, const dd_device_batch *, const dd_result *, void *, size_t, void *, int, int, int, int, unsigned long long *);
+static int launch_faster_long_range(const dd_params *, const dd_device_batch *, const dd_result *, void *, size_t, void *, int, int, int, int, unsigned long long *);
+// stats: {pairs, most pairs of one workgroup} / {pairs, most pairs of one workgroup, most items of one workgroup, 0}
+static thread_local LongPath g_long = {"long path", "dd_workspace_bytes_long", 2, {1, 2, -1, -1}, launch_long_range, dd_workspace_bytes_long, {}};
+static thread_local LongPath g_flong = {"--faster long path", "dd_workspace_bytes_faster_long", 4, {1, 2, 4, -1}, launch_faster_long_range,
+                                        dd_workspace_bytes_faster_long, {}};
+
+// ---------------- long windows of the main model (long_kernel.hip) ----------------
 // Plan of a long launch: K states per thread (numS <= 256 K, K = 1, 2, 4, 8, 16), LDS, and the persistent grid: the chip's resident
 // workgroups (LDS- and register-limited: 2 per CU, 1 at K = 16), shrunk so that header + lists + one back-pointer tile per workgroup stay
 // within DD_LONG_WS_BUDGET.
@@ -1316,10 +1424,8 @@ static int long_plan(int n_windows, int max_hap_len, int max_read_len, int n_qua
     lp.lds = ddl::long_lds_layout(lp.K, max_read_len, A);
     if (lp.lds + 64 > 160u * 1024u) return fail(DD_ERR_UNSUPPORTED, "long path: LDS layout too large");
     const unsigned per_cu = std::max(1u, std::min(lp.K >= 16 ? 1u : 2u, (unsigned)((160u * 1024u) / (lp.lds + 64))));
-    auto al = [](uint64_t v) { return (v + 255u) & ~(uint64_t)255u; };
-    lp.off_lpoff = al(DD_LONG_WS_HEADER + 4 * (uint64_t)std::max(n_windows, 1));
-    lp.off_tiles = al(lp.off_lpoff + 8 * (uint64_t)(n_windows + 1));
-    lp.stash_off = al((uint64_t)max_read_len * DD_LONG_THREADS * lp.K);
+    long_list_layout(n_windows, lp.off_lpoff, lp.off_tiles);
+    lp.stash_off = al256((uint64_t)max_read_len * DD_LONG_THREADS * lp.K);
     lp.tile_bytes = lp.stash_off + 16 * (uint64_t)DD_LONG_THREADS * lp.K;
     uint64_t grid = 256u * per_cu;
     const uint64_t fit = DD_LONG_WS_BUDGET > lp.off_tiles ? (DD_LONG_WS_BUDGET - lp.off_tiles) / lp.tile_bytes : 0;
@@ -1330,56 +1436,32 @@ static int long_plan(int n_windows, int max_hap_len, int max_read_len, int n_qua
     return DD_SUCCESS;
 }
 
-struct LongRec {
-    int64_t v[DD_LONG_LOG_FIELDS];
-    const unsigned long long *stats;     // device: {pairs, most pairs of one workgroup}
-    hipStream_t stream;
-};
-static thread_local std::vector<LongRec> g_long_log;
-
 // one long launch over the windows [w_begin, w_end) (their reads: [read_begin, read_end)); stats: device words the kernel counts into
 static int launch_long_range(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes,
                              void *stream, int w_begin, int w_end, int read_begin, int read_end, unsigned long long *stats)
 {
-    int rc = check_params(p);
-    if (rc) return rc;
-    if (!b || !r || !r->ll || !r->status) return fail(DD_ERR_INVALID, "ll and status outputs are required");
-    if (b->long_max_hap_len <= 0 || b->long_max_read_len <= 0 || b->n_haps <= 0 || b->n_reads <= 0 || w_end <= w_begin) return DD_SUCCESS;
-    if (!b->win_skip) return fail(DD_ERR_INVALID, "long path: win_skip must hold dd_screen_windows_ex's classes");
+    int rc = long_front_checks(g_long, p, b, r, w_begin, w_end);
+    if (rc) return rc < 0 ? rc : DD_SUCCESS;
     ddl::LongArgs A;
     memset(&A, 0, sizeof(A));
     LongPlan lp;
     if ((rc = long_plan(b->n_windows, b->long_max_hap_len, b->long_max_read_len, b->n_qual, lp, A))) return rc;
-    if (!workspace || workspace_bytes < lp.ws_bytes)
-        return fail(DD_ERR_INVALID, "workspace too small for the long path: allocate dd_workspace_bytes_long() bytes");
-    A.n_windows = b->n_windows; A.w_begin = w_begin; A.w_end = w_end; A.read_begin = read_begin; A.read_end = read_end;
-    A.win_hap_off = b->win_hap_off; A.win_read_off = b->win_read_off; A.win_hap_start = b->win_hap_start;
-    A.hap_seq_off = b->hap_seq_off; A.hap_seq = b->hap_seq; A.hap_var_off = b->hap_var_off; A.hap_var = b->hap_var; A.hap_var_flank = b->hap_var_flank;
-    A.read_seq_off = b->read_seq_off; A.read_seq = b->read_seq; A.read_qidx = b->read_qidx; A.read_mqidx = b->read_mqidx;
-    A.read_start = b->read_start; A.read_flags = b->read_flags;
-    A.win_pair_off = b->win_pair_off; A.win_hpos_off = b->win_hpos_off; A.win_varcov_off = b->win_varcov_off;
-    A.tables = b->tables; A.sym_lut = b->sym_lut; A.win_class = b->win_skip;
+    if ((rc = long_fill_args(g_long, A, p, b, r, workspace, workspace_bytes, lp.ws_bytes, w_begin, w_end, read_begin, read_end, stats))) return rc;
+    A.read_flags = b->read_flags; A.sym_lut = b->sym_lut;
     if (p->mapUnmappedReads) {
         if (!b->read_mate_pos || !b->read_mate_len || !b->read_lib || !b->lib_off || !b->lib_logprob || !b->lib_log95)
             return fail(DD_ERR_INVALID, "mapUnmappedReads needs the mate arrays and the library log tables");
         A.read_mate_pos = b->read_mate_pos; A.read_mate_len = b->read_mate_len; A.read_lib = b->read_lib;
         A.lib_off = b->lib_off; A.lib_logprob = b->lib_logprob; A.lib_log95 = b->lib_log95;
     }
-    A.out = *r;
-    A.D = p->maxLengthDel + 1; A.maxLengthDel = p->maxLengthDel; A.padCover = p->padCover; A.bMid = p->bMid; A.maxMismatch = p->maxMismatch;
+    A.D = p->maxLengthDel + 1; A.bMid = p->bMid;
     A.max_read_len = b->long_max_read_len;
-    A.ws = static_cast<unsigned char *>(workspace);
-    A.stats = stats ? stats : reinterpret_cast<unsigned long long *>(A.ws + DD_LONG_HDR_STATS);
     A.off_lpoff = lp.off_lpoff; A.off_tiles = lp.off_tiles; A.tile_bytes = lp.tile_bytes; A.stash_off = lp.stash_off;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool onhap = r->onHap && r->offHapHMQ;
     HIP_TRY(ddl::launch_long(lp.K, A, lp.grid, lp.lds, onhap, st));
-    LongRec rec;
     const int64_t v[DD_LONG_LOG_FIELDS] = {(int64_t)lp.grid, -1, -1, (int64_t)lp.ws_bytes, lp.K, b->long_max_hap_len, b->long_max_read_len, (int64_t)lp.lds};
-    memcpy(rec.v, v, sizeof(v));
-    rec.stats = A.stats;
-    rec.stream = st;
-    g_long_log.push_back(rec);
+    long_log_push(g_long, v, A.stats, st);
     return DD_SUCCESS;
 }
 
@@ -1396,29 +1478,12 @@ size_t dd_workspace_bytes_long(const dd_params *p, const dd_device_batch *b)
 
 int dd_launch_device_long(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes, void *stream)
 {
-    g_long_log.clear();
+    g_long.log.clear();
     if (!b) return fail(DD_ERR_INVALID, "null batch");
     return launch_long_range(p, b, r, workspace, workspace_bytes, stream, 0, b->n_windows, 0, b->n_reads, nullptr);
 }
 
-int dd_long_launch_log(int64_t *out, int max_records)
-{   // see include/dindel_hmm.h
-    const int n = (int)g_long_log.size();
-    for (int i = 0; i < n && i < max_records && out; i++) {
-        LongRec &r = g_long_log[(size_t)i];
-        if (r.stats && r.v[1] < 0) {
-            unsigned long long st[2] = {0, 0};
-            if (hipStreamSynchronize(r.stream) == hipSuccess && hipMemcpy(st, r.stats, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess) {
-                r.v[1] = (int64_t)st[0];
-                r.v[2] = (int64_t)st[1];
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-        memcpy(out + (size_t)i * DD_LONG_LOG_FIELDS, r.v, sizeof(r.v));
-    }
-    return n;
-}
+int dd_long_launch_log(int64_t *out, int max_records) { return long_read_log(g_long, out, max_records); }   // see include/dindel_hmm.h
 
 // ---------------- long windows of the --faster model (faster_long_kernel.hip) ----------------
 // Plan of a launch: LDS for the shape, and the persistent grid: the chip's resident workgroups (LDS-limited, at most 2 per CU: the kernel is
@@ -1435,9 +1500,7 @@ static int fl_plan(const dd_device_batch *b, FLPlan &fp, ddf::FLArgs &A)
     fp.lds = ddf::fl_lds_layout(mh, mr, A);
     if (fp.lds + 64 > 160u * 1024u) return fail(DD_ERR_UNSUPPORTED, "--faster long path: LDS layout too large");
     const unsigned per_cu = std::max(1u, std::min(2u, (unsigned)((160u * 1024u) / (fp.lds + 64))));
-    auto al = [](uint64_t v) { return (v + 255u) & ~(uint64_t)255u; };
-    fp.off_ioff = al(DD_FL_WS_HEADER + 4 * (uint64_t)std::max(b->n_windows, 1));
-    fp.off_tiles = al(fp.off_ioff + 8 * (uint64_t)(std::max(b->n_windows, 0) + 1));
+    long_list_layout(b->n_windows, fp.off_ioff, fp.off_tiles);
     const uint64_t wg_bytes = DD_FL_PAIRS * ddf::fl_tile_layout(mh, mr, A);
     uint64_t grid = 256u * per_cu;
     const uint64_t items = (uint64_t)std::max(b->n_haps, 0) * (((uint64_t)std::max(b->n_reads, 0) + DD_FL_PAIRS - 1) / DD_FL_PAIRS);
@@ -1451,47 +1514,21 @@ static int fl_plan(const dd_device_batch *b, FLPlan &fp, ddf::FLArgs &A)
     return DD_SUCCESS;
 }
 
-struct FLRec {
-    int64_t v[DD_FASTER_LONG_LOG_FIELDS];
-    const unsigned long long *stats;     // device: {pairs, most pairs of one workgroup, most items of one workgroup, 0}
-    hipStream_t stream;
-};
-static thread_local std::vector<FLRec> g_fl_log;
-
 // one launch over the windows [w_begin, w_end) (their reads: [read_begin, read_end)); stats: 4 device words the kernel counts into
 static int launch_faster_long_range(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes,
                                     void *stream, int w_begin, int w_end, int read_begin, int read_end, unsigned long long *stats)
 {
-    int rc = check_params(p);
-    if (rc) return rc;
-    if (!b || !r || !r->ll || !r->status) return fail(DD_ERR_INVALID, "ll and status outputs are required");
-    if (b->long_max_hap_len <= 0 || b->long_max_read_len <= 0 || b->n_haps <= 0 || b->n_reads <= 0 || w_end <= w_begin) return DD_SUCCESS;
-    if (!b->win_skip) return fail(DD_ERR_INVALID, "--faster long path: win_skip must hold dd_screen_windows_ex's classes");
+    int rc = long_front_checks(g_flong, p, b, r, w_begin, w_end);
+    if (rc) return rc < 0 ? rc : DD_SUCCESS;
     ddf::FLArgs A;
     memset(&A, 0, sizeof(A));
     FLPlan fp;
     if ((rc = fl_plan(b, fp, A))) return rc;
-    if (!workspace || workspace_bytes < fp.ws_bytes)
-        return fail(DD_ERR_INVALID, "workspace too small for the --faster long path: allocate dd_workspace_bytes_faster_long() bytes");
-    A.n_windows = b->n_windows; A.w_begin = w_begin; A.w_end = w_end; A.read_begin = read_begin; A.read_end = read_end;
-    A.win_hap_off = b->win_hap_off; A.win_read_off = b->win_read_off; A.win_hap_start = b->win_hap_start;
-    A.hap_seq_off = b->hap_seq_off; A.hap_seq = b->hap_seq; A.hap_var_off = b->hap_var_off; A.hap_var = b->hap_var; A.hap_var_flank = b->hap_var_flank;
-    A.read_seq_off = b->read_seq_off; A.read_seq = b->read_seq; A.read_qidx = b->read_qidx; A.read_mqidx = b->read_mqidx;
-    A.read_start = b->read_start;
-    A.win_pair_off = b->win_pair_off; A.win_hpos_off = b->win_hpos_off; A.win_varcov_off = b->win_varcov_off;
-    A.tables = b->tables; A.win_class = b->win_skip;
-    A.out = *r;
-    A.maxLengthDel = p->maxLengthDel; A.padCover = p->padCover; A.maxMismatch = p->maxMismatch;
-    A.ws = static_cast<unsigned char *>(workspace);
-    A.stats = stats ? stats : reinterpret_cast<unsigned long long *>(A.ws + DD_FL_HDR_STATS);
+    if ((rc = long_fill_args(g_flong, A, p, b, r, workspace, workspace_bytes, fp.ws_bytes, w_begin, w_end, read_begin, read_end, stats))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_TRY(ddf::launch_faster_long(A, fp.grid, fp.lds, r->onHap && r->offHapHMQ, st));
-    FLRec rec;
     const int64_t v[DD_FASTER_LONG_LOG_FIELDS] = {(int64_t)fp.grid, -1, -1, (int64_t)fp.ws_bytes, -1, b->long_max_hap_len, b->long_max_read_len, (int64_t)fp.lds};
-    memcpy(rec.v, v, sizeof(v));
-    rec.stats = A.stats;
-    rec.stream = st;
-    g_fl_log.push_back(rec);
+    long_log_push(g_flong, v, A.stats, st);
     return DD_SUCCESS;
 }
 
@@ -1508,30 +1545,12 @@ size_t dd_workspace_bytes_faster_long(const dd_params *p, const dd_device_batch 
 
 int dd_launch_device_faster_long(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes, void *stream)
 {
-    g_fl_log.clear();
+    g_flong.log.clear();
     if (!b) return fail(DD_ERR_INVALID, "null batch");
     return launch_faster_long_range(p, b, r, workspace, workspace_bytes, stream, 0, b->n_windows, 0, b->n_reads, nullptr);
 }
 
-int dd_faster_long_launch_log(int64_t *out, int max_records)
-{   // see include/dindel_hmm.h
-    const int n = (int)g_fl_log.size();
-    for (int i = 0; i < n && i < max_records && out; i++) {
-        FLRec &r = g_fl_log[(size_t)i];
-        if (r.stats && r.v[1] < 0) {
-            unsigned long long st[4] = {0, 0, 0, 0};
-            if (hipStreamSynchronize(r.stream) == hipSuccess && hipMemcpy(st, r.stats, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess) {
-                r.v[1] = (int64_t)st[0];
-                r.v[2] = (int64_t)st[1];
-                r.v[4] = (int64_t)st[2];
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-        memcpy(out + (size_t)i * DD_FASTER_LONG_LOG_FIELDS, r.v, sizeof(r.v));
-    }
-    return n;
-}
+int dd_faster_long_launch_log(int64_t *out, int max_records) { return long_read_log(g_flong, out, max_records); }   // see include/dindel_hmm.h
 
 int dd_plan_info(const dd_params *p, int max_hap_len, int max_read_len, int n_qual, int avg_reads, int n_haps, int32_t out[10])
 {
@@ -1788,8 +1807,8 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
 {
     StageClock clk;
     launch_log_clear();
-    g_long_log.clear();
-    g_fl_log.clear();
+    g_long.log.clear();
+    g_flong.log.clear();
     int rc = check_params(p);
     if (rc) return rc;
     if (!r || !r->ll || !r->status) return fail(DD_ERR_INVALID, "ll and status outputs are required");
@@ -1819,6 +1838,7 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
     // (DD_OPT_LONG_WINDOWS_FASTER: the same for the --faster model, with its own classes and its own kernel)
     const bool fl_on = model == MODEL_S && (options & DD_OPT_LONG_WINDOWS_FASTER);
     const bool long_on = (model == MODEL_FBMAXERR && (options & DD_OPT_LONG_WINDOWS)) || fl_on;
+    LongPath &long_path = fl_on ? g_flong : g_long;           // the model's long path (used only if long_on)
     int32_t long_max[4] = {0, 0, 0, 0};
     int n_skip;
     if (long_on) {
@@ -1895,7 +1915,7 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
     size_t lws_bytes = 0;                                   // long path: its own workspace per stream
     if (long_on && long_max[2] > 0) {
         db.long_max_hap_len = long_max[2]; db.long_max_read_len = long_max[3];
-        lws_bytes = fl_on ? dd_workspace_bytes_faster_long(p, &db) : dd_workspace_bytes_long(p, &db);
+        lws_bytes = long_path.workspace_bytes(p, &db);
         if (!lws_bytes) return fail(DD_ERR_UNSUPPORTED, "long path: no plan for this shape");
     }
 
@@ -1934,17 +1954,8 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
         // ~80 MB per 256-window batch at 8 haplotypes — instead of waiting for a staged copy whose blit kernels share the CUs with the
         // batch that is running (profiles/r03/window_loop_timeline.txt).  DD_ZERO_COPY_IN=0 switches it off (A/B).
         static const bool zero_copy_in = !(getenv("DD_ZERO_COPY_IN") && !strcmp(getenv("DD_ZERO_COPY_IN"), "0"));
-        auto mapped_in = [&](const void *host, size_t bytes) -> const void * {
-            if (!zero_copy_in || !host || !bytes) return nullptr;
-            hipPointerAttribute_t a, e;
-            if (hipPointerGetAttributes(&a, host) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-            if (a.type != hipMemoryTypeHost || !a.devicePointer) return nullptr;
-            if (hipPointerGetAttributes(&e, static_cast<const unsigned char *>(host) + bytes - 1) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-            if (e.type != hipMemoryTypeHost || !e.devicePointer ||
-                static_cast<unsigned char *>(e.devicePointer) - static_cast<unsigned char *>(a.devicePointer) != (ptrdiff_t)(bytes - 1)) return nullptr;
-            return a.devicePointer;
-        };
-        const void *ms = mapped_in(b->read_seq, (size_t)sz.read_bases), *mq = mapped_in(b->read_qidx, (size_t)sz.read_bases);
+        const void *ms = zero_copy_in ? mapped_device_ptr(b->read_seq, (size_t)sz.read_bases) : nullptr;
+        const void *mq = zero_copy_in ? mapped_device_ptr(b->read_qidx, (size_t)sz.read_bases) : nullptr;
         if (ms && mq) { db.read_seq = static_cast<const char *>(ms); db.read_qidx = static_cast<const uint8_t *>(mq); }
         else { UP(read_seq, sz.read_bases); UP(read_qidx, sz.read_bases); }
     }
@@ -1984,23 +1995,12 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
     // 300 ms of such kernels on the CUs beside 410 ms of HMM kernels for configs[1].)  status and offHapHMQ stay in HBM: the
     // onHap kernel reads them back.  DD_ZERO_COPY=0 switches this off (A/B).
     static const bool zero_copy_on = !(getenv("DD_ZERO_COPY") && !strcmp(getenv("DD_ZERO_COPY"), "0"));
-    auto mapped = [&](void *host, size_t bytes) -> void * {
-        if (!zero_copy_on || !host || !bytes) return nullptr;
-        hipPointerAttribute_t a;
-        if (hipPointerGetAttributes(&a, host) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        if (a.type != hipMemoryTypeHost || !a.devicePointer) return nullptr;
-        hipPointerAttribute_t e;                                   // the last byte belongs to the same registered range
-        if (hipPointerGetAttributes(&e, static_cast<unsigned char *>(host) + bytes - 1) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        if (e.type != hipMemoryTypeHost || !e.devicePointer ||
-            static_cast<unsigned char *>(e.devicePointer) - static_cast<unsigned char *>(a.devicePointer) != (ptrdiff_t)(bytes - 1)) return nullptr;
-        return a.devicePointer;
-    };
     struct { bool ll, llOn, llOff, mLogBQ, offHap, numIndels, numMismatch, nBQT, nmmBQT, nMMLeft, nMMRight, firstBase, lastBase, hpos, var_covered,
              status, onHap, var_fcov, offHapHMQ; } direct;
     memset(&direct, 0, sizeof(direct));
     int n_direct = 0;
 #define OUT(field, n) if (r->field) { \
-        void *m = mapped(r->field, (size_t)(n) * sizeof(*r->field)); \
+        void *m = zero_copy_on ? mapped_device_ptr(r->field, (size_t)(n) * sizeof(*r->field)) : nullptr; \
         if (m) { dr.field = static_cast<decltype(dr.field)>(m); direct.field = true; n_direct++; } \
         else if ((rc = dev.alloc(&dr.field, (size_t)(n)))) return rc; }
 #define OUT_DEVICE(field, n) if (r->field && (rc = dev.alloc(&dr.field, (size_t)(n)))) return rc
@@ -2018,11 +2018,11 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
         if (ws_bytes && (rc = dev.alloc(&ws[i], ws_bytes))) return rc;
     struct { hipStream_t s[2]; } streams = {{ctx.s[0], ctx.s[1]}};
     unsigned char *lws[2] = {nullptr, nullptr};
-    unsigned long long *long_stats = nullptr;               // 2 words per window block's long launch
+    unsigned long long *long_stats = nullptr;               // long_path.n_stats (2 or 4) words per window block's long launch
     if (lws_bytes) {
         for (int i = 0; i < 2; i++)
             if ((rc = dev.alloc(&lws[i], lws_bytes))) return rc;
-        if ((rc = dev.alloc(&long_stats, (size_t)4 * 64))) return rc;      // (4 words per block for the --faster model's launch)
+        if ((rc = dev.alloc(&long_stats, (size_t)4 * 64))) return rc;      // 64 blocks at most, 4 words at most
     }
 
     // Chunked, double-buffered execution: contiguous window blocks alternate between two streams, and the D2H
@@ -2089,9 +2089,7 @@ static int compute_likelihoods_impl(Model model, const dd_params *p, const dd_ba
         if (lws_bytes) {
             bool any = false;
             for (int w = w0; w < w1 && !any; w++) any = win_skip[(size_t)w] == DD_WIN_LONG;
-            if (any && fl_on) {
-                if ((rc = launch_faster_long_range(p, &db, &dr, lws[c & 1], lws_bytes, streams.s[c & 1], w0, w1, q0, q1, long_stats + 4 * c))) return rc;
-            } else if (any && (rc = launch_long_range(p, &db, &dr, lws[c & 1], lws_bytes, streams.s[c & 1], w0, w1, q0, q1, long_stats + 2 * c))) return rc;
+            if (any && (rc = long_path.launch_range(p, &db, &dr, lws[c & 1], lws_bytes, streams.s[c & 1], w0, w1, q0, q1, long_stats + long_path.n_stats * c))) return rc;
         }
         if (!staged && c > 0 && (rc = download(c - 1))) return rc;
     }

@@ -23,60 +23,15 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <stdint.h>
-#include <type_traits>
 #include "hmm_kernel.h"
+#include "kernel_common.h"
+#include "faster_model.h"   // the model itself: helpers, SStateHMM, the end of a pair
 
 namespace ddk {
 
-#define FAST_EPS 1e-7
+using namespace ddfm;
+
 #define FAST_CHUNK 256   /* reads ordered at a time (capi.cpp sizes the LDS for it) */
-#define FNEG_INF (-__builtin_huge_val())
-
-__device__ __forceinline__ int fast_map_char(unsigned c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 0; }
-
-// LDS traffic between lanes of one wavefront: DS operations of a wave execute in order; this only pins the compiler.
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// wave-uniform maximum of a value that is uniform inside each 16-lane group
-__device__ __forceinline__ int gmax4(int v)
-{
-    const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
-    const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
-    const int ab = a > b ? a : b, cd = c > d ? c : d;
-    return ab > cd ? ab : cd;
-}
-
-// bMid — ObservationModelS::computeBMid (Faster.cpp:60-88)
-__device__ __forceinline__ int fast_bmid(uint32_t hapStart, int hlen, uint32_t mReadStart, int L)
-{
-    const uint32_t hapEnd = hapStart + (uint32_t)hlen;
-    const uint32_t readEnd = mReadStart + (uint32_t)L - 1u;
-    int bMid;
-    if (mReadStart > hapEnd) bMid = 0;
-    else if (readEnd < hapStart) bMid = L - 1;
-    else {
-        const uint32_t olStart = (hapStart > mReadStart) ? hapStart : mReadStart;
-        const uint32_t olEnd = (hapEnd > readEnd) ? readEnd : hapEnd;
-        bMid = ((int)olEnd - (int)olStart) / 2 + (int)olStart - (int)mReadStart;
-    }
-    if (bMid < 0) bMid = 0;
-    if (bMid >= L) bMid = L - 1;
-    return bMid;
-}
-
-// `if (nv > cur + EPS) { cur = nv; bp = code; }` (Faster.cpp:383 and every other update of the model)
-#define FOLD(cur, bp, nvv, code, ok)                         \
-    do {                                                     \
-        const double nv__ = (nvv);                           \
-        const bool t__ = (ok) && nv__ > (cur) + FAST_EPS;    \
-        (cur) = t__ ? nv__ : (cur);                          \
-        (bp) = t__ ? (code) : (bp);                          \
-    } while (0)
 
 // 2 waves per SIMD: the 16-source loops want ~200 VGPRs; one more resident wave costs spills inside them, one fewer
 // leaves the LDS round trips of a read base exposed (measured 277 -> 160 ms at 4000 windows going from 1 to 2).
@@ -144,7 +99,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         __syncthreads();
         for (int hx = tid; hx < hlen - 4; hx += blockDim.x) {
             int key = 0;
-            for (int y = 0; y < 4; y++) key |= fast_map_char(shHap[hx + y]) << (2 * y);
+            for (int y = 0; y < 4; y++) key |= map_char(shHap[hx + y]) << (2 * y);
             atomicAdd(&cnt[key], 1);
         }
         __syncthreads();
@@ -163,7 +118,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         __syncthreads();
         for (int hx = tid; hx < hlen - 4; hx += blockDim.x) {
             int key = 0;
-            for (int y = 0; y < 4; y++) key |= fast_map_char(shHap[hx + y]) << (2 * y);
+            for (int y = 0; y < 4; y++) key |= map_char(shHap[hx + y]) << (2 * y);
             hpl[atomicAdd(&cnt[key], 1)] = (uint16_t)hx;
         }
         __syncthreads();
@@ -177,7 +132,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         for (int t = tid; t < nch; t += blockDim.x) {
             const int rr = r0 + cb + t;
             const int L = P.read_seq_off[rr + 1] - P.read_seq_off[rr];
-            skey[t] = ((uint32_t)fast_bmid(hapStart, hlen, P.read_start[rr], L) << 11) | (uint32_t)(L > 0 ? ((L - 1) & 2047) : 0);
+            skey[t] = ((uint32_t)bmid(hapStart, hlen, P.read_start[rr], L) << 11) | (uint32_t)(L > 0 ? ((L - 1) & 2047) : 0);
             // Outputs this model leaves at MLAlignment's defaults, written here coalesced over the chunk's pairs instead of
             // pair by pair from the group leaders (which go in bMid order).  A pair the reference throws for is finished here.
             const int64_t pair = pair_base + cb + t;
@@ -227,7 +182,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
             const int L = good ? Lraw : 0;
             if (__ballot(good) == 0) continue;
 
-            const int bMid = good ? fast_bmid(hapStart, hlen, P.read_start[rr], L) : 0;
+            const int bMid = good ? bmid(hapStart, hlen, P.read_start[rr], L) : 0;
             // stage the read, clear the vote histogram (bin index rpfb + L, rpfb in [-(L-4), hlen-5])
             const int F = L + hlen;
             for (int b = l16; b < L; b += 16)
@@ -237,7 +192,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
             // AlignHash (Faster.cpp:131-189): every read 4-mer votes for the diagonals of the equal haplotype 4-mers
             for (int x = l16; x <= L - 4; x += 16) {
                 int key = 0;
-                for (int y = 0; y < 4; y++) key |= fast_map_char(rd[x + y] & 0xFF) << (2 * y);
+                for (int y = 0; y < 4; y++) key |= map_char(rd[x + y] & 0xFF) << (2 * y);
                 const int e = bk[key + 1];
                 for (int p = bk[key]; p < e; p++) {
                     const int idx = (int)hpl[p] - x + L;
@@ -293,162 +248,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
             const int relMine = srt[l16];
             const bool act = good && l16 < S;
             const int Smax = gmax4(S);
-            const int code0 = l16, code1 = l16 | 16;
-            const int wI = 32 - __clz(l16 + 1);          // bits of the inserted-state field of bt_right: values 0..own+1
-
-            // ---------------- SStateHMM (:253-576) ----------------
-            auto emis = [&](int r, double &LM, double &ob) {            // logMatch[r] and obs[r][own diagonal] (:286-296)
-                const unsigned v = rd[r];
-                const double2 q = qt[v >> 8];
-                const int hp = relMine + r;
-                LM = q.x;
-                ob = (hp >= 0 && hp < hlen && (unsigned)shHap[hp] != (v & 0xFFu)) ? q.y : q.x;
-            };
-            // Transition terms between every source diagonal cs and this lane's diagonal (:339-352) are loop constants.
-            // A term that does not apply to this lane (wrong side of the diagonal order) is -inf, so the candidate it
-            // produces is -inf and can never pass `nv > cur + EPS`: no lane masks in the inner loops.
-            // Sources beyond the pair's S publish -inf, so the source loops may run to the next multiple of 4 of the
-            // wave's largest S: four fully unrolled instances, no per-source bounds checks.
-            double aN = 0.0, aI = 0.0;                  // previous base's values of this diagonal (0 at the read end)
-            double leftN = 0.0, leftI = 0.0;
-            auto passes = [&](auto nsc) {
-                constexpr int NS = decltype(nsc)::value;
-                int lv = l16;                               // opaque copy: keeps the per-source selects below from being hoisted
-                asm volatile("" : "+v"(lv));                // out of the read loop as 2 x 16 spilled lane constants
-            // from left to bMid (:373-416)
-            {
-                double tA[NS], tB[NS];
-                int dL[NS];
-#pragma unroll
-                for (int cs = 0; cs < NS; cs++) {
-                    const int df = srt[cs] - relMine;
-                    const double trI = (fabs((double)df) - 1.0) * IIf;
-                    tA[cs] = (cs < lv) ? trI + lE : (cs == lv ? l1mE : FNEG_INF);   // on-diagonal source cs <= own (:380-384)
-                    tB[cs] = (cs > lv) ? trI : FNEG_INF;                              // inserted source cs > own (:404-411)
-                    dL[cs] = (cs > lv) ? df : 0x7fffffff;                             // its condition relPos[cs]-r >= relPos[ns]
-                    asm volatile("" : "+v"(tA[cs]), "+v"(tB[cs]), "+v"(dL[cs]));           // keep them as plain register constants
-                }
-                const int rows = gmax4(bMid);
-                double LMn = 0.0, obn = 0.0;
-                if (act && bMid > 0) emis(0, LMn, obn);
-                for (int r = 0; r < rows; r++) {
-                    const bool rowact = act && r < bMid;
-                    const double LM = LMn, ob = obn;
-                    const double pvOwn = ob + aN;
-                    bc[l16] = rowact ? make_double2(pvOwn, aI) : make_double2(FNEG_INF, FNEG_INF);
-                    wave_sync();
-                    if (act && r + 1 < bMid) emis(r + 1, LMn, obn);
-                    double curN = -1000.0, curI = -1000.0;
-                    int bpN = 0, bpI = 32;                                      // untouched = the reference's bt 0: on-diagonal state of diagonal 0
-#pragma unroll
-                    for (int cs = 0; cs < NS; cs++) {
-                        {
-                            const double2 s = bc[cs];
-                            const double vA = s.x + tA[cs];
-                            const double vB = ((LM + tB[cs]) + lE) + s.y;
-                            FOLD(curN, bpN, fmax(vA, vB), cs, dL[cs] >= r);
-                        }
-                    }
-                    FOLD(curI, bpI, pvOwn + NIf, code0, true);                   // (:387-391)
-                    FOLD(curI, bpI, (LM + IIf) + aI, code1, true);               // (:396-400)
-                    if (rowact) {
-                        bt[r * 16 + l16] = (unsigned char)(bpN | (bpI & 48));   // bt_left: bits 0-3 source diagonal of the on-diagonal state (a source above the own diagonal is its inserted state); bit 4: the inserted state came from itself, bit 5: it was never set
-                        aN = curN; aI = curI;
-                    }
-                    wave_sync();
-                }
-            }
-            leftN = aN; leftI = aI;                     // alpha[bMid-1] (0 if bMid == 0)
-            // from right to bMid (:422-466)
-            aN = 0.0; aI = 0.0;
-            {
-                double tD[NS], tA[NS];
-                int dR[NS];
-#pragma unroll
-                for (int cs = 0; cs < NS; cs++) {
-                    const int df = srt[cs] - relMine;
-                    const double trI = (fabs((double)df) - 1.0) * IIf;
-                    tD[cs] = (cs < lv) ? trI : FNEG_INF;                  // into the inserted state of a higher diagonal (:453-461)
-                    tA[cs] = (cs > lv) ? trI + lE : FNEG_INF;             // on-diagonal source cs > own (:427-431); own: below
-                    dR[cs] = df;                                           // condition relPos[cs] > relPos[ns]-r
-                    asm volatile("" : "+v"(tD[cs]), "+v"(tA[cs]), "+v"(dR[cs]));
-                }
-                const int rows = gmax4(L - 1 - bMid);
-                double LMn = 0.0, obn = 0.0;
-                if (act && bMid < L - 1) emis(L - 1, LMn, obn);
-                for (int k = 0; k < rows; k++) {
-                    const int r = L - 1 - k;
-                    const bool rowact = act && r > bMid;
-                    const double LM = LMn, ob = obn;
-                    bc[l16] = rowact ? make_double2(ob, aN) : make_double2(FNEG_INF, 0.0);
-                    wave_sync();
-                    if (act && r - 1 > bMid) emis(r - 1, LMn, obn);
-                    double curN = -1000.0, curI = -1000.0;
-                    int bpN = -1, bpI = -1;                                     // untouched = the reference's bt 0
-                    FOLD(curN, bpN, (ob + aN) + l1mE, code0, true);              // own diagonal (:427-431)
-                    FOLD(curN, bpN, (LM + lE) + aI, code1, true);                // (:436-438)
-#pragma unroll
-                    for (int cs = 0; cs < NS; cs++) {
-                        {
-                            const double2 s = bc[cs];
-                            const double vD = ((s.x + NIf) + tD[cs]) + s.y;
-                            const double vA = (s.x + s.y) + tA[cs];
-                            FOLD(curI, bpI, vD, cs, dR[cs] > -r);
-                            FOLD(curN, bpN, vA, cs, true);
-                        }
-                    }
-                    FOLD(curI, bpI, (LM + IIf) + aI, code1, true);               // (:443-447)
-                    if (rowact) {
-                        // bt_right: two variable-width fields (widths depend on the diagonal, 8 bits in total at most):
-                        // low wI bits, inserted state: 0 never set, 1 itself, 2+cs on-diagonal source cs < own;
-                        // the rest, on-diagonal state: 0 never set, 1 own inserted state, 2+(cs-own) on-diagonal source cs >= own
-                        const int iIdx = bpI < 0 ? 0 : ((bpI & 16) ? 1 : bpI + 2);
-                        const int nIdx = bpN < 0 ? 0 : ((bpN & 16) ? 1 : bpN - l16 + 2);
-                        bt[r * 16 + l16] = (unsigned char)(iIdx | (nIdx << wI));
-                        aN = curN; aI = curI;
-                    }
-                    wave_sync();
-                }
-            }
-            };
-            if (Smax <= 4) passes(std::integral_constant<int, 4>());
-            else if (Smax <= 8) passes(std::integral_constant<int, 8>());
-            else if (Smax <= 12) passes(std::integral_constant<int, 12>());
-            else passes(std::integral_constant<int, 16>());
-            // join at bMid (:469-538): plain '>' maxima over x = ins*S + y
-            double ll = FNEG_INF;
-            int xH = 0;
-            {
-                double vN = FNEG_INF, vI = FNEG_INF, hN = FNEG_INF, hI = FNEG_INF;
-                if (act) {
-                    const int mqi = P.read_mqidx[rr];
-                    const double lOn = T[T_MAPQF + 2 * mqi], lOff = T[T_MAPQF + 2 * mqi + 1];
-                    double LM, ob;
-                    emis(bMid, LM, ob);
-                    const int hp = relMine + bMid;
-                    const bool on = hp >= 0 && hp < hlen;
-                    const bool hasR = bMid < L - 1, hasL = bMid > 0;
-                    vN = ob + ((on ? lOn : lOff) + l1mE);
-                    vI = LM + ((on ? lOn : lOff) + lE);
-                    hN = ob + ((on ? hqOn : hqOff) + l1mE);
-                    hI = LM + ((on ? hqOn : hqOff) + lE);
-                    if (hasR) { vN += aN; vI += aI; hN += aN; hI += aI; }
-                    if (hasL) { vN += leftN; vI += leftI; hN += leftN; hI += leftI; }
-                }
-                ll = vN > vI ? vN : vI;
-                double mh = hI > hN ? hI : hN;                       // first maximum: the on-diagonal state wins a tie
-                int mx = hI > hN ? 16 + l16 : l16;                   // order key: ins*16 + diagonal (same order as ins*S + y)
-#pragma unroll
-                for (int off = 8; off >= 1; off >>= 1) {
-                    const double oll = __shfl_xor(ll, off, 16), omh = __shfl_xor(mh, off, 16);
-                    const int omx = __shfl_xor(mx, off, 16);
-                    ll = oll > ll ? oll : ll;
-                    const bool tk = omh > mh || (omh == mh && omx < mx);
-                    mh = tk ? omh : mh;
-                    mx = tk ? omx : mx;
-                }
-                xH = (mh == FNEG_INF) ? 0 : mx;                      // nothing exceeded -inf: xmax stays 0 (:508)
-            }
+#include "faster_sstate.inc"   // SStateHMM (:253-576): sweeps and join; defines ll and xH
             // backtrack (:540-548); every lane of the group walks the same path.  code = diagonal | 16 if inserted.
             wave_sync();                                             // st aliases the histogram: all its readers are done
             if (l16 == 0 && good) st[bMid] = (int16_t)xH;
@@ -509,65 +309,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
                 } else hp = (xm == 0) ? DD_HPOS_LO : DD_HPOS_RO;
                 if (hp_out) hp_out[b] = (int16_t)hp;
             }
-#pragma unroll
-            for (int off = 8; off >= 1; off >>= 1) {
-                const int f = __shfl_xor(firstB, off, 16), l2 = __shfl_xor(lastB, off, 16);
-                firstB = f < firstB ? f : firstB;
-                lastB = l2 > lastB ? l2 : lastB;
-            }
-            if (firstB == 0x7fffffff) firstB = -1;
-            const int64_t vb = (nv > 0) ? P.win_varcov_off[w] + (int64_t)(P.hap_var_off[g] - P.hap_var_off[h0]) * R + (int64_t)ri * nv : 0;
-            if (P.out.var_covered && nv > 0 && good) {
-                for (int i = l16; i < nv; i += 16) {
-                    const int sR = P.hap_var[2 * (P.hap_var_off[g] + i)], eR = P.hap_var[2 * (P.hap_var_off[g] + i) + 1];
-                    P.out.var_covered[vb + i] = (firstB + P.padCover <= sR && lastB - P.padCover >= eR) ? 1 : 0;
-                }
-            }
-            // DetInDel::filterHaplotypes' per-read test (DInDel.cpp:1951-2054): this model leaves numIndels = 0 and
-            // offHapHMQ = false, so every read is selected, and its hpos may skip or repeat haplotype bases: the
-            // covered set is marked base by base (one bit per haplotype base).  Sentinel hpos values (< 0) never cover anything:
-            // an interval reaching below haplotype base 0 is never covered (the reference indexes the sequence with them there).
-            if (P.out.var_fcov && P.hap_var_flank && nv > 0) {
-                for (int i = 0; i < nv; i++) {
-                    const int32_t *fl = P.hap_var_flank + 3 * (size_t)(P.hap_var_off[g] + i);
-                    const int left = fl[0] - P.padCover, right = fl[1] + P.padCover, kind = fl[2];
-                    int cov = 0;
-                    if (kind != 0 && right >= left) {
-                        wave_sync();
-                        for (int x = l16; x < (hlen + 31) / 32; x += 16) bm[x] = 0;
-                        wave_sync();
-                        int nmm = 0;
-                        for (int b = l16; b < L; b += 16) {
-                            const int s2 = st[b];
-                            if (s2 >= 1 && s2 <= hlen) {
-                                const int hb = s2 - 1;
-                                if (hb >= left && hb <= right) {
-                                    atomicOr(&bm[hb >> 5], 1 << (hb & 31));
-                                    const unsigned hc = shHap[hb];
-                                    nmm += ((rd[b] & 0xFFu) != hc && (kind == 2 || hc != 'N')) ? 1 : 0;   // 'N' exempt for DEL (:1992)
-                                }
-                            }
-                        }
-                        wave_sync();
-                        int csize = 0;
-                        const int lo = left > 0 ? left : 0, hi = right < hlen - 1 ? right : hlen - 1;
-                        for (int x = lo + l16; x <= hi; x += 16) csize += (bm[x >> 5] >> (x & 31)) & 1;
-#pragma unroll
-                        for (int off = 8; off >= 1; off >>= 1) {
-                            nmm += __shfl_xor(nmm, off, 16);
-                            csize += __shfl_xor(csize, off, 16);
-                        }
-                        cov = (csize >= right - left + 1 && nmm <= P.maxMismatch) ? 1 : 0;
-                    }
-                    if (l16 == 0 && good) P.out.var_fcov[vb + i] = (uint8_t)cov;
-                }
-            }
-            if (l16 == 0 && good) {
-                P.out.ll[pair] = ll;
-                P.out.status[pair] = DD_PAIR_OK;             // computeLikelihoodsFaster has no ll checks
-                if (P.out.firstBase) P.out.firstBase[pair] = (int16_t)firstB;
-                if (P.out.lastBase) P.out.lastBase[pair] = (int16_t)lastB;
-            }
+#define FAST_ST_VISIBLE()     /* st is LDS: the wave_sync after mapState did it */
+#include "faster_pair_end.inc"   // firstBase / lastBase, var_covered, var_fcov, the final store
             wave_sync();
         }
         }   // chunk of reads
@@ -576,17 +319,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 
 hipError_t launch_faster(const KernelArgs &A, unsigned grid, int waves, size_t lds, hipStream_t st)
 {
-    // raised once per device to the CU's 160 KiB (see launch_one in hmm_kernel.hip: a per-launch value races between host threads)
+    // raised once per device to the CU's 160 KiB (a per-launch value races between host threads)
     static std::atomic<unsigned> raised(0u);
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = ddc::raise_lds_cap_once(reinterpret_cast<const void *>(&dd_faster_kernel), raised);
     if (e != hipSuccess) return e;
-    const unsigned bit = 1u << (dev & 31);
-    if (!(raised.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&dd_faster_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        raised.fetch_or(bit, std::memory_order_release);
-    }
     if (lds > 160u * 1024u) return hipErrorInvalidValue;
     hipLaunchKernelGGL(dd_faster_kernel, dim3(grid), dim3(waves * 64), lds, st, A);
     return hipGetLastError();

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dindel_hmm.h"
+#include "kernel_common.h"   /* the header words and lists both long paths share: DD_LWS_* */
 
 #define DD_FL_THREADS 256     /* one workgroup: four wavefronts x four 16-lane groups = 16 pairs at a time, all of ONE haplotype */
 #define DD_FL_PAIRS 16
@@ -18,13 +19,9 @@ namespace ddf {
  *   [off_ioff ...)  i64 item_off[n_windows + 1]        prefix sums of their item counts
  *   [off_tiles ...) grid x 16 x tile_bytes             per 16-lane group: back-pointers (16 B per read base), then at tile_off_freq the vote
  *                                                      histogram (two 16-bit bins per word), whose bytes later hold the state path */
-#define DD_FL_HDR_COUNTER 0
-#define DD_FL_HDR_NWIN 8
 #define DD_FL_HDR_ROUNDS 12
 #define DD_FL_HDR_ITEMS 16
 #define DD_FL_HDR_PAIRS 24
-#define DD_FL_HDR_STATS 32
-#define DD_FL_WS_HEADER 256
 
 struct FLArgs {
     int32_t n_windows, w_begin, w_end;                 /* windows [w_begin, w_end) of the batch are screened for class DD_WIN_LONG */

@@ -6,7 +6,8 @@
 // inserted} from both read ends to bMid, mapState, hpos, firstBase / lastBase, the coverage flags.  Same fp64 terms in the same order,
 // the same order in which candidates meet `nv > cur + 1e-7`, tables from dd_build_tables, -ffp-contract=off.  Quirks kept: the last 4-mer
 // of the haplotype is never hashed, non-ACGT hashes as 'A', offHap / offHapHMQ always 0, states right of the haplotype map to hap base
-// hlen-1.  The helpers are restated here; faster_kernel.hip is not touched.
+// hlen-1.  The model itself is shared with that kernel: helpers in faster_model.h, SStateHMM in faster_sstate.inc, the end of a pair in
+// faster_pair_end.inc; the prepass and the onHap pass are shared with long_kernel.hip (kernel_common.h).
 //
 // Why a kernel of its own: dd_faster_kernel keeps a pair's vote histogram (2 B per diagonal), read (2 B per base) and back-pointers
 // (16 B per base) in LDS — ~89 KB per pair at 4,094 x 4,096, and a wavefront needs two such areas.  Here
@@ -28,24 +29,15 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <stdint.h>
-#include <type_traits>
 #include "hmm_kernel.h"
+#include "kernel_common.h"
 #include "faster_long_kernel.h"
+#include "faster_model.h"
 
 namespace ddf {
 
-#define FL_EPS 1e-7
-#define FL_NEG_INF (-__builtin_huge_val())
-
-__device__ __forceinline__ int fl_map_char(unsigned c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 0; }
-
-// LDS traffic between lanes of one wavefront: DS operations of a wave execute in order; this only pins the compiler.
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using namespace ddfm;
+using ddc::up16;
 
 // HBM tile traffic between lanes of one wavefront: the stores have to have left the wave before another lane loads them
 __device__ __forceinline__ void tile_sync()
@@ -54,42 +46,6 @@ __device__ __forceinline__ void tile_sync()
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
-
-// wave-uniform maximum of a value that is uniform inside each 16-lane group
-__device__ __forceinline__ int gmax4(int v)
-{
-    const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
-    const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
-    const int ab = a > b ? a : b, cd = c > d ? c : d;
-    return ab > cd ? ab : cd;
-}
-
-// bMid — ObservationModelS::computeBMid (Faster.cpp:60-88)
-__device__ __forceinline__ int fl_bmid(uint32_t hapStart, int hlen, uint32_t mReadStart, int L)
-{
-    const uint32_t hapEnd = hapStart + (uint32_t)hlen;
-    const uint32_t readEnd = mReadStart + (uint32_t)L - 1u;
-    int bMid;
-    if (mReadStart > hapEnd) bMid = 0;
-    else if (readEnd < hapStart) bMid = L - 1;
-    else {
-        const uint32_t olStart = (hapStart > mReadStart) ? hapStart : mReadStart;
-        const uint32_t olEnd = (hapEnd > readEnd) ? readEnd : hapEnd;
-        bMid = ((int)olEnd - (int)olStart) / 2 + (int)olStart - (int)mReadStart;
-    }
-    if (bMid < 0) bMid = 0;
-    if (bMid >= L) bMid = L - 1;
-    return bMid;
-}
-
-// `if (nv > cur + EPS) { cur = nv; bp = code; }` (Faster.cpp:383 and every other update of the model)
-#define FL_FOLD(cur, bp, nvv, code, ok)                      \
-    do {                                                     \
-        const double nv__ = (nvv);                           \
-        const bool t__ = (ok) && nv__ > (cur) + FL_EPS;      \
-        (cur) = t__ ? nv__ : (cur);                          \
-        (bp) = t__ ? (code) : (bp);                          \
-    } while (0)
 
 // One workgroup: the windows of class DD_WIN_LONG with pairs, how many reads an item takes, and the items' prefix sums.
 __global__ void __launch_bounds__(1024) dd_faster_long_prepass(const FLArgs P)
@@ -100,7 +56,7 @@ __global__ void __launch_bounds__(1024) dd_faster_long_prepass(const FLArgs P)
     const int n = P.w_end - P.w_begin;
     const int seg = (n + 1023) / 1024;
     const int lo = P.w_begin + t * seg, hi = min(lo + seg, P.w_end);
-    // pass 1: pairs of the long windows -> reads per item
+    // pairs of the long windows -> reads per item
     long long pairs = 0;
     for (int w = lo; w < hi; w++) {
         const long long np = P.win_pair_off[w + 1] - P.win_pair_off[w];
@@ -117,46 +73,15 @@ __global__ void __launch_bounds__(1024) dd_faster_long_prepass(const FLArgs P)
     long long rounds = total_pairs / ((long long)DD_FL_PAIRS * 4 * (P.grid > 0 ? P.grid : 1));   // >= 4 items per workgroup when there is that much work
     rounds = rounds < 1 ? 1 : (rounds > DD_FL_MAX_ROUNDS ? DD_FL_MAX_ROUNDS : rounds);
     const int per_item = (int)rounds * DD_FL_PAIRS;
-    // pass 2: items per window = haplotypes x ceil(reads / per_item)
-    int cnt = 0;
-    long long items = 0;
-    for (int w = lo; w < hi; w++) {
-        const long long np = P.win_pair_off[w + 1] - P.win_pair_off[w];
-        if (P.win_class[w] == DD_WIN_LONG && np > 0) {
-            const int H = P.win_hap_off[w + 1] - P.win_hap_off[w], R = P.win_read_off[w + 1] - P.win_read_off[w];
-            cnt++;
-            items += (long long)H * ((R + per_item - 1) / per_item);
-        }
-    }
-    sc[t] = cnt; sp[t] = items;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {         // inclusive scan (Hillis-Steele)
-        const int c2 = t >= off ? sc[t - off] : 0;
-        const long long p2 = t >= off ? sp[t - off] : 0;
-        __syncthreads();
-        sc[t] += c2; sp[t] += p2;
-        __syncthreads();
-    }
-    int j = sc[t] - cnt;
-    long long off = sp[t] - items;
-    int32_t *lwin = reinterpret_cast<int32_t *>(P.ws + DD_FL_WS_HEADER);
-    int64_t *ioff = reinterpret_cast<int64_t *>(P.ws + P.off_ioff);
-    for (int w = lo; w < hi; w++) {
-        const long long np = P.win_pair_off[w + 1] - P.win_pair_off[w];
-        if (P.win_class[w] == DD_WIN_LONG && np > 0) {
-            const int H = P.win_hap_off[w + 1] - P.win_hap_off[w], R = P.win_read_off[w + 1] - P.win_read_off[w];
-            lwin[j] = w; ioff[j] = off; j++;
-            off += (long long)H * ((R + per_item - 1) / per_item);
-        }
-    }
+    // items per window = haplotypes x ceil(reads / per_item)
+    const long long items = ddc::long_prepass(P, P.off_ioff, 4, sc, sp, [&](int w) {
+        const int H = P.win_hap_off[w + 1] - P.win_hap_off[w], R = P.win_read_off[w + 1] - P.win_read_off[w];
+        return (long long)H * ((R + per_item - 1) / per_item);
+    });
     if (t == 1023) {
-        ioff[sc[t]] = sp[t];
-        *reinterpret_cast<unsigned long long *>(P.ws + DD_FL_HDR_COUNTER) = 0ull;
-        *reinterpret_cast<int32_t *>(P.ws + DD_FL_HDR_NWIN) = sc[t];
         *reinterpret_cast<int32_t *>(P.ws + DD_FL_HDR_ROUNDS) = (int32_t)rounds;
-        *reinterpret_cast<int64_t *>(P.ws + DD_FL_HDR_ITEMS) = sp[t];
+        *reinterpret_cast<int64_t *>(P.ws + DD_FL_HDR_ITEMS) = items;
         *reinterpret_cast<int64_t *>(P.ws + DD_FL_HDR_PAIRS) = total_pairs;
-        P.stats[0] = 0ull; P.stats[1] = 0ull; P.stats[2] = 0ull; P.stats[3] = 0ull;
     }
 }
 
@@ -192,9 +117,9 @@ __global__ void __launch_bounds__(DD_FL_THREADS) __attribute__((amdgpu_waves_per
 
     for (int i = tid; i < P.n_qual; i += blockDim.x) qt[i] = make_double2(T[T_QUAL + 4 * i], T[T_QUAL + 4 * i + 1]);
 
-    const int32_t *lwin = reinterpret_cast<const int32_t *>(P.ws + DD_FL_WS_HEADER);
+    const int32_t *lwin = reinterpret_cast<const int32_t *>(P.ws + DD_LWS_HEADER);
     const int64_t *ioff = reinterpret_cast<const int64_t *>(P.ws + P.off_ioff);
-    const int n_lwin = *reinterpret_cast<const int32_t *>(P.ws + DD_FL_HDR_NWIN);
+    const int n_lwin = *reinterpret_cast<const int32_t *>(P.ws + DD_LWS_HDR_NWIN);
     const int rounds = *reinterpret_cast<const int32_t *>(P.ws + DD_FL_HDR_ROUNDS);
     const int per_item = rounds * DD_FL_PAIRS;
     const long long n_items = *reinterpret_cast<const int64_t *>(P.ws + DD_FL_HDR_ITEMS);
@@ -203,7 +128,7 @@ __global__ void __launch_bounds__(DD_FL_THREADS) __attribute__((amdgpu_waves_per
 
     for (;;) {
         __syncthreads();                                            // the previous item's readers (LDS and s_item) are done
-        if (tid == 0) *s_item = (long long)atomicAdd(reinterpret_cast<unsigned long long *>(P.ws + DD_FL_HDR_COUNTER), 1ull);
+        if (tid == 0) *s_item = (long long)atomicAdd(reinterpret_cast<unsigned long long *>(P.ws + DD_LWS_HDR_COUNTER), 1ull);
         __syncthreads();
         const long long item = *s_item;
         if (item >= n_items) break;
@@ -239,7 +164,7 @@ __global__ void __launch_bounds__(DD_FL_THREADS) __attribute__((amdgpu_waves_per
             __syncthreads();
             for (int hx = tid; hx < hlen - 4; hx += blockDim.x) {
                 int key = 0;
-                for (int y = 0; y < 4; y++) key |= fl_map_char(shHap[hx + y]) << (2 * y);
+                for (int y = 0; y < 4; y++) key |= map_char(shHap[hx + y]) << (2 * y);
                 atomicAdd(&cnt[key], 1);
             }
             __syncthreads();
@@ -258,7 +183,7 @@ __global__ void __launch_bounds__(DD_FL_THREADS) __attribute__((amdgpu_waves_per
             __syncthreads();
             for (int hx = tid; hx < hlen - 4; hx += blockDim.x) {
                 int key = 0;
-                for (int y = 0; y < 4; y++) key |= fl_map_char(shHap[hx + y]) << (2 * y);
+                for (int y = 0; y < 4; y++) key |= map_char(shHap[hx + y]) << (2 * y);
                 hpl[atomicAdd(&cnt[key], 1)] = (uint16_t)hx;
             }
             __syncthreads();
@@ -307,7 +232,7 @@ __global__ void __launch_bounds__(DD_FL_THREADS) __attribute__((amdgpu_waves_per
             const int L = good ? Lraw : 0;
             if (__ballot(good) == 0) continue;
 
-            const int bMid = good ? fl_bmid(hapStart, hlen, P.read_start[rr], L) : 0;
+            const int bMid = good ? bmid(hapStart, hlen, P.read_start[rr], L) : 0;
             // stage the read, clear the vote histogram (bin index rpfb + L, rpfb in [-(L-4), hlen-5]); 16 bytes = 8 bins per lane and step
             const int F = L + hlen;
             const int nq = good ? ((F + 1) / 2 + 3) / 4 : 0;
@@ -319,7 +244,7 @@ __global__ void __launch_bounds__(DD_FL_THREADS) __attribute__((amdgpu_waves_per
             // AlignHash (Faster.cpp:131-189): every read 4-mer votes for the diagonals of the equal haplotype 4-mers
             for (int x = l16; x <= L - 4; x += 16) {
                 int key = 0;
-                for (int y = 0; y < 4; y++) key |= fl_map_char(rd[x + y] & 0xFF) << (2 * y);
+                for (int y = 0; y < 4; y++) key |= map_char(rd[x + y] & 0xFF) << (2 * y);
                 const int e = bk[key + 1];
                 for (int p = bk[key]; p < e; p++) {
                     const int idx = (int)hpl[p] - x + L;
@@ -386,162 +311,7 @@ __global__ void __launch_bounds__(DD_FL_THREADS) __attribute__((amdgpu_waves_per
             const int relMine = srt[l16];
             const bool act = good && l16 < S;
             const int Smax = gmax4(S);
-            const int code0 = l16, code1 = l16 | 16;
-            const int wI = 32 - __clz(l16 + 1);          // bits of the inserted-state field of bt_right: values 0..own+1
-
-            // ---------------- SStateHMM (:253-576) ----------------
-            auto emis = [&](int r, double &LM, double &ob) {            // logMatch[r] and obs[r][own diagonal] (:286-296)
-                const unsigned v = rd[r];
-                const double2 q = qt[v >> 8];
-                const int hp = relMine + r;
-                LM = q.x;
-                ob = (hp >= 0 && hp < hlen && (unsigned)shHap[hp] != (v & 0xFFu)) ? q.y : q.x;
-            };
-            // Transition terms between every source diagonal cs and this lane's diagonal (:339-352) are loop constants; a term that does
-            // not apply to this lane is -inf, so its candidate can never pass `nv > cur + EPS`.  Sources beyond the pair's S publish -inf,
-            // so the source loops run to the next multiple of 4 of the wave's largest S (dd_faster_kernel's scheme, same candidate order).
-            double aN = 0.0, aI = 0.0;                  // previous base's values of this diagonal (0 at the read end)
-            double leftN = 0.0, leftI = 0.0;
-            auto passes = [&](auto nsc) {
-                constexpr int NS = decltype(nsc)::value;
-                int lv = l16;                               // opaque copy: keeps the per-source selects below from being hoisted
-                asm volatile("" : "+v"(lv));                // out of the read loop as 2 x 16 spilled lane constants
-            // from left to bMid (:373-416)
-            {
-                double tA[NS], tB[NS];
-                int dL[NS];
-#pragma unroll
-                for (int cs = 0; cs < NS; cs++) {
-                    const int df = srt[cs] - relMine;
-                    const double trI = (fabs((double)df) - 1.0) * IIf;
-                    tA[cs] = (cs < lv) ? trI + lE : (cs == lv ? l1mE : FL_NEG_INF);   // on-diagonal source cs <= own (:380-384)
-                    tB[cs] = (cs > lv) ? trI : FL_NEG_INF;                              // inserted source cs > own (:404-411)
-                    dL[cs] = (cs > lv) ? df : 0x7fffffff;                               // its condition relPos[cs]-r >= relPos[ns]
-                    asm volatile("" : "+v"(tA[cs]), "+v"(tB[cs]), "+v"(dL[cs]));           // keep them as plain register constants
-                }
-                const int rows = gmax4(bMid);
-                double LMn = 0.0, obn = 0.0;
-                if (act && bMid > 0) emis(0, LMn, obn);
-                for (int r = 0; r < rows; r++) {
-                    const bool rowact = act && r < bMid;
-                    const double LM = LMn, ob = obn;
-                    const double pvOwn = ob + aN;
-                    bc[l16] = rowact ? make_double2(pvOwn, aI) : make_double2(FL_NEG_INF, FL_NEG_INF);
-                    wave_sync();
-                    if (act && r + 1 < bMid) emis(r + 1, LMn, obn);
-                    double curN = -1000.0, curI = -1000.0;
-                    int bpN = 0, bpI = 32;                                      // untouched = the reference's bt 0: on-diagonal state of diagonal 0
-#pragma unroll
-                    for (int cs = 0; cs < NS; cs++) {
-                        {
-                            const double2 s = bc[cs];
-                            const double vA = s.x + tA[cs];
-                            const double vB = ((LM + tB[cs]) + lE) + s.y;
-                            FL_FOLD(curN, bpN, fmax(vA, vB), cs, dL[cs] >= r);
-                        }
-                    }
-                    FL_FOLD(curI, bpI, pvOwn + NIf, code0, true);                   // (:387-391)
-                    FL_FOLD(curI, bpI, (LM + IIf) + aI, code1, true);               // (:396-400)
-                    if (rowact) {
-                        // bt_left: bits 0-3 source diagonal of the on-diagonal state (a source above the own diagonal is its inserted state);
-                        // bit 4: the inserted state came from itself, bit 5: it was never set.  The group's 16 bytes are one segment of the tile.
-                        bt[r * 16 + l16] = (unsigned char)(bpN | (bpI & 48));
-                        aN = curN; aI = curI;
-                    }
-                    wave_sync();
-                }
-            }
-            leftN = aN; leftI = aI;                     // alpha[bMid-1] (0 if bMid == 0)
-            // from right to bMid (:422-466)
-            aN = 0.0; aI = 0.0;
-            {
-                double tD[NS], tA[NS];
-                int dR[NS];
-#pragma unroll
-                for (int cs = 0; cs < NS; cs++) {
-                    const int df = srt[cs] - relMine;
-                    const double trI = (fabs((double)df) - 1.0) * IIf;
-                    tD[cs] = (cs < lv) ? trI : FL_NEG_INF;                  // into the inserted state of a higher diagonal (:453-461)
-                    tA[cs] = (cs > lv) ? trI + lE : FL_NEG_INF;             // on-diagonal source cs > own (:427-431); own: below
-                    dR[cs] = df;                                             // condition relPos[cs] > relPos[ns]-r
-                    asm volatile("" : "+v"(tD[cs]), "+v"(tA[cs]), "+v"(dR[cs]));
-                }
-                const int rows = gmax4(L - 1 - bMid);
-                double LMn = 0.0, obn = 0.0;
-                if (act && bMid < L - 1) emis(L - 1, LMn, obn);
-                for (int k = 0; k < rows; k++) {
-                    const int r = L - 1 - k;
-                    const bool rowact = act && r > bMid;
-                    const double LM = LMn, ob = obn;
-                    bc[l16] = rowact ? make_double2(ob, aN) : make_double2(FL_NEG_INF, 0.0);
-                    wave_sync();
-                    if (act && r - 1 > bMid) emis(r - 1, LMn, obn);
-                    double curN = -1000.0, curI = -1000.0;
-                    int bpN = -1, bpI = -1;                                     // untouched = the reference's bt 0
-                    FL_FOLD(curN, bpN, (ob + aN) + l1mE, code0, true);              // own diagonal (:427-431)
-                    FL_FOLD(curN, bpN, (LM + lE) + aI, code1, true);                // (:436-438)
-#pragma unroll
-                    for (int cs = 0; cs < NS; cs++) {
-                        {
-                            const double2 s = bc[cs];
-                            const double vD = ((s.x + NIf) + tD[cs]) + s.y;
-                            const double vA = (s.x + s.y) + tA[cs];
-                            FL_FOLD(curI, bpI, vD, cs, dR[cs] > -r);
-                            FL_FOLD(curN, bpN, vA, cs, true);
-                        }
-                    }
-                    FL_FOLD(curI, bpI, (LM + IIf) + aI, code1, true);               // (:443-447)
-                    if (rowact) {
-                        // bt_right: two variable-width fields (widths depend on the diagonal, 8 bits in total at most):
-                        // low wI bits, inserted state: 0 never set, 1 itself, 2+cs on-diagonal source cs < own;
-                        // the rest, on-diagonal state: 0 never set, 1 own inserted state, 2+(cs-own) on-diagonal source cs >= own
-                        const int iIdx = bpI < 0 ? 0 : ((bpI & 16) ? 1 : bpI + 2);
-                        const int nIdx = bpN < 0 ? 0 : ((bpN & 16) ? 1 : bpN - l16 + 2);
-                        bt[r * 16 + l16] = (unsigned char)(iIdx | (nIdx << wI));
-                        aN = curN; aI = curI;
-                    }
-                    wave_sync();
-                }
-            }
-            };
-            if (Smax <= 4) passes(std::integral_constant<int, 4>());
-            else if (Smax <= 8) passes(std::integral_constant<int, 8>());
-            else if (Smax <= 12) passes(std::integral_constant<int, 12>());
-            else passes(std::integral_constant<int, 16>());
-            // join at bMid (:469-538): plain '>' maxima over x = ins*S + y
-            double ll = FL_NEG_INF;
-            int xH = 0;
-            {
-                double vN = FL_NEG_INF, vI = FL_NEG_INF, hN = FL_NEG_INF, hI = FL_NEG_INF;
-                if (act) {
-                    const int mqi = P.read_mqidx[rr];
-                    const double lOn = T[T_MAPQF + 2 * mqi], lOff = T[T_MAPQF + 2 * mqi + 1];
-                    double LM, ob;
-                    emis(bMid, LM, ob);
-                    const int hp = relMine + bMid;
-                    const bool on = hp >= 0 && hp < hlen;
-                    const bool hasR = bMid < L - 1, hasL = bMid > 0;
-                    vN = ob + ((on ? lOn : lOff) + l1mE);
-                    vI = LM + ((on ? lOn : lOff) + lE);
-                    hN = ob + ((on ? hqOn : hqOff) + l1mE);
-                    hI = LM + ((on ? hqOn : hqOff) + lE);
-                    if (hasR) { vN += aN; vI += aI; hN += aN; hI += aI; }
-                    if (hasL) { vN += leftN; vI += leftI; hN += leftN; hI += leftI; }
-                }
-                ll = vN > vI ? vN : vI;
-                double mh = hI > hN ? hI : hN;                       // first maximum: the on-diagonal state wins a tie
-                int mx = hI > hN ? 16 + l16 : l16;                   // order key: ins*16 + diagonal (same order as ins*S + y)
-#pragma unroll
-                for (int off = 8; off >= 1; off >>= 1) {
-                    const double oll = __shfl_xor(ll, off, 16), omh = __shfl_xor(mh, off, 16);
-                    const int omx = __shfl_xor(mx, off, 16);
-                    ll = oll > ll ? oll : ll;
-                    const bool tk = omh > mh || (omh == mh && omx < mx);
-                    mh = tk ? omh : mh;
-                    mx = tk ? omx : mx;
-                }
-                xH = (mh == FL_NEG_INF) ? 0 : mx;                    // nothing exceeded -inf: xmax stays 0 (:508)
-            }
+#include "faster_sstate.inc"   // SStateHMM (:253-576): sweeps and join; defines ll and xH
             // backtrack (:540-548); every lane of the group walks the same path.  code = diagonal | 16 if inserted.  The rows come
             // from the tile 16 at a time (one 16-byte row per lane) through the scratch X, the next 16 already in flight; lane i keeps
             // the state of row 16 c + i, so the path goes out 32 bytes at a time.
@@ -647,64 +417,8 @@ __global__ void __launch_bounds__(DD_FL_THREADS) __attribute__((amdgpu_waves_per
                     }
                 }
             }
-#pragma unroll
-            for (int off = 8; off >= 1; off >>= 1) {
-                const int f = __shfl_xor(firstB, off, 16), l2 = __shfl_xor(lastB, off, 16);
-                firstB = f < firstB ? f : firstB;
-                lastB = l2 > lastB ? l2 : lastB;
-            }
-            if (firstB == 0x7fffffff) firstB = -1;
-            const int64_t vb = (nv > 0) ? P.win_varcov_off[w] + (int64_t)(P.hap_var_off[g] - P.hap_var_off[h0]) * R + (int64_t)ri * nv : 0;
-            if (P.out.var_covered && nv > 0 && good) {
-                for (int i = l16; i < nv; i += 16) {
-                    const int sR = P.hap_var[2 * (P.hap_var_off[g] + i)], eR = P.hap_var[2 * (P.hap_var_off[g] + i) + 1];
-                    P.out.var_covered[vb + i] = (firstB + P.padCover <= sR && lastB - P.padCover >= eR) ? 1 : 0;
-                }
-            }
-            // DetInDel::filterHaplotypes' per-read test (DInDel.cpp:1951-2054), as dd_faster_kernel does it: the covered set is marked
-            // base by base (one bit per haplotype base, <= 128 words of X); sentinel hpos values never cover anything.
-            if (P.out.var_fcov && P.hap_var_flank && nv > 0) {
-                tile_sync();                                         // the mapped states of the other lanes' bases
-                for (int i = 0; i < nv; i++) {
-                    const int32_t *fl = P.hap_var_flank + 3 * (size_t)(P.hap_var_off[g] + i);
-                    const int left = fl[0] - P.padCover, right = fl[1] + P.padCover, kind = fl[2];
-                    int cov = 0;
-                    if (kind != 0 && right >= left) {
-                        wave_sync();
-                        for (int x = l16; x < (hlen + 31) / 32; x += 16) bm[x] = 0;
-                        wave_sync();
-                        int nmm = 0;
-                        for (int b = l16; b < L; b += 16) {
-                            const int s2 = st[b];
-                            if (s2 >= 1 && s2 <= hlen) {
-                                const int hb = s2 - 1;
-                                if (hb >= left && hb <= right) {
-                                    atomicOr(&bm[hb >> 5], 1 << (hb & 31));
-                                    const unsigned hc = shHap[hb];
-                                    nmm += ((rd[b] & 0xFFu) != hc && (kind == 2 || hc != 'N')) ? 1 : 0;   // 'N' exempt for DEL (:1992)
-                                }
-                            }
-                        }
-                        wave_sync();
-                        int csize = 0;
-                        const int lo = left > 0 ? left : 0, hi = right < hlen - 1 ? right : hlen - 1;
-                        for (int x = lo + l16; x <= hi; x += 16) csize += (bm[x >> 5] >> (x & 31)) & 1;
-#pragma unroll
-                        for (int off = 8; off >= 1; off >>= 1) {
-                            nmm += __shfl_xor(nmm, off, 16);
-                            csize += __shfl_xor(csize, off, 16);
-                        }
-                        cov = (csize >= right - left + 1 && nmm <= P.maxMismatch) ? 1 : 0;
-                    }
-                    if (l16 == 0 && good) P.out.var_fcov[vb + i] = (uint8_t)cov;
-                }
-            }
-            if (l16 == 0 && good) {
-                P.out.ll[pair] = ll;
-                P.out.status[pair] = DD_PAIR_OK;             // computeLikelihoodsFaster has no ll checks
-                if (P.out.firstBase) P.out.firstBase[pair] = (int16_t)firstB;
-                if (P.out.lastBase) P.out.lastBase[pair] = (int16_t)lastB;
-            }
+#define FAST_ST_VISIBLE() tile_sync()   /* st is in the tile */
+#include "faster_pair_end.inc"   // firstBase / lastBase, var_covered, var_fcov, the final store
             wave_sync();
             tile_sync();                                      // the tile's readers are done before the next pair clears it
         }
@@ -716,33 +430,8 @@ __global__ void __launch_bounds__(DD_FL_THREADS) __attribute__((amdgpu_waves_per
     }
 }
 
-// onHap[r] of the long windows' reads (DInDel.cpp:1710, 1720): after the kernel, so that it sees their outputs; reads of other windows
-// are not touched
-__global__ void dd_faster_long_onhap_kernel(const FLArgs P)
-{
-    const int r = P.read_begin + blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= P.read_end) return;
-    int lo = 0, hi = P.n_windows;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (P.win_read_off[mid] <= r) lo = mid; else hi = mid;
-    }
-    const int w = lo;
-    if (w < P.w_begin || w >= P.w_end || P.win_class[w] != DD_WIN_LONG) return;
-    const int H = P.win_hap_off[w + 1] - P.win_hap_off[w];
-    const int r0 = P.win_read_off[w];
-    const int R = P.win_read_off[w + 1] - r0;
-    const int64_t base = P.win_pair_off[w] + (r - r0);
-    int on = 0;
-    for (int h = 0; h < H; h++) {
-        const int64_t p = base + (int64_t)h * R;
-        const int st = P.out.status[p];
-        if (st != DD_PAIR_HAPSIZE && st != DD_PAIR_UNSUPPORTED && !P.out.offHapHMQ[p]) on = 1;
-    }
-    P.out.onHap[r] = (uint8_t)on;
-}
-
-static uint32_t up16(size_t v) { return (uint32_t)((v + 15u) & ~(size_t)15u); }
+// onHap[r] of the long windows' reads, after the kernel (kernel_common.h)
+__global__ void dd_faster_long_onhap_kernel(const FLArgs P) { ddc::onhap_of_read(P); }
 
 size_t fl_lds_layout(int max_hap_len, int max_read_len, FLArgs &A)
 {
@@ -775,15 +464,8 @@ hipError_t launch_faster_long(const FLArgs &A, unsigned grid, size_t lds, bool o
     if (grid < 1) return hipErrorInvalidValue;
     // the dynamic-LDS cap is raised once per device, as for the other kernels
     static std::atomic<unsigned> raised(0u);
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    hipError_t e = ddc::raise_lds_cap_once(reinterpret_cast<const void *>(&dd_faster_long_kernel), raised);
     if (e != hipSuccess) return e;
-    const unsigned bit = 1u << (dev & 31);
-    if (!(raised.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&dd_faster_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        raised.fetch_or(bit, std::memory_order_release);
-    }
     if (lds > 160u * 1024u) return hipErrorInvalidValue;
     hipLaunchKernelGGL(dd_faster_long_prepass, dim3(1), dim3(1024), 0, st, A);
     e = hipGetLastError();

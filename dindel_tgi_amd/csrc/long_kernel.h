@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dindel_hmm.h"
+#include "kernel_common.h"   /* the header words and lists both long paths share: DD_LWS_* */
 
 #define DD_LONG_THREADS 256   /* one workgroup (four wavefronts) per pair */
 #define DD_LONG_PAD 32        /* pad states either side of the LDS row: jumps reach D <= 32 states */
@@ -12,14 +13,10 @@ namespace ddl {
 
 /* Workspace of a long launch (dd_workspace_bytes_long):
  *   [0, 256)        header: u64 item counter, i32 long windows, pad, i64 long pairs, u64 stats[2] (pairs computed, most pairs of one workgroup)
- *   [256, ...)      i32 long_win[n_windows]           windows of class 2, ascending
+ *   [256, ...)      i32 long_win[n_windows]           windows of class DD_WIN_LONG, ascending
  *   [off_lpoff ...) i64 long_pair_off[n_windows + 1]  prefix sums of their pair counts
  *   [off_tiles ...) grid x tile_bytes                 per workgroup: max_read_len rows x 256 K bytes of back-pointers, 2 x 256 K doubles */
-#define DD_LONG_HDR_COUNTER 0
-#define DD_LONG_HDR_NWIN 8
 #define DD_LONG_HDR_TOTAL 16
-#define DD_LONG_HDR_STATS 32
-#define DD_LONG_WS_HEADER 256
 
 struct LongArgs {
     int32_t n_windows, w_begin, w_end;                 /* windows [w_begin, w_end) of the batch are screened for class 2 */

@@ -22,9 +22,11 @@
 #include <stdint.h>
 #include <atomic>
 #include "hmm_kernel.h"
+#include "kernel_common.h"
 #include "long_kernel.h"
 
 namespace ddl {
+using ddc::up16;
 
 #define LNEG_INF (-__builtin_huge_val())
 #define L_EPS 1e-10
@@ -137,47 +139,13 @@ __device__ void block_argmax(const double (&vA)[K], const double (&vI)[K], int n
     __syncthreads();
 }
 
-// Classes of the windows [w_begin, w_end): the long ones (class 2, with pairs) in order, and the prefix sums of their pair counts.
-// One workgroup of 1024 threads, each over a contiguous segment of windows; zeroes the item counter and the stats.
+// The long windows of [w_begin, w_end) in order, and the prefix sums of their pair counts (kernel_common.h)
 __global__ void __launch_bounds__(1024) dd_long_prepass(const LongArgs P)
 {
     __shared__ int32_t sc[1024];
     __shared__ long long sp[1024];
-    const int t = threadIdx.x;
-    const int n = P.w_end - P.w_begin;
-    const int seg = (n + 1023) / 1024;
-    const int lo = P.w_begin + t * seg, hi = min(lo + seg, P.w_end);
-    int cnt = 0;
-    long long pairs = 0;
-    for (int w = lo; w < hi; w++) {
-        const long long np = P.win_pair_off[w + 1] - P.win_pair_off[w];
-        if (P.win_class[w] == 2 && np > 0) { cnt++; pairs += np; }
-    }
-    sc[t] = cnt; sp[t] = pairs;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {         // inclusive scan (Hillis-Steele)
-        const int c2 = t >= off ? sc[t - off] : 0;
-        const long long p2 = t >= off ? sp[t - off] : 0;
-        __syncthreads();
-        sc[t] += c2; sp[t] += p2;
-        __syncthreads();
-    }
-    int j = sc[t] - cnt;
-    long long off = sp[t] - pairs;
-    int32_t *lwin = reinterpret_cast<int32_t *>(P.ws + DD_LONG_WS_HEADER);
-    int64_t *lpoff = reinterpret_cast<int64_t *>(P.ws + P.off_lpoff);
-    for (int w = lo; w < hi; w++) {
-        const long long np = P.win_pair_off[w + 1] - P.win_pair_off[w];
-        if (P.win_class[w] == 2 && np > 0) { lwin[j] = w; lpoff[j] = off; j++; off += np; }
-    }
-    if (t == 1023) {
-        lpoff[sc[t]] = sp[t];
-        *reinterpret_cast<unsigned long long *>(P.ws + DD_LONG_HDR_COUNTER) = 0ull;
-        *reinterpret_cast<int32_t *>(P.ws + DD_LONG_HDR_NWIN) = sc[t];
-        *reinterpret_cast<int64_t *>(P.ws + DD_LONG_HDR_TOTAL) = sp[t];
-        P.stats[0] = 0ull;
-        P.stats[1] = 0ull;
-    }
+    const long long total = ddc::long_prepass(P, P.off_lpoff, 2, sc, sp, [&](int w) { return (long long)(P.win_pair_off[w + 1] - P.win_pair_off[w]); });
+    if (threadIdx.x == 1023) *reinterpret_cast<int64_t *>(P.ws + DD_LONG_HDR_TOTAL) = total;
 }
 
 template <int K>
@@ -207,10 +175,10 @@ __global__ void __launch_bounds__(NT, K >= 16 ? 1 : 2) dd_long_kernel(const Long
     for (int i = t; i <= HP_DEF; i += NT)
         shEN[i] = i < HP_DEF ? make_double2(T[T_HP + 2 * i], T[T_HP + 2 * i + 1]) : make_double2(T[TC_EDEF], T[TC_NDEF]);
 
-    unsigned long long *counter = reinterpret_cast<unsigned long long *>(P.ws + DD_LONG_HDR_COUNTER);
-    const int n_long = *reinterpret_cast<const int32_t *>(P.ws + DD_LONG_HDR_NWIN);
+    unsigned long long *counter = reinterpret_cast<unsigned long long *>(P.ws + DD_LWS_HDR_COUNTER);
+    const int n_long = *reinterpret_cast<const int32_t *>(P.ws + DD_LWS_HDR_NWIN);
     const long long total = *reinterpret_cast<const int64_t *>(P.ws + DD_LONG_HDR_TOTAL);
-    const int32_t *lwin = reinterpret_cast<const int32_t *>(P.ws + DD_LONG_WS_HEADER);
+    const int32_t *lwin = reinterpret_cast<const int32_t *>(P.ws + DD_LWS_HEADER);
     const int64_t *lpoff = reinterpret_cast<const int64_t *>(P.ws + P.off_lpoff);
     unsigned char *tile = P.ws + P.off_tiles + (size_t)blockIdx.x * P.tile_bytes;
     unsigned long long my_pairs = 0;
@@ -796,33 +764,8 @@ __global__ void __launch_bounds__(NT, K >= 16 ? 1 : 2) dd_long_kernel(const Long
     }
 }
 
-// onHap[r] of the long windows' reads (DInDel.cpp:1710, 1720): after the long kernel, so that it sees their outputs; reads of other
-// windows are not touched
-__global__ void dd_long_onhap_kernel(const LongArgs P)
-{
-    const int r = P.read_begin + blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= P.read_end) return;
-    int lo = 0, hi = P.n_windows;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (P.win_read_off[mid] <= r) lo = mid; else hi = mid;
-    }
-    const int w = lo;
-    if (P.win_class[w] != 2) return;
-    const int H = P.win_hap_off[w + 1] - P.win_hap_off[w];
-    const int r0 = P.win_read_off[w];
-    const int R = P.win_read_off[w + 1] - r0;
-    const int64_t base = P.win_pair_off[w] + (r - r0);
-    int on = 0;
-    for (int h = 0; h < H; h++) {
-        const int64_t p = base + (int64_t)h * R;
-        const int st = P.out.status[p];
-        if (st != DD_PAIR_HAPSIZE && st != DD_PAIR_UNSUPPORTED && !P.out.offHapHMQ[p]) on = 1;
-    }
-    P.out.onHap[r] = (uint8_t)on;
-}
-
-static uint32_t up16(size_t v) { return (uint32_t)((v + 15u) & ~(size_t)15u); }
+// onHap[r] of the long windows' reads, after the long kernel (kernel_common.h)
+__global__ void dd_long_onhap_kernel(const LongArgs P) { ddc::onhap_of_read(P); }
 
 size_t long_lds_layout(int K, int max_read_len, LongArgs &A)
 {
@@ -844,17 +787,10 @@ size_t long_lds_layout(int K, int max_read_len, LongArgs &A)
 template <int K>
 static hipError_t launch_k(const LongArgs &A, unsigned grid, size_t lds, hipStream_t st)
 {
-    // the dynamic-LDS cap is raised once per instance and device, as for the main kernels (hmm_kernel.hip launch_one)
-    static std::atomic<unsigned> raised(0u);             // bit d: done on device d
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    // the dynamic-LDS cap is raised once per instance and device
+    static std::atomic<unsigned> raised(0u);
+    const hipError_t e = ddc::raise_lds_cap_once(reinterpret_cast<const void *>(&dd_long_kernel<K>), raised);
     if (e != hipSuccess) return e;
-    const unsigned bit = 1u << (dev & 31);
-    if (!(raised.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&dd_long_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        raised.fetch_or(bit, std::memory_order_release);
-    }
     if (lds > 160u * 1024u) return hipErrorInvalidValue;
     hipLaunchKernelGGL(dd_long_kernel<K>, dim3(grid), dim3(NT), lds, st, A);
     return hipGetLastError();
