@@ -1,0 +1,131 @@
+// capi_internal.h — what the host units of the C ABI (include/dindel_hmm.h) share: plan.cpp, batch_host.cpp (neither calls the HIP runtime),
+// launch.cpp, host_path.cpp; each says in its first lines what it holds.  Host work is O(bases) bookkeeping only.  All likelihood
+// arithmetic happens in the kernels; there is no CPU path for it in this library.
+#ifndef DD_CAPI_INTERNAL_H
+#define DD_CAPI_INTERNAL_H
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+#include "hmm_kernel.h"
+#include "long_kernel.h"
+#include "faster_long_kernel.h"
+
+namespace ddh {
+constexpr size_t kCuLdsBytes = 160u * 1024u;   // LDS of one CU (gfx950)
+constexpr int kCUs = 256;                      // CUs of the chip
+
+extern thread_local std::string g_err;         // dd_last_error(): per host thread (batch_host.cpp)
+inline int fail(int code, const std::string &msg) { g_err = msg; return code; }
+
+#define HIP_TRY(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t _e = (expr);                                                                \
+        if (_e != hipSuccess)                                                                  \
+            return fail(DD_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));        \
+    } while (0)
+
+inline int check_params(const dd_params *p)
+{
+    if (!p) return fail(DD_ERR_INVALID, "null params");
+    if (p->forceReadOnHaplotype) return fail(DD_ERR_UNSUPPORTED, "forceReadOnHaplotype is not on the production path (DInDel.cpp:1446 only)");
+    if (p->maxLengthDel < 0 || p->maxLengthDel > DD_MAX_LENGTH_DEL) return fail(DD_ERR_UNSUPPORTED, "maxLengthDel outside [0,31]");
+    if (!(p->pError > 0.0 && p->pError < 1.0)) return fail(DD_ERR_INVALID, "pError outside (0,1)");
+    return DD_SUCCESS;
+}
+
+// which per-pair model an entry point runs
+enum Model { MODEL_FBMAXERR = 0 /* ObservationModelFBMaxErr, computeLikelihoods */, MODEL_S = 1 /* ObservationModelS, computeLikelihoodsFaster */ };
+
+// Every field of dd_result once, with the index space it lives in: PAIR one entry per pair, HPOS one per (pair, read base), VARCOV one per
+// (pair, variant of its haplotype), READ one per read; and whether it may be written in place into the caller's page-locked memory (0: status
+// and offHapHMQ stay in HBM, the onHap kernel reads them back).  The host-pointer path generates its in-place flags, output allocation,
+// downloads, staged copy-back and per-block pointer shift from this list (in this order: it is the order of the copies on a stream).
+#define DD_RESULT_FIELDS(X)                                                                                                      \
+    X(ll, PAIR, 1) X(llOn, PAIR, 1) X(llOff, PAIR, 1) X(mLogBQ, PAIR, 1) X(offHap, PAIR, 1) X(offHapHMQ, PAIR, 0) X(numIndels, PAIR, 1) \
+    X(numMismatch, PAIR, 1) X(nBQT, PAIR, 1) X(nmmBQT, PAIR, 1) X(nMMLeft, PAIR, 1) X(nMMRight, PAIR, 1) X(firstBase, PAIR, 1)     \
+    X(lastBase, PAIR, 1) X(status, PAIR, 0) X(hpos, HPOS, 1) X(var_covered, VARCOV, 1) X(var_fcov, VARCOV, 1) X(onHap, READ, 1)
+enum ResultSpace { SPACE_PAIR, SPACE_HPOS, SPACE_VARCOV, SPACE_READ };
+#define DD_FIELD_SIZE(f, space, in_place) + sizeof(dd_result::f)
+static_assert(0 DD_RESULT_FIELDS(DD_FIELD_SIZE) == sizeof(dd_result), "DD_RESULT_FIELDS must list every field of dd_result");
+#undef DD_FIELD_SIZE
+
+// ---- plan.cpp ----
+struct HapClassDef { int bound, G, K; };     // haplotypes up to `bound` bp: G pairs per wavefront, K positions per lane
+extern const HapClassDef kHapClasses[DD_N_HAP_CLASSES];
+int hap_class_of(int hap_len);
+bool pick_tiling(int max_hap_len, int Dt, int &G, int &K);
+int pick_Dt(int D);
+size_t lds_layout(int K, int Dt, int Lmax, int n_qual, int waves, bool gbt, int G, ddk::KernelArgs &A);
+size_t scratch_wave_bytes(int K, int Dt, int G, int max_read_len);
+
+// the workspace starts with the item counter of the dynamic (ragged) launches; the back-pointer tiles follow
+constexpr size_t DD_WS_HEADER = 256;
+
+// Launch plan: LDS-resident back-pointers when that keeps the CU as full as the registers allow, otherwise
+// the HBM-scratch build (GBT) with a persistent grid (one scratch tile per resident wave).
+struct Plan {
+    int K, Dt, waves, waves_per_cu;
+    int G = 1;               // pairs per wavefront (2: the half-wave builds)
+    bool gbt;
+    bool two_waves = false;  // K = 3 / D = 6 scratch build: the variant compiled for 2 waves per SIMD (LDS keeps fewer than 12 waves on the CU anyway)
+    size_t lds, scratch_bytes;
+    unsigned grid_cap;       // 0 = one workgroup per item
+};
+int make_plan(const dd_params *p, int max_hap_len, int max_read_len, int n_qual, Plan &pl, ddk::KernelArgs &A);
+int lds_read_threshold(const dd_params *p, int max_hap_len, int n_qual);
+int waves_for_reads(int64_t units, int maxw, int per_cu);
+int64_t pick_split(int64_t n_haps, int64_t units, int waves, int64_t min_blocks, int64_t resident = 0);
+int64_t resident_workgroups(size_t lds, int waves_per_cu, int waves);
+size_t lds_layout_fast(int max_hap_len, int max_read_len, int n_qual, int &waves, int &groups, ddk::KernelArgs &A);
+struct LongPlan { int K; size_t lds; unsigned grid; uint64_t off_lpoff, off_tiles, stash_off, tile_bytes, ws_bytes; };
+int long_plan(int n_windows, int max_hap_len, int max_read_len, int n_qual, LongPlan &lp, ddl::LongArgs &A);
+struct FLPlan { size_t lds; unsigned grid; uint64_t off_ioff, off_tiles, ws_bytes; };
+int fl_plan(const dd_device_batch *b, FLPlan &fp, ddf::FLArgs &A);
+
+// ---- batch_host.cpp ----
+int assign_symbols(const dd_batch *b, uint8_t *out);
+int screen_windows(const dd_batch *b, uint8_t *win_skip, int32_t max_len_out[2], const uint8_t *sym_lut, bool with_symbols);
+int screen_windows_ex(const dd_params *p, const dd_batch *b, uint32_t options, uint8_t *win_class, int32_t max_len_out[4],
+                      const uint8_t *sym_lut, bool with_symbols);
+int build_launch_classes(const dd_batch *b, const uint8_t *win_skip, const dd_params *p, int32_t *list, dd_length_classes *out);
+
+// ---- launch.cpp ----
+// One (haplotype-length class, read-length class) of a ragged batch: the launch plan (K, LDS tile) is made for
+// the class' own maxima instead of the batch-wide ones.
+struct LenClass {
+    const int32_t *hap_list = nullptr;   // device: haplotype indices of the class (sorted); nullptr = all haplotypes
+    int list_begin = 0, list_end = 0;    // range of hap_list this launch covers
+    int max_hap_len = 0, max_read_len = 0, min_read_len = 1;
+    int max_window_reads = 0, avg_window_reads = 0;   // reads of the class per window of the list (0 = not known)
+    int avg_read_len = 0;                             // mean length of the class' reads (0 = not known)
+    bool run_onhap = true;
+};
+// launch class L over its whole list; class_list: the device copy of the batch's class list
+LenClass len_class_of(const dd_launch_class &L, const int32_t *class_list, bool run_onhap);
+// Enqueue the path for haplotypes [hap_begin, hap_end) and reads [read_begin, read_end) of the batch (a
+// contiguous block of windows); hap_end < 0 means the whole batch.
+// overlapping_chunks: the caller alternates chunk launches between two streams (the host-pointer path)
+int launch_range(Model model, const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes,
+                 void *stream, int hap_begin, int hap_end, int read_begin, int read_end, bool overlapping_chunks, const LenClass *lc = nullptr);
+void launch_log_clear();
+
+static_assert(DD_LONG_LOG_FIELDS == DD_FASTER_LONG_LOG_FIELDS, "one record type serves both logs");
+struct LongRec {
+    int64_t v[DD_LONG_LOG_FIELDS];
+    const unsigned long long *stats;     // device words the launch counts into
+    hipStream_t stream;
+};
+// One long path: its name in the error texts, its stats words and the log fields they fill, and this thread's launch log.
+struct LongPath {
+    const char *name, *ws_fn;
+    int n_stats, stat_field[4];          // stats word i -> log field stat_field[i] (-1: none); also the stride of compute_likelihoods' stats words per window block
+    int (*launch_range)(const dd_params *, const dd_device_batch *, const dd_result *, void *, size_t, void *, int, int, int, int, unsigned long long *);
+    size_t (*workspace_bytes)(const dd_params *, const dd_device_batch *);
+    std::vector<LongRec> log;
+};
+extern thread_local LongPath g_long, g_flong;
+} // namespace ddh
+#endif

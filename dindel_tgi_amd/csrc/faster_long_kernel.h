@@ -1,4 +1,4 @@
-// faster_long_kernel.h — argument block and launcher of the --faster model's long-window kernel (faster_long_kernel.hip), shared with capi.cpp.
+// faster_long_kernel.h — argument block and launcher of the --faster model's long-window kernel (faster_long_kernel.hip), shared with the host units (capi_internal.h).
 #ifndef DD_FASTER_LONG_KERNEL_H
 #define DD_FASTER_LONG_KERNEL_H
 #include <hip/hip_runtime.h>

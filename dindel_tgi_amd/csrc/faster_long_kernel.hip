@@ -85,7 +85,7 @@ __global__ void __launch_bounds__(1024) dd_faster_long_prepass(const FLArgs P)
     }
 }
 
-// 2 waves per SIMD at most, as dd_faster_kernel: the 16-source loops want ~200 VGPRs.  Resident workgroups per CU are LDS-limited (capi.cpp).
+// 2 waves per SIMD at most, as dd_faster_kernel: the 16-source loops want ~200 VGPRs.  Resident workgroups per CU are LDS-limited (plan.cpp).
 __global__ void __launch_bounds__(DD_FL_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) dd_faster_long_kernel(const FLArgs P)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

@@ -1,4 +1,4 @@
-// long_kernel.h — argument block and launchers of the long-window kernel (long_kernel.hip), shared with capi.cpp.
+// long_kernel.h — argument block and launchers of the long-window kernel (long_kernel.hip), shared with the host units (capi_internal.h).
 #ifndef DD_LONG_KERNEL_H
 #define DD_LONG_KERNEL_H
 #include <hip/hip_runtime.h>

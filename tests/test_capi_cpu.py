@@ -256,7 +256,7 @@ def test_length_classes_and_library_tables_on_the_host(lib):
     assert lib.dd_build_length_classes(C.byref(b), None, C.byref(p), lst.ctypes.data_as(capi.c_i32p), C.byref(cls)) == 0
     hl = np.diff(pb.a["hap_seq_off"])
     rl = np.diff(pb.a["read_seq_off"])
-    hc = np.searchsorted(capi.HAP_CLASS_BOUNDS, hl, side="left")             # one class per lane tiling (capi.cpp kHapClasses)
+    hc = np.searchsorted(capi.HAP_CLASS_BOUNDS, hl, side="left")             # one class per lane tiling (plan.cpp kHapClasses)
     hw = np.repeat(np.arange(pb.n_windows), np.diff(pb.a["win_hap_off"]))
     # every window here has ONE read, so each haplotype is in exactly one launch: that of (its tiling, its read's interval)
     launches = [cls.launch[i] for i in range(cls.n_launches)]

@@ -8,7 +8,8 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FILES = ["include/dindel_hmm.h", "oracle/dd_oracle.c", "oracle/dd_oracle.h", "oracle/ref_bits.cpp", "DESIGN.md", "INTEGRATION.md",
          "dindel_tgi_amd/csrc/hmm_kernel.hip", "dindel_tgi_amd/csrc/faster_kernel.hip", "dindel_tgi_amd/csrc/genotype_kernel.hip",
-         "dindel_tgi_amd/csrc/capi.cpp", "dindel_tgi_amd/host/compute_likelihoods.hpp", "dindel_tgi_amd/host/compute_likelihoods.cpp",
+         "dindel_tgi_amd/csrc/capi_internal.h", "dindel_tgi_amd/csrc/plan.cpp", "dindel_tgi_amd/csrc/batch_host.cpp",
+         "dindel_tgi_amd/csrc/launch.cpp", "dindel_tgi_amd/csrc/host_path.cpp", "dindel_tgi_amd/host/compute_likelihoods.hpp", "dindel_tgi_amd/host/compute_likelihoods.cpp",
          "dindel_tgi_amd/host/genotype.hpp", "dindel_tgi_amd/host/genotype.cpp", "dindel_tgi_amd/host/cigar.hpp",
          "dindel_tgi_amd/host/cigar.cpp", "dindel_tgi_amd/host/dindel_types.hpp", "dindel_tgi_amd/host/glf_output.hpp",
          "dindel_tgi_amd/host/glf_to_vcf.hpp", "dindel_tgi_amd/host/glf_to_vcf.cpp", "dindel_tgi_amd/host/bam_reader.hpp",
@@ -27,7 +28,7 @@ def test_reference_citations_point_inside_the_files():
         for m in pat.finditer(open(os.path.join(ROOT, rel)).read()):
             name, a, b = m.group(1), int(m.group(2)), int(m.group(3) or m.group(2))
             if name not in nlines:
-                continue                                  # our own files (hmm_kernel.hip:…, capi.cpp …) are not reference citations
+                continue                                  # our own files (hmm_kernel.hip:…, plan.cpp …) are not reference citations
             n += 1
             if not (1 <= a <= b <= nlines[name]):
                 bad.append((rel, m.group(0), nlines[name]))

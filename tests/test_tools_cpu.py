@@ -95,3 +95,20 @@ _Zkernel_ok:
             n += 1
             assert C.check(body) == [], (path, name)
     assert n >= 100          # every instantiation of the main kernel was looked at
+
+
+def test_host_equivalence_tool_runs_and_repeats(tmp_path):
+    """tools/host_equivalence.py (the text record of the library's host decisions that two builds are compared by): at its reduced
+    grid it runs on the built library without a GPU, writes as many records as it reports, and two runs give the same file."""
+    tool = os.path.join(ROOT, "tools", "host_equivalence.py")
+    outs = []
+    for name in ("a.txt", "b.txt"):
+        r = subprocess.run([sys.executable, tool, str(tmp_path / name), "--reduced"], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        text = (tmp_path / name).read_text()
+        n = int(r.stdout.split("host_equivalence:")[1].split()[0])
+        assert n > 1000 and n == len(text.splitlines())
+        outs.append(text)
+    assert outs[0] == outs[1]
+    for kind in ("plan ", "plan DD_FORCE_GBT=1", "ws ", "ws-long ", "classes ", "screen-ex ", "sizes ", "partition ", "tables ", "refused "):
+        assert any(line.startswith(kind) for line in outs[0].splitlines()), kind

@@ -6,6 +6,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 SRC=$R/dindel_tgi_amd/csrc
 name=$1; K=$2; D=$3; shift 3
 mkdir -p $R/tools/_ab
+cd "$SRC"   # the sources of the library are named in csrc/Makefile only
 /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -fPIC -std=c++17 -ffp-contract=off -Wno-unused-result -DDD_ONLY_K=$K -DDD_ONLY_D=$D "$@" -I$SRC \
-    -shared -o $R/tools/_ab/lib_$name.so $SRC/hmm_kernel.hip $SRC/genotype_kernel.hip $SRC/faster_kernel.hip $SRC/capi.cpp
+    -shared -o $R/tools/_ab/lib_$name.so $(make -s print-sources)
 echo built tools/_ab/lib_$name.so

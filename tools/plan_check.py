@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Does the launch plan (LDS back-pointer tile vs HBM scratch, capi.cpp make_plan) pick the faster build?  For a grid of
+"""Does the launch plan (LDS back-pointer tile vs HBM scratch, plan.cpp make_plan) pick the faster build?  For a grid of
 (read length, haplotype length, maxLengthDel) the default plan is timed against both forced variants (DD_FORCE_GBT=0/1,
 where the shape allows them).  Prints one line per point and flags points where the default loses more than 5 %."""
 import json
