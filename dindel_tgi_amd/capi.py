@@ -33,6 +33,12 @@ DD_OPT_LONG_WINDOWS_FASTER = 2     # the --faster model's own long-window option
 DD_FASTER_LONG_WS_BUDGET = 512 << 20
 DD_WIN_MAIN, DD_WIN_UNSUPPORTED, DD_WIN_LONG = 0, 1, 2
 DD_LONG_WS_BUDGET = 512 << 20
+# device-side getCIGAR (opt-in): per-pair status codes, in the order of host/cigar.cpp's throw strings
+(DD_CIGAR_OK, DD_CIGAR_HAP_NOT_ALIGNED, DD_CIGAR_ERROR1, DD_CIGAR_ERROR2, DD_CIGAR_ERROR3, DD_CIGAR_ERROR4, DD_CIGAR_IMPOSSIBLE,
+ DD_CIGAR_OVERFLOW, DD_CIGAR_NOT_COMPUTED) = range(9)
+DD_CIGAR_DEFAULT_OPS_CAP = 8
+CIGAR_MESSAGES = {DD_CIGAR_HAP_NOT_ALIGNED: "Haplotype has not been aligned!", DD_CIGAR_ERROR1: "Error(1)!", DD_CIGAR_ERROR2: "Error(2)!",
+                  DD_CIGAR_ERROR3: "Error(3)!", DD_CIGAR_ERROR4: "Error(4)!", DD_CIGAR_IMPOSSIBLE: "How is this possible? (1)"}
 
 
 class dd_params(C.Structure):
@@ -126,6 +132,12 @@ class dd_length_classes(C.Structure):
     _fields_ = [("n_launches", C.c_int32), ("list_len", C.c_int32), ("launch", dd_launch_class * (N_HAP_CLASSES * N_READ_CLASSES))]
 
 
+class dd_cigar_result(C.Structure):
+    """Per pair: n_ops (int32), ops (uint32 [ops_cap]), ref_off (int32), status (int32).  Raw addresses: host arrays for
+    dd_compute_likelihoods_cigars, device arrays for dd_cigars_device."""
+    _fields_ = [("n_ops", C.c_void_p), ("ops", C.c_void_p), ("ref_off", C.c_void_p), ("status", C.c_void_p)]
+
+
 class dd_device_result(C.Structure):
     """dd_result with raw device addresses (same layout: every member is a pointer)."""
     _fields_ = [(n, C.c_void_p) for n, _ in RESULT_FIELDS]
@@ -136,7 +148,8 @@ EXPORTS = ["dd_params_struct_defaults", "dd_params_cli_defaults", "dd_batch_size
            "dd_launch_device", "dd_kernel_name", "dd_last_launch", "dd_launch_log", "dd_last_direct_outputs", "dd_pair_sum_offsets", "dd_pair_sums_device",
            "dd_pair_sums", "dd_map_pairs_device", "dd_map_pairs", "dd_last_error", "dd_abi_version", "dd_device_count",
            "dd_screen_windows_ex", "dd_compute_likelihoods_ex", "dd_workspace_bytes_long", "dd_launch_device_long", "dd_long_launch_log",
-           "dd_compute_likelihoods_faster_ex", "dd_workspace_bytes_faster_long", "dd_launch_device_faster_long", "dd_faster_long_launch_log"]
+           "dd_compute_likelihoods_faster_ex", "dd_workspace_bytes_faster_long", "dd_launch_device_faster_long", "dd_faster_long_launch_log",
+           "dd_cigars_device", "dd_compute_likelihoods_cigars"]
 
 _lib = None
 
@@ -202,6 +215,10 @@ def load():
     lib.dd_workspace_bytes_faster_long.restype = C.c_size_t
     lib.dd_launch_device_faster_long.argtypes = lib.dd_launch_device_long.argtypes
     lib.dd_faster_long_launch_log.argtypes = [c_i64p, C.c_int]
+    lib.dd_cigars_device.argtypes = [C.POINTER(dd_device_batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(dd_cigar_result),
+                                     C.c_int, C.c_void_p]
+    lib.dd_compute_likelihoods_cigars.argtypes = [C.POINTER(dd_params), C.POINTER(dd_batch), C.POINTER(dd_result), c_i32p, c_u8p,
+                                                  C.POINTER(dd_cigar_result), C.c_int, C.c_int, C.c_uint32]
     lib.dd_last_launch.argtypes = [C.POINTER(C.c_int32 * 8)]
     lib.dd_last_launch.restype = None
     lib.dd_launch_log.argtypes = [c_i32p, C.c_int]
@@ -281,6 +298,18 @@ def hpos_reference_codes(hpos):
     h = np.asarray(hpos).copy()
     h[h < DD_HPOS_INS_KEY0] = DD_HPOS_INS
     return h
+
+
+def cigar_ops(ops, n_ops):
+    """One pair's operations as [(op, len)] (op 0 = M, 1 = I, 2 = D, 4 = S): the first n_ops words of its ops row."""
+    return [(int(v) & 15, int(v) >> 4) for v in list(ops)[:int(n_ops)]]
+
+
+def cigar_string(ops, n_ops):
+    """One pair's CIGAR as text, e.g. '3S40M2I57M'; needs n_ops <= len(ops) (DD_CIGAR_OVERFLOW pairs hold only their first ops_cap operations)."""
+    if int(n_ops) > len(ops):
+        raise ValueError("the pair has %d operations, %d were kept (DD_CIGAR_OVERFLOW)" % (int(n_ops), len(ops)))
+    return "".join("%d%s" % (ln, "MIDNSHP=X"[op]) for op, ln in cigar_ops(ops, n_ops))
 
 
 def kernel_source_id(kernel="dd_hmm_kernel"):

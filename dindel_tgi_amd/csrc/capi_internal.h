@@ -12,6 +12,7 @@
 #include "hmm_kernel.h"
 #include "long_kernel.h"
 #include "faster_long_kernel.h"
+#include "cigar_kernel.h"
 
 namespace ddh {
 constexpr size_t kCuLdsBytes = 160u * 1024u;   // LDS of one CU (gfx950)
@@ -111,6 +112,11 @@ LenClass len_class_of(const dd_launch_class &L, const int32_t *class_list, bool 
 int launch_range(Model model, const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes,
                  void *stream, int hap_begin, int hap_end, int read_begin, int read_end, bool overlapping_chunks, const LenClass *lc = nullptr);
 void launch_log_clear();
+// the CIGAR launch (cigar_kernel.hip) over the pairs [pair_begin, pair_end) of the batch; pair_end < 0 = all of them (win_pair_off is a
+// device array: a caller that wants a range knows its bounds)
+int launch_cigars_range(const dd_device_batch *b, const int16_t *hpos_dev, const int32_t *status_dev, const int32_t *hap_ref_pos_dev,
+                        const uint8_t *hap_aligned_dev, const dd_cigar_result *out_dev, int ops_cap, void *stream, int64_t pair_begin,
+                        int64_t pair_end);
 
 static_assert(DD_LONG_LOG_FIELDS == DD_FASTER_LONG_LOG_FIELDS, "one record type serves both logs");
 struct LongRec {

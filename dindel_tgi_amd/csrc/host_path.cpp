@@ -192,7 +192,14 @@ struct StageClock {
     ~StageClock() { if (on) fprintf(stderr, "dd_timing:%s\n", line.c_str()); }
 };
 
-int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options = 0)
+// dd_compute_likelihoods_cigars: the haplotypes' reference positions in, the pairs' CIGARs out (host pointers)
+struct CigarRequest {
+    const int32_t *hap_ref_pos; const uint8_t *hap_aligned;
+    dd_cigar_result out; int ops_cap;
+};
+
+int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options = 0,
+                             const CigarRequest *cg = nullptr)
 {
     StageClock clk;
     launch_log_clear();
@@ -305,11 +312,13 @@ int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b,
                             (size_t)(sz.n_reads + 1) * 4 + (size_t)sz.read_bases * 2 + (size_t)sz.n_reads * 6 + n_var * 20 +
                             (size_t)sz.n_haps * 4 + (size_t)lcls.list_len * 4 + 64 + DD_TABLE_DOUBLES * 8 + 48 * 256 + (size_t)W + 256 +
                             (lib_log95.empty() ? 0 : (size_t)sz.n_reads * 9 + (lib_logprob.size() + lib_log95.size()) * 8 + (size_t)(b->n_libs + 1) * 4);
-    const size_t out_bytes = np * (4 * 8 + 2 + 8 * 2 + 4) + (size_t)sz.hpos_len * 2 + 2 * (size_t)sz.var_cov_len + (size_t)sz.n_reads + 24 * 256;
-    const bool staged = in_bytes + out_bytes <= (size_t)64 << 20;    // small batch: one H2D, one D2H through the pinned mirror
+    const size_t cigar_in = cg ? (size_t)sz.hap_bases * 4 + (size_t)sz.n_haps + 2 * 256 : 0;
+    const size_t cigar_out = cg ? np * (12 + 4 * (size_t)cg->ops_cap) + 4 * 256 : 0;
+    const size_t out_bytes = np * (4 * 8 + 2 + 8 * 2 + 4) + (size_t)sz.hpos_len * 2 + 2 * (size_t)sz.var_cov_len + (size_t)sz.n_reads + 24 * 256 + cigar_out;
+    const bool staged = in_bytes + cigar_in + out_bytes <= (size_t)64 << 20;    // small batch: one H2D, one D2H through the pinned mirror
     DeviceCtx &ctx = g_ctx.c;
     const size_t long_bytes = lws_bytes ? 2 * (lws_bytes + 256) + 32 * 64 + 256 : 0;
-    if ((rc = ctx.reserve(device, in_bytes + out_bytes + 2 * (ws_bytes + 256) + long_bytes, staged ? in_bytes + out_bytes : 0))) return rc;
+    if ((rc = ctx.reserve(device, in_bytes + cigar_in + out_bytes + 2 * (ws_bytes + 256) + long_bytes, staged ? in_bytes + cigar_in + out_bytes : 0))) return rc;
     clk.mark("reserve");
     DevBuf dev(ctx);
     dev.staged = staged;
@@ -360,6 +369,12 @@ int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b,
         if ((rc = dev.upload(&db.lib_log95, (const double *)lib_log95.data(), lib_log95.size()))) return rc;
     }
     if (!single_class && (rc = dev.upload(&class_list_dev, (const int32_t *)class_list.data(), (size_t)lcls.list_len))) return rc;
+    const int32_t *hap_ref_pos_dev = nullptr;
+    const uint8_t *hap_aligned_dev = nullptr;
+    if (cg) {
+        if ((rc = dev.upload(&hap_ref_pos_dev, cg->hap_ref_pos, (size_t)sz.hap_bases))) return rc;
+        if (cg->hap_aligned && (rc = dev.upload(&hap_aligned_dev, cg->hap_aligned, (size_t)sz.n_haps))) return rc;
+    }
     if ((rc = dev.flush_uploads(ctx.s[0]))) return rc;       // staged mode: the one H2D copy
     if (!staged) HIP_TRY(hipStreamSynchronize(nullptr));     // pageable uploads went through the null stream's DMA
     clk.mark("upload");
@@ -385,9 +400,24 @@ int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b,
         else if ((rc = dev.alloc(&dr.f, n))) return rc; }
     DD_RESULT_FIELDS(OUT)
 #undef OUT
+    // a CIGAR request reads hpos on the device: alignments the caller wants in page-locked memory are then staged in HBM and copied back
+    // like pageable ones, instead of being read back over the link by the CIGAR kernel
+    if (cg && direct.hpos) {
+        if ((rc = dev.alloc(&dr.hpos, (size_t)sz.hpos_len))) return rc;
+        direct.hpos = false; n_direct--;
+    }
     g_last_direct = n_direct;
     if (r->onHap && !r->offHapHMQ && (rc = dev.alloc(&dr.offHapHMQ, np))) return rc;   // onHap is derived from it
+    // CIGARs: the per-base alignments are needed on the device even when the caller does not want them back (r->hpos == NULL: nothing of
+    // them is copied), and the CIGAR arrays come back with the other outputs
+    dd_cigar_result dcg;
+    memset(&dcg, 0, sizeof(dcg));
+    if (cg) {
+        if ((rc = dev.alloc(&dcg.n_ops, np)) || (rc = dev.alloc(&dcg.ref_off, np)) || (rc = dev.alloc(&dcg.status, np)) ||
+            (rc = dev.alloc(&dcg.ops, np * (size_t)cg->ops_cap))) return rc;
+    }
     const size_t out_end = dev.used;
+    if (cg && !dr.hpos && (rc = dev.alloc(&dr.hpos, (size_t)sz.hpos_len))) return rc;   // (behind the outputs: not part of the staged copy back)
     unsigned char *ws[2] = {nullptr, nullptr};
     for (int i = 0; i < 2; i++)
         if (ws_bytes && (rc = dev.alloc(&ws[i], ws_bytes))) return rc;
@@ -424,6 +454,13 @@ int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b,
         hipStream_t st = streams.s[c & 1];
         const int w0 = cw[c], w1 = cw[c + 1];
         DD_RESULT_FIELDS(DOWN)
+        if (cg && pair_off[w1] > pair_off[w0]) {
+            const size_t p0 = (size_t)pair_off[w0], n = (size_t)(pair_off[w1] - pair_off[w0]), cap = (size_t)cg->ops_cap;
+            HIP_TRY(hipMemcpyAsync(cg->out.n_ops + p0, dcg.n_ops + p0, n * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(cg->out.ref_off + p0, dcg.ref_off + p0, n * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(cg->out.status + p0, dcg.status + p0, n * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(cg->out.ops + p0 * cap, dcg.ops + p0 * cap, n * cap * 4, hipMemcpyDeviceToHost, st));
+        }
         return DD_SUCCESS;
     };
     auto enqueue_and_collect = [&]() -> int {
@@ -455,6 +492,12 @@ int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b,
             for (int w = w0; w < w1 && !any; w++) any = win_skip[(size_t)w] == DD_WIN_LONG;
             if (any && (rc = long_path.launch_range(p, &db, &dr, lws[c & 1], lws_bytes, streams.s[c & 1], w0, w1, q0, q1, long_stats + long_path.n_stats * c))) return rc;
         }
+        // the block's CIGARs, behind its likelihood launches on the same stream (its ops start out zero: a pair's unused slots are defined)
+        if (cg && pair_off[w1] > pair_off[w0]) {
+            HIP_TRY(hipMemsetAsync(dcg.ops + (size_t)pair_off[w0] * cg->ops_cap, 0, (size_t)(pair_off[w1] - pair_off[w0]) * cg->ops_cap * 4, streams.s[c & 1]));
+            if ((rc = launch_cigars_range(&db, dr.hpos, dr.status, hap_ref_pos_dev, hap_aligned_dev, &dcg, cg->ops_cap, streams.s[c & 1],
+                                          pair_off[w0], pair_off[w1]))) return rc;
+        }
         if (!staged && c > 0 && (rc = download(c - 1))) return rc;
     }
     if (staged) {
@@ -465,6 +508,13 @@ int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b,
             if (r->f && n && !direct.f) memcpy(r->f, ctx.pinned + (reinterpret_cast<unsigned char *>(dr.f) - ctx.arena), n * sizeof(*r->f)); }
         DD_RESULT_FIELDS(BACK)
 #undef BACK
+        if (cg) {
+            const size_t cap = (size_t)cg->ops_cap;
+            memcpy(cg->out.n_ops, ctx.pinned + (reinterpret_cast<unsigned char *>(dcg.n_ops) - ctx.arena), np * 4);
+            memcpy(cg->out.ref_off, ctx.pinned + (reinterpret_cast<unsigned char *>(dcg.ref_off) - ctx.arena), np * 4);
+            memcpy(cg->out.status, ctx.pinned + (reinterpret_cast<unsigned char *>(dcg.status) - ctx.arena), np * 4);
+            memcpy(cg->out.ops, ctx.pinned + (reinterpret_cast<unsigned char *>(dcg.ops) - ctx.arena), np * cap * 4);
+        }
     } else {
         if ((rc = download(n_chunks - 1))) return rc;
         HIP_TRY(hipStreamSynchronize(streams.s[0]));
@@ -729,6 +779,17 @@ int dd_compute_likelihoods_ex(const dd_params *p, const dd_batch *b, dd_result *
 {
     if (options & ~DD_OPT_LONG_WINDOWS) return fail(DD_ERR_INVALID, "unknown option bits");
     return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device, options);
+}
+int dd_compute_likelihoods_cigars(const dd_params *p, const dd_batch *b, dd_result *r, const int32_t *hap_ref_pos, const uint8_t *hap_aligned,
+                                  const dd_cigar_result *cig, int ops_cap, int device, uint32_t options)
+{
+    if (options & ~DD_OPT_LONG_WINDOWS) return fail(DD_ERR_INVALID, "unknown option bits");
+    if (!hap_ref_pos) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_cigars: hap_ref_pos is required (Haplotype::refHpos per haplotype base)");
+    if (ops_cap < 1) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_cigars: ops_cap must be at least 1");
+    if (!cig || !cig->n_ops || !cig->ops || !cig->ref_off || !cig->status)
+        return fail(DD_ERR_INVALID, "dd_compute_likelihoods_cigars: every array of dd_cigar_result is required");
+    const CigarRequest cg = {hap_ref_pos, hap_aligned, *cig, ops_cap};
+    return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device, options, &cg);
 }
 int dd_compute_likelihoods_faster(const dd_params *p, const dd_batch *b, dd_result *r, int device)
 {

@@ -238,6 +238,30 @@ LenClass len_class_of(const dd_launch_class &L, const int32_t *class_list, bool 
     return lc;
 }
 
+// ---------------- device-side getCIGAR (cigar_kernel.hip) ----------------
+int launch_cigars_range(const dd_device_batch *b, const int16_t *hpos_dev, const int32_t *status_dev, const int32_t *hap_ref_pos_dev,
+                        const uint8_t *hap_aligned_dev, const dd_cigar_result *out_dev, int ops_cap, void *stream, int64_t pair_begin,
+                        int64_t pair_end)
+{
+    if (!b || !hpos_dev || !out_dev) return fail(DD_ERR_INVALID, "dd_cigars_device: null batch, hpos or output block");
+    if (!hap_ref_pos_dev) return fail(DD_ERR_INVALID, "dd_cigars_device: hap_ref_pos is required (Haplotype::refHpos per haplotype base)");
+    if (ops_cap < 1) return fail(DD_ERR_INVALID, "dd_cigars_device: ops_cap must be at least 1");
+    if (!out_dev->n_ops || !out_dev->ops || !out_dev->ref_off || !out_dev->status) return fail(DD_ERR_INVALID, "dd_cigars_device: every array of dd_cigar_result is required");
+    if (b->n_windows <= 0 || b->n_haps <= 0 || b->n_reads <= 0 || (pair_end >= 0 && pair_end <= pair_begin)) return DD_SUCCESS;
+    if (!b->win_hap_off || !b->win_read_off || !b->hap_seq_off || !b->read_seq_off || !b->win_pair_off || !b->win_hpos_off)
+        return fail(DD_ERR_INVALID, "dd_cigars_device: the batch lacks an offset array");
+    ddc::CigarArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n_windows = b->n_windows; A.pair_begin = pair_begin; A.pair_end = pair_end;
+    A.win_hap_off = b->win_hap_off; A.win_read_off = b->win_read_off; A.hap_seq_off = b->hap_seq_off; A.read_seq_off = b->read_seq_off;
+    A.win_pair_off = b->win_pair_off; A.win_hpos_off = b->win_hpos_off;
+    A.hpos = hpos_dev; A.pair_status = status_dev; A.hap_ref_pos = hap_ref_pos_dev; A.hap_aligned = hap_aligned_dev;
+    A.out = *out_dev; A.ops_cap = ops_cap;
+    A.max_pairs = pair_end >= 0 ? pair_end - pair_begin : (int64_t)b->n_haps * b->n_reads;
+    HIP_TRY(ddc::launch_cigars(A, static_cast<hipStream_t>(stream)));
+    return DD_SUCCESS;
+}
+
 // ---------------- long windows: what the two long paths share (long_kernel.hip for the main model, faster_long_kernel.hip for --faster) ----------------
 // The front checks of a long launch.  1: nothing to do (empty batch or range), 0: go on, < 0: error.
 static int long_front_checks(const LongPath &lp, const dd_params *p, const dd_device_batch *b, const dd_result *r, int w_begin, int w_end)
@@ -414,6 +438,12 @@ int dd_launch_device(const dd_params *p, const dd_device_batch *b, const dd_resu
 int dd_launch_device_faster(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *stream)
 {
     return launch_range(MODEL_S, p, b, r, nullptr, 0, stream, 0, -1, 0, 0, false);
+}
+
+int dd_cigars_device(const dd_device_batch *b, const int16_t *hpos_dev, const int32_t *status_dev, const int32_t *hap_ref_pos_dev,
+                     const uint8_t *hap_aligned_dev, const dd_cigar_result *out_dev, int ops_cap, void *stream)
+{   // the whole batch: the pair count is win_pair_off[n_windows], a device array, so the kernel reads its own bound there
+    return launch_cigars_range(b, hpos_dev, status_dev, hap_ref_pos_dev, hap_aligned_dev, out_dev, ops_cap, stream, 0, -1);
 }
 
 int dd_pair_sums_device(const dd_device_batch *b, const int64_t *win_hh_off_dev, int64_t n_slots,

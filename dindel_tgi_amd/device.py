@@ -28,13 +28,17 @@ def _to_dev(arr, device):
 class DeviceBatch:
     """A PackedBatch resident in HBM + the dd_device_batch that points at it."""
 
-    def __init__(self, pb: PackedBatch, params: capi.dd_params, device="cuda:0", long_windows=False, long_windows_faster=False):
+    def __init__(self, pb: PackedBatch, params: capi.dd_params, device="cuda:0", long_windows=False, long_windows_faster=False,
+                 cigars=False, ops_cap=capi.DD_CIGAR_DEFAULT_OPS_CAP, hap_ref_pos=None, hap_aligned=None):
         """long_windows: windows beyond the main kernels' limits (haplotypes up to 4,094 bp, reads up to 4,096 bp, and with maxLengthDel
         12..31 haplotypes over 574 bp) are computed by the long-window kernel after the main launch (dd_launch_device_long) instead of
         being marked DD_PAIR_UNSUPPORTED.  Off by default.
         long_windows_faster: the same for the --faster model: the batch is screened for that model (haplotypes over 766 bp or reads over
         1,024 bp, within the same long limits), and launch_faster() follows its main launch with dd_launch_device_faster_long.  A resident
-        batch is screened once, for one model: both flags together raise ValueError, and launch() on such a batch raises."""
+        batch is screened once, for one model: both flags together raise ValueError, and launch() on such a batch raises.
+        cigars: launch_cigars() turns the pairs' hpos into CIGARs on the device (dd_cigars_device) and results() also returns cigar_n_ops,
+        cigar_ops [n_pairs, ops_cap], cigar_ref_off and cigar_status.  hap_ref_pos: Haplotype::refHpos, one int32 per haplotype base
+        (laid out like hap_seq); hap_aligned: one byte per haplotype, 0 = not aligned (None = all aligned).  Off by default."""
         if long_windows and long_windows_faster:
             raise ValueError("long_windows and long_windows_faster screen the batch for different models: one resident batch, one screening")
         lib = capi.load()
@@ -131,6 +135,28 @@ class DeviceBatch:
         ws_long = lib.dd_workspace_bytes_faster_long if self.long_windows_faster else lib.dd_workspace_bytes_long
         self.long_ws_bytes = int(ws_long(C.byref(params), C.byref(db))) if self.n_long else 0
         self.long_ws = torch.empty(max(self.long_ws_bytes, 8), dtype=torch.uint8, device=self.device) if self.n_long else None
+        self.cigars = bool(cigars)
+        if self.cigars:
+            if hap_ref_pos is None:
+                raise ValueError("cigars=True needs hap_ref_pos (Haplotype::refHpos per haplotype base)")
+            hrp = np.ascontiguousarray(hap_ref_pos, np.int32)
+            if hrp.shape != (int(a["hap_seq_off"][pb.n_haps]),):
+                raise ValueError("hap_ref_pos must hold one entry per haplotype base")
+            if ops_cap < 1:
+                raise ValueError("ops_cap must be at least 1")
+            self.ops_cap = int(ops_cap)
+            t["hap_ref_pos"] = _to_dev(hrp, self.device)
+            if hap_aligned is not None:
+                hal = np.ascontiguousarray(hap_aligned, np.uint8)
+                if hal.shape != (pb.n_haps,):
+                    raise ValueError("hap_aligned must hold one byte per haplotype")
+                t["hap_aligned"] = _to_dev(hal, self.device)
+            npair = max(pb.n_pairs, 1)
+            self.cig = {"n_ops": torch.zeros(npair, dtype=torch.int32, device=self.device),
+                        "ops": torch.zeros(npair * self.ops_cap, dtype=torch.int32, device=self.device),    # uint32 bits
+                        "ref_off": torch.zeros(npair, dtype=torch.int32, device=self.device),
+                        "status": torch.zeros(npair, dtype=torch.int32, device=self.device)}
+            self.dcig = capi.dd_cigar_result(*[self.cig[k].data_ptr() for k in ("n_ops", "ops", "ref_off", "status")])
 
     def launch(self, stream=None):
         """Enqueue the path on `stream` (default: torch's current stream on this device). Asynchronous."""
@@ -163,7 +189,27 @@ class DeviceBatch:
             if rc != 0:
                 raise RuntimeError("dd_launch_device_faster_long rc=%d: %s" % (rc, capi.last_error()))
 
+    def launch_cigars(self, stream=None):
+        """The CIGAR of every pair from the hpos of the last launch() / launch_faster() (same stream, behind it). Asynchronous."""
+        if not self.cigars:
+            raise RuntimeError("this batch was built without cigars=True")
+        lib = capi.load()
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        hal = self.t["hap_aligned"].data_ptr() if "hap_aligned" in self.t else None
+        rc = lib.dd_cigars_device(C.byref(self.db), C.c_void_p(self.out["hpos"].data_ptr()), C.c_void_p(self.out["status"].data_ptr()),
+                                  C.c_void_p(self.t["hap_ref_pos"].data_ptr()), C.c_void_p(hal), C.byref(self.dcig), self.ops_cap,
+                                  C.c_void_p(stream.cuda_stream))
+        if rc != 0:
+            raise RuntimeError("dd_cigars_device rc=%d: %s" % (rc, capi.last_error()))
+
     def results(self):
         """Host copies (numpy) of the outputs, trimmed to their logical lengths."""
         torch.cuda.synchronize(self.device)
-        return {k: self.out[k][:self._n[k]].cpu().numpy() for k, _ in capi.RESULT_FIELDS}
+        res = {k: self.out[k][:self._n[k]].cpu().numpy() for k, _ in capi.RESULT_FIELDS}
+        if self.cigars:
+            n = self.pb.n_pairs
+            for k in ("n_ops", "ref_off", "status"):
+                res["cigar_" + k] = self.cig[k][:n].cpu().numpy()
+            res["cigar_ops"] = self.cig["ops"][:n * self.ops_cap].cpu().numpy().view(np.uint32).reshape(n, self.ops_cap)
+        return res

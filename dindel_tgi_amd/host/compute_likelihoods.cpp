@@ -223,7 +223,10 @@ struct BatchBlock {
     RawBuf<uint8_t> offHap, offHapHMQ, vcov, fcov;
     RawBuf<int16_t> numIndels, numMismatch, nBQT, nmmBQT, nMMLeft, nMMRight, firstBase, lastBase, hpos;
     RawBuf<int32_t> status;
-    BatchBlock() : W(0), faster(false), has_hpos(false) {}
+    bool has_cigars; int cig_cap;                        // device CIGARs (setDeviceCigars): per pair, ops at pair * cig_cap
+    RawBuf<int32_t> cig_n_ops, cig_ref_off, cig_status;
+    RawBuf<uint32_t> cig_ops;
+    BatchBlock() : W(0), faster(false), has_hpos(false), has_cigars(false), cig_cap(0) {}
 };
 
 struct PackScratch {
@@ -234,6 +237,8 @@ struct PackScratch {
     RawBuf<uint8_t> read_qidx;           // H2D copy then runs at link speed instead of through the driver's staging buffers
     std::vector<uint8_t> read_mqidx, read_flags, read_lib;
     std::vector<int32_t> read_mate_pos, read_mate_len;
+    std::vector<int32_t> hap_ref_pos;    // device CIGARs: Haplotype::refHpos per haplotype base
+    std::vector<uint8_t> hap_aligned;    // ... and whether the haplotype has one
 };
 
 namespace {
@@ -363,6 +368,12 @@ double WindowLikelihoods::mLogBQ(size_t h, size_t r) const { return blk_->mLogBQ
 bool WindowLikelihoods::offHap(size_t h, size_t r) const { return blk_->offHap[pair(h, r)] != 0; }
 bool WindowLikelihoods::offHapHMQ(size_t h, size_t r) const { return blk_->offHapHMQ[pair(h, r)] != 0; }
 int WindowLikelihoods::numIndels(size_t h, size_t r) const { return blk_->numIndels[pair(h, r)]; }
+bool WindowLikelihoods::hasDeviceCigars() const { return blk_ && blk_->has_cigars; }
+int WindowLikelihoods::cigarOpsCap() const { return blk_->cig_cap; }
+int WindowLikelihoods::cigarStatus(size_t h, size_t r) const { return blk_->cig_status[pair(h, r)]; }
+int WindowLikelihoods::cigarNumOps(size_t h, size_t r) const { return blk_->cig_n_ops[pair(h, r)]; }
+const uint32_t *WindowLikelihoods::cigarOps(size_t h, size_t r) const { return blk_->cig_ops.p + size_t(pair(h, r)) * size_t(blk_->cig_cap); }
+int WindowLikelihoods::cigarRefOff(size_t h, size_t r) const { return blk_->cig_ref_off[pair(h, r)]; }
 int WindowLikelihoods::indelCount(size_t h, size_t r) const
 {
     const BatchBlock &B = *blk_;
@@ -471,10 +482,10 @@ MLAlignment WindowLikelihoods::get(size_t h, size_t r) const
         if (!eng_) throw std::string("WindowLikelihoods::get: batch was run without alignments and the engine is gone");
         std::vector<WindowJob> one(1);
         one[0].haps = haps_; one[0].reads = reads_; one[0].leftPos = leftPos_; one[0].rightPos = leftPos_ + 1;
-        const bool keep = eng_->keepAlignments_;
-        eng_->keepAlignments_ = true;
-        try { eng_->runBatch(one, blk_->faster); } catch (...) { eng_->keepAlignments_ = keep; throw; }
-        eng_->keepAlignments_ = keep;
+        const bool keep = eng_->keepAlignments_, cig = eng_->deviceCigars_;
+        eng_->keepAlignments_ = true; eng_->deviceCigars_ = false;
+        try { eng_->runBatch(one, blk_->faster); } catch (...) { eng_->keepAlignments_ = keep; eng_->deviceCigars_ = cig; throw; }
+        eng_->keepAlignments_ = keep; eng_->deviceCigars_ = cig;
         if (!one[0].error.empty()) throw one[0].error;
         full_ = one[0].result.blk_;
     }
@@ -560,7 +571,10 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
     B.W = W; B.faster = faster; B.params = params;
     bool any_eager = false;
     for (int w = 0; w < W; w++) if (jobs[w].liks) any_eager = true;
-    B.has_hpos = keepAlignments_ || any_eager;
+    // device CIGARs: the pairs' CIGARs come back instead of their alignments (main model, lazy jobs only)
+    B.has_cigars = deviceCigars_ && !faster && !any_eager;
+    B.cig_cap = cigarOpsCap_;
+    B.has_hpos = !B.has_cigars && (keepAlignments_ || any_eager);
 
     // ---- pack (CSR), pass 1: sizes and offsets.  Per window in parallel (its haplotypes and reads are scattered objects: the pass is
     // cache misses), one serial prefix sum over the windows in between ----
@@ -636,6 +650,7 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
     S.read_qidx.reserve(size_t(n_read_bases) + 1); S.read_mqidx.resize(n_reads + 1); S.read_start.resize(n_reads + 1);
     S.read_flags.resize(n_reads + 1); S.hap_var.resize(2 * n_var + 1); S.hap_var_flank.resize(3 * n_var + 1);
     if (with_mates) { S.read_mate_pos.resize(n_reads + 1); S.read_mate_len.resize(n_reads + 1); }
+    if (B.has_cigars) { S.hap_ref_pos.resize(size_t(n_hap_bases) + 1); S.hap_aligned.resize(n_haps + 1); }
 
     const std::chrono::steady_clock::time_point t_pass1 = std::chrono::steady_clock::now();
     // ---- pass 2: the bytes, windows in parallel ----
@@ -650,6 +665,12 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
                 const Haplotype &H = (*J.haps)[h];
                 const int g = B.win_hap_off[w] + int(h);
                 memcpy(S.hap_seq.data() + S.hap_seq_off[size_t(g)], H.seq.data(), H.seq.size());
+                if (B.has_cigars) {                       // `hapRefPos.size() != hapSize` is getCIGAR's "Haplotype has not been aligned!"
+                    const bool aligned = H.refHpos.size() == H.seq.size();
+                    S.hap_aligned[size_t(g)] = aligned ? 1 : 0;
+                    int32_t *hr = S.hap_ref_pos.data() + S.hap_seq_off[size_t(g)];
+                    for (size_t b = 0; b < H.seq.size(); b++) hr[b] = aligned ? int32_t(H.refHpos[b]) : 0;
+                }
                 int32_t *hv = S.hap_var.data() + 2 * size_t(B.hap_var_off[g]);
                 int32_t *hf = S.hap_var_flank.data() + 3 * size_t(B.hap_var_off[g]);
                 for (std::map<int, AlignedVariant>::const_iterator it = H.indels.begin(); it != H.indels.end(); ++it) {
@@ -742,13 +763,25 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
     Rz.onHap = NULL;                                    // derived from offHapHMQ on the host (WindowLikelihoods::onHap)
     Rz.var_fcov = B.fcov.reserve(size_t(sz.var_cov_len) + 1); Rz.var_covered = B.vcov.reserve(size_t(sz.var_cov_len) + 1);
     if (B.has_hpos) Rz.hpos = B.hpos.reserve(size_t(sz.hpos_len) + 1);
+    dd_cigar_result Cg;
+    memset(&Cg, 0, sizeof(Cg));
+    if (B.has_cigars) {
+        Cg.n_ops = B.cig_n_ops.reserve(np); Cg.ref_off = B.cig_ref_off.reserve(np); Cg.status = B.cig_status.reserve(np);
+        Cg.ops = B.cig_ops.reserve(np * size_t(B.cig_cap));
+    }
+    lastHposBytes = B.has_hpos ? size_t(sz.hpos_len) * sizeof(int16_t) : 0;
+    lastCigarBytes = B.has_cigars ? size_t(sz.n_pairs) * (12 + 4 * size_t(B.cig_cap)) : 0;
     dd_params P = to_abi(params);
     if (faster) P.mapUnmappedReads = 0;                 // ObservationModelS has no insert-size prior
     const std::chrono::steady_clock::time_point t_packed = std::chrono::steady_clock::now();
     if (getenv("DD_TIMING"))
         fprintf(stderr, "pack_timing: windows=%d pass1=%.2fms pass2+alloc=%.2fms\n", W, std::chrono::duration<double, std::milli>(t_pass1 - t_start).count(),
                 std::chrono::duration<double, std::milli>(t_packed - t_pass1).count());
-    if (sz.n_pairs > 0) {
+    if (sz.n_pairs > 0 && B.has_cigars) {
+        const int rc = dd_compute_likelihoods_cigars(&P, &Bt, &Rz, S.hap_ref_pos.data(), S.hap_aligned.data(), &Cg, B.cig_cap, device_,
+                                                     longWindows_ ? DD_OPT_LONG_WINDOWS : 0u);
+        if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_cigars: ") + dd_last_error();
+    } else if (sz.n_pairs > 0) {
         const int rc = faster ? (longWindowsFaster_ ? dd_compute_likelihoods_faster_ex(&P, &Bt, &Rz, device_, DD_OPT_LONG_WINDOWS_FASTER)
                                                     : dd_compute_likelihoods_faster(&P, &Bt, &Rz, device_))
                      : longWindows_ ? dd_compute_likelihoods_ex(&P, &Bt, &Rz, device_, DD_OPT_LONG_WINDOWS) : dd_compute_likelihoods(&P, &Bt, &Rz, device_);

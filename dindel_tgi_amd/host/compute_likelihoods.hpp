@@ -83,6 +83,16 @@ public:
     // the full record of one pair, built on demand (variant maps, align string, hpos).  If the batch was run without
     // alignments (setKeepAlignments(false)) the window is recomputed once through the engine and cached.
     MLAlignment get(size_t h, size_t r) const;
+    // Device CIGARs (LikelihoodEngine::setDeviceCigars): getCIGAR of pair (h, r) as the device computed it from the alignment it kept —
+    // status (DD_CIGAR_* of include/dindel_hmm.h: 0, the code of the string getCIGAR throws, DD_CIGAR_OVERFLOW, DD_CIGAR_NOT_COMPUTED),
+    // the operation count (also beyond cigarOpsCap()), the first min(count, cap) BAM words (len << 4 | op) and the reference offset of the
+    // first aligned base (-1: none).  Straight from the batch's result block, like the scalars.
+    bool hasDeviceCigars() const;
+    int cigarOpsCap() const;
+    int cigarStatus(size_t h, size_t r) const;
+    int cigarNumOps(size_t h, size_t r) const;
+    const uint32_t *cigarOps(size_t h, size_t r) const;
+    int cigarRefOff(size_t h, size_t r) const;
     // all records, as the eager path fills them
     void toLiks(std::vector<std::vector<MLAlignment> > &liks, std::vector<int> &onHap) const;
 
@@ -149,12 +159,20 @@ public:
     // No effect on the main model; default off.
     void setLongWindowsFaster(bool v) { longWindowsFaster_ = v; }
     bool longWindowsFaster() const { return longWindowsFaster_; }
+    // true: computeLikelihoodsBatch packs every haplotype's refHpos and asks for the pairs' CIGARs (dd_compute_likelihoods_cigars) INSTEAD of
+    // their per-base alignments: 4 opsCap + 12 bytes per pair come back instead of 2 L, and the lazy views expose them (hasDeviceCigars()).
+    // get() on such a view recomputes the window with alignments, as for setKeepAlignments(false).  Main model, lazy jobs only: a batch with an
+    // eager job, and the --faster model, run as without it.  Default off.
+    void setDeviceCigars(bool v, int opsCap = 8) { deviceCigars_ = v; cigarOpsCap_ = opsCap < 1 ? 1 : opsCap; }
+    bool deviceCigars() const { return deviceCigars_; }
     // optional: have the calling thread's device cache (arena, staging mirror, streams) of this engine's device made now, for batches of
     // about `pairs` (haplotype, read) pairs — e.g. while the first batch is still being prepared.  Throws like the batch calls.
     void warmUp(size_t pairs);
 
     // wall time of the last batch call's three stages (tools/host_adapter_bench.cpp, bench.py)
     double lastPackSeconds = 0.0, lastDeviceSeconds = 0.0, lastUnpackSeconds = 0.0;
+    // bytes of per-base alignments (hpos) and of CIGAR arrays the last batch call brought back from the device
+    size_t lastHposBytes = 0, lastCigarBytes = 0;
 
     // ObservationModelFBMax::reportVariants (ObservationModelFB.cpp:1351-1475) from the device's hpos: fills
     // hpos, indels, snps, align, firstBase/lastBase, counters and the covered maps.  Exposed for tests.
@@ -175,6 +193,8 @@ private:
     bool keepAlignments_;
     bool longWindows_ = false;
     bool longWindowsFaster_ = false;
+    bool deviceCigars_ = false;
+    int cigarOpsCap_ = 8;
     std::vector<std::shared_ptr<BatchBlock> > spare_;   // result blocks of earlier calls; one nobody references any more is reused (warm pages)
     unsigned spareNext_ = 0;
     std::shared_ptr<PackScratch> scratch_;   // the packed inputs' buffers, reused between calls

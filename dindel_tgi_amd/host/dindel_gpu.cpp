@@ -35,6 +35,12 @@
 //   [--maxHapReadProd N] [--batchWindows N] [--prepareThreads N] [--computeThreads N] [--packThreads N] [--reduceThreads N] [--device D | --devices D0,D1,...] [--quiet]
 //   [--outputRealignedBAM]   per window PREFIX.ra.INDEX_TID_LEFT_RIGHT.bam with the reads realigned through the most likely haplotype
 //                     pair (DInDel.cpp:589-620; main model only, like the reference; the haplotype file needs its A records)
+//   [--deviceCigars [--cigarOpsCap N]]  with --outputRealignedBAM: the reads' CIGARs are computed on the device from the alignments it keeps
+//                     (at most N operations per read, default 8) and come back instead of the per-base alignments; a read with more
+//                     operations is redone on the host from its window's alignments — the whole window is recomputed once for that, one
+//                     window at a time, so a small N costs a recompute per affected window — (counted in the timing line).  The files are the
+//                     same byte for byte.  The engines then merge as many batches per launch as without realigned BAMs.  No effect
+//                     without --outputRealignedBAM (main model, like that option)
 //   [--timing]        one "timing:" line on stdout with the busy time of each stage
 //   [--prepareOnly]   stop after the prepare stage (no likelihoods, no calls: profiling the read selection on a GPU-less host)
 //   [--windowByWindow] tests: the writer re-does every window one after the other with a read buffer of its own (the reference's loop as it stands)
@@ -193,6 +199,10 @@ int main(int argc, char **argv)
             "dindel_gpu: the --analysis indels --doDiploid window loop with the likelihood step on the GPU\n"
             "  required: --bamFile F --varFile F --hapFile F --outputFile PREFIX          (writes PREFIX.glf.txt)\n"
             "  model:    [--faster] [--libFile F] [--filterHaplotypes] [--outputRealignedBAM] [--varFileIsOneBased]\n"
+            "            [--deviceCigars]  with --outputRealignedBAM: compute the realigned reads' CIGARs on the device and bring them back instead of the\n"
+            "                             per-base alignments (same files); [--cigarOpsCap N] operations kept per read (default 8), reads with more\n"
+            "                             are redone on the host, which recomputes their whole window with alignments once (one window at a time:\n"
+            "                             a small N makes that the run's bottleneck); no effect without --outputRealignedBAM\n"
             "            [--longWindows]  compute windows with a haplotype > 766 bp or a read > 1024 bp (up to 4,094 / 4,096; with --maxLengthIndel >= 12\n"
             "                             also haplotypes > 574 bp) instead of skipping them; main model only: no effect with --faster\n"
             "            [--longWindowsFaster]  with --faster: compute windows with a haplotype > 766 bp or a read > 1024 bp (up to 4,094 / 4,096) instead of\n"
@@ -209,7 +219,7 @@ int main(int argc, char **argv)
         if (a.compare(0, 2, "--") != 0) { std::cerr << "Unknown argument " << a << "\n"; return 2; }
         a = a.substr(2);
         if (a == "varFileIsOneBased" || a == "faster" || a == "filterHaplotypes" || a == "quiet" || a == "doDiploid" || a == "timing" || a == "outputRealignedBAM" ||
-            a == "prepareOnly" || a == "noLookBack" || a == "lateSkipsKnown" || a == "windowByWindow" || a == "longWindows" || a == "longWindowsFaster") opt[a] = "1";
+            a == "prepareOnly" || a == "noLookBack" || a == "lateSkipsKnown" || a == "windowByWindow" || a == "longWindows" || a == "longWindowsFaster" || a == "deviceCigars") opt[a] = "1";
         else if (i + 1 < argc) opt[a] = argv[++i];
         else { std::cerr << "Option --" << a << " needs a value\n"; return 2; }
     }
@@ -241,6 +251,8 @@ int main(int argc, char **argv)
         const bool faster = has("faster"), oneBased = has("varFileIsOneBased"), prepareOnly = has("prepareOnly");
         const bool realignedBAM = has("outputRealignedBAM") && !faster;                  // `params.outputRealignedBAM && params.slower`, :589
         rsp.keepRecords = realignedBAM;
+        const bool deviceCigars = realignedBAM && has("deviceCigars");                   // modifies --outputRealignedBAM only
+        const int cigarOpsCap = std::max(1, int(num("cigarOpsCap", 8)));
         unsigned hw = std::thread::hardware_concurrency();
         if (!hw) hw = 1;
         // defaults measured on a 16-CPU share of an MI355X host (profiles/r03/n2_pipeline.md): per window the read selection costs
@@ -332,7 +344,8 @@ int main(int argc, char **argv)
         // 256 windows, 41.3 in one of 1,024, and one kernel boundary instead of four)
         // (default 4; 2 when the per-base alignments come back too — --faster, --outputRealignedBAM —: the page-locked result blocks of such a
         // launch are 0.4 GB each, and making them costs a 100,000-window run more than the launches save it)
-        const int mergeBatches = std::max(1, int(num("mergeBatches", (has("faster") || has("outputRealignedBAM")) ? 2 : 4)));
+        // (with --deviceCigars a realigned-BAM run brings no alignments back: 4 again)
+        const int mergeBatches = std::max(1, int(num("mergeBatches", (has("faster") || (has("outputRealignedBAM") && !deviceCigars)) ? 2 : 4)));
         OrderedChannel toCompute(std::max(1L, ahead)), toReduce(long(computeThreads) * mergeBatches + 1);
         auto fail = [&](const std::string &s) {
             { std::lock_guard<std::mutex> lk(fatal_m); if (fatal.empty()) fatal = s; }
@@ -419,6 +432,11 @@ int main(int argc, char **argv)
         std::vector<std::thread> computeWorkers;
         std::atomic<int> computeLeft(computeThreads);
         std::atomic<long> nLaunches(0);
+        std::atomic<long long> hposBytes(0), cigarBytes(0), fallbackHposBytes(0);   // what the engines brought back from the device
+        std::atomic<long> cigarFallbacks(0);                                        // reads redone with getCIGAR on the host (--deviceCigars)
+        // --deviceCigars: the engine that recomputes a window WITH alignments for a read whose CIGAR did not fit; made at the first such read
+        std::mutex fallback_m;
+        std::unique_ptr<LikelihoodEngine> fallbackEngine;
         std::vector<double> t_ready_of(size_t(computeThreads), 0.0);         // when each engine had its device context, arena and streams
         for (int ct = 0; ct < computeThreads; ct++) computeWorkers.push_back(std::thread([&, ct]() {
             BatchPtr b;
@@ -426,7 +444,8 @@ int main(int argc, char **argv)
                 LikelihoodEngine engine(obs, devices[size_t(ct) % devices.size()]);
                 engine.setThrowOnPositiveLikelihood(false);
                 // diploidGLF reads scalars and covered flags only; the --faster model's indel count (DInDel.cpp:3529) needs hpos
-                engine.setKeepAlignments(faster || realignedBAM);
+                engine.setKeepAlignments(faster || (realignedBAM && !deviceCigars));
+                engine.setDeviceCigars(deviceCigars, cigarOpsCap);
                 engine.setLongWindows(longWindows);
                 engine.setLongWindowsFaster(longWindowsFaster);
                 if (packThreads > 0) engine.setHostThreads(packThreads);
@@ -470,6 +489,7 @@ int main(int argc, char **argv)
                         }
                         t_pack_of[size_t(ct)] += engine.lastPackSeconds; t_device_of[size_t(ct)] += engine.lastDeviceSeconds;
                         t_unpack_of[size_t(ct)] += engine.lastUnpackSeconds;
+                        hposBytes += (long long)engine.lastHposBytes; cigarBytes += (long long)engine.lastCigarBytes;
                         nLaunches++;
                     }
                     t_compute_of[size_t(ct)] += seconds_since(t0);
@@ -502,7 +522,22 @@ int main(int argc, char **argv)
                         if (realignedBAM) {                                      // DInDel.cpp:589-620
                             const std::pair<int, int> best = maxLikelihoodPair(*T.haps, T.reads, J->result, int(T.leftPos), T.candidates, dip);
                             std::vector<CIGAR> cigars;
-                            realignedCigars(*T.haps, T.reads, J->result, best, int(T.leftPos), cigars);
+                            long fallbacks = 0;
+                            realignedCigars(*T.haps, T.reads, J->result, best, int(T.leftPos), cigars, [&]() -> WindowLikelihoods {
+                                std::lock_guard<std::mutex> lk(fallback_m);
+                                if (!fallbackEngine) {
+                                    fallbackEngine.reset(new LikelihoodEngine(obs, devices[0]));
+                                    fallbackEngine->setThrowOnPositiveLikelihood(false);
+                                    fallbackEngine->setLongWindows(longWindows);
+                                }
+                                std::vector<WindowJob> one(1);
+                                one[0].haps = T.haps; one[0].reads = &T.reads; one[0].leftPos = T.leftPos; one[0].rightPos = T.rightPos;
+                                fallbackEngine->computeLikelihoodsBatch(one);
+                                fallbackHposBytes += (long long)fallbackEngine->lastHposBytes;
+                                if (!one[0].error.empty()) throw std::string(one[0].error);
+                                return one[0].result;
+                            }, &fallbacks);
+                            cigarFallbacks += fallbacks;
                             std::vector<int> onHap(T.reads.size());
                             for (size_t r = 0; r < onHap.size(); r++) onHap[r] = J->result.onHap(r);
                             writeRealignedBAMFile(realignedBAMFileName(outputPrefix, T.index, T.tid, T.leftPos, T.rightPos, rsp.minReadOverlap),
@@ -545,7 +580,8 @@ int main(int argc, char **argv)
                     if (!redo.engine) {
                         redo.engine.reset(new LikelihoodEngine(obs, devices[0]));
                         redo.engine->setThrowOnPositiveLikelihood(false);
-                        redo.engine->setKeepAlignments(faster || realignedBAM);
+                        redo.engine->setKeepAlignments(faster || (realignedBAM && !deviceCigars));
+                        redo.engine->setDeviceCigars(deviceCigars, cigarOpsCap);
                         redo.engine->setLongWindows(longWindows);
                         redo.engine->setLongWindowsFaster(longWindowsFaster);
                     }
@@ -553,6 +589,7 @@ int main(int argc, char **argv)
                     J.haps = T.haps; J.reads = &T.reads; J.leftPos = T.leftPos; J.rightPos = T.rightPos;
                     one.push_back(J);
                     if (faster) redo.engine->computeLikelihoodsFasterBatch(one); else redo.engine->computeLikelihoodsBatch(one);
+                    hposBytes += (long long)redo.engine->lastHposBytes; cigarBytes += (long long)redo.engine->lastCigarBytes;
                 }
                 reduceWindow(T, one.empty() ? NULL : &one[0]);
                 redo.fetcher->windowDone(T.skipped, T.fileLeftPos);
@@ -711,6 +748,10 @@ int main(int argc, char **argv)
             if (from + 1 < progress.size() && progress.back().first > progress[from].first)
                 std::cout << " steady_windows_per_s=" << double(progress.back().second - progress[from].second) / (progress.back().first - progress[from].first);
             std::cout << " launches=" << nLaunches.load();
+            // bytes of per-base alignments / of CIGAR arrays the window loop's engines brought back; --deviceCigars: reads redone on the host
+            // and the alignment bytes those windows' recomputation brought back
+            std::cout << " hpos_bytes=" << hposBytes.load() << " cigar_bytes=" << cigarBytes.load() << " cigar_host_fallbacks=" << cigarFallbacks.load()
+                      << " fallback_hpos_bytes=" << fallbackHposBytes.load();
             // when the first batch and the first 1 / 5 / 20 / 50 / 100 % of the windows were written (seconds since start)
             std::cout << " engines_ready_at=";
             for (size_t i = 0; i < t_ready_of.size(); i++) std::cout << (i ? "," : "") << t_ready_of[i];

@@ -719,6 +719,79 @@ int ddh_fixture_json(const char *path, const int *indices, int n, char *out, int
     }
 }
 
+// Device CIGARs through the adapter: the windows once with alignments (host path: realignedCigars = getCIGAR per read) and once with
+// setDeviceCigars(true, ops_cap) (lazy views + the overload), for EVERY haplotype pair (h1 <= h2) of every window.  hap_ref_pos: the
+// haplotypes' refHpos, flat, one entry per haplotype base; hap_aligned[h] == 0 leaves a haplotype without one.  Reports the pairs whose
+// outcome (every read's operations and refPos, or the thrown string) differs, the reads redone on the host, the alignment and CIGAR bytes
+// the device-CIGAR batch brought back, and whether its views kept no alignments.
+int ddh_device_cigars_json(int W, const int *n_haps, const int *n_reads, const char *haps_nl, const char *reads_nl, const double *quals,
+                           const double *mapq, const double *pos_first, const int *unmapped, const unsigned *leftPos, const double *pd,
+                           const int *pi, const int *hap_ref_pos, const int *hap_aligned, int ops_cap, int device, char *out, int cap)
+{
+    try {
+        HookWindows Wn;
+        parse_windows(W, n_haps, n_reads, haps_nl, reads_nl, quals, mapq, pos_first, unmapped, leftPos, Wn);
+        size_t g = 0, at = 0;
+        for (int w = 0; w < W; w++)
+            for (size_t h = 0; h < Wn.haps[size_t(w)].size(); h++, g++) {
+                Haplotype &H = Wn.haps[size_t(w)][h];
+                if (hap_aligned[g]) H.refHpos.assign(hap_ref_pos + at, hap_ref_pos + at + H.size());
+                at += H.size();
+            }
+        LikelihoodEngine host(make_params(pd, pi), device), dev(make_params(pd, pi), device), again(make_params(pd, pi), device);
+        host.setThrowOnPositiveLikelihood(true); dev.setThrowOnPositiveLikelihood(true); again.setThrowOnPositiveLikelihood(true);
+        dev.setKeepAlignments(false);
+        dev.setDeviceCigars(true, ops_cap);
+        std::vector<WindowJob> a(static_cast<size_t>(W)), b(static_cast<size_t>(W));
+        for (int w = 0; w < W; w++) {
+            a[size_t(w)].haps = b[size_t(w)].haps = &Wn.haps[size_t(w)];
+            a[size_t(w)].reads = b[size_t(w)].reads = &Wn.reads[size_t(w)];
+            a[size_t(w)].leftPos = b[size_t(w)].leftPos = Wn.left[size_t(w)];
+            a[size_t(w)].rightPos = b[size_t(w)].rightPos = Wn.left[size_t(w)] + 1;
+        }
+        host.computeLikelihoodsBatch(a);
+        dev.computeLikelihoodsBatch(b);
+        long mismatch = 0, fallbacks = 0, pairs = 0, thrown = 0, views = 0;
+        for (int w = 0; w < W; w++) {
+            if (a[size_t(w)].error != b[size_t(w)].error) mismatch++;
+            if (!a[size_t(w)].error.empty()) continue;
+            if (b[size_t(w)].result.hasDeviceCigars() && !a[size_t(w)].result.hasDeviceCigars()) views++;
+            const std::vector<Haplotype> &haps = Wn.haps[size_t(w)];
+            const std::vector<Read> &reads = Wn.reads[size_t(w)];
+            for (size_t h1 = 0; h1 < haps.size(); h1++)
+                for (size_t h2 = h1; h2 < haps.size(); h2++, pairs++) {
+                    std::vector<CIGAR> ca, cb;
+                    std::string ea, eb;
+                    try { realignedCigars(haps, reads, a[size_t(w)].result, std::make_pair(int(h1), int(h2)), int(Wn.left[size_t(w)]), ca); }
+                    catch (std::string &e) { ea = e; }
+                    try {
+                        realignedCigars(haps, reads, b[size_t(w)].result, std::make_pair(int(h1), int(h2)), int(Wn.left[size_t(w)]), cb, [&]() -> WindowLikelihoods {
+                            std::vector<WindowJob> one(1, a[size_t(w)]);
+                            one[0].result = WindowLikelihoods();
+                            again.computeLikelihoodsBatch(one);
+                            return one[0].result;
+                        }, &fallbacks);
+                    } catch (std::string &e) { eb = e; }
+                    if (!ea.empty()) thrown++;
+                    if (ea != eb) { mismatch++; continue; }
+                    if (!ea.empty()) continue;
+                    bool same = ca.size() == cb.size();
+                    for (size_t r = 0; same && r < ca.size(); r++)
+                        same = ca[r].refPos == cb[r].refPos && static_cast<const std::vector<std::pair<int, int> > &>(ca[r]) == static_cast<const std::vector<std::pair<int, int> > &>(cb[r]);
+                    if (!same) mismatch++;
+                }
+        }
+        std::ostringstream os;
+        os << "{\"mismatch\":" << mismatch << ",\"pairs\":" << pairs << ",\"thrown\":" << thrown << ",\"fallbacks\":" << fallbacks
+           << ",\"views\":" << views << ",\"hpos_bytes\":" << dev.lastHposBytes << ",\"cigar_bytes\":" << dev.lastCigarBytes
+           << ",\"host_hpos_bytes\":" << host.lastHposBytes << "}";
+        return emit(os.str(), out, cap);
+    } catch (std::string &e) {
+        return emit(std::string("{\"throw\":\"") + e + "\"}", out, cap);
+    }
+}
+
+
 // writeRealignedBAMFile on the records bam_fetch hands over for (tid, [beg, end)), in that order: read k gets the CIGAR
 // (op, len) pairs cig[cigOff[k] .. cigOff[k + 1]) with refPos[k] if onHap[k], else it is copied.  Returns the number of reads, or < 0.
 int ddh_write_realigned(const char *inBam, const char *tid, int beg, int end, const char *outBam, const int *onHap, const int *cig, const int *cigOff,

@@ -1,5 +1,6 @@
 // realigned_bam.cpp — see realigned_bam.hpp.  Line references are to the reference's DInDel.cpp.
 #include "realigned_bam.hpp"
+#include "../../include/dindel_hmm.h"
 #include <algorithm>
 #include <cmath>
 #include <sstream>
@@ -47,6 +48,41 @@ void realignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read>
         }
         const MLAlignment ml = liks.get(hmax, r);
         cigars[r] = getCIGAR(haps[hmax].refHpos, haps[hmax].size(), ml, reads[r].size(), refSeqPos);
+    }
+}
+
+void realignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, std::pair<int, int> pair,
+                     int refSeqPos, std::vector<CIGAR> &cigars, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks)
+{
+    if (!liks.hasDeviceCigars()) { realignedCigars(haps, reads, liks, pair, refSeqPos, cigars); return; }
+    static const char *const thrown[] = {"", "Haplotype has not been aligned!", "Error(1)!", "Error(2)!", "Error(3)!", "Error(4)!", "How is this possible? (1)"};
+    cigars.assign(reads.size(), CIGAR());
+    const size_t h1 = size_t(pair.first), h2 = size_t(pair.second);
+    WindowLikelihoods full;
+    for (size_t r = 0; r < reads.size(); r++) {                                              // :596-611
+        size_t hmax = h1;
+        if (fabs(liks.ll(h1, r) - liks.ll(h2, r)) < 1e-8) {
+            if (haps[h1].countIndels() < haps[h2].countIndels()) hmax = h1; else hmax = h2;
+        } else {
+            if (liks.ll(h1, r) > liks.ll(h2, r)) hmax = h1; else hmax = h2;
+        }
+        const int st = liks.cigarStatus(hmax, r);
+        if (st >= DD_CIGAR_HAP_NOT_ALIGNED && st <= DD_CIGAR_IMPOSSIBLE) throw std::string(thrown[st]);
+        if (st == DD_CIGAR_OK) {
+            const uint32_t *ops = liks.cigarOps(hmax, r);
+            const int n = liks.cigarNumOps(hmax, r), off = liks.cigarRefOff(hmax, r);
+            CIGAR &c = cigars[r];
+            for (int i = 0; i < n; i++) c.push_back(CIGAR::CIGOp(int(ops[i] & 15u), int(ops[i] >> 4)));
+            c.refPos = off < 0 ? -1 : refSeqPos + off;                                       // no aligned base: refPos stays -1
+            continue;
+        }
+        // DD_CIGAR_OVERFLOW (or a pair the device did not compute): this read on the host, from the window's alignments
+        if (!full.valid()) {
+            if (!withAlignments) throw std::string("realignedCigars: a read needs the host getCIGAR and no alignments are at hand");
+            full = withAlignments();
+        }
+        cigars[r] = getCIGAR(haps[hmax].refHpos, haps[hmax].size(), full.get(hmax, r), reads[r].size(), refSeqPos);
+        if (hostFallbacks) ++*hostFallbacks;
     }
 }
 

@@ -5,6 +5,7 @@
 // getCIGAR itself is host/cigar.cpp.  The BAM is written by the own BGZF writer (bam_reader.hpp); libbam is not in the image.
 #ifndef DINDEL_REALIGNED_BAM_HPP
 #define DINDEL_REALIGNED_BAM_HPP
+#include <functional>
 #include <string>
 #include <vector>
 #include "bam_reader.hpp"
@@ -24,6 +25,14 @@ std::pair<int, int> maxLikelihoodPair(const std::vector<Haplotype> &haps, const 
 // Throws getCIGAR's strings.
 void realignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, std::pair<int, int> pair,
                      int refSeqPos, std::vector<CIGAR> &cigars);
+
+// The same with device CIGARs (LikelihoodEngine::setDeviceCigars, liks.hasDeviceCigars()): the haplotype of the pair is picked per read
+// exactly as above, and the read's CIGAR is the one the device computed for that (haplotype, read) pair.  A status that names a throw
+// raises the string getCIGAR throws there.  A read whose CIGAR has more operations than the batch's cap (DD_CIGAR_OVERFLOW) is redone
+// with getCIGAR on the host from `withAlignments()` — the same window computed with its per-base alignments, asked for at most once per
+// call — and counted in *hostFallbacks.  Without device CIGARs in `liks` this is the function above.
+void realignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, std::pair<int, int> pair,
+                     int refSeqPos, std::vector<CIGAR> &cigars, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks);
 
 // The name the reference gives the window's file: PREFIX.ra.INDEX_TID_(leftPos+minReadOverlap)_(rightPos-minReadOverlap).bam (:614-618)
 std::string realignedBAMFileName(const std::string &prefix, int index, const std::string &tid, uint32_t leftPos, uint32_t rightPos, int minReadOverlap);

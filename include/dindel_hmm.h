@@ -404,6 +404,53 @@ int dd_launch_device_faster_long(const dd_params *p, const dd_device_batch *b, c
 #define DD_FASTER_LONG_LOG_FIELDS 8
 int dd_faster_long_launch_log(int64_t *out, int max_records);
 
+/* ---- device-side getCIGAR (opt-in) --------------------------------------------------------- */
+/* The CIGAR of every (haplotype, read) pair — DetInDel::getCIGAR, reference DInDel.cpp:728-882 (host/cigar.cpp restates it and is the
+ * specification) — computed on the device from the hpos the likelihood kernels left there, so that a realigned BAM needs
+ * 4 * ops_cap + 12 bytes per pair instead of the pair's 2 L bytes of hpos.  Nothing changes for callers that do not ask for it.
+ * Per pair, in pair order (liks[h][r], like dd_result):
+ *   status   DD_CIGAR_*: 0, or the string getCIGAR throws there, or DD_CIGAR_OVERFLOW, or DD_CIGAR_NOT_COMPUTED
+ *   n_ops    the number of operations, also when it exceeds ops_cap (0 when status names a throw or DD_CIGAR_NOT_COMPUTED)
+ *   ops      [ops_cap] per pair, BAM-encoded len << 4 | op with op 0 = M, 1 = I, 2 = D, 4 = S; the first min(n_ops, ops_cap) are written.
+ *            A pair whose status names a throw has n_ops 0, but the walk may have written operations into its row before it threw: the
+ *            row's contents are then unspecified.  DD_CIGAR_NOT_COMPUTED pairs' rows are never written
+ *   ref_off  reference offset of the first aligned base: CIGAR::refPos = refSeqStart + ref_off; -1 when the read has no aligned base
+ *            (one soft clip over the whole read; refPos stays -1 there) and whenever n_ops is 0 */
+typedef struct dd_cigar_result {
+    int32_t  *n_ops;
+    uint32_t *ops;
+    int32_t  *ref_off;
+    int32_t  *status;
+} dd_cigar_result;
+#define DD_CIGAR_OK               0
+#define DD_CIGAR_HAP_NOT_ALIGNED  1   /* "Haplotype has not been aligned!" (hap_aligned[h] == 0) */
+#define DD_CIGAR_ERROR1           2   /* "Error(1)!" */
+#define DD_CIGAR_ERROR2           3   /* "Error(2)!" */
+#define DD_CIGAR_ERROR3           4   /* "Error(3)!" */
+#define DD_CIGAR_ERROR4           5   /* "Error(4)!" */
+#define DD_CIGAR_IMPOSSIBLE       6   /* "How is this possible? (1)" */
+#define DD_CIGAR_OVERFLOW         7   /* n_ops > ops_cap: the first ops_cap operations are there, the caller redoes this pair on the host */
+#define DD_CIGAR_NOT_COMPUTED     8   /* the pair's dd_result.status is not DD_PAIR_OK: its hpos is not read and its ops are not written */
+#define DD_CIGAR_DEFAULT_OPS_CAP  8
+/* Enqueue the CIGAR launch for the whole batch on `stream`, behind the likelihood launch(es) that wrote hpos_dev (dd_launch_device,
+ * dd_launch_device_long, dd_launch_device_faster, dd_launch_device_faster_long alike: hpos is only read).  All DEVICE pointers:
+ *   hpos_dev         dd_result.hpos as the kernels write it (inserted bases carry their key, DD_HPOS_IS_INS: read as MLAlignment::INS)
+ *   status_dev       dd_result.status (NULL = every pair was computed)
+ *   hap_ref_pos_dev  Haplotype::refHpos (hap.ml.hpos of the reference): one int32 per haplotype base at the haplotype's hap_seq_off —
+ *                    the base's offset on the window's reference sequence (>= 0) or a negative MLAlignment code
+ *   hap_aligned_dev  one byte per haplotype, 0 = "Haplotype has not been aligned!" (NULL = all aligned)
+ *   out_dev          device arrays: n_ops, ref_off, status [n_pairs], ops [n_pairs * ops_cap]; ops_cap >= 1
+ * Of the batch it reads n_windows, win_hap_off, win_read_off, hap_seq_off, read_seq_off, win_pair_off and win_hpos_off.  An hpos entry
+ * beyond its haplotype (the host would read past the vector) is read as the haplotype's last base.  Asynchronous, no allocation. */
+int dd_cigars_device(const dd_device_batch *b, const int16_t *hpos_dev, const int32_t *status_dev, const int32_t *hap_ref_pos_dev,
+                     const uint8_t *hap_aligned_dev, const dd_cigar_result *out_dev, int ops_cap, void *stream);
+/* Host pointers: dd_compute_likelihoods_ex (options: 0 or DD_OPT_LONG_WINDOWS) followed by the CIGAR launch; cig's arrays (host memory,
+ * sized as above) are filled.  hap_ref_pos [hap_seq_off[n_haps]] is required, hap_aligned [n_haps] may be NULL (all aligned).
+ * r->hpos may be NULL: the per-base alignments then stay on the device — the point of this entry.  Everything else as
+ * dd_compute_likelihoods_ex. */
+int dd_compute_likelihoods_cigars(const dd_params *p, const dd_batch *b, dd_result *r, const int32_t *hap_ref_pos, const uint8_t *hap_aligned,
+                                  const dd_cigar_result *cig, int ops_cap, int device, uint32_t options);
+
 /* ---- N1 (next row): read sums of the diploid genotype reduction --------------------------- */
 /* S[w][h1*H_w+h2] (h1<=h2) = sum over the window's reads, in order, of log(0.5)+addLogs(ll[h1][r], ll[h2][r])
  * — the inner loop of DetInDel::diploidGLF, reference DInDel.cpp:3085-3091 (and :3372-3374); addLogs is

@@ -5,6 +5,9 @@ per window drawn from the reference and one variant haplotype (a heterozygous si
 --dir, runs the driver and prints windows/s with the driver's own stage split.
 
     python tools/n2_pipeline_bench.py [--windows 2000] [--reads 200] [--batch 256] [--dir /tmp/n2bench] [--faster]
+    python tools/n2_pipeline_bench.py --realigned [--device-cigars] [--reps 3] [--driver PATH/dindel_gpu]
+--realigned adds --outputRealignedBAM (one BAM per window next to the .glf.txt; their bytes go into the md5), --device-cigars the driver's
+--deviceCigars; --driver times another build of the driver (e.g. the parent commit's) on the same files.
 """
 import argparse
 import hashlib
@@ -30,6 +33,10 @@ ap.add_argument("--sweep", action="store_true", help="run a list of batch sizes 
 ap.add_argument("--extra", default="", help="further driver options, blank-separated")
 ap.add_argument("--vcf", action="store_true", help="afterwards: dindel_glf2vcf on the .glf.txt, and the calls against the variants the reads were drawn with")
 ap.add_argument("--ragged", action="store_true", help="windows of 90-330 bp, 2-12 haplotypes, 20-400 reads of 60-150 bp each (default: uniform 120 bp / 8 / 200 x 100 bp)")
+ap.add_argument("--realigned", action="store_true", help="run with --outputRealignedBAM")
+ap.add_argument("--device-cigars", action="store_true", help="with --realigned: the driver's --deviceCigars")
+ap.add_argument("--reps", type=int, default=2, help="runs per configuration")
+ap.add_argument("--driver", default="", help="path of the dindel_gpu to time (default: this tree's)")
 ap.add_argument("--procs", type=int, default=min(16, os.cpu_count() or 1), help="processes writing the sample")
 args = ap.parse_args()
 os.makedirs(args.dir, exist_ok=True)
@@ -205,14 +212,17 @@ try:
     env["LD_LIBRARY_PATH"] = os.path.join(os.path.dirname(torch.__file__), "lib") + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
 except ImportError:
     pass
-base = [os.path.join(host, "dindel_gpu"), "--bamFile", bam, "--varFile", vf, "--hapFile", hf, "--outputFile", os.path.join(args.dir, "out"), "--timing"]
+base = [args.driver or os.path.join(host, "dindel_gpu"), "--bamFile", bam, "--varFile", vf, "--hapFile", hf, "--outputFile", os.path.join(args.dir, "out"), "--timing"]
 if args.sweep:
     configs = [["--batchWindows", str(b), "--computeThreads", str(c), "--prepareThreads", str(p), "--reduceThreads", str(r), "--packThreads", str(k)] + f
                for f in ([], ["--faster"]) for (b, c, p, r, k) in ((256, 2, 6, 6, 4), (256, 2, 8, 4, 4), (256, 2, 10, 4, 4), (128, 2, 8, 4, 4), (256, 3, 8, 4, 2))]
 else:
-    configs = [["--batchWindows", str(args.batch)] + (["--faster"] if args.faster else []) + args.extra.split()]
+    configs = [["--batchWindows", str(args.batch)] + (["--faster"] if args.faster else []) + (["--outputRealignedBAM"] if args.realigned else []) +
+               (["--deviceCigars"] if args.device_cigars else []) + args.extra.split()]
 for cfg in configs:
-    for rep in range(2):
+    for rep in range(args.reps):
+        for old in [f for f in os.listdir(args.dir) if f.startswith("out.ra.")]:
+            os.remove(os.path.join(args.dir, old))
         t0 = time.time()
         out = subprocess.run(base + cfg, env=env, capture_output=True, text=True)
         dt = time.time() - t0
@@ -224,8 +234,12 @@ for cfg in configs:
         calls = sum(1 for l in rows if " dip.map " in l)
         skipped = sum(1 for l in rows[1:] if l and not l.startswith("ok "))
         timing = [l for l in out.stdout.split("\n") if l.startswith("timing:")]
+        ra = sorted(f for f in os.listdir(args.dir) if f.startswith("out.ra."))
+        ra_md5 = hashlib.md5()
+        for f in ra:
+            ra_md5.update(f.encode()); ra_md5.update(open(os.path.join(args.dir, f), "rb").read())
         print(json.dumps(dict(rep=rep, windows=args.windows, options=" ".join(cfg), seconds=round(dt, 3), windows_per_s=round(args.windows / dt, 1),
-                              dip_map_lines=calls, skipped=skipped, md5=hashlib.md5(text.encode()).hexdigest(), driver=timing[-1] if timing else None)), flush=True)
+                              dip_map_lines=calls, skipped=skipped, md5=hashlib.md5(text.encode()).hexdigest(), realigned_bams=len(ra), realigned_md5=ra_md5.hexdigest() if ra else None, driver=timing[-1] if timing else None)), flush=True)
 
 if args.vcf:
     lst = os.path.join(args.dir, "glf_files.txt")
