@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -146,6 +147,20 @@ private:
     std::map<std::string, int> strToTID;
     std::map<std::string, std::string> rg2lib;
     std::vector<RefIndex> index;
+};
+
+// One open BamFile per path, in the order given: the handles of one read buffer's pools.  pointers() is what ReadFetcher takes (and keeps a
+// reference to: the set outlives the fetcher).  A path that cannot be opened throws like BamFile's constructor.
+class BamFileSet {
+public:
+    BamFileSet() {}
+    explicit BamFileSet(const std::vector<std::string> &paths) { for (size_t i = 0; i < paths.size(); i++) open(paths[i]); }
+    void open(const std::string &path) { owned.push_back(std::unique_ptr<BamFile>(new BamFile(path))); ptrs.push_back(owned.back().get()); }
+    std::vector<BamFile *> &pointers() { return ptrs; }
+    const BamFile &operator[](size_t i) const { return *owned[i]; }
+private:
+    std::vector<std::unique_ptr<BamFile> > owned;
+    std::vector<BamFile *> ptrs;
 };
 
 template <class F> void BamFile::fetchImpl(int tid, int beg, int end, F callback, bool whole)

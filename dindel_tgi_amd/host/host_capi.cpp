@@ -914,19 +914,18 @@ int ddh_get_reads_pools_json(const char *bamPaths, const char *libFile, const ch
                              const char *filterReadAux, int withBuffer, char *out, int cap)
 {
     try {
-        std::vector<std::unique_ptr<BamFile> > handles;
-        std::vector<BamFile *> bams;
+        BamFileSet bams;
         {
             std::istringstream list(bamPaths);
             std::string path;
-            while (std::getline(list, path)) if (!path.empty()) { handles.push_back(std::unique_ptr<BamFile>(new BamFile(path))); bams.push_back(handles.back().get()); }
+            while (std::getline(list, path)) if (!path.empty()) bams.open(path);
         }
         LibraryCollection libs;
         if (libFile && *libFile) libs.addFromFile(libFile);
         ReadSelectionParameters p;
         p.maxReads = size_t(prm[0]); p.maxReadLength = size_t(prm[1]); p.minReadOverlap = prm[2]; p.mapUnmappedReads = prm[3] != 0; p.mapQualThreshold = mapQualThreshold;
         p.filterReadAux = filterReadAux ? filterReadAux : "";
-        ReadFetcher f(bams, libs, p);
+        ReadFetcher f(bams.pointers(), libs, p);
         std::ostringstream os;
         os.precision(17);
         os << "[";

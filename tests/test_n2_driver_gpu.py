@@ -185,6 +185,33 @@ def test_driver_batching_is_exact_and_vcf_follows(scene):
     assert all(l[6] == "PASS" for l in body)
 
 
+def test_driver_merges_waiting_batches_into_one_launch(scene):
+    """--mergeBatches: an engine that finds further batches waiting moves their jobs into one vector, computes them in one call and moves them
+    back to their batches.  Single-window batches, not merged: one launch per window that reaches the likelihood step — windows 1-5 (the
+    short haplotype of window 5 included: its error comes from that step); window 6 is skipped by read selection and has no job.  Merged up to
+    four at a time on one engine: fewer launches or as many, never none.  The files equal the one of a single 64-window batch either way."""
+    import re
+
+    def run(prefix, *extra):
+        env = dict(os.environ)
+        import torch
+        env["LD_LIBRARY_PATH"] = os.path.join(os.path.dirname(torch.__file__), "lib") + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
+        out = str(scene["tmp"] / prefix)
+        r = subprocess.run([os.path.join(HOST, "dindel_gpu"), "--bamFile", scene["bam"], "--varFile", scene["vf"], "--hapFile", scene["hf"], "--outputFile", out,
+                            "--quiet", "--timing", "--batchWindows", "1", "--computeThreads", "1", *extra], env=env, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        timing = [l for l in r.stdout.split("\n") if l.startswith("timing:")]
+        assert len(timing) == 1, r.stdout
+        print(timing[0])
+        return open(out + ".glf.txt").read(), int(re.search(r" launches=(\d+) ", timing[0]).group(1))
+    whole = open(run_driver(scene, "m64", "--batchWindows", "64")[0]).read()
+    single, n_single = run("m1", "--mergeBatches", "1")
+    merged, n_merged = run("m4", "--mergeBatches", "4", "--prepareThreads", "4")
+    assert single == whole and merged == whole
+    assert n_single == 5
+    assert 1 <= n_merged <= n_single
+
+
 def test_driver_skips_windows_over_the_hap_read_product(scene):
     """--maxHapReadProd (DInDel.cpp:395-399): a window with more haplotypes x reads than the limit is skipped with the reference's message
     and the others are called as before."""
