@@ -37,6 +37,10 @@ DD_LONG_WS_BUDGET = 512 << 20
 (DD_CIGAR_OK, DD_CIGAR_HAP_NOT_ALIGNED, DD_CIGAR_ERROR1, DD_CIGAR_ERROR2, DD_CIGAR_ERROR3, DD_CIGAR_ERROR4, DD_CIGAR_IMPOSSIBLE,
  DD_CIGAR_OVERFLOW, DD_CIGAR_NOT_COMPUTED) = range(9)
 DD_CIGAR_DEFAULT_OPS_CAP = 8
+# alignHaplotypes on the device: per-pair status codes and the launch geometry record
+DD_ALIGN_OK, DD_ALIGN_EMPTY, DD_ALIGN_TOO_LONG, DD_ALIGN_BAD_REF = range(4)
+DD_ALIGN_WS_BUDGET = 512 << 20
+ALIGN_LOG_FIELDS = ["grid", "waves", "tile_bytes", "lds_block", "pairs", "ws_bytes", "max_draws", "guard_trips"]
 CIGAR_MESSAGES = {DD_CIGAR_HAP_NOT_ALIGNED: "Haplotype has not been aligned!", DD_CIGAR_ERROR1: "Error(1)!", DD_CIGAR_ERROR2: "Error(2)!",
                   DD_CIGAR_ERROR3: "Error(3)!", DD_CIGAR_ERROR4: "Error(4)!", DD_CIGAR_IMPOSSIBLE: "How is this possible? (1)"}
 
@@ -138,6 +142,18 @@ class dd_cigar_result(C.Structure):
     _fields_ = [("n_ops", C.c_void_p), ("ops", C.c_void_p), ("ref_off", C.c_void_p), ("status", C.c_void_p)]
 
 
+class dd_align_batch(C.Structure):
+    """References and the haplotypes aligned against them.  Raw addresses: host arrays for dd_align_haplotypes and
+    dd_align_workspace_bytes, device arrays for dd_align_haplotypes_device."""
+    _fields_ = [("n_refs", C.c_int32), ("ref_off", C.c_void_p), ("ref_seq", C.c_void_p), ("n_pairs", C.c_int32), ("pair_ref", C.c_void_p),
+                ("hap_off", C.c_void_p), ("hap_seq", C.c_void_p)]
+
+
+class dd_align_result(C.Structure):
+    """score, status (int32 [n_pairs]) and ref_pos (int16, laid out like hap_seq); raw addresses like dd_align_batch."""
+    _fields_ = [("score", C.c_void_p), ("status", C.c_void_p), ("ref_pos", C.c_void_p)]
+
+
 class dd_device_result(C.Structure):
     """dd_result with raw device addresses (same layout: every member is a pointer)."""
     _fields_ = [(n, C.c_void_p) for n, _ in RESULT_FIELDS]
@@ -149,7 +165,8 @@ EXPORTS = ["dd_params_struct_defaults", "dd_params_cli_defaults", "dd_batch_size
            "dd_pair_sums", "dd_map_pairs_device", "dd_map_pairs", "dd_last_error", "dd_abi_version", "dd_device_count",
            "dd_screen_windows_ex", "dd_compute_likelihoods_ex", "dd_workspace_bytes_long", "dd_launch_device_long", "dd_long_launch_log",
            "dd_compute_likelihoods_faster_ex", "dd_workspace_bytes_faster_long", "dd_launch_device_faster_long", "dd_faster_long_launch_log",
-           "dd_cigars_device", "dd_compute_likelihoods_cigars"]
+           "dd_cigars_device", "dd_compute_likelihoods_cigars",
+           "dd_align_haplotypes", "dd_align_workspace_bytes", "dd_align_haplotypes_device", "dd_align_last_launch"]
 
 _lib = None
 
@@ -219,6 +236,13 @@ def load():
                                      C.c_int, C.c_void_p]
     lib.dd_compute_likelihoods_cigars.argtypes = [C.POINTER(dd_params), C.POINTER(dd_batch), C.POINTER(dd_result), c_i32p, c_u8p,
                                                   C.POINTER(dd_cigar_result), C.c_int, C.c_int, C.c_uint32]
+    lib.dd_align_haplotypes.argtypes = [C.POINTER(dd_align_batch), C.POINTER(dd_align_result), C.c_int]
+    lib.dd_align_workspace_bytes.argtypes = [C.POINTER(dd_align_batch)]
+    lib.dd_align_workspace_bytes.restype = C.c_size_t
+    lib.dd_align_haplotypes_device.argtypes = [C.POINTER(dd_align_batch), C.POINTER(dd_align_result), C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                               C.c_void_p]
+    lib.dd_align_last_launch.argtypes = [C.POINTER(C.c_int64 * len(ALIGN_LOG_FIELDS))]
+    lib.dd_align_last_launch.restype = None
     lib.dd_last_launch.argtypes = [C.POINTER(C.c_int32 * 8)]
     lib.dd_last_launch.restype = None
     lib.dd_launch_log.argtypes = [c_i32p, C.c_int]

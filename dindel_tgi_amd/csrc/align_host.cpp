@@ -1,0 +1,171 @@
+// align_host.cpp — host side of the haplotype-to-reference alignment (hapalign_kernel.hip): validation of a dd_align_batch, the grid /
+// workspace rule, the device-pointer launch and the host-pointer entry (its own allocations: one call per batch of windows).
+#include "capi_internal.h"
+#include "hapalign_kernel.h"
+
+namespace ddh {
+namespace {
+
+struct AlignShape { int64_t ref_bytes, hap_bytes; int max_ref_len, max_hap_len; };
+
+// this thread's last launch: the host-side fields, and where its two device words are (read on demand, or cached by the host entry,
+// whose workspace does not outlive the call)
+struct AlignLast { int64_t v[DD_ALIGN_LOG_FIELDS]; const unsigned char *ws; hipStream_t stream; bool have_stats; };
+thread_local AlignLast g_align_last = {{0, 0, 0, 0, 0, 0, 0, 0}, nullptr, nullptr, true};
+
+int read_align_stats()
+{
+    AlignLast &L = g_align_last;
+    if (L.have_stats || !L.ws) return DD_SUCCESS;
+    uint32_t hdr[4];
+    HIP_TRY(hipStreamSynchronize(L.stream));
+    HIP_TRY(hipMemcpy(hdr, L.ws, sizeof(hdr), hipMemcpyDeviceToHost));
+    L.v[6] = hdr[DD_ALIGN_HDR_MAX_DRAWS]; L.v[7] = hdr[DD_ALIGN_HDR_TRIPS];
+    L.have_stats = true;
+    return DD_SUCCESS;
+}
+
+// offsets start at 0 and never decrease; pair_ref in range.  The maxima leave out what the kernel refuses (too long).
+int check_align_batch(const dd_align_batch *b, AlignShape &s)
+{
+    if (!b) return fail(DD_ERR_INVALID, "null align batch");
+    if (b->n_refs < 0 || b->n_pairs < 0) return fail(DD_ERR_INVALID, "negative count in align batch");
+    if (!b->ref_off || !b->hap_off) return fail(DD_ERR_INVALID, "null offset array in align batch");
+    if (b->n_pairs > 0 && !b->pair_ref) return fail(DD_ERR_INVALID, "null pair_ref in align batch");
+    s = AlignShape{0, 0, 0, 0};
+    if (b->ref_off[0] != 0) return fail(DD_ERR_INVALID, "ref_off does not start at 0");
+    if (b->hap_off[0] != 0) return fail(DD_ERR_INVALID, "hap_off does not start at 0");
+    for (int i = 0; i < b->n_refs; i++) {
+        const int64_t n = (int64_t)b->ref_off[i + 1] - b->ref_off[i];
+        if (n < 0) return fail(DD_ERR_INVALID, "ref_off decreases at reference " + std::to_string(i));
+        if (n <= DD_LONG_MAX_HAP_LEN) s.max_ref_len = std::max(s.max_ref_len, (int)n);
+    }
+    for (int i = 0; i < b->n_pairs; i++) {
+        const int64_t n = (int64_t)b->hap_off[i + 1] - b->hap_off[i];
+        if (n < 0) return fail(DD_ERR_INVALID, "hap_off decreases at pair " + std::to_string(i));
+        if (n <= DD_LONG_MAX_HAP_LEN) s.max_hap_len = std::max(s.max_hap_len, (int)n);
+        if (b->pair_ref[i] < 0 || b->pair_ref[i] >= b->n_refs) return fail(DD_ERR_INVALID, "pair_ref out of range at pair " + std::to_string(i));
+    }
+    s.ref_bytes = b->ref_off[b->n_refs];
+    s.hap_bytes = b->hap_off[b->n_pairs];
+    if (s.ref_bytes > 0 && !b->ref_seq) return fail(DD_ERR_INVALID, "null ref_seq in align batch");
+    if (s.hap_bytes > 0 && !b->hap_seq) return fail(DD_ERR_INVALID, "null hap_seq in align batch");
+    s.max_ref_len = std::max(s.max_ref_len, 1);
+    s.max_hap_len = std::max(s.max_hap_len, 1);
+    return DD_SUCCESS;
+}
+
+// workgroups of the full grid: one wavefront per pair up to the persistent grid's size, fewer while the tiles exceed the budget
+unsigned align_full_grid(int64_t n_pairs, uint64_t tile_bytes)
+{
+    int64_t blocks = std::max<int64_t>(1, (n_pairs + DD_ALIGN_WAVES - 1) / DD_ALIGN_WAVES);
+    blocks = std::min<int64_t>(blocks, DD_ALIGN_MAX_BLOCKS);
+    const int64_t fit = (int64_t)(DD_ALIGN_WS_BUDGET / (tile_bytes * DD_ALIGN_WAVES));
+    return (unsigned)std::max<int64_t>(1, std::min(blocks, fit));
+}
+
+} // namespace
+} // namespace ddh
+
+using namespace ddh;
+
+extern "C" {
+
+size_t dd_align_workspace_bytes(const dd_align_batch *shape)
+{
+    AlignShape s;
+    if (check_align_batch(shape, s)) return 0;
+    const uint64_t tile = dda::align_tile_bytes(s.max_ref_len, s.max_hap_len);
+    return DD_ALIGN_WS_HEADER + (size_t)align_full_grid(shape->n_pairs, tile) * DD_ALIGN_WAVES * tile;
+}
+
+int dd_align_haplotypes_device(const dd_align_batch *b, const dd_align_result *r, int max_ref_len, int max_hap_len, void *workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    if (!b || !r) return fail(DD_ERR_INVALID, "dd_align_haplotypes_device: null batch or result");
+    if (b->n_refs < 0 || b->n_pairs < 0) return fail(DD_ERR_INVALID, "dd_align_haplotypes_device: negative count");
+    if (max_ref_len < 1 || max_ref_len > DD_LONG_MAX_HAP_LEN || max_hap_len < 1 || max_hap_len > DD_LONG_MAX_HAP_LEN)
+        return fail(DD_ERR_INVALID, "dd_align_haplotypes_device: max_ref_len / max_hap_len outside 1 ... DD_LONG_MAX_HAP_LEN");
+    if (b->n_pairs == 0) return DD_SUCCESS;
+    if (!b->ref_off || !b->ref_seq || !b->pair_ref || !b->hap_off || !b->hap_seq || !r->score || !r->status || !r->ref_pos)
+        return fail(DD_ERR_INVALID, "dd_align_haplotypes_device: null array");
+    if (!workspace) return fail(DD_ERR_INVALID, "dd_align_haplotypes_device: null workspace");
+    const uint64_t tile = dda::align_tile_bytes(max_ref_len, max_hap_len);
+    const uint64_t wg_bytes = tile * DD_ALIGN_WAVES;
+    if (workspace_bytes < DD_ALIGN_WS_HEADER + wg_bytes)
+        return fail(DD_ERR_INVALID, "dd_align_haplotypes_device: workspace too small for one workgroup (dd_align_workspace_bytes)");
+    const unsigned grid = (unsigned)std::min<uint64_t>(align_full_grid(b->n_pairs, tile), (workspace_bytes - DD_ALIGN_WS_HEADER) / wg_bytes);
+    dda::AlignArgs A;
+    A.n_refs = b->n_refs; A.n_pairs = b->n_pairs;
+    A.ref_off = b->ref_off; A.ref_seq = reinterpret_cast<const uint8_t *>(b->ref_seq);
+    A.pair_ref = b->pair_ref; A.hap_off = b->hap_off; A.hap_seq = reinterpret_cast<const uint8_t *>(b->hap_seq);
+    A.score = r->score; A.status = r->status; A.ref_pos = r->ref_pos;
+    A.max_ref_len = max_ref_len; A.max_hap_len = max_hap_len;
+    A.K = (max_hap_len + 63) / 64;
+    A.ws = static_cast<unsigned char *>(workspace);
+    A.tile_bytes = tile;
+    const int64_t rec[DD_ALIGN_LOG_FIELDS] = {(int64_t)grid, (int64_t)grid * DD_ALIGN_WAVES, (int64_t)tile, (int64_t)dda::align_lds_bytes(A.K),
+                                              (int64_t)b->n_pairs, (int64_t)(DD_ALIGN_WS_HEADER + grid * wg_bytes), -1, -1};
+    memcpy(g_align_last.v, rec, sizeof(rec));
+    g_align_last.ws = A.ws; g_align_last.stream = static_cast<hipStream_t>(stream); g_align_last.have_stats = false;
+    HIP_TRY(dda::launch_hapalign(A, grid, static_cast<hipStream_t>(stream)));
+    return DD_SUCCESS;
+}
+
+void dd_align_last_launch(int64_t out[DD_ALIGN_LOG_FIELDS])
+{
+    (void)read_align_stats();                  // a failure leaves -1 in the two device fields
+    if (out) memcpy(out, g_align_last.v, sizeof(g_align_last.v));
+}
+
+int dd_align_haplotypes(const dd_align_batch *b, dd_align_result *r, int device)
+{
+    AlignShape s;
+    int rc = check_align_batch(b, s);
+    if (rc) return rc;
+    if (!r) return fail(DD_ERR_INVALID, "null align result");
+    if (b->n_pairs > 0 && (!r->score || !r->status)) return fail(DD_ERR_INVALID, "null score or status in align result");
+    if (s.hap_bytes > 0 && !r->ref_pos) return fail(DD_ERR_INVALID, "null ref_pos in align result");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(DD_ERR_NO_DEVICE, "no HIP device: the haplotype alignment has no CPU fallback in this library");
+    if (device < 0 || device >= ndev) return fail(DD_ERR_NO_DEVICE, "device ordinal out of range");
+    HIP_TRY(hipSetDevice(device));
+    if (b->n_pairs == 0) return DD_SUCCESS;
+
+    // one allocation, 256-byte aligned pieces: offsets, sequences, outputs, workspace
+    const size_t ws_bytes = dd_align_workspace_bytes(b);
+    const size_t P = (size_t)b->n_pairs, R = (size_t)b->n_refs;
+    size_t off = 0;
+    auto take = [&off](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255u) & ~size_t(255u); return o; };
+    const size_t o_roff = take((R + 1) * 4), o_rseq = take((size_t)s.ref_bytes), o_pref = take(P * 4), o_hoff = take((P + 1) * 4),
+                 o_hseq = take((size_t)s.hap_bytes), o_score = take(P * 4), o_status = take(P * 4), o_rpos = take((size_t)s.hap_bytes * 2),
+                 o_ws = take(ws_bytes);
+    struct Mem {
+        unsigned char *p = nullptr;
+        ~Mem() { if (p) (void)hipFree(p); }
+    } mem;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&mem.p), off));
+    unsigned char *d = mem.p;
+    HIP_TRY(hipMemcpy(d + o_roff, b->ref_off, (R + 1) * 4, hipMemcpyHostToDevice));
+    if (s.ref_bytes) HIP_TRY(hipMemcpy(d + o_rseq, b->ref_seq, (size_t)s.ref_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d + o_pref, b->pair_ref, P * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d + o_hoff, b->hap_off, (P + 1) * 4, hipMemcpyHostToDevice));
+    if (s.hap_bytes) HIP_TRY(hipMemcpy(d + o_hseq, b->hap_seq, (size_t)s.hap_bytes, hipMemcpyHostToDevice));
+    dd_align_batch db = *b;
+    db.ref_off = reinterpret_cast<const int32_t *>(d + o_roff); db.ref_seq = reinterpret_cast<const char *>(d + o_rseq);
+    db.pair_ref = reinterpret_cast<const int32_t *>(d + o_pref); db.hap_off = reinterpret_cast<const int32_t *>(d + o_hoff);
+    db.hap_seq = reinterpret_cast<const char *>(d + o_hseq);
+    const dd_align_result dr = {reinterpret_cast<int32_t *>(d + o_score), reinterpret_cast<int32_t *>(d + o_status),
+                                reinterpret_cast<int16_t *>(d + o_rpos)};
+    if ((rc = dd_align_haplotypes_device(&db, &dr, s.max_ref_len, s.max_hap_len, d + o_ws, ws_bytes, nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if ((rc = read_align_stats())) return rc;  // the workspace goes with this call
+    g_align_last.ws = nullptr;
+    HIP_TRY(hipMemcpy(r->score, dr.score, P * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(r->status, dr.status, P * 4, hipMemcpyDeviceToHost));
+    if (s.hap_bytes) HIP_TRY(hipMemcpy(r->ref_pos, dr.ref_pos, (size_t)s.hap_bytes * 2, hipMemcpyDeviceToHost));
+    return DD_SUCCESS;
+}
+
+} // extern "C"

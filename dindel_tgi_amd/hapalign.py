@@ -1,0 +1,144 @@
+"""alignHaplotypes on the device: candidate haplotypes against their window's reference sequence (dd_align_haplotypes).
+
+The arithmetic is the library's HIP kernel (csrc/hapalign_kernel.hip); there is no Python or CPU implementation behind this module.
+`align_haplotypes` is the host-pointer entry, `DeviceAlign` keeps the batch in torch tensors and launches on a given stream, and
+`gapped_rows` rebuilds the two gapped rows of an alignment from the per-base reference offsets the kernel returns.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+
+_DNA = np.zeros(256, np.uint8)                    # seqan::Dna of a byte: every other byte is an A
+for _c, _v in (("C", 1), ("G", 2), ("T", 3), ("U", 3)):
+    _DNA[ord(_c)] = _DNA[ord(_c.lower())] = _v
+
+
+def dna_text(seq):
+    """The sequence as the alignment sees it: ACGT of the bytes' seqan::Dna codes."""
+    return np.frombuffer(b"ACGT", np.uint8)[_DNA[np.frombuffer(bytes(seq), np.uint8)]].tobytes().decode()
+
+
+def pack(refs, haps, pair_ref):
+    """numpy arrays of a dd_align_batch: ref_off, ref_seq, pair_ref, hap_off, hap_seq."""
+    refs, haps = [bytes(r) for r in refs], [bytes(h) for h in haps]
+    if len(pair_ref) != len(haps):
+        raise ValueError("one pair_ref entry per haplotype")
+    a = {"ref_off": np.concatenate([[0], np.cumsum([len(r) for r in refs], dtype=np.int64)]).astype(np.int32),
+         "hap_off": np.concatenate([[0], np.cumsum([len(h) for h in haps], dtype=np.int64)]).astype(np.int32),
+         "pair_ref": np.ascontiguousarray(pair_ref, np.int32),
+         "ref_seq": np.frombuffer(b"".join(refs), np.uint8).copy(), "hap_seq": np.frombuffer(b"".join(haps), np.uint8).copy()}
+    return a
+
+
+def _struct(a, addr):
+    b = capi.dd_align_batch()
+    b.n_refs, b.n_pairs = len(a["ref_off"]) - 1, len(a["hap_off"]) - 1
+    for k in ("ref_off", "ref_seq", "pair_ref", "hap_off", "hap_seq"):
+        setattr(b, k, addr(a[k]))
+    return b
+
+
+def _host_addr(arr):
+    return arr.ctypes.data if arr.size else None
+
+
+def host_batch(a):
+    """dd_align_batch over the numpy arrays of pack() (which must stay alive)."""
+    return _struct(a, _host_addr)
+
+
+def align_haplotypes(refs, haps, pair_ref, device=0):
+    """Align haps[i] (bytes) globally against refs[pair_ref[i]].  Returns dict(score int32 [n], status int32 [n], ref_pos int16 laid
+    out like the concatenated haplotypes, hap_off int32 [n + 1]): ref_pos[hap_off[i] + b] is the 0-based offset of the reference
+    base that base b of haplotype i is paired with, or -1 - n when it faces a gap, n = the number of reference bases left of its column."""
+    lib = capi.load()
+    a = pack(refs, haps, pair_ref)
+    n = len(haps)
+    out = {"score": np.zeros(max(n, 1), np.int32), "status": np.zeros(max(n, 1), np.int32),
+           "ref_pos": np.zeros(max(int(a["hap_off"][-1]), 1), np.int16)}
+    b = host_batch(a)
+    r = capi.dd_align_result(out["score"].ctypes.data, out["status"].ctypes.data, out["ref_pos"].ctypes.data)
+    rc = lib.dd_align_haplotypes(C.byref(b), C.byref(r), device)
+    if rc != 0:
+        raise RuntimeError("dd_align_haplotypes: %d %s" % (rc, capi.last_error()))
+    return {"score": out["score"][:n], "status": out["status"][:n], "ref_pos": out["ref_pos"][:int(a["hap_off"][-1])], "hap_off": a["hap_off"]}
+
+
+def gapped_rows(ref, hap, ref_pos):
+    """The two gapped rows (reference, haplotype) of one alignment, as SeqAn prints them: ACGT of the converted bases, '-' for a gap.
+    ref_pos: the pair's slice of the result.  A base that faces a gap carries -1 - n, n = the reference bases left of its column
+    (DD_ALIGN_GAP_REFS), which is what orders it against deleted reference bases next to it."""
+    r, h = dna_text(ref), dna_text(hap)
+    row0, row1, nxt = [], [], 0
+    for b, p in enumerate(np.asarray(ref_pos).tolist()):
+        upto = p if p >= 0 else -1 - p                   # reference bases in front of this column: deleted ones first
+        if not nxt <= upto <= len(r) - (p >= 0):
+            raise ValueError("ref_pos does not describe an alignment")
+        row0.append(r[nxt:upto]); row1.append("-" * (upto - nxt))
+        nxt = upto
+        if p < 0:
+            row0.append("-"); row1.append(h[b])
+        else:
+            row0.append(r[p]); row1.append(h[b])
+            nxt = p + 1
+    row0.append(r[nxt:]); row1.append("-" * (len(r) - nxt))
+    return "".join(row0), "".join(row1)
+
+
+def last_launch():
+    """This thread's last alignment launch: dict(grid, waves, tile_bytes, lds_block, pairs, ws_bytes, max_draws, guard_trips); the last
+    two come from the workspace header (after a DeviceAlign launch the object must still be alive; the call synchronises its stream)."""
+    out = (C.c_int64 * len(capi.ALIGN_LOG_FIELDS))()
+    capi.load().dd_align_last_launch(C.byref(out))
+    return dict(zip(capi.ALIGN_LOG_FIELDS, list(out)))
+
+
+class DeviceAlign:
+    """An alignment batch resident in HBM: torch owns the tensors and the stream, dd_align_haplotypes_device does the work."""
+
+    def __init__(self, refs, haps, pair_ref, device="cuda:0", max_workgroups=None):
+        """max_workgroups: give the launch a workspace for no more than that many workgroups (the grid follows the workspace); None = the
+        full grid of dd_align_workspace_bytes."""
+        import torch
+        from .device import _to_dev
+        lib = capi.load()
+        self.a = pack(refs, haps, pair_ref)
+        self.n_pairs = len(haps)
+        self.hap_bytes = int(self.a["hap_off"][-1])
+        self.device = torch.device(device)
+        hb = host_batch(self.a)
+        self.ws_bytes = lib.dd_align_workspace_bytes(C.byref(hb))
+        if self.ws_bytes == 0:
+            raise ValueError("dd_align_workspace_bytes: " + capi.last_error())
+        lim = capi.DD_LONG_MAX_HAP_LEN
+        rl, hl = np.diff(self.a["ref_off"]), np.diff(self.a["hap_off"])
+        self.max_ref_len = max(int(rl[rl <= lim].max(initial=1)), 1)
+        self.max_hap_len = max(int(hl[hl <= lim].max(initial=1)), 1)
+        if max_workgroups is not None:
+            tile = ((self.max_ref_len + 64) * self.max_hap_len + 255) // 256 * 256
+            self.ws_bytes = min(self.ws_bytes, 256 + 4 * tile * max(int(max_workgroups), 1))
+        self.t = {k: _to_dev(v, self.device) for k, v in self.a.items()}
+        self.score = torch.zeros(max(self.n_pairs, 1), dtype=torch.int32, device=self.device)
+        self.status = torch.zeros(max(self.n_pairs, 1), dtype=torch.int32, device=self.device)
+        self.ref_pos = torch.zeros(max(self.hap_bytes, 1), dtype=torch.int16, device=self.device)
+        self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
+        self.batch = _struct(self.t, lambda t: t.data_ptr())
+        self.result = capi.dd_align_result(self.score.data_ptr(), self.status.data_ptr(), self.ref_pos.data_ptr())
+
+    def launch(self, stream=None):
+        """Enqueue the alignment on `stream` (a torch stream; None = the current one).  Asynchronous."""
+        import torch
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        rc = capi.load().dd_align_haplotypes_device(C.byref(self.batch), C.byref(self.result), self.max_ref_len, self.max_hap_len,
+                                                    self.workspace.data_ptr(), self.ws_bytes, st.cuda_stream)
+        if rc != 0:
+            raise RuntimeError("dd_align_haplotypes_device: %d %s" % (rc, capi.last_error()))
+
+    def results(self):
+        """Synchronise and copy back: the dict align_haplotypes returns."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        return {"score": self.score.cpu().numpy()[:self.n_pairs], "status": self.status.cpu().numpy()[:self.n_pairs],
+                "ref_pos": self.ref_pos.cpu().numpy()[:self.hap_bytes], "hap_off": self.a["hap_off"]}

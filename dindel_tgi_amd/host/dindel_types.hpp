@@ -130,6 +130,9 @@ public:
     // hap.ml.hpos of the reference (Haplotype.hpp: `MLAlignment ml`, filled by alignHaplotypes): for every haplotype base its
     // offset on the window's reference sequence, or a negative MLAlignment code.  Only getCIGAR reads it; empty = not aligned.
     std::vector<int> refHpos;
+    // Haplotype::align of the reference (ml.align of alignHaplotypes): per reference base 'R', 'D' or the SNP's letter.  Filled by
+    // alignHaplotypesBatch only; the haplotype file does not carry it and the likelihood path does not read it.
+    std::string align;
     size_t size() const { return seq.size(); }
     const char &operator[](size_t i) const { return seq[i]; }
     // reference Haplotype.hpp:254-270

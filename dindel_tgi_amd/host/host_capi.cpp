@@ -675,7 +675,8 @@ int ddh_fast_inflate_check(const unsigned char *comp, int clen, const unsigned c
 unsigned ddh_fast_crc32(unsigned crc, const unsigned char *buf, int n) { return fastCrc32(crc, buf, size_t(n)); }
 
 // the haplotype fixture as the driver sees it: for the windows asked for, [index, leftPos, rightPos, [[seq, [[kind, key, string, startHap,
-// endHap, startRead, endRead, leftFlankHap, rightFlankHap, leftFlankRead, rightFlankRead], ...]], ...]] (null: no such window)
+// endHap, startRead, endRead, leftFlankHap, rightFlankHap, leftFlankRead, rightFlankRead], ...]], ...]] (null: no such window); a window
+// with an R record has its reference sequence as a fifth element
 int ddh_fixture_json(const char *path, const int *indices, int n, char *out, int cap)
 {
     try {
@@ -708,7 +709,9 @@ int ddh_fixture_json(const char *path, const int *indices, int n, char *out, int
                 }
                 os << "]";
             }
-            os << "]]";
+            os << "]";
+            if (!w->refSeq.empty()) os << ",\"" << w->refSeq << "\"";      // the R record, when the file carries one: a fifth element
+            os << "]";
         }
         os << "]";
         return emit(os.str(), out, cap);

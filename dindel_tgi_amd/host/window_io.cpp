@@ -228,6 +228,9 @@ void parseFixtureStretch(const char *p, const char *end, int lineNo, const std::
             w.leftPos = uint32_t(integer(2, "Cannot read window record")); w.rightPos = uint32_t(integer(3, "Cannot read window record"));
             out.push_back(w);
             cur = &out.back();
+        } else if (tag == 'R') {
+            if (!cur || tok.size() < 2) throw bad("Cannot read reference sequence record");
+            cur->refSeq.assign(tok[1].first, tok[1].second);
         } else if (tag == 'H') {
             if (!cur || tok.size() < 2) throw bad("Cannot read haplotype record");
             cur->haps.push_back(Haplotype(std::string(tok[1].first, tok[1].second)));
@@ -348,11 +351,24 @@ const WindowHaplotypes *HaplotypeFixture::find(int index) const
             if (one.size() != 1) throw std::string("Cannot read window record of ").append(fileName_);
             e.win.index = one[0].index; e.win.leftPos = one[0].leftPos; e.win.rightPos = one[0].rightPos;
             e.win.haps.swap(one[0].haps);
+            e.win.refSeq.swap(one[0].refSeq);
             e.state = 1;
         } catch (std::string &msg) { e.error = msg; e.state = 2; }
     }
     if (e.state == 2) { Error err; err.message = e.error; throw err; }
     return &e.win;
+}
+
+void HaplotypeFixture::listWindows(std::vector<int> &indices, std::vector<int> &lines) const
+{
+    std::vector<std::pair<size_t, int> > byOffset;
+    for (std::map<int, Entry>::const_iterator it = windows.begin(); it != windows.end(); ++it) byOffset.push_back(std::make_pair(it->second.begin, it->first));
+    std::sort(byOffset.begin(), byOffset.end());
+    indices.clear(); lines.clear();
+    for (size_t i = 0; i < byOffset.size(); i++) {
+        indices.push_back(byOffset[i].second);
+        lines.push_back(windows.find(byOffset[i].second)->second.lineBase + 1);
+    }
 }
 
 void HaplotypeFixture::release(int index) const

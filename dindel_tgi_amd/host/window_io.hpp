@@ -59,9 +59,12 @@ public:
 //   V I|S <key> <string> <startHap> <endHap> <startRead> <endRead> <leftFlankHap> <rightFlankHap> <leftFlankRead> <rightFlankRead>
 //   A <refpos of base 0> <refpos of base 1> ...      optional, after H: the haplotype's alignment to the window's reference
 //                                                    sequence (hap.ml.hpos; -1 = inserted base), needed by --outputRealignedBAM
+//   R <reference sequence of the block>              optional, after W: getRefSeq(leftPos + 1, rightPos + 1), upper-cased — the input of
+//                                                    dindel_hapalign, which aligns the H records against it; dindel_gpu ignores it
 struct WindowHaplotypes {
     int index; uint32_t leftPos, rightPos;
     std::vector<Haplotype> haps;
+    std::string refSeq;          // the R record; empty = none
 };
 // The file is indexed when it is opened (where each W record starts; a later record of an index replaces an earlier one) and a window's
 // records are parsed the first time it is asked for — by the thread that asks, so the workers that prepare windows side by side share
@@ -76,6 +79,8 @@ public:
     // the caller is done with what find(index) returned: the parsed records are dropped (a later find() parses them again), so that a
     // long run holds the windows in flight only
     void release(int index) const;
+    // the windows of the file in file order: their indices and the (1-based) line of each one's W record
+    void listWindows(std::vector<int> &indices, std::vector<int> &lines) const;
 private:
     struct Entry { size_t begin, end; int lineBase; mutable int state; mutable WindowHaplotypes win; mutable std::string error; };
     std::string fileName_;

@@ -451,6 +451,63 @@ int dd_cigars_device(const dd_device_batch *b, const int16_t *hpos_dev, const in
 int dd_compute_likelihoods_cigars(const dd_params *p, const dd_batch *b, dd_result *r, const int32_t *hap_ref_pos, const uint8_t *hap_aligned,
                                   const dd_cigar_result *cig, int ops_cap, int device, uint32_t options);
 
+/* ---- alignHaplotypes: candidate haplotypes against the window's reference sequence ---------- */
+/* The arithmetic of DetInDel::alignHaplotypes (reference DInDel.cpp:1427-1524): SeqAn's globalAlignment with
+ * Score<int>(-1, -460, -100, -960) and no free end gaps, i.e. _align_gotoh / _align_gotoh_trace of seqan/graph_align/graph_align_gotoh.h,
+ * tie rules and traceback state machine included.  Row 0 (columns) is the reference window, row 1 (rows) the haplotype; both are read as
+ * seqan::Dna (A/a 0, C/c 1, G/g 2, T/t/U/u 3, every other byte 0 = A).  match -1, mismatch -460, a gap of n bases -960 - 100 (n - 1).
+ * A batch is n_refs reference sequences and n_pairs haplotypes, each naming its reference; all offsets are in bytes of their sequence
+ * array and start at 0.  The host conversion to Haplotype::indels / snps / ml.hpos is the C++ adapter's (host/align_haplotypes.cpp). */
+typedef struct dd_align_batch {
+    int32_t        n_refs;
+    const int32_t *ref_off;    /* [n_refs + 1] */
+    const char    *ref_seq;    /* [ref_off[n_refs]] */
+    int32_t        n_pairs;
+    const int32_t *pair_ref;   /* [n_pairs] index of the pair's reference */
+    const int32_t *hap_off;    /* [n_pairs + 1] */
+    const char    *hap_seq;    /* [hap_off[n_pairs]] */
+} dd_align_batch;
+/* Per pair: score (the alignment's, int32) and status; per haplotype base, laid out like hap_seq: the 0-based offset of the reference
+ * base it is paired with, or a negative value when it faces a gap: DD_ALIGN_GAP(n) = -1 - n, n = the number of reference bases left of
+ * its column.  Reference bases no haplotype base names are deleted, and n places an inserted base among them: SeqAn writes a block
+ * substitution as deletion then insertion (n = the end of the deleted run) but an overhang at the matrix edge the other way round, and
+ * convertAlignment treats the two differently, so the offsets of the paired bases alone do not determine the alignment.  A pair whose
+ * status is not DD_ALIGN_OK has score 0 and its ref_pos slice all -1; its neighbours are untouched. */
+#define DD_ALIGN_IS_GAP(v)    ((v) < 0)
+#define DD_ALIGN_GAP_REFS(v)  (-1 - (v))
+typedef struct dd_align_result {
+    int32_t *score;     /* [n_pairs] */
+    int32_t *status;    /* [n_pairs] DD_ALIGN_* */
+    int16_t *ref_pos;   /* [hap_off[n_pairs]] */
+} dd_align_result;
+#define DD_ALIGN_OK        0
+#define DD_ALIGN_EMPTY     1   /* either sequence has length 0 (checked first) */
+#define DD_ALIGN_TOO_LONG  2   /* a length above DD_LONG_MAX_HAP_LEN (device entry: above the max_*_len of the launch) */
+#define DD_ALIGN_BAD_REF   3   /* device entry only: pair_ref outside [0, n_refs); the host entries return DD_ERR_INVALID instead */
+/* Host pointers in, host pointers out; the library owns device memory and the launch.  DD_ERR_INVALID (before any launch) for null
+ * pointers, offsets that do not start at 0 or decrease, and a pair_ref out of range; DD_ERR_NO_DEVICE without a GPU. */
+int dd_align_haplotypes(const dd_align_batch *b, dd_align_result *r, int device);
+/* Workspace bytes of a launch over a batch of this shape (HOST pointers; the offsets and pair_ref are read): the header and one trace tile of
+ * (longest reference + 64) x (longest haplotype) bytes per wavefront of the grid, lengths above the limit not counted.  The grid is one
+ * wavefront per pair, four wavefronts per workgroup, at most 2,048 workgroups, and shrinks so the tiles stay within 512 MiB, never below
+ * one workgroup.  The batch's longest pair sizes every wavefront's tile and LDS rows: one 4,000-bp haplotype among 130-bp ones costs the
+ * whole launch its occupancy, so a caller with such outliers gives them a launch of their own.  0 on a malformed shape (dd_last_error). */
+size_t dd_align_workspace_bytes(const dd_align_batch *shape);
+/* Device pointers: the arrays of b_dev and r_dev live on the device, n_refs and n_pairs are values.  max_ref_len / max_hap_len
+ * (1 ... DD_LONG_MAX_HAP_LEN) size the trace tile; longer pairs come back DD_ALIGN_TOO_LONG.  The grid is what workspace_bytes allows
+ * (at least the header and four tiles, else DD_ERR_INVALID; dd_align_workspace_bytes gives the full grid).  The contents of the offset
+ * arrays cannot be checked here.  Asynchronous on `stream`, no allocation; the pair counter in the workspace header is zeroed on the
+ * stream in front of the launch, so a workspace can be reused by consecutive launches of one stream. */
+int dd_align_haplotypes_device(const dd_align_batch *b_dev, const dd_align_result *r_dev, int max_ref_len, int max_hap_len,
+                               void *workspace, size_t workspace_bytes, void *stream);
+/* The last alignment launch on this host thread: {grid (workgroups), wavefronts, tile bytes, LDS bytes per workgroup, pairs, workspace
+ * bytes used, most pairs one wavefront drew, wavefronts stopped by the draw guard}.  The last two are read from the workspace header:
+ * after dd_align_haplotypes_device this synchronises the launch's stream and the workspace must still be allocated (-1 if the read fails).
+ * The guard count is 0 unless the persistent loop's draw went wrong (a wavefront that iterates more often than the batch has pairs is
+ * stopped and counted): the tests assert it. */
+#define DD_ALIGN_LOG_FIELDS 8
+void dd_align_last_launch(int64_t out[DD_ALIGN_LOG_FIELDS]);
+
 /* ---- N1 (next row): read sums of the diploid genotype reduction --------------------------- */
 /* S[w][h1*H_w+h2] (h1<=h2) = sum over the window's reads, in order, of log(0.5)+addLogs(ll[h1][r], ll[h2][r])
  * — the inner loop of DetInDel::diploidGLF, reference DInDel.cpp:3085-3091 (and :3372-3374); addLogs is
