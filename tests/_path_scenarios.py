@@ -1,0 +1,434 @@
+"""One small batch that reaches every per-pair code path of the main HMM kernel (helper; no tests in here).
+
+scenario_windows(hap_len, read_len, mld, rng) builds windows whose longest haplotype is hap_len bp (so hap_len decides the lane tiling) and
+whose reads are read_len bp unless a family says otherwise.  The constructions are those of tests/test_gpu_edge_cases.py,
+tests/test_insert_prior.py and tests/test_gpu_half_wave.py, restated with an explicit random generator so that a batch is a function of
+(hap_len, read_len, mld, seed).  Families (the keys of the returned index map; "family.part" keys are subsets the CPU tests look at):
+
+  redo      reads whose best log-likelihood is below -99 (the bound of the pass that leaves the RO chain out), next to ordinary reads
+  ties      tandem repeats AC / CAG / T and a homopolymer: exact ties (updateMax's tie-break, the near-tie join replay)
+  ends      overhanging reads, reads at / beyond hapEnd and before hapStart, wrapped and far-left starts, an unmapped read, 1- and 2-bp
+            reads, insertions at the first / last read base and at the haplotype ends, a deletion ladder 1 .. mld + 1
+  bytes     N runs, IUPAC and lower-case bytes in haplotypes and reads
+  quals     every Phred 0..93, the literals of test_quality_extremes_and_full_tables, a filler up to 256 distinct base qualities in the
+            batch, the mapping-quality ladder past the Phred-100 cap
+  flags     (not a set of pairs of its own: every haplotype of the main windows carries variants of kinds 1 and 2; the key lists the
+            pairs of those windows)
+  mates     all 16 combinations of the mate flags over two libraries
+  screened  a window the screen rejects (an empty read), one without reads, one without haplotypes, the hapSize-error pair (mld >= 5)
+  chunk     only for half-wave tilings (G == 2 in capi.HAP_CLASSES): 300 reads of 36 / 48 / 60 bp in one window
+"""
+import numpy as np
+
+from dindel_tgi_amd import capi
+from dindel_tgi_amd.batch import ReadRec, Window, phred_to_prob
+from tests.test_insert_prior import library
+
+HAP_START = 1000
+FAMILIES = ("redo", "ties", "ends", "bytes", "quals", "flags", "mates", "screened", "chunk")
+REDO_MIN_LEN = 260            # as in test_low_likelihood_pairs_redo_with_ro_chain (250 bp): at Phred 2-4 the best path costs 0.4-0.65 per base
+CHUNK_READS, CHUNK_LENS = 300, (36, 48, 60)
+Q30, Q20, Q10 = (float(v) for v in phred_to_prob([30, 20, 10]))
+MQ = float(phred_to_prob([40])[0])
+
+
+def rnd(rng, n, alphabet="ACGT"):
+    return "".join(rng.choice(list(alphabet), n)) if n > 0 else ""
+
+
+def mutate(rng, s, rate):
+    out = list(s)
+    for i in range(len(out)):
+        if rng.random() < rate:
+            out[i] = str(rng.choice(list("ACGT")))
+    return "".join(out)
+
+
+def seq_at(rng, hap, off, L):
+    """L bases of hap from offset off; random bases where the read hangs over an end."""
+    return "".join(hap[i] if 0 <= i < len(hap) else str(rng.choice(list("ACGT"))) for i in range(off, off + L))
+
+
+def spread_reads(rng, src, n, L, q=Q30, mq=MQ, sub=0.02):
+    """n reads of L bp at offsets spread evenly from a quarter read left of the haplotype to a quarter read beyond it: some cover the
+    middle, some an end, whatever the haplotype's length."""
+    lo, hi = -(L // 4), len(src) - L + L // 4
+    reads = []
+    for i in range(n):
+        off = lo + (hi - lo) * i // max(1, n - 1) if n > 1 else (lo + hi) // 2
+        reads.append(ReadRec(mutate(rng, seq_at(rng, src, off, L), sub), [q] * L, mq, HAP_START + off))
+    return reads
+
+
+def shorter(hap, k, at, mld):
+    """hap without k bases at `at` — or hap itself when that would make it no longer than maxLengthDel (hapSize error belongs to `screened`)."""
+    return hap[:at] + hap[at + k:] if len(hap) - k > max(mld, 3) else hap
+
+
+def variants(haps):
+    """One DEL-kind variant in the middle and one INS-kind variant at the left end of every haplotype (hap_vars, hap_var_flanks)."""
+    hv, hf = [], []
+    for h in haps:
+        m = len(h) // 2
+        hv.append([(m, m + 1), (1, 2)])
+        hf.append([(m - 1, m + 2, 1), (0, 3, 2)])
+    return hv, hf
+
+
+def redo_reads(rng, hap, L, n=6):
+    reads = []
+    for i in range(n):
+        off = int(rng.integers(-(L // 3), max(1, len(hap) - L + L // 3) + 1)) if len(hap) + L // 3 > L else -(L // 3)
+        q = float(phred_to_prob([2 + (i % 3)])[0])
+        reads.append(ReadRec(mutate(rng, seq_at(rng, hap, off, L), 0.2), [q] * L, [1 - 1e-16, 0.5, 0.999999][i % 3], HAP_START + off))
+    return reads
+
+
+def ends_reads(rng, hap, L, mld):
+    """-> (reads, indices of the deletion-ladder reads 1 .. mld + 1 within them)."""
+    Hs = len(hap)
+    S = HAP_START
+    ov = max(1, min(L // 3, 15))
+    tail = min(L, Hs)
+    mid = (Hs - L) // 2
+    reads = [ReadRec(seq_at(rng, hap, -ov, L), [Q30] * L, MQ, S - ov),                        # hangs over the left end
+             ReadRec(seq_at(rng, hap, Hs - L + ov, L), [Q20] * L, MQ, S + Hs - L + ov),       # ... the right end
+             ReadRec(hap[Hs - tail:], [Q30] * tail, MQ, S + Hs),                              # starts exactly at hapEnd
+             ReadRec(hap[Hs - tail:], [Q30] * tail, MQ, S + Hs + 1),                          # one base beyond it
+             ReadRec(hap[:tail], [Q30] * tail, MQ, S - tail),                                 # ends one base before hapStart
+             ReadRec(hap[:tail], [Q30] * tail, MQ, S - tail + 1),                             # overlaps only its last base
+             ReadRec(seq_at(rng, hap, mid, L), [Q30] * L, MQ, 0xFFFFFFFF),                    # uint32(-1.0) start
+             ReadRec(seq_at(rng, hap, mid, L), [Q30] * L, MQ, 3),                             # far left of the window
+             ReadRec(seq_at(rng, hap, mid, L), [Q30] * L, MQ, S + mid, unmapped=True),
+             ReadRec(hap[10:11], [Q20], MQ, S + 10),                                          # L = 1
+             ReadRec(hap[10:12], [Q20, Q10], MQ, S + 10)]                                     # L = 2
+    for ln in range(1, 5):                                                                    # insertions at the first / last read base
+        ins = rnd(rng, ln)
+        body = max(1, L - ln)
+        off = max(0, (Hs - body) // 2)
+        core = seq_at(rng, hap, off, body)
+        reads.append(ReadRec(ins + core, [Q30] * (ln + body), MQ, S + off - ln))
+        reads.append(ReadRec(core + ins, [Q30] * (ln + body), MQ, S + off))
+    for ln in (1, 4):                                                                         # ... right at the haplotype ends
+        ins = rnd(rng, ln)
+        body = max(1, min(L - ln, Hs))
+        reads.append(ReadRec(ins + hap[:body], [Q30] * (ln + body), MQ, S - ln))
+        reads.append(ReadRec(hap[Hs - body:] + ins, [Q30] * (ln + body), MQ, S + Hs - body))
+    ladder = []
+    for ln in range(1, mld + 2):                                                              # deletion of ln bases in the middle of the read
+        Lr = min(L, Hs - ln)
+        left = Lr // 2
+        c = left + (Hs - ln - Lr) // 2
+        s = hap[c - left:c] + hap[c + ln:c + ln + Lr - left]
+        ladder.append(len(reads))
+        reads.append(ReadRec(s, [Q30] * len(s), MQ, S + c - left))
+    return reads, ladder
+
+
+def quals_reads(rng, hap, L, used):
+    """Reads over the mapping-quality ladder whose base qualities run through Phred 0..93, the literals and a filler that brings the batch
+    to 256 distinct base qualities (`used`: the values the other families take, all of them in the Phred table)."""
+    table = [float(v) for v in phred_to_prob(np.arange(0, 94))] + [1e-16, 0.5, 0.25, 0.95, 0.950000001, 0.949999999]
+    table = sorted(set(table))                                                                # (Phred 0 is clamped to the literal 1e-16)
+    seen = set(table) | set(used)
+    assert len(seen) == len(table), "the other families keep to the Phred table"
+    fill = []
+    for v in np.linspace(0.3, 0.99999, 400):
+        if len(seen) == 256:
+            break
+        if float(v) not in seen:
+            seen.add(float(v)); fill.append(float(v))
+    todo = table + fill
+    mqs = [min(1.0 - 10.0 ** (-ph / 10.0), 1.0 - 1e-16) if ph else 0.0 for ph in (0, 3, 9, 21, 30, 42, 63, 80, 99, 100, 101, 120, 150)]
+    mqs += [1e-16, 0.5, 0.9, 0.99, 1 - 1e-10, 1 - 1e-11, 1 - 1e-16]
+    n = max(len(mqs), (len(todo) + L - 1) // L)
+    reads = []
+    for i in range(n):
+        q = todo[:L]
+        todo = todo[L:]
+        q = q + [float(v) for v in rng.choice(table, L - len(q))]
+        off = (len(hap) - L) * (i % 7) // 6 if len(hap) > L else -((L - len(hap)) // 2)
+        good = seq_at(rng, hap, off, L)
+        s = (good, rnd(rng, L), mutate(rng, good, 0.15))[i % 3]                               # belongs, does not belong, mismatches
+        reads.append(ReadRec(s, q, mqs[i % len(mqs)], HAP_START + off))
+    assert not todo
+    return reads
+
+
+def mates_reads(rng, haps, L, libs):
+    """All 16 combinations of (paired, mate_unmapped, mate_reverse, mate_same_tid), then six paired reads with a mapped mate on the same
+    chromosome: both orientations x both libraries, one of unknown mate length, one unmapped itself.
+    -> (reads, indices with a usable mate, indices without): the reference applies the prior only to a paired read whose mate is
+    mapped, on the same chromosome and of known length (ObservationModelFB.cpp:279-283)."""
+    combos = [(bool(i & 1), bool(i & 2), bool(i & 4), bool(i & 8), (i >> 2) & 1, (36, 76, 100)[i % 3], False) for i in range(16)]
+    combos += [(True, False, rev, True, lib, 76, False) for rev in (False, True) for lib in (0, 1)]
+    combos += [(True, False, False, True, 0, -1, False), (True, False, True, True, 1, 100, True)]
+    reads, usable, unusable = [], [], []
+    for i, (paired, m_unm, m_rev, same, lib, mlen, unmapped) in enumerate(combos):
+        src = haps[i % len(haps)]
+        off = (len(src) - L) * (i % 5) // 4 if len(src) > L else -((L - len(src)) // 2)
+        mode = int(np.argmax(libs[lib][0]))
+        mpos = HAP_START + off + (-mode if m_rev else mode) + int(rng.integers(-40, 40))
+        reads.append(ReadRec(mutate(rng, seq_at(rng, src, off, L), 0.02), [float(v) for v in phred_to_prob(rng.integers(5, 41, L))], MQ,
+                             HAP_START + off, unmapped=unmapped, paired=paired, mate_unmapped=m_unm, mate_reverse=m_rev, mate_same_tid=same,
+                             mate_pos=mpos, mate_len=mlen, lib=lib))
+        (usable if paired and not m_unm and same and mlen != -1 else unusable).append(i)
+    return reads, usable, unusable
+
+
+def ties_windows(rng, hap_len, L, mld):
+    ws = []
+    rep_len = max(12, min(60, hap_len // 2))
+    for unit in ("AC", "CAG", "T"):
+        n_rep = rep_len // len(unit)
+        left = (hap_len - n_rep * len(unit)) // 2
+        hap = rnd(rng, left) + unit * n_rep + rnd(rng, hap_len - left - n_rep * len(unit))
+        rep = unit * (n_rep + 40)
+        reads = [ReadRec(rep[:k], [Q30] * k, MQ, HAP_START + left) for k in sorted({max(2, rep_len // 5), max(3, 2 * rep_len // 5), max(4, rep_len // 2)})]
+        k = n_rep * len(unit) + 2 * len(unit) + 4                                             # longer than the repeat
+        reads.append(ReadRec(rep[:k], [Q20] * k, float(phred_to_prob([20])[0]), HAP_START + left - len(unit) - 2))
+        reads += spread_reads(rng, hap, 2, L)
+        ws.append(Window(HAP_START, [hap, shorter(hap, len(unit), left, mld), rnd(rng, hap_len)], reads))
+    n1, n2 = min(30, hap_len), (90 if hap_len >= 80 else hap_len + 10)
+    ws.append(Window(HAP_START, ["A" * hap_len], [ReadRec("A" * n1, [Q30] * n1, MQ, HAP_START + min(10, hap_len - n1)),
+                                                  ReadRec("A" * n2, [Q20] * n2, 0.9, HAP_START - 10)]))
+    return ws
+
+
+def bytes_window(rng, hap_len, L, mld):
+    alpha, prob = list("ACGTNRYKMacgtn"), [.2, .2, .2, .2, .03, .02, .02, .01, .01, .03, .03, .02, .02, .01]
+    hap = list(rng.choice(alpha, hap_len, p=prob))
+    for i, ch in enumerate("NRYKMacgtn"):                                                     # every special byte at least once
+        hap[(3 + 2 * i) % hap_len] = ch
+    hap = "".join(hap)
+    c = hap_len // 2
+    hapN = rnd(rng, hap_len)
+    hapN = hapN[:c] + "NNN" + hapN[c + 3:]                                                    # --changeINStoN style haplotype
+    hap2 = shorter(hap, 3, hap_len // 3, mld)
+    reads = []
+    for i, src in enumerate((hap, hap2, hapN, hap, hapN, hap2)):
+        off = (len(src) - L) * (i % 4) // 3 if len(src) > L else -((L - len(src)) // 2)
+        s = seq_at(rng, src, off, L)
+        s = "".join(ch if rng.random() > 0.05 else str(rng.choice(list("ACGTNRWSacg"))) for ch in s)
+        reads.append(ReadRec(s, [float(v) for v in phred_to_prob(rng.integers(2, 42, L))], MQ, HAP_START + off))
+    off = max(0, c - L // 2)
+    s = seq_at(rng, hapN.replace("N", "A"), off, L)
+    k = min(L - 1, L // 2)
+    reads.append(ReadRec(s[:k] + "N" + s[k + 1:], [Q30] * L, MQ, HAP_START + off))
+    if L >= 8:
+        reads.append(ReadRec(s[:2] + "R" + s[3:L - 4] + "nY" + s[L - 2:], [Q20] * L, MQ, HAP_START + off))
+    nN = min(L, 40)
+    reads.append(ReadRec("N" * nN, [Q10] * nN, 0.99, HAP_START + off))
+    return Window(HAP_START, [hap, hap2, hapN], reads)
+
+
+def scenario_windows(hap_len, read_len, mld, rng):
+    """-> (windows, libraries, index): the windows, the `libraries` argument of batch.pack, and a dict from family name (and "family.part")
+    to the indices of its pairs in the packed batch (window-major, then haplotype, then read: the layout of the result arrays)."""
+    L = int(read_len)
+    G = next(c[1] for c in capi.HAP_CLASSES if hap_len <= c[0])
+    libs = [library(rng, 600, 300), library(rng, 200, 80)]
+    windows, index = [], {k: [] for k in FAMILIES}
+    n_pairs = [0]
+
+    def add(window, families):
+        """families: {name: read indices within the window, or None for every read}."""
+        H, R = len(window.haps), len(window.reads)
+        for name, rs in families.items():
+            rs = range(R) if rs is None else rs
+            index.setdefault(name, []).extend(n_pairs[0] + h * R + r for h in range(H) for r in rs)
+        windows.append(window)
+        n_pairs[0] += H * R
+        return len(windows) - 1
+
+    # ---- the main windows: the same three haplotypes, one window per family (the oracle works on windows in parallel) ----
+    hap = rnd(rng, hap_len)
+    haps = [hap, shorter(hap, 2, hap_len // 2, mld), shorter(hap, 1, hap_len // 3, mld)]
+    hv, hf = variants(haps)
+
+    def main(reads, families):
+        return add(Window(HAP_START, haps, reads, hap_vars=hv, hap_var_flanks=hf), dict(families, flags=None))
+
+    Lredo = max(L, REDO_MIN_LEN)
+    low = redo_reads(rng, hap, Lredo)
+    ordinary = spread_reads(rng, hap, 4, L) + spread_reads(rng, haps[1], 2, L) + spread_reads(rng, hap, 2, Lredo)   # the last two share the redo reads' launch
+    main(low + ordinary, {"redo": range(len(low)), "redo.ordinary": range(len(low), len(low) + len(ordinary))})
+    e_reads, ladder = ends_reads(rng, hap, L, mld)
+    main(e_reads[:ladder[0]], {"ends": None})
+    first = n_pairs[0]
+    main(e_reads[ladder[0]:], {"ends": None})
+    index["ends.ladder"] = [first + i for i in range(len(ladder))]                          # on the haplotype the ladder is cut out of
+    m_reads, usable, unusable = mates_reads(rng, haps, L, libs)
+    index["mates.window"] = [main(m_reads, {"mates": None, "mates.usable": usable, "mates.unusable": unusable})]
+    used = {float(v) for v in phred_to_prob(np.arange(2, 42))} | {Q30, Q20, Q10}
+    main(quals_reads(rng, hap, L, used), {"quals": None})
+
+    for w in ties_windows(rng, hap_len, L, mld):
+        hv, hf = variants(w.haps)
+        w.hap_vars, w.hap_var_flanks = hv, hf
+        add(w, {"ties": None, "flags": None})
+    w = bytes_window(rng, hap_len, L, mld)
+    w.hap_vars, w.hap_var_flanks = variants(w.haps)
+    add(w, {"bytes": None, "flags": None})
+
+    # ---- screened: skipped and failed pairs in the same batch ----
+    small = rnd(rng, min(80, hap_len))
+    add(Window(HAP_START, [small, small[:20] + small[22:]], [ReadRec("", [], MQ, HAP_START)]), {"screened": None, "screened.rejected": None})
+    add(Window(HAP_START, [small], []), {"screened": None})
+    add(Window(HAP_START, [], spread_reads(rng, small, 3, min(L, 30))), {"screened": None})
+    if mld >= 5:
+        rs = spread_reads(rng, small, 5, min(L, 30))
+        add(Window(HAP_START, [small, "ACGT"], rs, hap_vars=[[(20, 22)], [(1, 2), (0, 3)]], hap_var_flanks=[[(19, 23, 1)], [(0, 3, 2), (1, 2, 1)]]),
+            {"screened": None})
+        index["screened.hapsize"] = list(range(n_pairs[0] - len(rs), n_pairs[0]))
+
+    # ---- chunk: more reads than one ordering chunk of the half-wave builds, three lengths ----
+    if G == 2:
+        alt = shorter(hap, 2, hap_len // 2, mld)
+        rs = []
+        for i in range(CHUNK_READS):
+            src, Lr = (hap, alt)[i & 1], CHUNK_LENS[i % 3]
+            off = int(rng.integers(-(Lr // 4), max(1, len(src) - Lr + Lr // 4)))
+            rs.append(ReadRec(mutate(rng, seq_at(rng, src, off, Lr), 0.02), [float(phred_to_prob([int(rng.integers(5, 41))])[0])] * Lr, MQ,
+                              HAP_START + off))
+        index["chunk.window"] = [add(Window(HAP_START, [hap, alt], rs), {"chunk": None})]
+    return windows, libs, {k: np.asarray(v, np.int64) for k, v in index.items()}
+
+
+def element_pairs(pb):
+    """For every element of the arrays that are not laid out per pair, the pair it belongs to: dict(hpos=, var_covered=, var_fcov=, onHap=)
+    (onHap is per read: the read's pair with the window's first haplotype, -1 in a window without haplotypes)."""
+    a = pb.a
+    hpos = np.full(max(pb.hpos_len, 1), -1, np.int64)
+    var = np.full(max(pb.var_cov_len, 1), -1, np.int64)
+    on = np.full(max(pb.n_reads, 1), -1, np.int64)
+    for w in range(pb.n_windows):
+        h0, h1 = int(a["win_hap_off"][w]), int(a["win_hap_off"][w + 1])
+        r0, r1 = int(a["win_read_off"][w]), int(a["win_read_off"][w + 1])
+        H, R = h1 - h0, r1 - r0
+        p0 = int(pb.win_pair_off[w])
+        if H and R:
+            on[r0:r1] = p0 + np.arange(R)
+        rl = np.diff(a["read_seq_off"][r0:r1 + 1]).astype(np.int64)
+        per_hap = np.repeat(np.arange(R), rl)                                                # read of every base of the window
+        o = int(pb.win_hpos_off[w])
+        for h in range(H):
+            hpos[o:o + len(per_hap)] = p0 + h * R + per_hap
+            o += len(per_hap)
+        v = int(pb.win_varcov_off[w])
+        for g in range(h0, h1):
+            nv = int(a["hap_var_off"][g + 1] - a["hap_var_off"][g])
+            var[v:v + nv * R] = p0 + (g - h0) * R + np.repeat(np.arange(R), nv)
+            v += nv * R
+    return dict(hpos=hpos, var_covered=var, var_fcov=var, onHap=on)
+
+
+def family_of(pair, index):
+    """The scenario families (top-level keys) a pair belongs to, as text."""
+    names = [k for k in FAMILIES if k in index and pair in set(index[k].tolist())]
+    return "+".join(n for n in names if n != "flags" or len(names) == 1) or "none"
+
+
+def first_difference(got, want, pb, index):
+    """None when got equals want in everything tests/test_gpu_parity.assert_same compares — and in the hpos of every computed pair, which
+    assert_same leaves out of a batch that holds hapSize-error pairs; else (array name, element, pair, family) of the difference with the
+    lowest pair index."""
+    from tests.test_gpu_parity import F64_KEYS, INT_KEYS
+    ok = want["status"][:pb.n_pairs] != capi.DD_PAIR_HAPSIZE
+    elem = element_pairs(pb)
+    n_of = {"hpos": pb.hpos_len, "var_covered": pb.var_cov_len, "var_fcov": pb.var_cov_len, "onHap": pb.n_reads}
+    best = None
+    for k in ["status"] + [k for k in INT_KEYS if k != "status"] + F64_KEYS:
+        if k in n_of:
+            n = n_of[k]
+            bad = np.nonzero(got[k][:n] != want[k][:n])[0]
+            if k == "hpos":
+                bad = bad[ok[elem[k][bad]]]                  # (the hpos of a hapSize-error pair is not written)
+            pairs = elem[k][bad]
+        else:
+            g, w = got[k][:pb.n_pairs], want[k][:pb.n_pairs]
+            bad = np.nonzero((g != w) & (ok | (k == "status")))[0]
+            pairs = bad
+        if bad.size and (best is None or int(pairs.min()) < best[2]):
+            i = int(np.argmin(pairs))
+            best = (k, int(bad[i]), int(pairs[i]))
+    return None if best is None else best + (family_of(best[2], index),)
+
+
+def with_screened(got, want, pb, index):
+    """-> (got', want'): the arrays to compare when the batch holds the window the screen rejects.  The library defines four values of such
+    a pair (include/dindel_hmm.h, hmm_kernel.hip mark_unsupported): DD_PAIR_UNSUPPORTED, ll = 0, offHap = offHapHMQ = 1, and its reads are on
+    no haplotype; want' has them in place of the oracle's.  The pair's other values are not written by the library: both copies get 0
+    there.  (The window's one read is empty: it has no hpos element, and its haplotypes carry no variant.)"""
+    got, exp = {k: v.copy() for k, v in got.items()}, {k: v.copy() for k, v in want.items()}
+    rej = index["screened.rejected"]
+    for k in exp:
+        if k not in ("hpos", "var_covered", "var_fcov", "onHap", "status", "ll", "offHap", "offHapHMQ"):
+            exp[k][rej] = 0
+            got[k][rej] = 0
+    exp["status"][rej] = capi.DD_PAIR_UNSUPPORTED
+    exp["ll"][rej] = 0.0
+    exp["offHap"][rej] = 1
+    exp["offHapHMQ"][rej] = 1
+    reads = np.nonzero(np.isin(element_pairs(pb)["onHap"][:pb.n_reads], rej))[0]
+    exp["onHap"][reads] = 0
+    return got, exp
+
+
+# ---- the grid the CPU reach tests and the GPU matrix share ----
+# (maxLengthDel, read length): the cases of tests/test_gpu_persistent_rounds.py with (5, 330) for the K = 3 two-waves variant, then what
+# tests/test_path_scenarios_cpu.py's sweep of dd_plan_info showed missing under the default environment
+GRID = [(5, 100), (10, 100), (11, 100), (15, 100), (5, 36), (5, 330), (10, 194), (11, 36)]
+
+
+def hap_lengths(mld):
+    """Every class bound (the last lane full: RO and the end states on the tiling's edge) and every previous bound + 1, without what the plan
+    rejects: the D = 32 build above 574 bp, haplotypes that leave no variant longer than maxLengthDel."""
+    out = []
+    for c, bound in enumerate(capi.HAP_CLASS_BOUNDS):
+        for hl in ((capi.HAP_CLASS_BOUNDS[c - 1] + 1 if c else 1), bound):
+            if (mld > 11 and hl > 574) or hl <= mld:
+                continue
+            out.append(hl)
+    return out
+
+
+def batch_for(hap_len, read_len, mld):
+    """-> (PackedBatch, index map) of the grid point; the seed is a function of the point."""
+    from dindel_tgi_amd.batch import pack
+    ws, libs, index = scenario_windows(hap_len, read_len, mld, np.random.default_rng(1000003 * mld + 1009 * read_len + hap_len))
+    return pack(ws, libraries=libs), index
+
+
+def params_for(mld, map_unmapped=1):
+    p = capi.params_cli_defaults()
+    p.maxLengthDel = mld
+    p.mapUnmappedReads = map_unmapped
+    return p
+
+
+def kernel_name(rec):
+    """A capi.launch_log() record as the kernel's name (launch.cpp dd_kernel_name): dd_hmm_kernel<K, D, GBT, FOLD, OCC, G>."""
+    return "dd_hmm_kernel<%d, %d, %s, %s, %d, %d>" % (rec["K"], rec["D"], "true" if rec["gbt"] else "false", "true" if rec["fold"] else "false",
+                                                      rec["occ"], rec["pairs_per_wave"])
+
+
+def planned_builds(lib, p, pb):
+    """The (K, Dt, gbt, G, hap class, max read) of every launch the library plans for the batch under the current environment — host arithmetic
+    only (dd_screen_windows, dd_build_length_classes, dd_plan_info): what capi.launch_log() reports after a run, without a device."""
+    import ctypes as C
+    b = pb.ctypes_batch()
+    skip = np.zeros(max(pb.n_windows, 1), np.uint8)
+    mx = (C.c_int32 * 2)()
+    assert lib.dd_screen_windows(C.byref(b), skip.ctypes.data_as(capi.c_u8p), C.byref(mx)) >= 0, capi.last_error()
+    cls = capi.dd_length_classes()
+    lst = np.zeros(max(pb.n_haps, 1) * capi.N_READ_CLASSES + 1, np.int32)
+    assert lib.dd_build_length_classes(C.byref(b), skip.ctypes.data_as(capi.c_u8p), C.byref(p), lst.ctypes.data_as(capi.c_i32p), C.byref(cls)) == 0, capi.last_error()
+    out = []
+    for i in range(cls.n_launches):
+        L = cls.launch[i]
+        info = (C.c_int32 * 10)()
+        assert lib.dd_plan_info(C.byref(p), L.max_hap_len, L.max_read_len, len(pb.a["qual_table"]), max(L.avg_window_reads, 1), max(L.list_len, 1),
+                                C.byref(info)) == 0, capi.last_error()
+        out.append((info[0], info[1], info[2], info[8], L.hap_class, L.max_read_len))
+    return out

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Long randomised GPU-vs-oracle parity campaign (both models), beyond what the test-suite budget allows.
   python tests/fuzz_campaign.py [--seconds 300] [--seed0 0]
-Every round draws a shape class, parameters and adversarial windows (tests/test_gpu_fuzz.make_windows plus
-synth.generate mixes), runs the C ABI and the oracle (16 threads) and requires bit-equality.  Prints one line per
-round; exits non-zero at the first mismatch after dumping the seed."""
+Every round draws a shape class, parameters and adversarial windows (tests/test_gpu_fuzz.make_windows — one round in four of
+that kind takes the path scenarios of tests/_path_scenarios.py instead — plus synth.generate mixes), runs the C ABI and
+the oracle (16 threads) and requires bit-equality.  Prints one line per round ("kind 0s": a scenario round); exits non-zero at the first mismatch after dumping the seed."""
 import argparse
 import os
 import sys
@@ -16,6 +16,7 @@ from dindel_tgi_amd import capi, synth
 from dindel_tgi_amd.batch import pack
 from tests import _oracle
 from tests.test_gpu_fuzz import make_windows
+from tests._path_scenarios import scenario_windows
 from tests.test_gpu_parity import assert_same, run_host_api
 from tests.test_gpu_faster import assert_same_faster, run_faster
 
@@ -48,10 +49,17 @@ while time.time() < t_end:
         max_hap = int(rng.choice([23, 40, 62, 87, 126, 151, 190, 215, 254, 400, 755]))   # make_windows adds up to 7 inserted bases; every lane tiling incl. the half-wave ones
         if p.maxLengthDel > 11 and max_hap > 560:
             max_hap = 560
-        ws = make_windows(rng, int(rng.integers(5, 60)), max_hap, int(rng.choice([30, 100, 160, 300, 700])), min_hap=1,
-                          with_vars=bool(rng.random() < 0.6))
         libs = None
-        if rng.random() < 0.5:                                          # insert-size prior inputs (mapUnmappedReads)
+        scenario = rng.random() < 0.25                                  # every per-pair path at a random shape (tests/_path_scenarios.py)
+        if scenario:
+            hap_len = int(rng.integers(max(40, p.maxLengthDel + 4), (574 if p.maxLengthDel > 11 else 766) + 1))
+            ws, libs, _index = scenario_windows(hap_len, int(rng.integers(20, 200)), p.maxLengthDel, rng)
+            ws = [w for w in ws if all(len(r.seq) for r in w.reads)]     # (without the window the screen rejects: the oracle has no status for it)
+            p.mapUnmappedReads = int(rng.random() < 0.85)
+        else:
+            ws = make_windows(rng, int(rng.integers(5, 60)), max_hap, int(rng.choice([30, 100, 160, 300, 700])), min_hap=1,
+                              with_vars=bool(rng.random() < 0.6))
+        if not scenario and rng.random() < 0.5:                         # insert-size prior inputs (mapUnmappedReads)
             from tests.test_insert_prior import library
             libs = [library(rng, int(rng.integers(1, 900)), int(rng.integers(1, 400))) for _ in range(int(rng.integers(1, 4)))]
             p.mapUnmappedReads = int(rng.random() < 0.85)
@@ -117,7 +125,7 @@ while time.time() < t_end:
         print(str(e)[:2000], flush=True)
         sys.exit(1)
     pairs += pb.n_pairs
-    print("round %d seed %d kind %d pairs %d (total %d) max_hap %d max_read %d mld %d ok" %
-          (rnd, seed, kind, pb.n_pairs, pairs, pb.max_hap_len, pb.max_read_len, p.maxLengthDel), flush=True)
+    print("round %d seed %d kind %s pairs %d (total %d) max_hap %d max_read %d mld %d ok" %
+          (rnd, seed, "0s" if kind == 0 and scenario else kind, pb.n_pairs, pairs, pb.max_hap_len, pb.max_read_len, p.maxLengthDel), flush=True)
     rnd += 1
 print("campaign ok: %d rounds, %d pairs per model" % (rnd, pairs))
