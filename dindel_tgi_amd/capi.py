@@ -41,6 +41,10 @@ DD_CIGAR_DEFAULT_OPS_CAP = 8
 DD_ALIGN_OK, DD_ALIGN_EMPTY, DD_ALIGN_TOO_LONG, DD_ALIGN_BAD_REF = range(4)
 DD_ALIGN_WS_BUDGET = 512 << 20
 ALIGN_LOG_FIELDS = ["grid", "waves", "tile_bytes", "lds_block", "pairs", "ws_bytes", "max_draws", "guard_trips"]
+# the indel events of an alignment (dd_align_events records)
+DD_ALIGN_EVENT_INS, DD_ALIGN_EVENT_DEL = 1, 2
+DD_ALIGN_EVENTS_MAX_CAP = 4096
+ALIGN_EVENTS_LOG_FIELDS = ["grid", "pairs", "max_draws", "guard_trips"]
 CIGAR_MESSAGES = {DD_CIGAR_HAP_NOT_ALIGNED: "Haplotype has not been aligned!", DD_CIGAR_ERROR1: "Error(1)!", DD_CIGAR_ERROR2: "Error(2)!",
                   DD_CIGAR_ERROR3: "Error(3)!", DD_CIGAR_ERROR4: "Error(4)!", DD_CIGAR_IMPOSSIBLE: "How is this possible? (1)"}
 
@@ -154,6 +158,11 @@ class dd_align_result(C.Structure):
     _fields_ = [("score", C.c_void_p), ("status", C.c_void_p), ("ref_pos", C.c_void_p)]
 
 
+class dd_align_events(C.Structure):
+    """One indel of one pair as convertAlignment keys it: kind (DD_ALIGN_EVENT_*), ref, len, hap."""
+    _fields_ = [("kind", C.c_int16), ("ref", C.c_int16), ("len", C.c_int16), ("hap", C.c_int16)]
+
+
 class dd_device_result(C.Structure):
     """dd_result with raw device addresses (same layout: every member is a pointer)."""
     _fields_ = [(n, C.c_void_p) for n, _ in RESULT_FIELDS]
@@ -166,7 +175,8 @@ EXPORTS = ["dd_params_struct_defaults", "dd_params_cli_defaults", "dd_batch_size
            "dd_screen_windows_ex", "dd_compute_likelihoods_ex", "dd_workspace_bytes_long", "dd_launch_device_long", "dd_long_launch_log",
            "dd_compute_likelihoods_faster_ex", "dd_workspace_bytes_faster_long", "dd_launch_device_faster_long", "dd_faster_long_launch_log",
            "dd_cigars_device", "dd_compute_likelihoods_cigars",
-           "dd_align_haplotypes", "dd_align_workspace_bytes", "dd_align_haplotypes_device", "dd_align_last_launch"]
+           "dd_align_haplotypes", "dd_align_workspace_bytes", "dd_align_haplotypes_device", "dd_align_last_launch",
+           "dd_align_events_device", "dd_align_haplotypes_events", "dd_align_events_last_launch"]
 
 _lib = None
 
@@ -243,6 +253,10 @@ def load():
                                                C.c_void_p]
     lib.dd_align_last_launch.argtypes = [C.POINTER(C.c_int64 * len(ALIGN_LOG_FIELDS))]
     lib.dd_align_last_launch.restype = None
+    lib.dd_align_events_device.argtypes = [C.POINTER(dd_align_batch), C.POINTER(dd_align_result), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.dd_align_haplotypes_events.argtypes = [C.POINTER(dd_align_batch), C.POINTER(dd_align_result), C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    lib.dd_align_events_last_launch.argtypes = [C.POINTER(C.c_int64 * len(ALIGN_EVENTS_LOG_FIELDS))]
+    lib.dd_align_events_last_launch.restype = None
     lib.dd_last_launch.argtypes = [C.POINTER(C.c_int32 * 8)]
     lib.dd_last_launch.restype = None
     lib.dd_launch_log.argtypes = [c_i32p, C.c_int]

@@ -1,0 +1,32 @@
+// align_events_kernel.h — argument block and launcher of the indel-event extraction (align_events_kernel.hip), shared with align_host.cpp.
+#ifndef DD_ALIGN_EVENTS_KERNEL_H
+#define DD_ALIGN_EVENTS_KERNEL_H
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "hapalign_kernel.h"
+
+namespace dda {
+
+/* The event launch runs behind an alignment launch and keeps its three words in that launch's workspace header (DD_ALIGN_WS_HEADER bytes,
+ * of which the alignment uses words 0 ... 2): zeroed on the stream in front of the event launch. */
+#define DD_EVENTS_HDR_COUNTER 4       /* header word: u32 pair counter of the event launch */
+#define DD_EVENTS_HDR_MAX_DRAWS 5     /* header word: most pairs one wavefront drew */
+#define DD_EVENTS_HDR_TRIPS 6         /* header word: wavefronts that left through the draw guard: 0 */
+
+struct EventsArgs {
+    int32_t n_refs, n_pairs;
+    const int32_t *ref_off;              /* [n_refs + 1]: the reference length decides INS against RO */
+    const int32_t *pair_ref, *hap_off;   /* [n_pairs], [n_pairs + 1] */
+    const int32_t *status;               /* [n_pairs] as the alignment left it */
+    const int16_t *ref_pos;              /* laid out like hap_seq */
+    int32_t *n_events;                   /* [n_pairs] */
+    dd_align_events *events;             /* [n_pairs * events_cap] */
+    int32_t events_cap;
+    unsigned int *hdr;                   /* the alignment workspace's header, as u32 words */
+};
+
+unsigned events_grid(int64_t n_pairs);
+hipError_t launch_align_events(const EventsArgs &A, hipStream_t st);
+
+} // namespace dda
+#endif

@@ -1,7 +1,9 @@
 // align_host.cpp — host side of the haplotype-to-reference alignment (hapalign_kernel.hip): validation of a dd_align_batch, the grid /
-// workspace rule, the device-pointer launch and the host-pointer entry (its own allocations: one call per batch of windows).
+// workspace rule, the device-pointer launch and the host-pointer entry (its own allocations: one call per batch of windows); and the same
+// three for the indel-event extraction that runs behind an alignment launch (align_events_kernel.hip).
 #include "capi_internal.h"
 #include "hapalign_kernel.h"
+#include "align_events_kernel.h"
 
 namespace ddh {
 namespace {
@@ -12,6 +14,22 @@ struct AlignShape { int64_t ref_bytes, hap_bytes; int max_ref_len, max_hap_len; 
 // whose workspace does not outlive the call)
 struct AlignLast { int64_t v[DD_ALIGN_LOG_FIELDS]; const unsigned char *ws; hipStream_t stream; bool have_stats; };
 thread_local AlignLast g_align_last = {{0, 0, 0, 0, 0, 0, 0, 0}, nullptr, nullptr, true};
+
+// this thread's last event launch; its device words are in the header of the alignment workspace it ran behind
+struct EventsLast { int64_t v[DD_ALIGN_EVENTS_LOG_FIELDS]; const unsigned char *ws; hipStream_t stream; bool have_stats; };
+thread_local EventsLast g_events_last = {{0, 0, 0, 0}, nullptr, nullptr, true};
+
+int read_events_stats()
+{
+    EventsLast &L = g_events_last;
+    if (L.have_stats || !L.ws) return DD_SUCCESS;
+    uint32_t hdr[3];
+    HIP_TRY(hipStreamSynchronize(L.stream));
+    HIP_TRY(hipMemcpy(hdr, L.ws + 4 * DD_EVENTS_HDR_COUNTER, sizeof(hdr), hipMemcpyDeviceToHost));
+    L.v[2] = hdr[DD_EVENTS_HDR_MAX_DRAWS - DD_EVENTS_HDR_COUNTER]; L.v[3] = hdr[DD_EVENTS_HDR_TRIPS - DD_EVENTS_HDR_COUNTER];
+    L.have_stats = true;
+    return DD_SUCCESS;
+}
 
 int read_align_stats()
 {
@@ -118,14 +136,58 @@ void dd_align_last_launch(int64_t out[DD_ALIGN_LOG_FIELDS])
     if (out) memcpy(out, g_align_last.v, sizeof(g_align_last.v));
 }
 
-int dd_align_haplotypes(const dd_align_batch *b, dd_align_result *r, int device)
+int dd_align_events_device(const dd_align_batch *b, const dd_align_result *r, int32_t *n_events, dd_align_events *events, int events_cap,
+                           void *stream)
+{
+    if (!b || !r) return fail(DD_ERR_INVALID, "dd_align_events_device: null batch or result");
+    if (b->n_refs < 0 || b->n_pairs < 0) return fail(DD_ERR_INVALID, "dd_align_events_device: negative count");
+    if (events_cap < 1 || events_cap > DD_ALIGN_EVENTS_MAX_CAP)
+        return fail(DD_ERR_INVALID, "dd_align_events_device: events_cap outside 1 ... DD_ALIGN_EVENTS_MAX_CAP");
+    if (b->n_pairs == 0) return DD_SUCCESS;
+    if (!b->ref_off || !b->pair_ref || !b->hap_off || !r->status || !r->ref_pos || !n_events || !events)
+        return fail(DD_ERR_INVALID, "dd_align_events_device: null array");
+    if (reinterpret_cast<uintptr_t>(events) & 7u) return fail(DD_ERR_INVALID, "dd_align_events_device: events must be 8-byte aligned");
+    if (!g_align_last.ws)
+        return fail(DD_ERR_INVALID, "dd_align_events_device: no alignment launch of this thread to run behind (its workspace header holds the pair counter)");
+    dda::EventsArgs A;
+    A.n_refs = b->n_refs; A.n_pairs = b->n_pairs;
+    A.ref_off = b->ref_off; A.pair_ref = b->pair_ref; A.hap_off = b->hap_off;
+    A.status = r->status; A.ref_pos = r->ref_pos;
+    A.n_events = n_events; A.events = events; A.events_cap = events_cap;
+    A.hdr = reinterpret_cast<unsigned int *>(const_cast<unsigned char *>(g_align_last.ws));
+    const int64_t rec[DD_ALIGN_EVENTS_LOG_FIELDS] = {(int64_t)dda::events_grid(b->n_pairs), (int64_t)b->n_pairs, -1, -1};
+    memcpy(g_events_last.v, rec, sizeof(rec));
+    g_events_last.ws = g_align_last.ws; g_events_last.stream = static_cast<hipStream_t>(stream); g_events_last.have_stats = false;
+    HIP_TRY(dda::launch_align_events(A, static_cast<hipStream_t>(stream)));
+    return DD_SUCCESS;
+}
+
+void dd_align_events_last_launch(int64_t out[DD_ALIGN_EVENTS_LOG_FIELDS])
+{
+    (void)read_events_stats();                 // a failure leaves -1 in the two device fields
+    if (out) memcpy(out, g_events_last.v, sizeof(g_events_last.v));
+}
+
+} // extern "C"
+
+namespace ddh {
+namespace {
+
+// the two host-pointer entries: ev = nullptr is dd_align_haplotypes; with events the slice comes back only where the caller has room for it
+struct EventsOut { int32_t *n_events; dd_align_events *events; int cap; };
+
+int align_host_entry(const dd_align_batch *b, dd_align_result *r, const EventsOut *ev, int device)
 {
     AlignShape s;
     int rc = check_align_batch(b, s);
     if (rc) return rc;
     if (!r) return fail(DD_ERR_INVALID, "null align result");
     if (b->n_pairs > 0 && (!r->score || !r->status)) return fail(DD_ERR_INVALID, "null score or status in align result");
-    if (s.hap_bytes > 0 && !r->ref_pos) return fail(DD_ERR_INVALID, "null ref_pos in align result");
+    if (!ev && s.hap_bytes > 0 && !r->ref_pos) return fail(DD_ERR_INVALID, "null ref_pos in align result");
+    if (ev) {
+        if (ev->cap < 1 || ev->cap > DD_ALIGN_EVENTS_MAX_CAP) return fail(DD_ERR_INVALID, "events_cap outside 1 ... DD_ALIGN_EVENTS_MAX_CAP");
+        if (b->n_pairs > 0 && (!ev->n_events || !ev->events)) return fail(DD_ERR_INVALID, "null n_events or events");
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(DD_ERR_NO_DEVICE, "no HIP device: the haplotype alignment has no CPU fallback in this library");
@@ -136,11 +198,12 @@ int dd_align_haplotypes(const dd_align_batch *b, dd_align_result *r, int device)
     // one allocation, 256-byte aligned pieces: offsets, sequences, outputs, workspace
     const size_t ws_bytes = dd_align_workspace_bytes(b);
     const size_t P = (size_t)b->n_pairs, R = (size_t)b->n_refs;
+    const size_t ev_bytes = ev ? P * (size_t)ev->cap * sizeof(dd_align_events) : 0;
     size_t off = 0;
     auto take = [&off](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255u) & ~size_t(255u); return o; };
     const size_t o_roff = take((R + 1) * 4), o_rseq = take((size_t)s.ref_bytes), o_pref = take(P * 4), o_hoff = take((P + 1) * 4),
                  o_hseq = take((size_t)s.hap_bytes), o_score = take(P * 4), o_status = take(P * 4), o_rpos = take((size_t)s.hap_bytes * 2),
-                 o_ws = take(ws_bytes);
+                 o_ws = take(ws_bytes), o_nev = take(ev ? P * 4 : 0), o_ev = take(ev_bytes);
     struct Mem {
         unsigned char *p = nullptr;
         ~Mem() { if (p) (void)hipFree(p); }
@@ -159,13 +222,40 @@ int dd_align_haplotypes(const dd_align_batch *b, dd_align_result *r, int device)
     const dd_align_result dr = {reinterpret_cast<int32_t *>(d + o_score), reinterpret_cast<int32_t *>(d + o_status),
                                 reinterpret_cast<int16_t *>(d + o_rpos)};
     if ((rc = dd_align_haplotypes_device(&db, &dr, s.max_ref_len, s.max_hap_len, d + o_ws, ws_bytes, nullptr))) return rc;
+    if (ev) {
+        // records no event reaches stay 0: the caller's array is overwritten as a whole
+        HIP_TRY(hipMemsetAsync(d + o_ev, 0, ev_bytes, nullptr));
+        rc = dd_align_events_device(&db, &dr, reinterpret_cast<int32_t *>(d + o_nev), reinterpret_cast<dd_align_events *>(d + o_ev), ev->cap, nullptr);
+        if (rc) { g_align_last.ws = nullptr; g_events_last.ws = nullptr; return rc; }
+    }
     HIP_TRY(hipStreamSynchronize(nullptr));
     if ((rc = read_align_stats())) return rc;  // the workspace goes with this call
     g_align_last.ws = nullptr;
+    if (ev) {
+        if ((rc = read_events_stats())) return rc;
+        g_events_last.ws = nullptr;
+    }
     HIP_TRY(hipMemcpy(r->score, dr.score, P * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(r->status, dr.status, P * 4, hipMemcpyDeviceToHost));
-    if (s.hap_bytes) HIP_TRY(hipMemcpy(r->ref_pos, dr.ref_pos, (size_t)s.hap_bytes * 2, hipMemcpyDeviceToHost));
+    if (s.hap_bytes && r->ref_pos) HIP_TRY(hipMemcpy(r->ref_pos, dr.ref_pos, (size_t)s.hap_bytes * 2, hipMemcpyDeviceToHost));
+    if (ev) {
+        HIP_TRY(hipMemcpy(ev->n_events, d + o_nev, P * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ev->events, d + o_ev, ev_bytes, hipMemcpyDeviceToHost));
+    }
     return DD_SUCCESS;
+}
+
+} // namespace
+} // namespace ddh
+
+extern "C" {
+
+int dd_align_haplotypes(const dd_align_batch *b, dd_align_result *r, int device) { return align_host_entry(b, r, nullptr, device); }
+
+int dd_align_haplotypes_events(const dd_align_batch *b, dd_align_result *r, int32_t *n_events, dd_align_events *events, int events_cap, int device)
+{
+    const EventsOut ev = {n_events, events, events_cap};
+    return align_host_entry(b, r, &ev, device);
 }
 
 } // extern "C"

@@ -1,7 +1,8 @@
 """alignHaplotypes on the device: candidate haplotypes against their window's reference sequence (dd_align_haplotypes).
 
 The arithmetic is the library's HIP kernel (csrc/hapalign_kernel.hip); there is no Python or CPU implementation behind this module.
-`align_haplotypes` is the host-pointer entry, `DeviceAlign` keeps the batch in torch tensors and launches on a given stream, and
+`align_haplotypes` is the host-pointer entry, `align_events` the one that brings back indel events (csrc/align_events_kernel.hip)
+instead of the per-base slice, `DeviceAlign` keeps the batch in torch tensors and launches on a given stream, and
 `gapped_rows` rebuilds the two gapped rows of an alignment from the per-base reference offsets the kernel returns.
 """
 import ctypes as C
@@ -64,6 +65,38 @@ def align_haplotypes(refs, haps, pair_ref, device=0):
     if rc != 0:
         raise RuntimeError("dd_align_haplotypes: %d %s" % (rc, capi.last_error()))
     return {"score": out["score"][:n], "status": out["status"][:n], "ref_pos": out["ref_pos"][:int(a["hap_off"][-1])], "hap_off": a["hap_off"]}
+
+
+EVENT_FIELDS = ("kind", "ref", "len", "hap")
+
+
+def align_events(refs, haps, pair_ref, events_cap=8, device=0, with_ref_pos=False):
+    """Align like align_haplotypes and return the indel events of every pair instead of its slice: dict(score, status, n_events int32
+    [n], events int16 [n, events_cap, 4] with the fields of EVENT_FIELDS, hap_off).  n_events is the true count; a pair with
+    n_events > events_cap holds its first events_cap records.  with_ref_pos=True also copies the slice back (ref_pos)."""
+    lib = capi.load()
+    a = pack(refs, haps, pair_ref)
+    n, nb = len(haps), int(a["hap_off"][-1])
+    cap = max(int(events_cap), 1)
+    out = {"score": np.zeros(max(n, 1), np.int32), "status": np.zeros(max(n, 1), np.int32), "n_events": np.zeros(max(n, 1), np.int32),
+           "events": np.zeros((max(n, 1), cap, 4), np.int16), "ref_pos": np.zeros(max(nb, 1), np.int16)}
+    b = host_batch(a)
+    r = capi.dd_align_result(out["score"].ctypes.data, out["status"].ctypes.data, out["ref_pos"].ctypes.data if with_ref_pos else None)
+    rc = lib.dd_align_haplotypes_events(C.byref(b), C.byref(r), out["n_events"].ctypes.data, out["events"].ctypes.data, int(events_cap), device)
+    if rc != 0:
+        raise RuntimeError("dd_align_haplotypes_events: %d %s" % (rc, capi.last_error()))
+    res = {"score": out["score"][:n], "status": out["status"][:n], "n_events": out["n_events"][:n], "events": out["events"][:n],
+           "hap_off": a["hap_off"]}
+    if with_ref_pos:
+        res["ref_pos"] = out["ref_pos"][:nb]
+    return res
+
+
+def events_last_launch():
+    """This thread's last event launch: dict(grid, pairs, max_draws, guard_trips) (dd_align_events_last_launch)."""
+    out = (C.c_int64 * len(capi.ALIGN_EVENTS_LOG_FIELDS))()
+    capi.load().dd_align_events_last_launch(C.byref(out))
+    return dict(zip(capi.ALIGN_EVENTS_LOG_FIELDS, list(out)))
 
 
 def gapped_rows(ref, hap, ref_pos):
@@ -142,3 +175,28 @@ class DeviceAlign:
         torch.cuda.synchronize(self.device)
         return {"score": self.score.cpu().numpy()[:self.n_pairs], "status": self.status.cpu().numpy()[:self.n_pairs],
                 "ref_pos": self.ref_pos.cpu().numpy()[:self.hap_bytes], "hap_off": self.a["hap_off"]}
+
+    def launch_events(self, events_cap=8, stream=None, fill=0):
+        """Enqueue the event extraction behind launch() on the same stream: fills self.n_events (int32 [n_pairs]) and self.events
+        (int16 [n_pairs, events_cap, 4]).  The kernel writes only the records it counts; the rest of self.events is preset to `fill`
+        (None: left as it is, the tensors of the previous call are reused).  Asynchronous."""
+        import torch
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        cap = max(int(events_cap), 1)
+        with torch.cuda.stream(st):
+            if getattr(self, "events", None) is None or self.events.shape[1] != cap:
+                self.n_events = torch.zeros(max(self.n_pairs, 1), dtype=torch.int32, device=self.device)
+                self.events = torch.zeros((max(self.n_pairs, 1), cap, 4), dtype=torch.int16, device=self.device)
+            if fill is not None:
+                self.n_events.zero_()
+                self.events.fill_(fill)
+        rc = capi.load().dd_align_events_device(C.byref(self.batch), C.byref(self.result), self.n_events.data_ptr(), self.events.data_ptr(),
+                                                int(events_cap), st.cuda_stream)
+        if rc != 0:
+            raise RuntimeError("dd_align_events_device: %d %s" % (rc, capi.last_error()))
+
+    def event_results(self):
+        """Synchronise and copy back n_events and events of the last launch_events()."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        return {"n_events": self.n_events.cpu().numpy()[:self.n_pairs], "events": self.events.cpu().numpy()[:self.n_pairs]}

@@ -24,6 +24,7 @@ public:
     // for an unknown sequence; stops early at end of file (the script would spin there).
     std::string get(const std::string &tid, long pos1based, int len);
     bool has(const std::string &tid) const { return ft.find(tid) != ft.end(); }
+    long length(const std::string &tid) const { std::map<std::string, Target>::const_iterator it = ft.find(tid); return it == ft.end() ? -1 : it->second.len; }
     std::vector<std::string> names() const;                // in .fai order
 private:
     struct Target { long len, offset, blen, llen; };

@@ -967,3 +967,19 @@ int ddh_get_reads_pools_json(const char *bamPaths, const char *libFile, const ch
 }
 
 } // extern "C"
+
+// ---- candidate discovery (host/candidates.hpp): the one piece of it the tests take as given ---------------------------------------------
+#include "candidates.hpp"
+
+extern "C" {
+
+// The order in which the reference's position table — a __gnu_cxx::hash_map<int, ...> — is walked after it received `keys` in this
+// sequence (repeats allowed): out receives the distinct keys in that order, their number is returned.
+int ddh_hash_map_order(const int *keys, int n, int *out)
+{
+    const std::vector<int> order = dindel::hashMapOrder(std::vector<int>(keys, keys + (n > 0 ? n : 0)));
+    for (size_t i = 0; i < order.size(); i++) out[i] = order[i];
+    return int(order.size());
+}
+
+} // extern "C"

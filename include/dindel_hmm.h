@@ -508,6 +508,43 @@ int dd_align_haplotypes_device(const dd_align_batch *b_dev, const dd_align_resul
 #define DD_ALIGN_LOG_FIELDS 8
 void dd_align_last_launch(int64_t out[DD_ALIGN_LOG_FIELDS]);
 
+/* ---- indel events of an alignment: what convertAlignment puts into hap.indels, without the slice ---------- */
+/* One indel of one pair, as convertAlignment (reference ObservationModelSeqAn.hpp:142-269) would record it in hap.indels: keys, types,
+ * lengths and read positions only — no strings, no flanks, no SNPs.
+ *   kind  DD_ALIGN_EVENT_INS or DD_ALIGN_EVENT_DEL
+ *   ref   the map key: reference bases left of the event (an insertion sits in front of reference base `ref`, a deletion starts there)
+ *   len   inserted haplotype bases / deleted reference bases
+ *   hap   first inserted haplotype base; for a deletion the haplotype base behind it (its read positions are hap - 1 and hap)
+ * Rules, walking the haplotype bases in order (upto = reference bases left of the base's column, nxt = reference bases consumed so far):
+ * gap-facing bases with upto == 0 are LO and give nothing; upto > nxt in front of a base is a deletion, recorded only once a paired
+ * base has been seen; a maximal run of gap-facing bases with one upto = n gives an insertion only if 0 < n < reference length (else RO);
+ * reference bases behind the last haplotype base give nothing.  Events come in slice order, a deletion in front of base b before an
+ * insertion that starts at b. */
+typedef struct dd_align_events {
+    int16_t kind, ref, len, hap;
+} dd_align_events;
+#define DD_ALIGN_EVENT_INS 1
+#define DD_ALIGN_EVENT_DEL 2
+#define DD_ALIGN_EVENTS_MAX_CAP 4096
+/* Device pointers.  Reads what the dd_align_haplotypes_device launch of b_dev / r_dev left in r_dev->status and r_dev->ref_pos and writes
+ * per pair n_events_dev[pair] (the true count, also when it exceeds events_cap; 0 for a pair whose status is not DD_ALIGN_OK) and the
+ * first min(count, events_cap) records of events_dev[pair * events_cap ...]; nothing else of events_dev is written.  It runs BEHIND
+ * dd_align_haplotypes_device: same host thread, same stream, that launch's workspace still allocated — its pair counter and guard words
+ * live in that workspace's header (DD_ERR_INVALID when this thread has launched no alignment).  events_cap 1 ... DD_ALIGN_EVENTS_MAX_CAP.
+ * Asynchronous on `stream`, no allocation. */
+int dd_align_events_device(const dd_align_batch *b_dev, const dd_align_result *r_dev, int32_t *n_events_dev, dd_align_events *events_dev,
+                           int events_cap, void *stream);
+/* Host pointers: dd_align_haplotypes followed by the event launch.  score, status, n_events [n_pairs] and events [n_pairs * events_cap]
+ * always come back; r->ref_pos may be NULL, then no slice is copied back (the point of this entry: 8 * events_cap + 12 bytes per pair
+ * instead of two per haplotype base).  A pair with n_events > events_cap holds its first events_cap records; the caller redoes it from
+ * the slice.  Validation and errors as dd_align_haplotypes. */
+int dd_align_haplotypes_events(const dd_align_batch *b, dd_align_result *r, int32_t *n_events, dd_align_events *events, int events_cap,
+                               int device);
+/* The last event launch on this host thread: {grid (workgroups), pairs, most pairs one wavefront drew, wavefronts stopped by the draw
+ * guard}; the last two as in dd_align_last_launch (0 is the only healthy guard count). */
+#define DD_ALIGN_EVENTS_LOG_FIELDS 4
+void dd_align_events_last_launch(int64_t out[DD_ALIGN_EVENTS_LOG_FIELDS]);
+
 /* ---- N1 (next row): read sums of the diploid genotype reduction --------------------------- */
 /* S[w][h1*H_w+h2] (h1<=h2) = sum over the window's reads, in order, of log(0.5)+addLogs(ll[h1][r], ll[h2][r])
  * — the inner loop of DetInDel::diploidGLF, reference DInDel.cpp:3085-3091 (and :3372-3374); addLogs is
