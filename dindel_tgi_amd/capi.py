@@ -45,6 +45,10 @@ ALIGN_LOG_FIELDS = ["grid", "waves", "tile_bytes", "lds_block", "pairs", "ws_byt
 DD_ALIGN_EVENT_INS, DD_ALIGN_EVENT_DEL = 1, 2
 DD_ALIGN_EVENTS_MAX_CAP = 4096
 ALIGN_EVENTS_LOG_FIELDS = ["grid", "pairs", "max_draws", "guard_trips"]
+# the block table of a window's haplotype distribution: per-window status codes, limits and the launch record
+DD_HAPDIST_OK, DD_HAPDIST_TOO_WIDE, DD_HAPDIST_OVERFLOW, DD_HAPDIST_HOST = range(4)
+DD_HAPDIST_MAX_WINDOW, DD_HAPDIST_MAX_DISTINCT, DD_HAPDIST_MAX_INS_POS = 1024, 16, 64
+HAP_BLOCKS_LOG_FIELDS = ["grid", "windows", "max_draws", "guard_trips"]
 CIGAR_MESSAGES = {DD_CIGAR_HAP_NOT_ALIGNED: "Haplotype has not been aligned!", DD_CIGAR_ERROR1: "Error(1)!", DD_CIGAR_ERROR2: "Error(2)!",
                   DD_CIGAR_ERROR3: "Error(3)!", DD_CIGAR_ERROR4: "Error(4)!", DD_CIGAR_IMPOSSIBLE: "How is this possible? (1)"}
 
@@ -163,6 +167,24 @@ class dd_align_events(C.Structure):
     _fields_ = [("kind", C.c_int16), ("ref", C.c_int16), ("len", C.c_int16), ("hap", C.c_int16)]
 
 
+class dd_hap_batch(C.Structure):
+    """Windows and the reads laid over them (block table of the haplotype distribution).  Raw addresses: host arrays for
+    dd_hap_blocks_compute and dd_hap_blocks_offsets, device arrays for dd_hap_blocks_device."""
+    _fields_ = [("n_windows", C.c_int32), ("win_rs", C.c_void_p), ("win_ref_off", C.c_void_p), ("ref_seq", C.c_void_p),
+                ("win_read_off", C.c_void_p), ("n_reads", C.c_int32), ("read_pos", C.c_void_p), ("read_flag", C.c_void_p),
+                ("read_op_off", C.c_void_p), ("ops", C.c_void_p), ("read_base_off", C.c_void_p), ("bases", C.c_void_p)]
+
+
+HAP_BLOCKS_WINDOW_FIELDS = ("status", "n_blocks", "n_entries", "n_ins_ops", "n_ins_pos", "left")
+HAP_BLOCKS_OFFSET_FIELDS = ("blk_off", "ent_off", "ins_off")
+HAP_BLOCKS_TABLE_FIELDS = ("blocks", "entries", "ins_ops", "ins_pos")
+
+
+class dd_hap_blocks(C.Structure):
+    """The block tables of a dd_hap_batch; raw addresses like dd_hap_batch."""
+    _fields_ = [(n, C.c_void_p) for n in HAP_BLOCKS_WINDOW_FIELDS + HAP_BLOCKS_OFFSET_FIELDS + HAP_BLOCKS_TABLE_FIELDS]
+
+
 class dd_device_result(C.Structure):
     """dd_result with raw device addresses (same layout: every member is a pointer)."""
     _fields_ = [(n, C.c_void_p) for n, _ in RESULT_FIELDS]
@@ -176,7 +198,8 @@ EXPORTS = ["dd_params_struct_defaults", "dd_params_cli_defaults", "dd_batch_size
            "dd_compute_likelihoods_faster_ex", "dd_workspace_bytes_faster_long", "dd_launch_device_faster_long", "dd_faster_long_launch_log",
            "dd_cigars_device", "dd_compute_likelihoods_cigars",
            "dd_align_haplotypes", "dd_align_workspace_bytes", "dd_align_haplotypes_device", "dd_align_last_launch",
-           "dd_align_events_device", "dd_align_haplotypes_events", "dd_align_events_last_launch"]
+           "dd_align_events_device", "dd_align_haplotypes_events", "dd_align_events_last_launch",
+           "dd_hap_blocks_offsets", "dd_hap_blocks_workspace_bytes", "dd_hap_blocks_device", "dd_hap_blocks_compute", "dd_hap_blocks_last_launch"]
 
 _lib = None
 
@@ -257,6 +280,14 @@ def load():
     lib.dd_align_haplotypes_events.argtypes = [C.POINTER(dd_align_batch), C.POINTER(dd_align_result), C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     lib.dd_align_events_last_launch.argtypes = [C.POINTER(C.c_int64 * len(ALIGN_EVENTS_LOG_FIELDS))]
     lib.dd_align_events_last_launch.restype = None
+    lib.dd_hap_blocks_offsets.argtypes = [C.POINTER(dd_hap_batch), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dd_hap_blocks_workspace_bytes.argtypes = []
+    lib.dd_hap_blocks_workspace_bytes.restype = C.c_size_t
+    lib.dd_hap_blocks_device.argtypes = [C.POINTER(dd_hap_batch), C.POINTER(dd_hap_blocks), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
+                                         C.c_void_p]
+    lib.dd_hap_blocks_compute.argtypes = [C.POINTER(dd_hap_batch), C.POINTER(dd_hap_blocks), C.c_int]
+    lib.dd_hap_blocks_last_launch.argtypes = [C.POINTER(C.c_int64 * len(HAP_BLOCKS_LOG_FIELDS))]
+    lib.dd_hap_blocks_last_launch.restype = None
     lib.dd_last_launch.argtypes = [C.POINTER(C.c_int32 * 8)]
     lib.dd_last_launch.restype = None
     lib.dd_launch_log.argtypes = [c_i32p, C.c_int]

@@ -1,0 +1,28 @@
+// hapdist_kernel.h — argument block and launcher of the block-table kernel (hapdist_kernel.hip), shared with hapdist_host.cpp.
+#ifndef DD_HAPDIST_KERNEL_H
+#define DD_HAPDIST_KERNEL_H
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/dindel_hmm.h"
+
+namespace dda {
+
+#define DD_HAPDIST_WAVES 4            /* wavefronts per workgroup, one window each */
+#define DD_HAPDIST_MAX_BLOCKS 512     /* workgroups of the persistent grid: two per CU */
+#define DD_HAPDIST_WS_BYTES 256       /* the workspace: a header of u32 words */
+#define DD_HAPDIST_HDR_COUNTER 0      /* header word: u32 window counter */
+#define DD_HAPDIST_HDR_MAX_DRAWS 1    /* header word: most windows one wavefront drew */
+#define DD_HAPDIST_HDR_TRIPS 2        /* header word: wavefronts that left through the draw guard: 0 */
+
+struct HapdistArgs {
+    dd_hap_batch b;
+    dd_hap_blocks t;
+    int64_t max_blk, max_ent, max_ins;
+    unsigned int *hdr;
+};
+
+unsigned hapdist_grid(int64_t n_windows);
+hipError_t launch_hapdist(const HapdistArgs &A, hipStream_t st);
+
+} // namespace dda
+#endif

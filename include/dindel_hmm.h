@@ -545,6 +545,69 @@ int dd_align_haplotypes_events(const dd_align_batch *b, dd_align_result *r, int3
 #define DD_ALIGN_EVENTS_LOG_FIELDS 4
 void dd_align_events_last_launch(int64_t out[DD_ALIGN_EVENTS_LOG_FIELDS]);
 
+/* ---- block table of a window's empirical haplotype distribution (HaplotypeDistribution / HapBlock) ---------- */
+/* Windows and the reads laid over them, CSR-packed.  Raw addresses: host arrays for dd_hap_blocks_compute, device arrays for
+ * dd_hap_blocks_device.  A window is the reference piece [rs, rs + len) (len = win_ref_off[w + 1] - win_ref_off[w], the bytes as
+ * getRefSeq returned them) and the reads win_read_off[w] ... win_read_off[w + 1], in getReads' order.  A read is its 0-based position,
+ * its BAM flag, its CIGAR as BAM words (len << 4 | op) and its bases as letters (=ACMGRSVTWYHKDBN). */
+typedef struct dd_hap_batch {
+    int32_t n_windows;
+    const int32_t *win_rs;            /* [n_windows] */
+    const int32_t *win_ref_off;       /* [n_windows + 1], starts at 0 */
+    const char *ref_seq;
+    const int32_t *win_read_off;      /* [n_windows + 1], starts at 0 */
+    int32_t n_reads;
+    const int32_t *read_pos;          /* [n_reads] */
+    const int32_t *read_flag;         /* [n_reads] */
+    const int32_t *read_op_off;       /* [n_reads + 1], starts at 0 */
+    const uint32_t *ops;
+    const int32_t *read_base_off;     /* [n_reads + 1], starts at 0 */
+    const char *bases;
+} dd_hap_batch;
+/* Per-window status.  A window whose status is not DD_HAPDIST_OK has nothing but its status written. */
+#define DD_HAPDIST_OK 0
+#define DD_HAPDIST_TOO_WIDE 1         /* the reference piece is longer than DD_HAPDIST_MAX_WINDOW */
+#define DD_HAPDIST_OVERFLOW 2         /* a block with more than DD_HAPDIST_MAX_DISTINCT strings, more than DD_HAPDIST_MAX_INS_POS insertion
+                                       * positions, or more blocks / entries / insertions than the window's capacity in dd_hap_blocks */
+#define DD_HAPDIST_HOST 3             /* the reference throws on this window (an operation it does not know, "Mag niet."), or the input is one
+                                       * the closed form does not cover (empty reference piece, negative position with operations, a CIGAR
+                                       * longer than its read's bases): the caller runs its literal path */
+#define DD_HAPDIST_MAX_WINDOW 1024
+#define DD_HAPDIST_MAX_DISTINCT 16
+#define DD_HAPDIST_MAX_INS_POS 64
+/* The tables.  Capacities are the caller's: window w owns blocks[blk_off[w] ... blk_off[w + 1]), entries[ent_off[w] ... ent_off[w + 1])
+ * and ins_ops / ins_pos[ins_off[w] ... ins_off[w + 1]); dd_hap_blocks_offsets fills the three offset arrays with capacities no OK window
+ * can exceed except through DD_HAPDIST_OVERFLOW.  Raw addresses like dd_hap_batch.
+ *   blocks   one word per block inside the window, in position order: start - rs (bits 0-15), length 1 ... 4 (16-19), entries (20-25),
+ *            index of the entry equal to the reference piece (26-31)
+ *   entries  two words per entry, blocks back to back, a block's entries in std::string order: key (the bytes big-endian, left-aligned),
+ *            count (covering segments that show it; the reference counts once)
+ *   ins_ops  two words per insertion operation (length > 0) that starts inside the window, in (read, operation) order: read index inside the
+ *            window, operation index << 16 | (position - rs)
+ *   ins_pos  two words per insertion position in order of creation: position - rs, and what the empty (reference) entry collected from
+ *            operations crossing the position after its creation (its count is that + 1)
+ *   left     bit 0: a segment covers rs - 1 (the block left of the window ends there); bit 1: a segment starts left of rs */
+typedef struct dd_hap_blocks {
+    int32_t *status, *n_blocks, *n_entries, *n_ins_ops, *n_ins_pos, *left;   /* [n_windows] each */
+    const int32_t *blk_off, *ent_off, *ins_off;                              /* [n_windows + 1] each, start at 0 */
+    uint32_t *blocks, *entries, *ins_ops, *ins_pos;
+} dd_hap_blocks;
+/* Host pointers, no device: blk_off / ent_off / ins_off [n_windows + 1] for a batch (blocks: the window's length; entries: 4 per position
+ * + 64; insertions: the insertion operations of the window's reads). */
+int dd_hap_blocks_offsets(const dd_hap_batch *b, int32_t *blk_off, int32_t *ent_off, int32_t *ins_off);
+/* Bytes of the workspace dd_hap_blocks_device needs (the window counter and the draw guard's words). */
+size_t dd_hap_blocks_workspace_bytes(void);
+/* Device pointers, any stream, no allocation.  The offsets are checked on the device against nothing but themselves: max_blk, max_ent
+ * and max_ins are the lengths of blocks, entries / 2 and ins_ops / 2 = ins_pos / 2 the caller allocated, and no store goes past them. */
+int dd_hap_blocks_device(const dd_hap_batch *b_dev, const dd_hap_blocks *t_dev, int64_t max_blk, int64_t max_ent, int64_t max_ins,
+                         void *workspace, size_t workspace_bytes, void *stream);
+/* Host pointers: validates, copies, launches, copies back.  DD_ERR_INVALID before any launch; DD_ERR_NO_DEVICE without a GPU. */
+int dd_hap_blocks_compute(const dd_hap_batch *b, dd_hap_blocks *t, int device);
+/* The last block-table launch on this host thread: {grid (workgroups), windows, most windows one wavefront drew, wavefronts stopped by the
+ * draw guard}; the last two as in dd_align_last_launch (0 is the only healthy guard count). */
+#define DD_HAP_BLOCKS_LOG_FIELDS 4
+void dd_hap_blocks_last_launch(int64_t out[DD_HAP_BLOCKS_LOG_FIELDS]);
+
 /* ---- N1 (next row): read sums of the diploid genotype reduction --------------------------- */
 /* S[w][h1*H_w+h2] (h1<=h2) = sum over the window's reads, in order, of log(0.5)+addLogs(ll[h1][r], ll[h2][r])
  * — the inner loop of DetInDel::diploidGLF, reference DInDel.cpp:3085-3091 (and :3372-3374); addLogs is
