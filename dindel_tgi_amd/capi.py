@@ -45,6 +45,10 @@ ALIGN_LOG_FIELDS = ["grid", "waves", "tile_bytes", "lds_block", "pairs", "ws_byt
 DD_ALIGN_EVENT_INS, DD_ALIGN_EVENT_DEL = 1, 2
 DD_ALIGN_EVENTS_MAX_CAP = 4096
 ALIGN_EVENTS_LOG_FIELDS = ["grid", "pairs", "max_draws", "guard_trips"]
+# the variants of an alignment (dd_hap_variant records, dd_hap_variants_summary); the launch record has ALIGN_EVENTS_LOG_FIELDS
+DD_HAP_VARIANT_SNP, DD_HAP_VARIANT_DEL_UNSEEN = 3, 4
+DD_HAP_VARIANTS_LO_FIRST, DD_HAP_VARIANTS_RO_LAST, DD_HAP_VARIANTS_HOST = 1, 2, 4
+DD_HAP_VARIANTS_MAX_CAP = 4096
 # the block table of a window's haplotype distribution: per-window status codes, limits and the launch record
 DD_HAPDIST_OK, DD_HAPDIST_TOO_WIDE, DD_HAPDIST_OVERFLOW, DD_HAPDIST_HOST = range(4)
 DD_HAPDIST_MAX_WINDOW, DD_HAPDIST_MAX_DISTINCT, DD_HAPDIST_MAX_INS_POS = 1024, 16, 64
@@ -167,6 +171,16 @@ class dd_align_events(C.Structure):
     _fields_ = [("kind", C.c_int16), ("ref", C.c_int16), ("len", C.c_int16), ("hap", C.c_int16)]
 
 
+class dd_hap_variant(C.Structure):
+    """One variant of one pair with the four values of setFlanking: kind (DD_ALIGN_EVENT_INS / _DEL, DD_HAP_VARIANT_*), key, len, start_read."""
+    _fields_ = [(n, C.c_int16) for n in ("kind", "key", "len", "start_read", "left_flank_hap", "right_flank_hap", "left_flank_read", "right_flank_read")]
+
+
+class dd_hap_variants_summary(C.Structure):
+    """Per pair: the true record count, ml.firstBase / ml.lastBase and DD_HAP_VARIANTS_* flags."""
+    _fields_ = [(n, C.c_int32) for n in ("n_variants", "first_base", "last_base", "flags")]
+
+
 class dd_hap_batch(C.Structure):
     """Windows and the reads laid over them (block table of the haplotype distribution).  Raw addresses: host arrays for
     dd_hap_blocks_compute and dd_hap_blocks_offsets, device arrays for dd_hap_blocks_device."""
@@ -199,6 +213,7 @@ EXPORTS = ["dd_params_struct_defaults", "dd_params_cli_defaults", "dd_batch_size
            "dd_cigars_device", "dd_compute_likelihoods_cigars",
            "dd_align_haplotypes", "dd_align_workspace_bytes", "dd_align_haplotypes_device", "dd_align_last_launch",
            "dd_align_events_device", "dd_align_haplotypes_events", "dd_align_events_last_launch",
+           "dd_hap_variants_device", "dd_align_haplotypes_variants", "dd_hap_variants_last_launch",
            "dd_hap_blocks_offsets", "dd_hap_blocks_workspace_bytes", "dd_hap_blocks_device", "dd_hap_blocks_compute", "dd_hap_blocks_last_launch"]
 
 _lib = None
@@ -280,6 +295,10 @@ def load():
     lib.dd_align_haplotypes_events.argtypes = [C.POINTER(dd_align_batch), C.POINTER(dd_align_result), C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     lib.dd_align_events_last_launch.argtypes = [C.POINTER(C.c_int64 * len(ALIGN_EVENTS_LOG_FIELDS))]
     lib.dd_align_events_last_launch.restype = None
+    lib.dd_hap_variants_device.argtypes = [C.POINTER(dd_align_batch), C.POINTER(dd_align_result), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.dd_align_haplotypes_variants.argtypes = [C.POINTER(dd_align_batch), C.POINTER(dd_align_result), C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    lib.dd_hap_variants_last_launch.argtypes = [C.POINTER(C.c_int64 * len(ALIGN_EVENTS_LOG_FIELDS))]
+    lib.dd_hap_variants_last_launch.restype = None
     lib.dd_hap_blocks_offsets.argtypes = [C.POINTER(dd_hap_batch), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.dd_hap_blocks_workspace_bytes.argtypes = []
     lib.dd_hap_blocks_workspace_bytes.restype = C.c_size_t

@@ -1,9 +1,11 @@
 // align_host.cpp — host side of the haplotype-to-reference alignment (hapalign_kernel.hip): validation of a dd_align_batch, the grid /
 // workspace rule, the device-pointer launch and the host-pointer entry (its own allocations: one call per batch of windows); and the same
-// three for the indel-event extraction that runs behind an alignment launch (align_events_kernel.hip).
+// three for the indel-event extraction and for the variant extraction that run behind an alignment launch (align_events_kernel.hip,
+// hap_variants_kernel.hip).
 #include "capi_internal.h"
 #include "hapalign_kernel.h"
 #include "align_events_kernel.h"
+#include "hap_variants_kernel.h"
 
 namespace ddh {
 namespace {
@@ -27,6 +29,21 @@ int read_events_stats()
     HIP_TRY(hipStreamSynchronize(L.stream));
     HIP_TRY(hipMemcpy(hdr, L.ws + 4 * DD_EVENTS_HDR_COUNTER, sizeof(hdr), hipMemcpyDeviceToHost));
     L.v[2] = hdr[DD_EVENTS_HDR_MAX_DRAWS - DD_EVENTS_HDR_COUNTER]; L.v[3] = hdr[DD_EVENTS_HDR_TRIPS - DD_EVENTS_HDR_COUNTER];
+    L.have_stats = true;
+    return DD_SUCCESS;
+}
+
+// this thread's last variants launch, likewise
+thread_local EventsLast g_variants_last = {{0, 0, 0, 0}, nullptr, nullptr, true};
+
+int read_variants_stats()
+{
+    EventsLast &L = g_variants_last;
+    if (L.have_stats || !L.ws) return DD_SUCCESS;
+    uint32_t hdr[3];
+    HIP_TRY(hipStreamSynchronize(L.stream));
+    HIP_TRY(hipMemcpy(hdr, L.ws + 4 * DD_VARIANTS_HDR_COUNTER, sizeof(hdr), hipMemcpyDeviceToHost));
+    L.v[2] = hdr[DD_VARIANTS_HDR_MAX_DRAWS - DD_VARIANTS_HDR_COUNTER]; L.v[3] = hdr[DD_VARIANTS_HDR_TRIPS - DD_VARIANTS_HDR_COUNTER];
     L.have_stats = true;
     return DD_SUCCESS;
 }
@@ -168,22 +185,61 @@ void dd_align_events_last_launch(int64_t out[DD_ALIGN_EVENTS_LOG_FIELDS])
     if (out) memcpy(out, g_events_last.v, sizeof(g_events_last.v));
 }
 
+int dd_hap_variants_device(const dd_align_batch *b, const dd_align_result *r, dd_hap_variants_summary *summary, dd_hap_variant *variants, int cap,
+                           void *stream)
+{
+    if (!b || !r) return fail(DD_ERR_INVALID, "dd_hap_variants_device: null batch or result");
+    if (b->n_refs < 0 || b->n_pairs < 0) return fail(DD_ERR_INVALID, "dd_hap_variants_device: negative count");
+    if (cap < 1 || cap > DD_HAP_VARIANTS_MAX_CAP) return fail(DD_ERR_INVALID, "dd_hap_variants_device: cap outside 1 ... DD_HAP_VARIANTS_MAX_CAP");
+    if (b->n_pairs == 0) return DD_SUCCESS;
+    if (!b->ref_off || !b->ref_seq || !b->pair_ref || !b->hap_off || !b->hap_seq || !r->status || !r->ref_pos || !summary || !variants)
+        return fail(DD_ERR_INVALID, "dd_hap_variants_device: null array");
+    if (reinterpret_cast<uintptr_t>(variants) & 7u) return fail(DD_ERR_INVALID, "dd_hap_variants_device: variants must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(summary) & 3u) return fail(DD_ERR_INVALID, "dd_hap_variants_device: summary must be 4-byte aligned");
+    if (!g_align_last.ws)
+        return fail(DD_ERR_INVALID, "dd_hap_variants_device: no alignment launch of this thread to run behind (its workspace header holds the pair counter)");
+    dda::VariantsArgs A;
+    A.n_refs = b->n_refs; A.n_pairs = b->n_pairs;
+    A.ref_off = b->ref_off; A.ref_seq = reinterpret_cast<const uint8_t *>(b->ref_seq);
+    A.pair_ref = b->pair_ref; A.hap_off = b->hap_off; A.hap_seq = reinterpret_cast<const uint8_t *>(b->hap_seq);
+    A.status = r->status; A.ref_pos = r->ref_pos;
+    A.summary = summary; A.variants = variants; A.cap = cap;
+    A.hdr = reinterpret_cast<unsigned int *>(const_cast<unsigned char *>(g_align_last.ws));
+    const int64_t rec[DD_ALIGN_EVENTS_LOG_FIELDS] = {(int64_t)dda::variants_grid(b->n_pairs), (int64_t)b->n_pairs, -1, -1};
+    memcpy(g_variants_last.v, rec, sizeof(rec));
+    g_variants_last.ws = g_align_last.ws; g_variants_last.stream = static_cast<hipStream_t>(stream); g_variants_last.have_stats = false;
+    HIP_TRY(dda::launch_hap_variants(A, static_cast<hipStream_t>(stream)));
+    return DD_SUCCESS;
+}
+
+void dd_hap_variants_last_launch(int64_t out[DD_ALIGN_EVENTS_LOG_FIELDS])
+{
+    (void)read_variants_stats();               // a failure leaves -1 in the two device fields
+    if (out) memcpy(out, g_variants_last.v, sizeof(g_variants_last.v));
+}
+
 } // extern "C"
 
 namespace ddh {
 namespace {
 
-// the two host-pointer entries: ev = nullptr is dd_align_haplotypes; with events the slice comes back only where the caller has room for it
+// the three host-pointer entries: ev = va = nullptr is dd_align_haplotypes; with events or variants the slice comes back only where the
+// caller has room for it
 struct EventsOut { int32_t *n_events; dd_align_events *events; int cap; };
+struct VariantsOut { dd_hap_variants_summary *summary; dd_hap_variant *variants; int cap; };
 
-int align_host_entry(const dd_align_batch *b, dd_align_result *r, const EventsOut *ev, int device)
+int align_host_entry(const dd_align_batch *b, dd_align_result *r, const EventsOut *ev, int device, const VariantsOut *va = nullptr)
 {
     AlignShape s;
     int rc = check_align_batch(b, s);
     if (rc) return rc;
     if (!r) return fail(DD_ERR_INVALID, "null align result");
     if (b->n_pairs > 0 && (!r->score || !r->status)) return fail(DD_ERR_INVALID, "null score or status in align result");
-    if (!ev && s.hap_bytes > 0 && !r->ref_pos) return fail(DD_ERR_INVALID, "null ref_pos in align result");
+    if (!ev && !va && s.hap_bytes > 0 && !r->ref_pos) return fail(DD_ERR_INVALID, "null ref_pos in align result");
+    if (va) {
+        if (va->cap < 1 || va->cap > DD_HAP_VARIANTS_MAX_CAP) return fail(DD_ERR_INVALID, "cap outside 1 ... DD_HAP_VARIANTS_MAX_CAP");
+        if (b->n_pairs > 0 && (!va->summary || !va->variants)) return fail(DD_ERR_INVALID, "null summary or variants");
+    }
     if (ev) {
         if (ev->cap < 1 || ev->cap > DD_ALIGN_EVENTS_MAX_CAP) return fail(DD_ERR_INVALID, "events_cap outside 1 ... DD_ALIGN_EVENTS_MAX_CAP");
         if (b->n_pairs > 0 && (!ev->n_events || !ev->events)) return fail(DD_ERR_INVALID, "null n_events or events");
@@ -199,11 +255,13 @@ int align_host_entry(const dd_align_batch *b, dd_align_result *r, const EventsOu
     const size_t ws_bytes = dd_align_workspace_bytes(b);
     const size_t P = (size_t)b->n_pairs, R = (size_t)b->n_refs;
     const size_t ev_bytes = ev ? P * (size_t)ev->cap * sizeof(dd_align_events) : 0;
+    const size_t va_bytes = va ? P * (size_t)va->cap * sizeof(dd_hap_variant) : 0;
     size_t off = 0;
     auto take = [&off](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255u) & ~size_t(255u); return o; };
     const size_t o_roff = take((R + 1) * 4), o_rseq = take((size_t)s.ref_bytes), o_pref = take(P * 4), o_hoff = take((P + 1) * 4),
                  o_hseq = take((size_t)s.hap_bytes), o_score = take(P * 4), o_status = take(P * 4), o_rpos = take((size_t)s.hap_bytes * 2),
-                 o_ws = take(ws_bytes), o_nev = take(ev ? P * 4 : 0), o_ev = take(ev_bytes);
+                 o_ws = take(ws_bytes), o_nev = take(ev ? P * 4 : 0), o_ev = take(ev_bytes),
+                 o_sum = take(va ? P * sizeof(dd_hap_variants_summary) : 0), o_va = take(va_bytes);
     struct Mem {
         unsigned char *p = nullptr;
         ~Mem() { if (p) (void)hipFree(p); }
@@ -228,9 +286,19 @@ int align_host_entry(const dd_align_batch *b, dd_align_result *r, const EventsOu
         rc = dd_align_events_device(&db, &dr, reinterpret_cast<int32_t *>(d + o_nev), reinterpret_cast<dd_align_events *>(d + o_ev), ev->cap, nullptr);
         if (rc) { g_align_last.ws = nullptr; g_events_last.ws = nullptr; return rc; }
     }
+    if (va) {
+        // records no variant reaches stay 0: the caller's array is overwritten as a whole
+        HIP_TRY(hipMemsetAsync(d + o_va, 0, va_bytes, nullptr));
+        rc = dd_hap_variants_device(&db, &dr, reinterpret_cast<dd_hap_variants_summary *>(d + o_sum), reinterpret_cast<dd_hap_variant *>(d + o_va), va->cap, nullptr);
+        if (rc) { g_align_last.ws = nullptr; g_variants_last.ws = nullptr; return rc; }
+    }
     HIP_TRY(hipStreamSynchronize(nullptr));
     if ((rc = read_align_stats())) return rc;  // the workspace goes with this call
     g_align_last.ws = nullptr;
+    if (va) {
+        if ((rc = read_variants_stats())) return rc;
+        g_variants_last.ws = nullptr;
+    }
     if (ev) {
         if ((rc = read_events_stats())) return rc;
         g_events_last.ws = nullptr;
@@ -241,6 +309,10 @@ int align_host_entry(const dd_align_batch *b, dd_align_result *r, const EventsOu
     if (ev) {
         HIP_TRY(hipMemcpy(ev->n_events, d + o_nev, P * 4, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(ev->events, d + o_ev, ev_bytes, hipMemcpyDeviceToHost));
+    }
+    if (va) {
+        HIP_TRY(hipMemcpy(va->summary, d + o_sum, P * sizeof(dd_hap_variants_summary), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(va->variants, d + o_va, va_bytes, hipMemcpyDeviceToHost));
     }
     return DD_SUCCESS;
 }
@@ -256,6 +328,12 @@ int dd_align_haplotypes_events(const dd_align_batch *b, dd_align_result *r, int3
 {
     const EventsOut ev = {n_events, events, events_cap};
     return align_host_entry(b, r, &ev, device);
+}
+
+int dd_align_haplotypes_variants(const dd_align_batch *b, dd_align_result *r, dd_hap_variants_summary *summary, dd_hap_variant *variants, int cap, int device)
+{
+    const ddh::VariantsOut va = {summary, variants, cap};
+    return align_host_entry(b, r, nullptr, device, &va);
 }
 
 } // extern "C"

@@ -2,7 +2,8 @@
 
 The arithmetic is the library's HIP kernel (csrc/hapalign_kernel.hip); there is no Python or CPU implementation behind this module.
 `align_haplotypes` is the host-pointer entry, `align_events` the one that brings back indel events (csrc/align_events_kernel.hip)
-instead of the per-base slice, `DeviceAlign` keeps the batch in torch tensors and launches on a given stream, and
+instead of the per-base slice, `align_variants` the one that brings back every variant with its flanks (csrc/hap_variants_kernel.hip),
+`DeviceAlign` keeps the batch in torch tensors and launches on a given stream, and
 `gapped_rows` rebuilds the two gapped rows of an alignment from the per-base reference offsets the kernel returns.
 """
 import ctypes as C
@@ -96,6 +97,38 @@ def events_last_launch():
     """This thread's last event launch: dict(grid, pairs, max_draws, guard_trips) (dd_align_events_last_launch)."""
     out = (C.c_int64 * len(capi.ALIGN_EVENTS_LOG_FIELDS))()
     capi.load().dd_align_events_last_launch(C.byref(out))
+    return dict(zip(capi.ALIGN_EVENTS_LOG_FIELDS, list(out)))
+
+
+VARIANT_FIELDS = ("kind", "key", "len", "start_read", "left_flank_hap", "right_flank_hap", "left_flank_read", "right_flank_read")
+SUMMARY_FIELDS = ("n_variants", "first_base", "last_base", "flags")
+
+
+def align_variants(refs, haps, pair_ref, cap=16, device=0, with_ref_pos=False):
+    """Align like align_haplotypes and return every pair's variants instead of its slice: dict(score, status, summary int32 [n, 4] with
+    the fields of SUMMARY_FIELDS, variants int16 [n, cap, 8] with the fields of VARIANT_FIELDS, hap_off).  n_variants is the true count;
+    a pair with more than `cap` holds its first `cap` records.  with_ref_pos=True also copies the slice back (ref_pos)."""
+    lib = capi.load()
+    a = pack(refs, haps, pair_ref)
+    n, nb = len(haps), int(a["hap_off"][-1])
+    c = max(int(cap), 1)
+    out = {"score": np.zeros(max(n, 1), np.int32), "status": np.zeros(max(n, 1), np.int32), "summary": np.zeros((max(n, 1), 4), np.int32),
+           "variants": np.zeros((max(n, 1), c, 8), np.int16), "ref_pos": np.zeros(max(nb, 1), np.int16)}
+    b = host_batch(a)
+    r = capi.dd_align_result(out["score"].ctypes.data, out["status"].ctypes.data, out["ref_pos"].ctypes.data if with_ref_pos else None)
+    rc = lib.dd_align_haplotypes_variants(C.byref(b), C.byref(r), out["summary"].ctypes.data, out["variants"].ctypes.data, int(cap), device)
+    if rc != 0:
+        raise RuntimeError("dd_align_haplotypes_variants: %d %s" % (rc, capi.last_error()))
+    res = {"score": out["score"][:n], "status": out["status"][:n], "summary": out["summary"][:n], "variants": out["variants"][:n], "hap_off": a["hap_off"]}
+    if with_ref_pos:
+        res["ref_pos"] = out["ref_pos"][:nb]
+    return res
+
+
+def variants_last_launch():
+    """This thread's last variants launch: dict(grid, pairs, max_draws, guard_trips) (dd_hap_variants_last_launch)."""
+    out = (C.c_int64 * len(capi.ALIGN_EVENTS_LOG_FIELDS))()
+    capi.load().dd_hap_variants_last_launch(C.byref(out))
     return dict(zip(capi.ALIGN_EVENTS_LOG_FIELDS, list(out)))
 
 
@@ -200,3 +233,28 @@ class DeviceAlign:
         import torch
         torch.cuda.synchronize(self.device)
         return {"n_events": self.n_events.cpu().numpy()[:self.n_pairs], "events": self.events.cpu().numpy()[:self.n_pairs]}
+
+    def launch_variants(self, cap=16, stream=None, fill=0):
+        """Enqueue the variant extraction behind launch() on the same stream: fills self.summary (int32 [n_pairs, 4]) and self.variants
+        (int16 [n_pairs, cap, 8]).  The kernel writes only the records it counts; the rest of self.variants is preset to `fill`
+        (None: left as it is, the tensors of the previous call are reused).  Asynchronous."""
+        import torch
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        c = max(int(cap), 1)
+        with torch.cuda.stream(st):
+            if getattr(self, "variants", None) is None or self.variants.shape[1] != c:
+                self.summary = torch.zeros((max(self.n_pairs, 1), 4), dtype=torch.int32, device=self.device)
+                self.variants = torch.zeros((max(self.n_pairs, 1), c, 8), dtype=torch.int16, device=self.device)
+            if fill is not None:
+                self.summary.zero_()
+                self.variants.fill_(fill)
+        rc = capi.load().dd_hap_variants_device(C.byref(self.batch), C.byref(self.result), self.summary.data_ptr(), self.variants.data_ptr(),
+                                                int(cap), st.cuda_stream)
+        if rc != 0:
+            raise RuntimeError("dd_hap_variants_device: %d %s" % (rc, capi.last_error()))
+
+    def variant_results(self):
+        """Synchronise and copy back summary and variants of the last launch_variants()."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        return {"summary": self.summary.cpu().numpy()[:self.n_pairs], "variants": self.variants.cpu().numpy()[:self.n_pairs]}

@@ -8,6 +8,7 @@
 #define DINDEL_ALIGN_HAPLOTYPES_HPP
 #include <string>
 #include <vector>
+#include "../../include/dindel_hmm.h"
 #include "dindel_types.hpp"
 #include "window_io.hpp"
 
@@ -32,9 +33,37 @@ void addRefVariant(Haplotype &hap, int rp);
 // stays, its index in the window as it came in.
 void finishWindowHaplotypes(WindowHaplotypes &w, const std::string &refSeq, const std::vector<std::vector<int> > &refPos, std::vector<int> *kept = NULL);
 
+// ---- the variants of an alignment as fixed-size records (dd_hap_variant, include/dindel_hmm.h): csrc/hap_variants_kernel.hip makes them on
+//      the device, hapVariantsHost here, word for word the same: the kernel's twin, as blockTableHost is the block table's ----
+// Flat arrays as dd_hap_variants_device takes them, host pointers: status and refPos as the alignment left them; summary [n_pairs],
+// variants [n_pairs * cap].  Only the records a pair counts are written.
+void hapVariantsHost(const dd_align_batch &b, const int32_t *status, const int16_t *refPos, dd_hap_variants_summary *summary, dd_hap_variant *variants, int cap);
+// hap.indels, hap.snps and hap.align from a pair's n records (n <= cap), strings formed from the two sequences by position, assigned in
+// record order so that a later record of one key replaces an earlier one
+void haplotypeFromVariants(const std::string &refSeq, Haplotype &hap, const dd_hap_variant *v, int n);
+// hap.refHpos (= ml.hpos) from the slice, a linear walk: hlen = the reference sequence's length
+void refHposFromSlice(int hlen, const int16_t *refPos, int rlen, std::vector<int> &refHpos);
+// finishWindowHaplotypes from records: summary / variants of the window's haplotypes in order (variants[h * cap ...]).  slices[h]: the
+// haplotype's slice or NULL.  A pair flagged DD_HAP_VARIANTS_HOST or with more than cap records goes through convertHaplotypeAlignment and
+// needs its slice (std::string thrown without); for the others a slice fills refHpos, and without one refHpos stays empty.
+void finishWindowHaplotypesFromVariants(WindowHaplotypes &w, const std::string &refSeq, const dd_hap_variants_summary *summary, const dd_hap_variant *variants,
+                                        int cap, const std::vector<const int16_t *> &slices, std::vector<int> *kept = NULL);
+
+// how alignHaplotypesBatch turns the alignments into variants
+enum ConvertMode {
+    CONVERT_HOST,       // the slice comes back, convertHaplotypeAlignment per haplotype
+    CONVERT_DEVICE      // dd_hap_variants_kernel behind the alignment: records and summaries come back; the slice only with needRefHpos, or
+                        // (a second alignment call) when a pair needs the host conversion after all
+};
+const int kHapVariantsCap = 16;       // records per pair of a CONVERT_DEVICE launch
+
 // One device call for all windows' haplotypes (refSeqs[i] belongs to wins[i]), then finishWindowHaplotypes per window.
 // Throws std::string: the library's error text, or the first pair the device could not align (an empty or over-long sequence).
-void alignHaplotypesBatch(std::vector<WindowHaplotypes> &wins, const std::vector<std::string> &refSeqs, int device);
+// With `errors` a window's own failure (such a pair, or what its conversion throws) is not thrown: errors[i] holds the text, wins[i] is left
+// without haplotypes and the other windows are finished; an empty string means the window is done.
+// needRefHpos = false (CONVERT_DEVICE only): nobody reads Haplotype::refHpos, it stays empty and the slice stays on the device.
+void alignHaplotypesBatch(std::vector<WindowHaplotypes> &wins, const std::vector<std::string> &refSeqs, int device, std::vector<std::string> *errors = NULL,
+                          ConvertMode mode = CONVERT_HOST, bool needRefHpos = true);
 
 } // namespace dindel
 #endif

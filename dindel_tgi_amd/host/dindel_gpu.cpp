@@ -1,10 +1,14 @@
 // dindel_gpu — the --analysis indels --doDiploid window loop on the GPU likelihood path:
-//   (BAM + .bai, window file, haplotype fixture[, library file])  ->  PREFIX.glf.txt
+//   (BAM + .bai, window file, reference FASTA | haplotype file[, library file])  ->  PREFIX.glf.txt
 //
 // Restates DetInDel::detectIndels (reference DInDel.cpp:1265-1424) as prepare-N / compute / reduce-N:
-//   prepare  per window, in file order: getReads (get_reads.cpp) and the window's candidate haplotypes.  The reference BUILDS
-//            those (getHaplotypes, DInDel.cpp:1526-1645: HaplotypeDistribution, SeqAn alignment) — out of this repository's
-//            scope; they are read from a fixture file (window_io.hpp) instead;
+//   prepare  per window, in file order: getReads (get_reads.cpp) and the window's candidate haplotypes.  With --ref FASTA they are BUILT
+//            here as the reference builds them (getHaplotypes, DInDel.cpp:1526-1645), for all windows of a batch at once from the reads just
+//            selected: the block tables of the empirical distribution and the alignment to the reference on the device
+//            (getHaplotypesBatch, alignHaplotypesBatch: one launch each per batch), the variants of every alignment by the variants
+//            kernel behind it (--hostConvert: on the host), then the maxHapReadProd check of :395-399.  What getHaplotypes throws becomes
+//            the window's skipped line and a late skip (below); where it returns `true` (:1569, :1581) the window writes no line.
+//            With --hapFile they are read from a haplotype file instead (window_io.hpp), and --ref has no effect;
 //   compute  LikelihoodEngine::computeLikelihoodsBatch over the N prepared windows (one launch sequence on the GPU);
 //   reduce   per window: diploidGLF (diploid_glf.cpp) -> the window's lines, or the skipped-window line with the message the
 //            reference would print ("error_" + what was thrown); lines are written in file order.
@@ -17,7 +21,8 @@
 // mapping qualities follows it, so a worker does not start a batch with an empty buffer: it first replays read selection over the
 // batch's look-back (the preceding windows of the chromosome back to one whose reads have all left the buffer by the batch's first
 // window), which leaves the buffer in the state the window-by-window loop would have.  What a worker cannot see is a window skipped
-// AFTER read selection (an exception of the likelihood or genotyping step: "hapSize error.", "Nan detected", ...): the reference empties
+// AFTER read selection (an exception of the haplotype construction under --ref, of the likelihood or of the genotyping step: "hapblock",
+// "Not enough blocks.", "hapSize error.", "Nan detected", ...): the reference empties
 // the buffer after it (DInDel.cpp:1404-1405).  The writer sees it: from the window behind such a LATE skip it re-prepares, from an empty
 // buffer and window by window, every window whose buffer could still hold a record of that moment (same chromosome, leftPos less than
 // 2 maxInsert + 200 behind the first re-prepared window's rightPos) with a read fetcher, an engine and the reduce step of its own, and
@@ -29,7 +34,9 @@
 // region" fires on buffer size + records fetched > 100 * maxRead, which at a batch's first window is counted as after a reset.)
 //
 // Options (names follow the reference's CLI, DInDel.cpp:4079-4170):
-//   --bamFile F | --bamFiles LIST   --varFile F [--varFileIsOneBased] --hapFile F --outputFile PREFIX [--libFile F] [--faster] [--filterHaplotypes]
+//   --bamFile F | --bamFiles LIST   --varFile F [--varFileIsOneBased] --ref FASTA | --hapFile F   --outputFile PREFIX [--libFile F] [--faster] [--filterHaplotypes]
+//   --ref mode only (the reference's names and defaults, DInDel.cpp:4127, :4132, :4139): [--maxHap N] [--skipMaxHap N] [--changeINStoN]
+//                     [--hostDistribution] block tables on the host   [--hostConvert] alignments to variants on the host
 //   [--maxRead N] [--maxReadLength N] [--minReadOverlap N] [--mapQualThreshold X] [--pError X] [--pMut X] [--maxLengthIndel N]
 //   [--filterReadAux STR] [--flankRefSeq N] [--flankMaxMismatch N] [--priorSNP X] [--priorIndel X] [--capMapQualThreshold X] [--capMapQualFast X]
 //   [--maxHapReadProd N] [--batchWindows N] [--prepareThreads N] [--computeThreads N] [--packThreads N] [--reduceThreads N] [--device D | --devices D0,D1,...] [--quiet]
@@ -42,7 +49,8 @@
 //                     same byte for byte.  The engines then merge as many batches per launch as without realigned BAMs.  No effect
 //                     without --outputRealignedBAM (main model, like that option)
 //   [--timing]        one "timing:" line on stdout with the busy time of each stage
-//   [--prepareOnly]   stop after the prepare stage (no likelihoods, no calls: profiling the read selection on a GPU-less host)
+//   [--prepareOnly]   stop after the prepare stage (no likelihoods, no calls: profiling the read selection on a GPU-less host); with --ref
+//                     in front of the haplotype stage, which needs the device
 //   [--windowByWindow] tests: the writer re-does every window one after the other with a read buffer of its own (the reference's loop as it stands)
 //   [--longWindows]   windows beyond the main kernels' limits (a haplotype > 766 bp, a read > 1024 bp, or with --maxLengthIndel >= 12 a
 //                     haplotype > 574 bp) are computed by the long-window kernel (haplotypes up to 4,094 bp, reads up to 4,096 bp) instead
@@ -67,8 +75,11 @@
 #include "batch_channels.hpp"
 #include "compute_likelihoods.hpp"
 #include "diploid_glf.hpp"
+#include "align_haplotypes.hpp"
 #include "get_reads.hpp"
 #include "glf_output.hpp"
+#include "glf_to_vcf.hpp"
+#include "haplotypes.hpp"
 #include "realigned_bam.hpp"
 #include "window_io.hpp"
 
@@ -80,10 +91,14 @@ struct WindowTask {
     AlignedCandidates candidates;
     std::vector<Read> reads;
     const std::vector<Haplotype> *haps;
+    std::vector<Haplotype> built;        // --ref: the haplotypes made for this window in the run (haps points here); reused with the batch
     std::string message;                 // "ok" or the skipped message
+    std::string note;                    // --ref: what getHaplotypes prints on cerr for this window; the writer prints it in window order
     bool skipped;
+    bool passedOver;                     // --ref: getHaplotypes returned true (DInDel.cpp:1569 / :1581): no likelihoods, no line, not a skipped window
     bool lateSkip;                       // skipped by the likelihood or genotyping step, i.e. after read selection (DInDel.cpp:1369-1408)
     std::string lines;                   // what the reduce stage wrote for this window
+    bool computes() const { return !skipped && !passedOver; }    // the window reaches the likelihood step
     WindowJob job() const                // the window as the likelihood step takes it
     {
         WindowJob J;
@@ -113,6 +128,9 @@ double seconds_since(const TimePoint &t0) { return std::chrono::duration<double>
 struct Options {
     ObservationModelParameters obs; ReadSelectionParameters rsp; DiploidParameters dip;
     std::string varFile, hapFile, outputPrefix, libFile;
+    std::string refFile;                 // --ref without --hapFile: the haplotypes are built in the run (empty: they come from hapFile)
+    HaplotypeOptions hap;                // --ref mode: --maxHap, --skipMaxHap, --changeINStoN, --hostDistribution (maxHapReadProd is the run's)
+    bool hostConvert;                    // --ref mode: convertHaplotypeAlignment on the host instead of the variants kernel
     std::string bamList;                 // --bamFiles LIST (read during set-up, behind the library file)
     std::vector<std::string> bamPaths;   // --bamFile, or LIST's files once set-up has read it
     double maxHapReadProd;
@@ -127,7 +145,14 @@ struct Options {
 
 const char *const kHelp =
     "dindel_gpu: the --analysis indels --doDiploid window loop with the likelihood step on the GPU\n"
-    "  required: --bamFile F --varFile F --hapFile F --outputFile PREFIX          (writes PREFIX.glf.txt)\n"
+    "  required: --bamFile F --varFile F --outputFile PREFIX and --ref FASTA or --hapFile F          (writes PREFIX.glf.txt)\n"
+    "  haplotypes: --ref FASTA (with FASTA.fai)  every window's candidate haplotypes are built in the run from the reads it selected: the block\n"
+    "                             tables and the alignment to the reference on the device, one launch each per batch of windows\n"
+    "            [--maxHap N]     combinations the blocks are thinned to (default 8)      [--skipMaxHap N]  a window with more haplotypes is passed\n"
+    "            [--changeINStoN] candidate insertions enter the haplotypes as N          over (default 200)\n"
+    "            [--hostDistribution]  the block tables on the host instead of the device\n"
+    "            [--hostConvert]  the variants of every alignment are made on the host from its slice instead of by the variants kernel\n"
+    "            --hapFile F      the haplotypes come from a file instead (W / H / V / A records); with both, --hapFile wins and these have no effect\n"
     "  model:    [--faster] [--libFile F] [--filterHaplotypes] [--outputRealignedBAM] [--varFileIsOneBased]\n"
     "            [--deviceCigars]  with --outputRealignedBAM: compute the realigned reads' CIGARs on the device and bring them back instead of the\n"
     "                             per-base alignments (same files); [--cigarOpsCap N] operations kept per read (default 8), reads with more\n"
@@ -144,7 +169,7 @@ const char *const kHelp =
     "  files:    --varFile: the reference's window file; --hapFile: W / H / V / A records (host/window_io.hpp)\n";
 // the options without a value; any other --NAME takes the next argument as its value, whatever its name
 const char *const kFlags[] = {"varFileIsOneBased", "faster", "filterHaplotypes", "quiet", "doDiploid", "timing", "outputRealignedBAM", "prepareOnly", "noLookBack",
-                              "lateSkipsKnown", "windowByWindow", "longWindows", "longWindowsFaster", "deviceCigars"};
+                              "lateSkipsKnown", "windowByWindow", "longWindows", "longWindowsFaster", "deviceCigars", "changeINStoN", "hostDistribution", "hostConvert"};
 
 std::vector<int> commaInts(const std::string &list)      // "3,5,,8" -> 3 5 8
 {
@@ -177,10 +202,13 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     auto has = [&](const char *k) { return opt.find(k) != opt.end(); };
     auto num = [&](const char *k, double dflt) { return has(k) ? atof(opt[k].c_str()) : dflt; };
     exitCode = 1;
-    for (const char *need : {"varFile", "hapFile", "outputFile"})
+    for (const char *need : {"varFile", "outputFile"})
         if (!has(need)) { std::cerr << "Please specify --" << need << "\n"; return false; }
+    if (!has("hapFile") && !has("ref")) { std::cerr << "Please specify --ref (haplotypes built in the run) or --hapFile (haplotypes from a file)\n"; return false; }
     if (!has("bamFile") && !has("bamFiles")) { std::cerr << "Error: Specify either --bamFile or --bamFiles." << std::endl; return false; }   // DInDel.cpp:4215-4218
-    o.varFile = opt["varFile"]; o.hapFile = opt["hapFile"]; o.outputPrefix = opt["outputFile"];
+    o.varFile = opt["varFile"]; o.outputPrefix = opt["outputFile"];
+    if (has("hapFile")) o.hapFile = opt["hapFile"];                  // --hapFile wins when both are given
+    else o.refFile = opt["ref"];
     if (has("bamFile")) o.bamPaths.push_back(opt["bamFile"]);        // --bamFile wins when both are given (DInDel.cpp:4220-4226)
     else o.bamList = opt["bamFiles"];
     o.faster = has("faster"); o.oneBased = has("varFileIsOneBased"); o.prepareOnly = has("prepareOnly"); o.quiet = has("quiet"); o.timing = has("timing");
@@ -199,7 +227,7 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     ReadSelectionParameters &rsp = o.rsp;
     rsp.maxReads = size_t(num("maxRead", double(rsp.maxReads))); rsp.maxReadLength = size_t(num("maxReadLength", double(rsp.maxReadLength)));
     rsp.minReadOverlap = int(num("minReadOverlap", rsp.minReadOverlap)); rsp.mapQualThreshold = num("mapQualThreshold", rsp.mapQualThreshold);
-    rsp.quiet = o.quiet; rsp.keepRecords = o.realignedBAM;
+    rsp.quiet = o.quiet; rsp.keepRecords = o.realignedBAM || !o.refFile.empty();   // (the haplotype stage reads CIGAR, flag and raw letters from the record)
     if (has("filterReadAux")) rsp.filterReadAux = opt["filterReadAux"];
     if (has("libFile")) {                    // the reference: --libFile switches mapUnmappedReads on (DInDel.cpp:4268-4272)
         o.libFile = opt["libFile"];
@@ -208,6 +236,14 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     o.dip.priorSNP = num("priorSNP", o.dip.priorSNP); o.dip.priorIndel = num("priorIndel", o.dip.priorIndel);
     o.dip.filterHaplotypes = has("filterHaplotypes"); o.dip.quiet = o.quiet;
     o.maxHapReadProd = num("maxHapReadProd", 10000000.0);
+    if (!o.refFile.empty()) {                // DInDel.cpp:4127, :4132, :4139
+        if (num("maxHap", 8) < 1 || num("skipMaxHap", 200) < 1) { std::cerr << "--maxHap and --skipMaxHap must be at least 1\n"; exitCode = 2; return false; }
+        o.hap.maxHap = size_t(num("maxHap", 8)); o.hap.skipMaxHap = size_t(num("skipMaxHap", 200)); o.hap.maxHapReadProd = o.maxHapReadProd;
+        o.hap.changeINStoN = has("changeINStoN"); o.hap.hostDistribution = has("hostDistribution");
+    }
+    o.hostConvert = has("hostConvert");
+    {
+    }
     o.batchWindows = std::max(1, int(num("batchWindows", 256)));
     o.devices = commaInts(has("devices") ? opt["devices"] : (has("device") ? opt["device"] : std::string("0")));
     if (o.devices.empty()) o.devices.push_back(0);
@@ -244,6 +280,7 @@ public:
     int run();                                            // the exit code
 private:
     void prepareWindow(ReadFetcher &fetcher, WindowTask &T);
+    void buildHaplotypes(const std::vector<WindowTask *> &tasks, IndexedFasta &fasta, int device);
     void prepareWorker(int pt);
     void computeWorker(int ct);
     void reduceWindow(WindowTask &T, const WindowJob *J);
@@ -267,7 +304,8 @@ private:
     Options opt;
     LibraryCollection libraries;
     BamFileSet headerBam;                      // [0]: the first pool, opened before anything else happens ("Cannot open BAM file." / "Cannot open BAM index."); the header for --outputRealignedBAM
-    std::unique_ptr<HaplotypeFixture> fixture; // (thread-safe: parsed on demand by the prepare workers, released through Batch::toRelease)
+    std::unique_ptr<HaplotypeFixture> fixture; // (thread-safe: parsed on demand by the prepare workers, released through Batch::toRelease); none in --ref mode
+    bool refMode;                              // --ref without --hapFile: buildHaplotypes makes each window's haplotypes
     const char *dumpReads;                     // DINDEL_DUMP_READS, diagnostics: what each window hands to the likelihood step
     bool pooled;                               // several BAM pools and no --noLookBack (diagnostics: every batch starts with an empty buffer)
     uint32_t bufferSpan;                       // a record fetched for a window has left the buffer this far on
@@ -318,7 +356,7 @@ private:
         Redo() : active(false), first(false), reach(0) {}
         bool active, first;
         std::string tid; uint64_t reach;
-        BamFileSet bams; std::unique_ptr<ReadFetcher> fetcher; std::unique_ptr<LikelihoodEngine> engine;
+        BamFileSet bams; std::unique_ptr<ReadFetcher> fetcher; std::unique_ptr<LikelihoodEngine> engine; std::unique_ptr<IndexedFasta> fasta;
     } redo;
 };
 
@@ -342,7 +380,9 @@ WindowLoop::WindowLoop(const Options &options)
     }
     headerBam.open(opt.bamPaths[0]);
     for (size_t i = 1; i < opt.bamPaths.size(); i++) { BamFileSet probe; probe.open(opt.bamPaths[i]); }     // every pool opens, or the run ends here
-    fixture.reset(new HaplotypeFixture(opt.hapFile));
+    refMode = !opt.refFile.empty();
+    if (refMode) { IndexedFasta probe(opt.refFile); }        // the FASTA and its index open, or the run ends here; every worker opens its own
+    else fixture.reset(new HaplotypeFixture(opt.hapFile));
     pooled = opt.bamPaths.size() > 1 && !opt.noLookBack;
     bufferSpan = 2u * uint32_t(libraries.getMaxInsertSize()) + 200u;
     glfOutput.open(glfFile.c_str());
@@ -402,13 +442,15 @@ void WindowLoop::prepareWindow(ReadFetcher &fetcher, WindowTask &T)
 {
     try {
         fetcher.getReads(T.tid, T.fileLeftPos, T.fileRightPos, T.reads);
-        const WindowHaplotypes *wh = fixture->find(T.index);
-        if (!wh) throw std::string("no haplotypes for this window in the haplotype file");
-        T.haps = &wh->haps; T.leftPos = wh->leftPos; T.rightPos = wh->rightPos;
-        if (double(T.reads.size() * T.haps->size()) > opt.maxHapReadProd) {     // :395-399
-            std::stringstream os;
-            os << "skipped_numhap_times_numread>" << long(opt.maxHapReadProd);
-            throw os.str();
+        if (!refMode) {                                                         // --ref: buildHaplotypes follows, for the whole batch
+            const WindowHaplotypes *wh = fixture->find(T.index);
+            if (!wh) throw std::string("no haplotypes for this window in the haplotype file");
+            T.haps = &wh->haps; T.leftPos = wh->leftPos; T.rightPos = wh->rightPos;
+            if (double(T.reads.size() * T.haps->size()) > opt.maxHapReadProd) {     // :395-399
+                std::stringstream os;
+                os << "skipped_numhap_times_numread>" << long(opt.maxHapReadProd);
+                throw os.str();
+            }
         }
     } catch (std::string &s) {
         T.message = skippedMessage(s);
@@ -426,6 +468,84 @@ void WindowLoop::prepareWindow(ReadFetcher &fetcher, WindowTask &T)
     }
 }
 
+// ---- --ref: getHaplotypes (DInDel.cpp:1526-1645) for the windows of a batch whose reads are selected, and what empiricalDistributionMethod
+//      does with its result in front of the likelihood step (:393-405).  One block-table launch and one alignment launch for all of them
+//      (getHaplotypesBatch, alignHaplotypesBatch); the variants of each alignment come from the variants kernel behind the alignment
+//      launch, or with --hostConvert from convertHaplotypeAlignment on the host.
+//      What the reference THROWS here becomes the window's skipped line, and a late skip: read selection is over, the reference empties
+//      its read buffer behind the window (:1401-1408).  Where getHaplotypes RETURNS true the window is passed over: a cerr line, no row.
+//      A library error (no device, out of memory) is thrown on and ends the run. ----
+void WindowLoop::buildHaplotypes(const std::vector<WindowTask *> &tasks, IndexedFasta &fasta, int device)
+{
+    auto thrown = [](WindowTask &T, const std::string &what) { T.message = skippedMessage(what); T.skipped = true; T.lateSkip = true; T.haps = NULL; };
+    auto upper = [](std::string s) { for (size_t i = 0; i < s.size(); i++) s[i] = char(toupper((unsigned char)s[i])); return s; };
+    HapBatchData data;
+    std::vector<WindowCandidates> wins;
+    std::vector<WindowTask *> of;                           // wins[k] belongs to *of[k]
+    for (size_t i = 0; i < tasks.size(); i++) {
+        WindowTask &T = *tasks[i];
+        if (T.skipped) continue;
+        // :1530-1532, and getRefSeq (:269-287), which throws when nothing of the piece lies on the sequence
+        const uint32_t rs = int(T.fileLeftPos) > opt.rsp.minReadOverlap ? T.fileLeftPos - uint32_t(opt.rsp.minReadOverlap) : 0u;
+        const uint32_t re = T.fileRightPos + uint32_t(opt.rsp.minReadOverlap);
+        std::string piece;
+        try { piece = refPiece(fasta, T.tid, long(rs) + 1, long(re) + 1); } catch (std::string &e) { thrown(T, e); continue; }
+        if (piece.empty()) { thrown(T, "faidx error: len==0"); continue; }
+        data.addWindow(int32_t(rs), piece);
+        addWindowReads(data, T.reads);
+        WindowCandidates w;
+        w.leftPos = T.fileLeftPos; w.rightPos = T.fileRightPos; w.variants = T.candidates.variants; w.nReads = T.reads.size();
+        wins.push_back(w);
+        of.push_back(&T);
+    }
+    if (wins.empty()) return;
+    HaplotypeOptions hopt = opt.hap;
+    hopt.device = device;
+    getHaplotypesBatch(data, wins, hopt);
+    std::vector<WindowHaplotypes> toAlign;
+    std::vector<std::string> refSeqs;
+    std::vector<WindowTask *> aligned;
+    auto tooMany = [&](WindowTask &T, size_t nHaps) {       // :395-399
+        if (!(double(T.reads.size() * nHaps) > opt.maxHapReadProd)) return false;
+        std::stringstream os;
+        os << "skipped_numhap_times_numread>" << long(opt.maxHapReadProd);
+        thrown(T, os.str());
+        return true;
+    };
+    for (size_t k = 0; k < wins.size(); k++) {
+        WindowTask &T = *of[k];
+        const WindowCandidates &w = wins[k];
+        std::ostringstream note;
+        if (w.returnedSkip) {                               // :1569 (no haplotypes yet) / :1581 (all of them, unaligned): :395 still runs
+            note << "tid: " << T.tid << " pos: " << T.pos << " " << w.message << "\n";
+            if (!tooMany(T, w.hapsAtSkip)) { T.passedOver = true; note << "tid: " << T.tid << " pos:  " << T.pos << " SKIPPING!\n"; }
+        } else if (w.message == "Blocks are not consecutive.") {     // :1636-1639
+            note << "tid: " << T.tid << "pos: " << T.pos << w.message << "\n";
+            thrown(T, "hapblock");
+        } else if (!w.message.empty()) thrown(T, w.message);
+        else {
+            WindowHaplotypes in;
+            in.index = T.index; in.leftPos = w.leftPos; in.rightPos = w.rightPos;
+            for (size_t h = 0; h < w.haps.size(); h++) in.haps.push_back(Haplotype(w.haps[h]));
+            std::string ref;                                // :1461: getRefSeq(leftPos + 1, rightPos + 1) of the selected blocks
+            try { ref = upper(refPiece(fasta, T.tid, long(w.leftPos) + 1, long(w.rightPos) + 1)); } catch (std::string &e) { thrown(T, e); }
+            if (!T.skipped && ref.empty()) thrown(T, "faidx error: len==0");
+            if (!T.skipped) { toAlign.push_back(in); refSeqs.push_back(ref); aligned.push_back(&T); }
+        }
+        T.note = note.str();
+    }
+    std::vector<std::string> errors;
+    // Haplotype::refHpos is read by the realigned BAMs' CIGARs only (realignedCigars, the device CIGARs' hap_ref_pos)
+    alignHaplotypesBatch(toAlign, refSeqs, device, &errors, opt.hostConvert ? CONVERT_HOST : CONVERT_DEVICE, opt.realignedBAM);
+    for (size_t k = 0; k < toAlign.size(); k++) {
+        WindowTask &T = *aligned[k];
+        if (!errors[k].empty()) { thrown(T, errors[k]); continue; }
+        if (tooMany(T, toAlign[k].haps.size())) continue;   // on what the overhang filter and the duplicate-reference removal left
+        T.built.swap(toAlign[k].haps);
+        T.haps = &T.built; T.leftPos = toAlign[k].leftPos; T.rightPos = toAlign[k].rightPos;
+    }
+}
+
 // ---- prepare: whole batches side by side (own BAM handles and read buffer per worker), handed on in file order ----
 void WindowLoop::prepareWorker(int pt)
 {
@@ -433,10 +553,13 @@ void WindowLoop::prepareWorker(int pt)
         BamFileSet bams(opt.bamPaths);
         ReadFetcher fetcher(bams.pointers(), libraries, opt.rsp);
         std::vector<Read> replayed;
+        std::unique_ptr<IndexedFasta> fasta;
+        if (refMode && !opt.prepareOnly) fasta.reset(new IndexedFasta(opt.refFile));    // --prepareOnly stops in front of the haplotype stage
+        std::vector<WindowTask *> all;
         BatchPtr b;
         while (toPrepare.pop(b)) {
             const TimePoint t0 = now();
-            for (size_t i = 0; i < b->toRelease.size(); i++) fixture->release(b->toRelease[i]);      // noted by the writer at the batch's previous use
+            if (fixture) for (size_t i = 0; i < b->toRelease.size(); i++) fixture->release(b->toRelease[i]);      // noted by the writer at the batch's previous use
             b->toRelease.clear();
             std::string oldTid;
             bool primed = false;
@@ -456,6 +579,11 @@ void WindowLoop::prepareWorker(int pt)
                 if ((i == 0 && !primed) || T.tid != oldTid) { fetcher.newChromosome(); oldTid = T.tid; }     // DInDel.cpp:1327-1333
                 prepareWindow(fetcher, T);
                 fetcher.windowDone(resetsBehind(T.skipped, T.index), T.fileLeftPos);                         // :1401-1408
+            }
+            if (fasta) {
+                all.clear();
+                for (size_t i = 0; i < b->tasks.size(); i++) all.push_back(&b->tasks[i]);
+                buildHaplotypes(all, *fasta, opt.devices[size_t(pt) % opt.devices.size()]);
             }
             n.prepareOf[size_t(pt)] += seconds_since(t0);
             const long seq = b->seq;
@@ -487,7 +615,7 @@ void WindowLoop::computeWorker(int ct)
             for (size_t g = 0; g < group.size(); g++) {
                 Batch &B = *group[g];
                 B.jobOf.assign(B.tasks.size(), size_t(-1));
-                for (size_t i = 0; i < B.tasks.size(); i++) if (!B.tasks[i].skipped) { B.jobOf[i] = B.jobs.size(); B.jobs.push_back(B.tasks[i].job()); }
+                for (size_t i = 0; i < B.tasks.size(); i++) if (B.tasks[i].computes()) { B.jobOf[i] = B.jobs.size(); B.jobs.push_back(B.tasks[i].job()); }
                 nJobs += B.jobs.size();
             }
             if (nJobs > 0 && !opt.prepareOnly) {
@@ -529,7 +657,7 @@ void WindowLoop::reduceWindow(WindowTask &T, const WindowJob *J)
     std::ostringstream os;
     OutputData local = glfData;
     local.out = &os;
-    if (!T.skipped) {
+    if (T.computes()) {
         try {
             if (opt.injectedLateSkips.count(T.index)) throw std::string("hapSize error.");       // tests (--injectLateSkip)
             if (J) {
@@ -571,7 +699,7 @@ void WindowLoop::reduceBatch(Batch &B)
             for (;;) {
                 const size_t i = next.fetch_add(1);
                 if (i >= B.tasks.size()) break;
-                reduceWindow(B.tasks[i], (!B.tasks[i].skipped && !opt.prepareOnly) ? &B.jobs[B.jobOf[i]] : NULL);
+                reduceWindow(B.tasks[i], (B.tasks[i].computes() && !opt.prepareOnly) ? &B.jobs[B.jobOf[i]] : NULL);
             }
         } catch (std::exception &e) { next.store(B.tasks.size()); fail(std::string("reduce: ") + e.what()); }
         catch (...) { next.store(B.tasks.size()); fail("reduce: unknown exception"); }
@@ -595,10 +723,14 @@ void WindowLoop::rePrepare(WindowTask &T)
         redo.fetcher.reset(new ReadFetcher(redo.bams.pointers(), libraries, opt.rsp));
     }
     if (redo.first) { redo.fetcher->newChromosome(); redo.reach = uint64_t(T.fileRightPos) + bufferSpan; redo.first = false; }   // the reset of DInDel.cpp:1404-1405
-    T.skipped = false; T.lateSkip = false; T.message = "ok";
+    T.skipped = false; T.lateSkip = false; T.passedOver = false; T.message = "ok"; T.note.clear(); T.haps = NULL;
     prepareWindow(*redo.fetcher, T);
+    if (refMode && !opt.prepareOnly) {
+        if (!redo.fasta) redo.fasta.reset(new IndexedFasta(opt.refFile));
+        buildHaplotypes(std::vector<WindowTask *>(1, &T), *redo.fasta, opt.devices[0]);
+    }
     std::vector<WindowJob> one;
-    if (!T.skipped && !opt.prepareOnly) {
+    if (T.computes() && !opt.prepareOnly) {
         if (!redo.engine) {
             redo.engine.reset(new LikelihoodEngine(opt.obs, opt.devices[0]));
             configureStageEngine(*redo.engine);
@@ -628,6 +760,7 @@ void WindowLoop::writeBatch(Batch &B)
             else rePrepare(T);
         }
         if (T.lateSkip && pooled && !opt.lateSkipsKnown && !opt.windowByWindow) { redo.active = true; redo.first = true; redo.tid = T.tid; }
+        if (!T.note.empty()) std::cerr << T.note << std::flush;                                            // DInDel.cpp:1570, :1582, :1637, :404
         if (T.skipped) {
             std::cerr << "skipped " << T.tid << " " << T.pos << " reason: " << T.message << std::endl;     // DInDel.cpp:1383
             n.skipped++;
@@ -649,14 +782,14 @@ void WindowLoop::writer()
             writeBatch(*b);
             // the haplotypes of these windows can go: noted here, dropped by the prepare worker that takes the batch next
             // (side by side with the others, not in this thread's serial part)
-            for (size_t i = 0; i < b->tasks.size(); i++) if (b->tasks[i].haps) { b->toRelease.push_back(b->tasks[i].index); b->tasks[i].haps = NULL; }
+            for (size_t i = 0; i < b->tasks.size(); i++) if (b->tasks[i].haps) { if (fixture) b->toRelease.push_back(b->tasks[i].index); b->tasks[i].haps = NULL; }
             b->jobs.clear();                                              // drops the batch's views: its result block can be reused
             b->jobOf.clear();
             recycled.give(b);
             n.reduce += seconds_since(t0);
         }
     });
-    redo.engine.reset(); redo.fetcher.reset();            // made by this thread, dropped by it
+    redo.engine.reset(); redo.fetcher.reset(); redo.fasta.reset();            // made by this thread, dropped by it
 }
 
 // ---- the window file, in file order (main thread) ----
@@ -711,7 +844,7 @@ int WindowLoop::readWindowFile()                          // 1: the file is not 
         T.lines.clear();
         T.candidates = cand; T.tid = cand.tid; T.pos = uint32_t(cand.centerPos);
         T.fileLeftPos = T.leftPos = uint32_t(cand.leftPos); T.fileRightPos = T.rightPos = uint32_t(cand.rightPos);
-        T.haps = NULL; T.skipped = false; T.lateSkip = false; T.message = "ok";
+        T.haps = NULL; T.skipped = false; T.lateSkip = false; T.passedOver = false; T.message = "ok"; T.note.clear();
         T.index = ++index;
         if (pooled) {
             Batch::Before W = { T.tid, T.fileLeftPos, T.fileRightPos, T.index };

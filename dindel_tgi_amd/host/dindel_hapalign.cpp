@@ -2,7 +2,7 @@
 // tool: reads candidate haplotypes with their block's reference sequence (W / R / H records, host/window_io.hpp), aligns every haplotype
 // against its reference on the GPU (one launch per batch of windows) and writes the W / H / A / V file dindel_gpu --hapFile reads.
 //
-//   dindel_hapalign --hapFile IN --outputFile OUT [--device D] [--batchWindows N] [--quiet]
+//   dindel_hapalign --hapFile IN --outputFile OUT [--device D] [--batchWindows N] [--hostConvert] [--quiet]
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,12 +15,14 @@
 using namespace dindel;
 
 static const char *kUsage =
-    "usage: dindel_hapalign --hapFile IN --outputFile OUT [--device D] [--batchWindows N] [--quiet]\n"
+    "usage: dindel_hapalign --hapFile IN --outputFile OUT [--device D] [--batchWindows N] [--hostConvert] [--quiet]\n"
     "  --hapFile IN       W <index> <leftPos> <rightPos> / R <reference sequence of the block> / H <sequence> records;\n"
     "                     A and V records of the input are ignored\n"
     "  --outputFile OUT   W / H / A / V records (no R): the haplotype file of dindel_gpu --hapFile\n"
     "  --device D         GPU ordinal (default 0)\n"
     "  --batchWindows N   windows per device launch (default 1024)\n"
+    "  --hostConvert      the variants of every alignment are made on the host from its slice (convertAlignment as a string walk)\n"
+    "                     instead of by the variants kernel on the device; the output is the same bytes either way\n"
     "  --quiet            no progress on stderr\n"
     "  --help             this text\n";
 
@@ -47,12 +49,13 @@ int main(int argc, char **argv)
 {
     std::string hapFile, outFile;
     int device = 0, batchWindows = 1024;
-    bool quiet = false;
+    bool quiet = false, hostConvert = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         const bool has = i + 1 < argc;
         if (a == "--help" || a == "-h") { std::cout << kUsage; return 0; }
         else if (a == "--quiet") quiet = true;
+        else if (a == "--hostConvert") hostConvert = true;
         else if (a == "--hapFile" && has) hapFile = argv[++i];
         else if (a == "--outputFile" && has) outFile = argv[++i];
         else if (a == "--device" && has) device = atoi(argv[++i]);
@@ -90,7 +93,7 @@ int main(int argc, char **argv)
                 refs.push_back(w->refSeq);
                 fx.release(indices[k]);
             }
-            alignHaplotypesBatch(wins, refs, device);
+            alignHaplotypesBatch(wins, refs, device, NULL, hostConvert ? CONVERT_HOST : CONVERT_DEVICE, true);    // (the A records need refHpos)
             for (size_t k = 0; k < wins.size(); k++) { nKept += wins[k].haps.size(); writeWindow(out, wins[k]); }
             if (!quiet) std::cerr << "dindel_hapalign: " << w1 << " of " << indices.size() << " windows\n";
         }

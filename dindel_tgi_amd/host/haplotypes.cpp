@@ -524,20 +524,20 @@ std::vector<std::string> generateHaplotypes(const std::vector<HapBlockTable> &hb
 
 void haplotypesFromTable(const WindowTable &t, uint32_t rs, const HaplotypeOptions &opt, WindowCandidates &win)
 {
-    win.haps.clear(); win.message.clear();
+    win.haps.clear(); win.message.clear(); win.returnedSkip = false; win.hapsAtSkip = 0;
     try {
         std::vector<HapBlockTable> hbs = selectBlocks(t, rs, win.leftPos, win.rightPos);
         const uint32_t start = hbs.front().start, end = hbs.back().end;
         const double logNum = setThresholds(hbs, opt.maxHap);
         if (logNum > log(double(opt.skipMaxHap))) {                                       // DInDel.cpp:1569
             std::ostringstream os; os << "too many haplotypes [>exp(" << logNum << ")]";
-            win.message = os.str();
+            win.message = os.str(); win.returnedSkip = true;
             return;
         }
         std::vector<std::string> haps = generateHaplotypes(hbs, win.variants, opt.changeINStoN);
         if (haps.size() > opt.skipMaxHap || double(haps.size() * win.nReads) > opt.maxHapReadProd) {   // DInDel.cpp:1581
             std::ostringstream os; os << "too many haplotypes [>" << haps.size() << "] numreads: " << win.nReads;
-            win.message = os.str();
+            win.message = os.str(); win.returnedSkip = true; win.hapsAtSkip = haps.size();
             return;
         }
         win.haps.swap(haps);
@@ -561,7 +561,7 @@ void getHaplotypesBatch(const HapBatchData &data, std::vector<WindowCandidates> 
             if (stats) stats[ok ? 0 : 1]++;
             const WindowTable table = ok ? tableFromFlat(b, t, w) : sequentialTable(b, w);
             haplotypesFromTable(table, uint32_t(data.winRs[size_t(w)]), opt, win);
-        } catch (std::string &e) { win.haps.clear(); win.message = e; }
+        } catch (std::string &e) { win.haps.clear(); win.message = e; win.returnedSkip = false; win.hapsAtSkip = 0; }
     }
 }
 

@@ -15,6 +15,8 @@
 
 namespace dindel {
 
+class IndexedFasta;
+
 // one string of a block with what setFrequencies leaves on it
 struct BlockEntry { std::string seq; int count; bool isRef; double freq; };
 // a block: [start, end] on the reference; an insertion block sits in front of `start` and has end = start - 1 once selected
@@ -71,13 +73,22 @@ struct WindowCandidates {
     size_t nReads;
     std::vector<std::string> haps;             // out
     std::string message;                       // out: empty, or why the window has no haplotypes (the reference's text)
-    WindowCandidates() : leftPos(0), rightPos(0), nReads(0) {}
+    // out, with a message: getHaplotypes RETURNED true (DInDel.cpp:1569 / :1581: a cerr line, nothing thrown) with this many haplotypes
+    // made (0 at :1569); false: `message` is a thrown string, which the window loop turns into the window's skipped line
+    bool returnedSkip; size_t hapsAtSkip;
+    WindowCandidates() : leftPos(0), rightPos(0), nReads(0), returnedSkip(false), hapsAtSkip(0) {}
 };
 // one window from its table: selectBlocks, setThresholds, the two skip tests of DInDel.cpp:1569 / :1581, generateHaplotypes
 void haplotypesFromTable(const WindowTable &t, uint32_t rs, const HaplotypeOptions &opt, WindowCandidates &win);
 // a batch: one device call (or blockTableHost with opt.hostDistribution), sequentialTable for the windows that are not OK, then the host
 // steps per window.  stats, if given: {windows OK on the table path, windows through sequentialTable}.  Throws std::string on a library error.
 void getHaplotypesBatch(const HapBatchData &data, std::vector<WindowCandidates> &wins, const HaplotypeOptions &opt, size_t stats[2] = 0);
+
+// what the tool and the window loop's haplotype stage (dindel_gpu --ref) share (host/haplotypes_main.cpp):
+// getRefSeq(first1, last1) of the reference: 1-based, inclusive, cut at the sequence's end, letters as the file has them
+std::string refPiece(IndexedFasta &fa, const std::string &tid, long first1, long last1);
+// the selected reads of the window added last, from their records (ReadSelectionParameters::keepRecords): CIGAR, flag, raw letters
+void addWindowReads(HapBatchData &data, const std::vector<Read> &reads);
 
 // the tool (host/dindel_haplotypes.cpp)
 int haplotypesMain(int argc, char **argv);

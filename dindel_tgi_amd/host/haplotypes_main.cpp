@@ -1,6 +1,9 @@
 // haplotypes_main.cpp — the tool dindel_haplotypes: BAM + FASTA + window file -> the W / R / H records dindel_hapalign reads
 // (host/window_io.hpp).  Per window: getReads (get_reads.cpp, the selection dindel_gpu makes), the reads' CIGARs, flags and raw letters
 // from their records, then getHaplotypesBatch (host/haplotypes.cpp) for every --batchWindows windows.
+// Known difference from the reference, kept by this tool: the read buffer is emptied behind a window whose getReads threw, not behind one
+// whose haplotype construction threw (it learns that a batch later), and such a window's message does not travel through the W / R / H
+// file.  dindel_gpu --ref builds the haplotypes inside the window loop and has neither difference.
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -40,7 +43,8 @@ std::string upper(std::string s)
     return s;
 }
 
-// getRefSeq(first1, last1) of the reference: 1-based, inclusive, cut at the sequence's end
+} // namespace
+
 std::string refPiece(IndexedFasta &fa, const std::string &tid, long first1, long last1)
 {
     const long len = fa.length(tid);
@@ -50,7 +54,20 @@ std::string refPiece(IndexedFasta &fa, const std::string &tid, long first1, long
     return fa.get(tid, first1, int(last1 - first1 + 1));
 }
 
-} // namespace
+void addWindowReads(HapBatchData &data, const std::vector<Read> &reads)
+{
+    std::vector<uint32_t> cigar;
+    std::string letters;
+    for (size_t r = 0; r < reads.size(); r++) {
+        if (!reads[r].record) throw std::string("a selected read came without its record");
+        const RawBamView v(reads[r].record->data(), reads[r].record->size());
+        cigar.resize(v.nCigar());
+        for (uint32_t k = 0; k < v.nCigar(); k++) cigar[k] = v.cigar(k);
+        letters.resize(size_t(std::max(v.lSeq(), 0)));
+        for (int32_t x = 0; x < v.lSeq(); x++) letters[size_t(x)] = v.base(x);
+        data.addRead(v.pos(), int32_t(v.flag()), cigar.data(), cigar.size(), letters);
+    }
+}
 
 int haplotypesMain(int argc, char **argv)
 {
@@ -150,17 +167,7 @@ int haplotypesMain(int argc, char **argv)
             // DInDel.cpp:1530-1532
             const uint32_t rs = cand.leftPos > rsp.minReadOverlap ? uint32_t(cand.leftPos - rsp.minReadOverlap) : 0u, re = uint32_t(cand.rightPos + rsp.minReadOverlap);
             data.addWindow(int32_t(rs), refPiece(fa, cand.tid, long(rs) + 1, long(re) + 1));
-            std::vector<uint32_t> cigar;
-            std::string letters;
-            for (size_t r = 0; r < reads.size(); r++) {
-                if (!reads[r].record) throw std::string("dindel_haplotypes: a selected read came without its record");
-                const RawBamView v(reads[r].record->data(), reads[r].record->size());
-                cigar.resize(v.nCigar());
-                for (uint32_t k = 0; k < v.nCigar(); k++) cigar[k] = v.cigar(k);
-                letters.resize(size_t(std::max(v.lSeq(), 0)));
-                for (int32_t x = 0; x < v.lSeq(); x++) letters[size_t(x)] = v.base(x);
-                data.addRead(v.pos(), int32_t(v.flag()), cigar.data(), cigar.size(), letters);
-            }
+            addWindowReads(data, reads);
             WindowCandidates w;
             w.leftPos = uint32_t(cand.leftPos); w.rightPos = uint32_t(cand.rightPos); w.variants = cand.variants; w.nReads = reads.size();
             wins.push_back(w);

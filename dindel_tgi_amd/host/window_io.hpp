@@ -1,6 +1,6 @@
 // window_io.hpp — the text inputs of the window loop: the realignment-window ("variants") file, the
-// library insert-size file and — in place of the reference's candidate-haplotype construction, which is out of this
-// repository's scope — a haplotype fixture file.
+// library insert-size file and a haplotype file: dindel_gpu --hapFile reads a window's candidate haplotypes from it instead of building
+// them (--ref: haplotypes.hpp, align_haplotypes.hpp); dindel_haplotypes writes and dindel_hapalign reads and writes the same records.
 //   AlignedCandidates, VariantFile::getLineVector     reference VariantFile.hpp:38-70, :188-289
 //   LibraryCollection (addFromFile, getMaxInsertSize)  reference Library.hpp:135-253
 #ifndef DINDEL_WINDOW_IO_HPP

@@ -545,6 +545,52 @@ int dd_align_haplotypes_events(const dd_align_batch *b, dd_align_result *r, int3
 #define DD_ALIGN_EVENTS_LOG_FIELDS 4
 void dd_align_events_last_launch(int64_t out[DD_ALIGN_EVENTS_LOG_FIELDS]);
 
+/* ---- variants of an alignment: everything convertAlignment and getFlankingCoordinatesBetter give per haplotype, without strings ---- */
+/* One variant of one pair, in column order (reference ObservationModelSeqAn.hpp:37-269).  Strings are not produced: the caller forms
+ * "+...", "-...", "X=>X" from the two sequences by position.
+ *   kind        DD_ALIGN_EVENT_INS, DD_ALIGN_EVENT_DEL, DD_HAP_VARIANT_SNP, or DD_HAP_VARIANT_DEL_UNSEEN: deleted reference bases in
+ *               front of the first paired base, which convertAlignment marks 'D' in hap.align but does not record as a variant
+ *   key         the map key (hb): reference bases left of the variant
+ *   len         inserted haplotype bases / deleted reference bases / 1
+ *   start_read  AlignedVariant::startRead: first inserted base; the base in front of a deletion; the SNP's base
+ *   left_flank_hap ... right_flank_read   the four arguments of AlignedVariant::setFlanking, in its order (0 for DEL_UNSEEN, and for
+ *               an insertion that raised DD_HAP_VARIANTS_HOST)
+ * The classification rules are those of dd_align_events, a SNP being a paired base whose seqan::Dna letter differs from the reference
+ * base's.  Records of a later column come later; a deletion in front of base b comes before what base b itself gives.  Two records
+ * may carry one key (an insertion, then a deletion that starts behind it): the later one replaces the earlier in hap.indels.
+ * No field truncates: sequences are at most DD_LONG_MAX_HAP_LEN = 4,094 bases, so key, len, start_read and the haplotype flanks are
+ * at most 4,094 and the read flanks, sums of a read position and a difference of reference positions, at most 8,188 and never
+ * negative (getFlankingCoordinatesBetter clamps the left one at 0 and start_read of a recorded deletion is at least 0). */
+typedef struct dd_hap_variant {
+    int16_t kind, key, len, start_read, left_flank_hap, right_flank_hap, left_flank_read, right_flank_read;
+} dd_hap_variant;
+#define DD_HAP_VARIANT_SNP 3
+#define DD_HAP_VARIANT_DEL_UNSEEN 4
+/* Per pair.  n_variants: the true number of records, also beyond the launch's cap.  first_base / last_base: ml.firstBase (-1: no paired
+ * base) and ml.lastBase as convertAlignment leaves them.  flags: DD_HAP_VARIANTS_* .  A pair whose status is not DD_ALIGN_OK has all
+ * four 0 and no records. */
+typedef struct dd_hap_variants_summary {
+    int32_t n_variants, first_base, last_base, flags;
+} dd_hap_variants_summary;
+#define DD_HAP_VARIANTS_LO_FIRST 1   /* haplotype base 0 is MLAlignment::LO */
+#define DD_HAP_VARIANTS_RO_LAST  2   /* the last haplotype base is MLAlignment::RO and the haplotype has more than one base */
+#define DD_HAP_VARIANTS_HOST     4   /* a flank of this pair has no closed form (an insertion at least as long as the reference sequence):
+                                        convert the pair on the host from its slice */
+#define DD_HAP_VARIANTS_MAX_CAP 4096
+/* Device pointers; runs BEHIND dd_align_haplotypes_device exactly like dd_align_events_device (same thread, same stream, that launch's
+ * workspace still allocated: header words of its own).  Writes summary_dev[pair] for every pair and the first min(n_variants, cap)
+ * records of variants_dev[pair * cap ...] (8-byte aligned); nothing else of variants_dev is written.  Reads both sequences of b_dev.
+ * cap 1 ... DD_HAP_VARIANTS_MAX_CAP.  Asynchronous on `stream`, no allocation. */
+int dd_hap_variants_device(const dd_align_batch *b_dev, const dd_align_result *r_dev, dd_hap_variants_summary *summary_dev,
+                           dd_hap_variant *variants_dev, int cap, void *stream);
+/* Host pointers: dd_align_haplotypes followed by the variants launch.  score, status, summary [n_pairs] and variants [n_pairs * cap]
+ * always come back (records the kernel did not write are 0); r->ref_pos may be NULL, then no slice is copied back.  Validation and
+ * errors as dd_align_haplotypes. */
+int dd_align_haplotypes_variants(const dd_align_batch *b, dd_align_result *r, dd_hap_variants_summary *summary, dd_hap_variant *variants,
+                                 int cap, int device);
+/* The last variants launch on this host thread: the fields of dd_align_events_last_launch. */
+void dd_hap_variants_last_launch(int64_t out[DD_ALIGN_EVENTS_LOG_FIELDS]);
+
 /* ---- block table of a window's empirical haplotype distribution (HaplotypeDistribution / HapBlock) ---------- */
 /* Windows and the reads laid over them, CSR-packed.  Raw addresses: host arrays for dd_hap_blocks_compute, device arrays for
  * dd_hap_blocks_device.  A window is the reference piece [rs, rs + len) (len = win_ref_off[w + 1] - win_ref_off[w], the bytes as
