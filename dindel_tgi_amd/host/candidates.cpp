@@ -445,6 +445,8 @@ const char *kUsage =
     "  --quiet                       no progress on stdout\n"
     "  --help                        this text\n";
 
+} // namespace
+
 void parseRegion(const std::string &region, int &start, int &end)          // reference DInDel.cpp:3892-3905
 {
     std::string filtered;
@@ -454,8 +456,6 @@ void parseRegion(const std::string &region, int &start, int &end)          // re
     if (!(a >> start)) throw std::string("Cannot parse region for start!");
     if (!(b >> end)) throw std::string("Cannot parse region end!");
 }
-
-} // namespace
 
 // the option checks, their order, messages and exit codes: reference DInDel.cpp:4188-4298
 int candidatesMain(int argc, char **argv, AlignHook hook, void *hookData)

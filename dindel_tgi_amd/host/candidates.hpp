@@ -91,6 +91,9 @@ void candidatesFromRegion(const std::vector<std::string> &bamFiles, const std::s
 void realignCandidateFile(const std::string &varFile, bool isOneBased, const std::string &outputFile, IndexedFasta &fa,
                           const CandidateOptions &opt, CandidateStats &stats);
 
+// --region "A-B" (commas allowed in the numbers) -> [start, end); throws std::string (reference DInDel.cpp:3892-3905)
+void parseRegion(const std::string &region, int &start, int &end);
+
 // the tool (host/dindel_candidates.cpp is this call); hook as in CandidateOptions
 int candidatesMain(int argc, char **argv, AlignHook hook, void *hookData);
 

@@ -48,6 +48,16 @@
 //                     window at a time, so a small N costs a recompute per affected window — (counted in the timing line).  The files are the
 //                     same byte for byte.  The engines then merge as many batches per launch as without realigned BAMs.  No effect
 //                     without --outputRealignedBAM (main model, like that option)
+//   [--discover]      no --varFile: the run starts with the discovery stage (host/discover.hpp) on --devices[0] — candidate indels from the CIGARs
+//                     of --bamFile (or, with --tid NAME --region A-B, of every file of --bamFiles), each realigned on the device, to
+//                     PREFIX.variants.txt and PREFIX.libraries.txt exactly as `dindel_candidates --analysis getCIGARindels` writes them
+//                     ([--batchCandidates N] [--eventsCap N] [--hostConvert] are that tool's), then the windows of python/makeWindows.py:129-207
+//                     to PREFIX.windows.txt as `dindel_windows --oneFile` writes them ([--minDist N] [--minCount N] [--maxCount M]) —
+//                     and the loop reads that file as if it had been given as --varFile.  Needs --ref; --hapFile beside it is an error.
+//                     The stage is a barrier: windows are clusters of the whole candidate table.  The three files stay on disk.
+//   [--useLibraries]  with --discover (whole-file run): PREFIX.libraries.txt is this run's --libFile; an explicit --libFile wins
+//   [--vcf F [--sampleID ID]]  after the loop PREFIX.glf.txt is converted to the VCF F as dindel_glf2vcf does with a list naming that one
+//                     file (glf_to_vcf.hpp; python/mergeOutputDiploid.py:240-317); needs --ref
 //   [--timing]        one "timing:" line on stdout with the busy time of each stage
 //   [--prepareOnly]   stop after the prepare stage (no likelihoods, no calls: profiling the read selection on a GPU-less host); with --ref
 //                     in front of the haplotype stage, which needs the device
@@ -75,6 +85,7 @@
 #include "batch_channels.hpp"
 #include "compute_likelihoods.hpp"
 #include "diploid_glf.hpp"
+#include "discover.hpp"
 #include "align_haplotypes.hpp"
 #include "get_reads.hpp"
 #include "glf_output.hpp"
@@ -141,11 +152,25 @@ struct Options {
     bool realignedBAM, deviceCigars;
     bool keepAlignments;                 // the per-base alignments come back from the device (--faster; --outputRealignedBAM without --deviceCigars)
     std::set<int> injectedLateSkips;
+    bool discover;                       // --discover: the discovery stage writes varFile (= disc.windowsFile()) before the loop starts
+    DiscoverOptions disc;
+    std::string vcfFile, vcfRef, sampleID;   // --vcf F: PREFIX.glf.txt -> F after the loop, with the FASTA of --ref
 };
 
 const char *const kHelp =
     "dindel_gpu: the --analysis indels --doDiploid window loop with the likelihood step on the GPU\n"
     "  required: --bamFile F --varFile F --outputFile PREFIX and --ref FASTA or --hapFile F          (writes PREFIX.glf.txt)\n"
+    "        or: --discover --bamFile F --ref FASTA --outputFile PREFIX        from a BAM and a FASTA alone: the candidates and the windows are made first\n"
+    "  discover: --discover       the run starts with the discovery stage on the first device: candidate indels from the CIGARs of --bamFile, each\n"
+    "                             realigned on the device, to PREFIX.variants.txt and PREFIX.libraries.txt (dindel_candidates --analysis getCIGARindels),\n"
+    "                             then their windows to PREFIX.windows.txt (dindel_windows --oneFile), which the loop reads as its --varFile; the\n"
+    "                             stage is a barrier in front of the loop; --hapFile cannot be given with it\n"
+    "            [--tid NAME --region A-B]  candidates of that region only, from --bamFile or every file of --bamFiles (no PREFIX.libraries.txt)\n"
+    "            [--minDist N]    candidates at most N bases apart share a window (default 20)\n"
+    "            [--minCount N] [--maxCount M]  keep only candidates seen N ... M times (given one, the other is 2 / 10000000; default: keep all)\n"
+    "            [--batchCandidates N] [--eventsCap N]  candidates per launch (65536) and indel events kept per alignment (8) of the realignment\n"
+    "            [--useLibraries] PREFIX.libraries.txt becomes this run's --libFile (an explicit --libFile wins)\n"
+    "  output:   [--vcf F]        after the loop, convert PREFIX.glf.txt to the VCF F (dindel_glf2vcf on that one file); needs --ref   [--sampleID ID]\n"
     "  haplotypes: --ref FASTA (with FASTA.fai)  every window's candidate haplotypes are built in the run from the reads it selected: the block\n"
     "                             tables and the alignment to the reference on the device, one launch each per batch of windows\n"
     "            [--maxHap N]     combinations the blocks are thinned to (default 8)      [--skipMaxHap N]  a window with more haplotypes is passed\n"
@@ -169,7 +194,7 @@ const char *const kHelp =
     "  files:    --varFile: the reference's window file; --hapFile: W / H / V / A records (host/window_io.hpp)\n";
 // the options without a value; any other --NAME takes the next argument as its value, whatever its name
 const char *const kFlags[] = {"varFileIsOneBased", "faster", "filterHaplotypes", "quiet", "doDiploid", "timing", "outputRealignedBAM", "prepareOnly", "noLookBack",
-                              "lateSkipsKnown", "windowByWindow", "longWindows", "longWindowsFaster", "deviceCigars", "changeINStoN", "hostDistribution", "hostConvert"};
+                              "lateSkipsKnown", "windowByWindow", "longWindows", "longWindowsFaster", "deviceCigars", "changeINStoN", "hostDistribution", "hostConvert", "discover", "useLibraries"};
 
 std::vector<int> commaInts(const std::string &list)      // "3,5,,8" -> 3 5 8
 {
@@ -202,16 +227,44 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     auto has = [&](const char *k) { return opt.find(k) != opt.end(); };
     auto num = [&](const char *k, double dflt) { return has(k) ? atof(opt[k].c_str()) : dflt; };
     exitCode = 1;
+    o.discover = has("discover");
     for (const char *need : {"varFile", "outputFile"})
-        if (!has(need)) { std::cerr << "Please specify --" << need << "\n"; return false; }
+        if (!has(need) && !(o.discover && !strcmp(need, "varFile"))) { std::cerr << "Please specify --" << need << "\n"; return false; }
+    if (o.discover && has("hapFile")) { std::cerr << "--discover builds the haplotypes in the run: --hapFile cannot be given with it\n"; return false; }
+    if (o.discover && !has("ref")) { std::cerr << "Please specify --ref: --discover needs the reference FASTA\n"; return false; }
+    if (has("vcf") && !has("ref")) { std::cerr << "Please specify --ref: --vcf needs the reference FASTA\n"; return false; }
     if (!has("hapFile") && !has("ref")) { std::cerr << "Please specify --ref (haplotypes built in the run) or --hapFile (haplotypes from a file)\n"; return false; }
     if (!has("bamFile") && !has("bamFiles")) { std::cerr << "Error: Specify either --bamFile or --bamFiles." << std::endl; return false; }   // DInDel.cpp:4215-4218
     o.varFile = opt["varFile"]; o.outputPrefix = opt["outputFile"];
+    if (has("vcf")) { o.vcfFile = opt["vcf"]; o.vcfRef = opt["ref"]; o.sampleID = has("sampleID") ? opt["sampleID"] : std::string("SAMPLE"); }
+    if (o.discover) {                        // (the window file is ours: zero-based, whatever --varFileIsOneBased says)
+        DiscoverOptions &d = o.disc;
+        d.outputPrefix = o.outputPrefix; d.refFile = opt["ref"];
+        o.varFile = d.windowsFile();
+        if (has("region") != has("tid")) { std::cerr << "--tid and --region go together: --tid NAME --region A-B\n"; return false; }
+        if (!has("region") && !has("bamFile")) { std::cerr << "Can extract the full set of indels from only BAM file at a time.\n"; return false; }
+        if (has("region")) {
+            d.haveRegion = true; d.tid = opt["tid"];
+            try { parseRegion(opt["region"], d.start, d.end); } catch (const std::string &s) { std::cerr << s << "\n"; return false; }
+        }
+        d.minDist = long(num("minDist", 20));
+        d.filter = has("minCount") || has("maxCount");
+        d.minCount = long(num("minCount", 2)); d.maxCount = long(num("maxCount", 10000000));
+        d.candidates.batchCandidates = int(num("batchCandidates", d.candidates.batchCandidates));
+        d.candidates.eventsCap = int(num("eventsCap", d.candidates.eventsCap));
+        if (d.candidates.batchCandidates < 1) { std::cerr << "--batchCandidates must be at least 1\n"; exitCode = 2; return false; }
+        if (d.candidates.eventsCap < 1 || d.candidates.eventsCap > DD_ALIGN_EVENTS_MAX_CAP) { std::cerr << "--eventsCap must be 1 ... 4096\n"; exitCode = 2; return false; }
+        d.candidates.hostConvert = has("hostConvert"); d.candidates.quiet = has("quiet");
+        if (has("useLibraries") && !has("libFile")) {
+            if (d.haveRegion) { std::cerr << "--useLibraries needs a whole-file run: with --region the discovery stage writes no library file\n"; return false; }
+            opt["libFile"] = d.librariesFile();
+        }
+    }
     if (has("hapFile")) o.hapFile = opt["hapFile"];                  // --hapFile wins when both are given
     else o.refFile = opt["ref"];
     if (has("bamFile")) o.bamPaths.push_back(opt["bamFile"]);        // --bamFile wins when both are given (DInDel.cpp:4220-4226)
     else o.bamList = opt["bamFiles"];
-    o.faster = has("faster"); o.oneBased = has("varFileIsOneBased"); o.prepareOnly = has("prepareOnly"); o.quiet = has("quiet"); o.timing = has("timing");
+    o.faster = has("faster"); o.oneBased = has("varFileIsOneBased") && !o.discover; o.prepareOnly = has("prepareOnly"); o.quiet = has("quiet"); o.timing = has("timing");
     o.longWindows = has("longWindows"); o.longWindowsFaster = has("longWindowsFaster");
     o.noLookBack = has("noLookBack"); o.lateSkipsKnown = has("lateSkipsKnown"); o.windowByWindow = has("windowByWindow");
     o.realignedBAM = has("outputRealignedBAM") && !o.faster;                      // `params.outputRealignedBAM && params.slower`, :589
@@ -247,6 +300,7 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     o.batchWindows = std::max(1, int(num("batchWindows", 256)));
     o.devices = commaInts(has("devices") ? opt["devices"] : (has("device") ? opt["device"] : std::string("0")));
     if (o.devices.empty()) o.devices.push_back(0);
+    o.disc.candidates.device = o.devices[0];
     // defaults measured on a 16-CPU share of an MI355X host (profiles/r03/n2_pipeline.md): per window the read selection costs
     // 0.10-0.20 ms of CPU, diploidGLF 0.09 ms, packing 0.025 ms; two engines per GPU keep it busy while one of them packs.  They
     // scale with the number of devices up to what the host has.
@@ -922,14 +976,36 @@ void WindowLoop::report()                                 // --timing: one line;
 }
 }
 
+// --discover: the stage in front of the loop (host/discover.hpp); throws std::string
+static void runDiscovery(Options &o)
+{
+    const TimePoint t0 = now();
+    DiscoverOptions &d = o.disc;
+    if (o.bamPaths.empty()) d.bamFiles = readBamList(o.bamList);
+    else d.bamFiles = o.bamPaths;
+    CandidateStats stats;
+    const long lines = discoverWindows(d, stats);
+    if (!o.quiet)
+        std::cout << "discovery: " << stats.candidates << " candidates in " << stats.batches << " launches (" << stats.dropped << " dropped, " << stats.overflowed
+                  << " redone on the host) -> " << lines << " window lines in " << d.windowsFile() << std::endl;
+    if (o.timing) std::cout << "discovery_seconds: " << seconds_since(t0) << std::endl;
+}
+
 int main(int argc, char **argv)
 {
     Options options;
     int exitCode = 0;
     if (!parseOptions(argc, argv, options, exitCode)) return exitCode;
     try {
-        WindowLoop loop(options);
-        return loop.run();
+        if (options.discover) runDiscovery(options);
+        int rc = 0;
+        {
+            WindowLoop loop(options);
+            rc = loop.run();
+        }
+        if (rc == 0 && !options.vcfFile.empty())
+            mergeOutputFiles(std::vector<std::string>(1, options.outputPrefix + ".glf.txt"), options.sampleID, options.vcfRef, 10, options.vcfFile, 20);
+        return rc;
     } catch (std::string &s) {
         std::cerr << "Exception: " << s << std::endl;
         return 1;

@@ -307,6 +307,12 @@ void mergeOutput(const std::string &glfFilesFile, const std::string &sampleID, c
         }
         okFiles.push_back(dat[0]);
     }
+    mergeOutputFiles(okFiles, sampleID, refFile, maxHPLen, vcfFile, filterQual);
+}
+
+void mergeOutputFiles(const std::vector<std::string> &okFiles, const std::string &sampleID, const std::string &refFile, int maxHPLen,
+                      const std::string &vcfFile, int filterQual)
+{
     std::cout << "Number of non-empty GLF files: " << okFiles.size() << "\n";
     std::ofstream fv(vcfFile.c_str());
     if (!fv.is_open()) throw std::string("Cannot open file ").append(vcfFile).append(" for writing.");

@@ -66,6 +66,9 @@ int processDiploidGLFFile(const std::string &glfFile, CallsByChrom &variants, In
 // remaining ones in Python-2 dict order, which is not reproducible — here they follow in lexicographic order.
 void mergeOutput(const std::string &glfFilesFile, const std::string &sampleID, const std::string &refFile, int maxHPLen,
                  const std::string &vcfFile, int filterQual = 20);
+// the same behind the list file: the .glf.txt files themselves (dindel_gpu --vcf converts the one file it wrote)
+void mergeOutputFiles(const std::vector<std::string> &glfFiles, const std::string &sampleID, const std::string &refFile, int maxHPLen,
+                      const std::string &vcfFile, int filterQual = 20);
 
 } // namespace dindel
 #endif
