@@ -56,6 +56,14 @@
 //                     and the loop reads that file as if it had been given as --varFile.  Needs --ref; --hapFile beside it is an error.
 //                     The stage is a barrier: windows are clusters of the whole candidate table.  The three files stay on disk.
 //   [--useLibraries]  with --discover (whole-file run): PREFIX.libraries.txt is this run's --libFile; an explicit --libFile wins
+//   [--candidateVCF F[,G...] [--minQual X] [--vcfCandidatesOnly]]  with --discover: known sites beside the sample's own candidates.
+//                     The indels of the VCFs (plain or .gz; records with QUAL `.` or >= X, default 1) go to PREFIX.vcf.variants.txt exactly as
+//                     `dindel_vcf2candidates` writes them (python/convertVCFToDindel.py:9-47; in a region run with that --tid / --region), are
+//                     realigned on the device to PREFIX.vcf.realigned.variants.txt exactly as `dindel_candidates --analysis realignCandidates`
+//                     writes them, and PREFIX.candidates.txt — what --minCount / --maxCount keep of PREFIX.variants.txt, then every known site
+//                     (the filter never acts on them) — is what the windows are made from.  --vcfCandidatesOnly: no pass over the BAM's
+//                     CIGARs, the known sites alone (--minCount / --maxCount / --useLibraries are errors then).  A conversion that fails
+//                     stops the run before any window is prepared.
 //   [--vcf F [--sampleID ID]]  after the loop PREFIX.glf.txt is converted to the VCF F as dindel_glf2vcf does with a list naming that one
 //                     file (glf_to_vcf.hpp; python/mergeOutputDiploid.py:240-317); needs --ref
 //   [--timing]        one "timing:" line on stdout with the busy time of each stage
@@ -170,6 +178,11 @@ const char *const kHelp =
     "            [--minCount N] [--maxCount M]  keep only candidates seen N ... M times (given one, the other is 2 / 10000000; default: keep all)\n"
     "            [--batchCandidates N] [--eventsCap N]  candidates per launch (65536) and indel events kept per alignment (8) of the realignment\n"
     "            [--useLibraries] PREFIX.libraries.txt becomes this run's --libFile (an explicit --libFile wins)\n"
+    "            [--candidateVCF F[,G...]]  known sites: the indels of these VCFs (plain or .gz) become candidates beside the sample's own, through\n"
+    "                             PREFIX.vcf.variants.txt (dindel_vcf2candidates), PREFIX.vcf.realigned.variants.txt (dindel_candidates --analysis\n"
+    "                             realignCandidates, on the device) and PREFIX.candidates.txt, which the windows are made from; --minCount / --maxCount\n"
+    "                             never filter them   [--minQual X] records with QUAL `.` or >= X (default 1)\n"
+    "            [--vcfCandidatesOnly]  with --candidateVCF: no pass over the CIGARs of the BAM, the known sites alone\n"
     "  output:   [--vcf F]        after the loop, convert PREFIX.glf.txt to the VCF F (dindel_glf2vcf on that one file); needs --ref   [--sampleID ID]\n"
     "  haplotypes: --ref FASTA (with FASTA.fai)  every window's candidate haplotypes are built in the run from the reads it selected: the block\n"
     "                             tables and the alignment to the reference on the device, one launch each per batch of windows\n"
@@ -194,7 +207,7 @@ const char *const kHelp =
     "  files:    --varFile: the reference's window file; --hapFile: W / H / V / A records (host/window_io.hpp)\n";
 // the options without a value; any other --NAME takes the next argument as its value, whatever its name
 const char *const kFlags[] = {"varFileIsOneBased", "faster", "filterHaplotypes", "quiet", "doDiploid", "timing", "outputRealignedBAM", "prepareOnly", "noLookBack",
-                              "lateSkipsKnown", "windowByWindow", "longWindows", "longWindowsFaster", "deviceCigars", "changeINStoN", "hostDistribution", "hostConvert", "discover", "useLibraries"};
+                              "lateSkipsKnown", "windowByWindow", "longWindows", "longWindowsFaster", "deviceCigars", "changeINStoN", "hostDistribution", "hostConvert", "discover", "useLibraries", "vcfCandidatesOnly"};
 
 std::vector<int> commaInts(const std::string &list)      // "3,5,,8" -> 3 5 8
 {
@@ -233,6 +246,13 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     if (o.discover && has("hapFile")) { std::cerr << "--discover builds the haplotypes in the run: --hapFile cannot be given with it\n"; return false; }
     if (o.discover && !has("ref")) { std::cerr << "Please specify --ref: --discover needs the reference FASTA\n"; return false; }
     if (has("vcf") && !has("ref")) { std::cerr << "Please specify --ref: --vcf needs the reference FASTA\n"; return false; }
+    if (has("candidateVCF") && !o.discover) { std::cerr << "--candidateVCF adds known sites to the discovery stage: it needs --discover\n"; return false; }
+    if (has("vcfCandidatesOnly") && !has("candidateVCF")) { std::cerr << "--vcfCandidatesOnly needs --candidateVCF\n"; return false; }
+    if (has("vcfCandidatesOnly") && has("useLibraries")) { std::cerr << "--useLibraries needs the pass over the BAM file: with --vcfCandidatesOnly the discovery stage writes no library file\n"; return false; }
+    if (has("vcfCandidatesOnly") && (has("minCount") || has("maxCount"))) {
+        std::cerr << "--minCount / --maxCount filter the sample's own candidates: with --vcfCandidatesOnly there are none\n";
+        return false;
+    }
     if (!has("hapFile") && !has("ref")) { std::cerr << "Please specify --ref (haplotypes built in the run) or --hapFile (haplotypes from a file)\n"; return false; }
     if (!has("bamFile") && !has("bamFiles")) { std::cerr << "Error: Specify either --bamFile or --bamFiles." << std::endl; return false; }   // DInDel.cpp:4215-4218
     o.varFile = opt["varFile"]; o.outputPrefix = opt["outputFile"];
@@ -242,10 +262,15 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
         d.outputPrefix = o.outputPrefix; d.refFile = opt["ref"];
         o.varFile = d.windowsFile();
         if (has("region") != has("tid")) { std::cerr << "--tid and --region go together: --tid NAME --region A-B\n"; return false; }
-        if (!has("region") && !has("bamFile")) { std::cerr << "Can extract the full set of indels from only BAM file at a time.\n"; return false; }
+        if (!has("region") && !has("bamFile") && !has("vcfCandidatesOnly")) { std::cerr << "Can extract the full set of indels from only BAM file at a time.\n"; return false; }
         if (has("region")) {
             d.haveRegion = true; d.tid = opt["tid"];
             try { parseRegion(opt["region"], d.start, d.end); } catch (const std::string &s) { std::cerr << s << "\n"; return false; }
+        }
+        if (has("candidateVCF")) {
+            d.candidateVCF = opt["candidateVCF"]; d.vcfCandidatesOnly = has("vcfCandidatesOnly");
+            if (d.candidateVCF.empty()) { std::cerr << "--candidateVCF needs the name of a VCF file\n"; return false; }
+            try { if (has("minQual")) d.minQual = pythonFloat(opt["minQual"]); } catch (const std::string &e) { std::cerr << "--minQual: " << e << "\n"; return false; }
         }
         d.minDist = long(num("minDist", 20));
         d.filter = has("minCount") || has("maxCount");
@@ -981,7 +1006,8 @@ static void runDiscovery(Options &o)
 {
     const TimePoint t0 = now();
     DiscoverOptions &d = o.disc;
-    if (o.bamPaths.empty()) d.bamFiles = readBamList(o.bamList);
+    if (d.vcfCandidatesOnly) d.bamFiles.clear();
+    else if (o.bamPaths.empty()) d.bamFiles = readBamList(o.bamList);
     else d.bamFiles = o.bamPaths;
     CandidateStats stats;
     const long lines = discoverWindows(d, stats);
