@@ -455,11 +455,42 @@ __global__ void __launch_bounds__(DD_WAVES * 64, OCC ? OCC : DD_MIN_WAVES_PER_SI
     //   masked block below (197 instructions) another 2.1 % (-> 235.9 ms).  It now also pays for K = 2 at D = 11 with LDS back-pointers
     //   (+1.4 %) and for the K = 2 scratch build at D = 6 (long reads, +3-4 %); the D = 11 scratch build still loses 4.5 % and K >= 3
     //   would need state 1's pair from another slot than the lane's last, so those keep the one-lane blocks (capi.cpp picks).
-    const bool foldRO = foldLO && kRO == K - 1 && numS <= NP - 3;
+    //   * RO in its lane's FIRST slot (K = 2, kRO == 0: every odd haplotype length) cannot take that form as it stands: its y = 1
+    //     candidate and its inserted state read the lane's own slot 1, the dead position RO+1 = numS.  The "mirrored" form makes that
+    //     slot a second copy of RO: both slots of lane laneRO start at beta[L-1] = 0, take eInc = 0 and the all-columns mask, and run
+    //     RO's recurrence through the generic code, so that slot 1 holds {beta[RO], eq} by itself — which is what slot 0 has to read
+    //     from the lane's registers.  The publish block is the one above, unchanged: it takes a[K-1] / ov[K-1] (the copy) and its two
+    //     stores land one position further right, on slots RO+2 {beta[RO], eq} and RO+3 {eq + beta[RO], Nn[RO]} — for K = 2 these are
+    //     lane laneRO+1's two slots in either form, so endA / endV are the same expressions.  Sum by sum (reference :1741-1742, :1750,
+    //     :1763-1767; one-lane block below):
+    //       slot RO+1, y = 2 (c_2 = 0, every other c = -inf):   (0 + (eq + beta[RO])) + Nn[RO]     from slot RO+3     -> stays RO
+    //       slot RO,   y = 3 (c_3 = 0, every other c = -inf):   (0 + (eq + beta[RO])) + Nn[RO]     from slot RO+3     -> stays RO
+    //       insertion edge of either slot, eInc = 0:            (eq + beta[numS+RO]) + 0                              -> numS+RO
+    //       inserted state of slot RO:    d = (eq + in) + II,   (ov[1] + a[1]) + NI = (eq + beta[RO]) + NI   from the lane's own slot 1
+    //       inserted state of slot RO+1:  d = (eq + in) + II,   (eq + beta[RO]) + NI                          from slot RO+2
+    //     Both slots start equal and evaluate the same sums on the same operands every read base (the candidates in front of the finite
+    //     one leave best = -inf, which it always beats; the insertion edge then meets the same "> best + EPS" test), so a[1] == a[0] and
+    //     in[1] == in[0] bit for bit, by induction over the read bases, and both equal the one-lane block's values: 0 + x and x + 0 are
+    //     x, and x + y is commutative.  Nothing finite leaks out of slot RO+1: a position x < RO reaches it only as src = x + y = RO+1 >
+    //     RO, whose constant is -inf (cInc), and position RO-1's inserted state reads src = RO, as always.  The positions RO+2 and RO+3
+    //     are dead ones of lane laneRO+1 (every c and eInc -inf there), exactly as position RO+1 is in the plain form.  After the pass
+    //     slot RO+1 leaves the join with -inf, like LO's idle position; the traceback reads RO's field there, where "stays" is the same
+    //     code 2 as in the plain form (slot RO itself stays with y = 3).  Room: RO+3 must stay left of LO's position NP-1 and of what it
+    //     reads, numS <= NP-4 — at K = 2 odd Hs <= 121; Hs = 123 keeps the one-lane block.  (Not for the register-lean builds, whose
+    //     constants come from the shC table: no FOLD build is one.)  Nothing inside the sweep changes for it: the one-lane block is
+    //     skipped (an empty exec mask) for the odd lengths too, 58 % of configs[1]'s haplotypes.  Measured (round 5,
+    //     profiles/r05/fold_mirrored_ab.txt): configs[1] 392.7-393.0 -> 381.7-382.1 ms per launch (+2.8 %), together with the one
+    //     per-lane emission mask below (203 -> 200 instructions per read base; that change alone LOST 1 %, the sweep's schedule
+    //     being what it is).  LDS back-pointers only: in the scratch build the extra scalar conditions pushed the publish mask and the
+    //     one-lane block's mask into spilled SGPRs (four v_readlane per read base, 199 -> 207 instructions) and 170-bp reads ran
+    //     0.5 % (even lengths) to 1.3 % (odd lengths) SLOWER than before, so that build keeps the one-lane block for kRO == 0.
+    const bool mirRO = !GBT && !LEAN && K == 2 && foldLO && kRO == 0 && numS <= NP - 4;
+    const bool foldRO = (foldLO && kRO == K - 1 && numS <= NP - 3) || mirRO;
     constexpr int k1 = 1 % K;                       // state 1 lives in lane 1 / K, slot k1
     const int lane1 = 1 / K;
     if (foldLO && lane == 63) eInc[K - 1] = E_1;
     if (foldRO && lane == laneRO) eInc[K - 1] = 0.0;
+    if (mirRO && lane == laneRO) eInc[0] = 0.0;
     // where this lane stores for its end state: lane 63 (LO) slots NP / NP+1, lane laneRO (RO, when folded) slots RO+1 / RO+2;
     // the owner of state 1 stores obs[1] + beta[1] into slot NP+2
     const bool isEnd = foldLO && (lane == 63 || (foldRO && lane == laneRO));
@@ -477,7 +508,10 @@ __global__ void __launch_bounds__(DD_WAVES * 64, OCC ? OCC : DD_MIN_WAVES_PER_SI
     double *pubA = isEnd ? endA : rowAd + 2 * ((3 % K) * AQ + PADQ + 64 + 3 / K);
     double *pubV = isEnd ? endV : oneV;
     const double pubC = isEnd ? endC : NN;
-    const unsigned mLast = (foldLO && lane == 63) ? 0xffffffffu : mOwn[K - 1];
+    // LO's idle position and RO's copy match every column in the right->middle pass.  They keep that mask for good instead of a second
+    // per-lane mask beside mOwn[K-1]: both are positions >= numS, whose left->middle and join values are -inf whatever emission (eq or uq,
+    // neither is +inf) is added to them, and which no position < numS reads in that pass (its sources lie below it).
+    if (foldLO && (lane == 63 || (mirRO && lane == laneRO))) mOwn[K - 1] = 0xffffffffu;
     static_assert(!FOLD || (K <= 2 && k1 == K - 1), "the folded publish block takes state 1 from its lane's last slot");
 
     const int64_t pair_base = P.win_pair_off[w] + (int64_t)(g - h0) * R;
@@ -651,10 +685,12 @@ __global__ void __launch_bounds__(DD_WAVES * 64, OCC ? OCC : DD_MIN_WAVES_PER_SI
                     for (int y = 1; y <= D; y++) {
                         if (lane == 63) cInc[K - 1][y - 1] = y == 2 ? lLL : (y == 3 ? lFL : NEG_INF);
                         if (foldRO && lane == laneRO) cInc[K - 1][y - 1] = y == 2 ? 0.0 : NEG_INF;
+                        if (mirRO && lane == laneRO) cInc[0][y - 1] = y == 3 ? 0.0 : NEG_INF;
                     }
                 }
             }
             if (foldLO && lane == 63) { a[K - 1] = 0.0; in[K - 1] = 0.0; }      // beta[L-1][LO] = beta[L-1][numS] = 0, at LO's position in this pass
+            if (mirRO && lane == laneRO) { a[K - 1] = 0.0; in[K - 1] = 0.0; }   // RO's copy: beta[L-1][RO] = beta[L-1][numS+RO] = 0
             auto cinc = [&](int k, int y) -> double {       // y = 1..D
                 if constexpr (LEAN && D > 12) {                 // D = 32 build: from the haplotype's tables, every read base (correct, not fast)
                     const int src = x0 + k + y;
@@ -676,14 +712,16 @@ __global__ void __launch_bounds__(DD_WAVES * 64, OCC ? OCC : DD_MIN_WAVES_PER_SI
                 double v[NVI], ov[NVI];
 #pragma unroll
                 for (int k = 0; k < K; k++) {
-                    const unsigned mk = (foldLO && k == K - 1) ? mLast : mOwn[k];
-                    ov[k] = ((mk >> col) & 1u) ? eq : uq;
+                    ov[k] = ((mOwn[k] >> col) & 1u) ? eq : uq;
                     v[k] = a[k];
                     rowA[k * AQ + PADQ + lane] = make_double2(a[k], ov[k]);
                 }
                 if constexpr (foldLO) {                            // what the end states' generic candidates read (after the owners' own slots)
                     // 8-byte stores (RO's two slots are ordinary positions whose owner has just stored its own pair there: both halves are
-                    // rewritten)
+                    // rewritten).  Two leftovers of this block were tried and measured to LOSE (profiles/r05/fold_mirrored_ab.txt): pinning
+                    // ov[K-1] + a[K-1] so that it is formed once (the compiler forms it in front of the mask, for slot 0's inserted state, and
+                    // again under it; one fp64 add fewer, 0.5 % slower), and a compare on pubFlag per read base in place of the mask's two
+                    // v_readlane from its spilled SGPR pair (one VALU instruction fewer, 0.2 % slower).
                     if (pubFlag) { pubA[0] = a[K - 1]; pubA[1] = ov[K - 1]; pubV[0] = ov[K - 1] + a[K - 1]; pubV[1] = pubC; }
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -808,7 +846,7 @@ __global__ void __launch_bounds__(DD_WAVES * 64, OCC ? OCC : DD_MIN_WAVES_PER_SI
         if (foldLO) {                      // LO's beta back to position 0, where the join and the left->middle pass have it
             const double tA = __shfl(a[K - 1], 63), tI = __shfl(in[K - 1], 63);
             if (lane == 0) { be_a[0] = tA; be_i[0] = tI; }
-            if (lane == 63) { be_a[K - 1] = NEG_INF; be_i[K - 1] = NEG_INF; }
+            if (lane == 63 || (mirRO && lane == laneRO)) { be_a[K - 1] = NEG_INF; be_i[K - 1] = NEG_INF; }   // the idle position / RO's copy
         }
 
         // The left->middle chain of RO / numS+RO is a sink: nothing else in that pass reads it, and it only matters
@@ -1130,8 +1168,8 @@ __global__ void __launch_bounds__(DD_WAVES * 64, OCC ? OCC : DD_MIN_WAVES_PER_SI
                 while (b < L - 1) {
                     unsigned f;
                     // where this pass kept the state's back-pointer field, and the code that means "stays": LO folded into the generic
-                    // code sits at position NP-1 and stays with y = 2 (as does a folded RO); the one-lane blocks use code 0
-                    const int xf = (foldLO && x == 0) ? NP - 1 : x;
+                    // code sits at position NP-1 and stays with y = 2 (as does a folded RO; a mirrored one in its copy at RO+1); the one-lane blocks use code 0
+                    const int xf = (foldLO && x == 0) ? NP - 1 : ((mirRO && x == RO) ? RO + 1 : x);
                     const unsigned stayCode = (x == 0 ? foldLO : foldRO) ? 2u : 0u;
                     if (!ins) {
                         const int left = L - 1 - b, maxrun = left < W ? left : W;
