@@ -199,6 +199,21 @@ class dd_hap_blocks(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in HAP_BLOCKS_WINDOW_FIELDS + HAP_BLOCKS_OFFSET_FIELDS + HAP_BLOCKS_TABLE_FIELDS]
 
 
+class dd_pooled_slots(C.Structure):
+    """Slots of the pooled analysis' EM loop: slot_window (int32 [n_slots]), slot_off (int64 [n_slots + 1]), compat (uint8).  Raw addresses:
+    host arrays for dd_pooled_em and dd_pooled_em_host, device arrays for dd_pooled_em_device."""
+    _fields_ = [("n_slots", C.c_int64), ("slot_window", C.c_void_p), ("slot_off", C.c_void_p), ("compat", C.c_void_p)]
+
+
+POOLED_RESULT_FIELDS = ("loglik", "freqs", "iters", "ediff")
+DD_POOLED_MAX_HAPS = 256
+
+
+class dd_pooled_result(C.Structure):
+    """loglik, ediff (double [n_slots]), iters (int32 [n_slots]), freqs (double, laid out like compat); raw addresses like dd_pooled_slots."""
+    _fields_ = [(n, C.c_void_p) for n in POOLED_RESULT_FIELDS]
+
+
 class dd_device_result(C.Structure):
     """dd_result with raw device addresses (same layout: every member is a pointer)."""
     _fields_ = [(n, C.c_void_p) for n, _ in RESULT_FIELDS]
@@ -214,7 +229,8 @@ EXPORTS = ["dd_params_struct_defaults", "dd_params_cli_defaults", "dd_batch_size
            "dd_align_haplotypes", "dd_align_workspace_bytes", "dd_align_haplotypes_device", "dd_align_last_launch",
            "dd_align_events_device", "dd_align_haplotypes_events", "dd_align_events_last_launch",
            "dd_hap_variants_device", "dd_align_haplotypes_variants", "dd_hap_variants_last_launch",
-           "dd_hap_blocks_offsets", "dd_hap_blocks_workspace_bytes", "dd_hap_blocks_device", "dd_hap_blocks_compute", "dd_hap_blocks_last_launch"]
+           "dd_hap_blocks_offsets", "dd_hap_blocks_workspace_bytes", "dd_hap_blocks_device", "dd_hap_blocks_compute", "dd_hap_blocks_last_launch",
+           "dd_pooled_em_device", "dd_pooled_em", "dd_pooled_em_host", "dd_pooled_math_eval"]
 
 _lib = None
 
@@ -307,6 +323,11 @@ def load():
     lib.dd_hap_blocks_compute.argtypes = [C.POINTER(dd_hap_batch), C.POINTER(dd_hap_blocks), C.c_int]
     lib.dd_hap_blocks_last_launch.argtypes = [C.POINTER(C.c_int64 * len(HAP_BLOCKS_LOG_FIELDS))]
     lib.dd_hap_blocks_last_launch.restype = None
+    lib.dd_pooled_em_device.argtypes = [C.POINTER(dd_device_batch), C.c_void_p, C.POINTER(dd_pooled_slots), C.c_int, C.c_double, C.c_double,
+                                        C.POINTER(dd_pooled_result), C.c_void_p]
+    lib.dd_pooled_em.argtypes = [C.POINTER(dd_batch), c_f64p, C.POINTER(dd_pooled_slots), C.c_double, C.c_double, C.POINTER(dd_pooled_result), C.c_int]
+    lib.dd_pooled_em_host.argtypes = lib.dd_pooled_em.argtypes
+    lib.dd_pooled_math_eval.argtypes = [C.c_int, c_f64p, c_f64p, C.c_int64]
     lib.dd_last_launch.argtypes = [C.POINTER(C.c_int32 * 8)]
     lib.dd_last_launch.restype = None
     lib.dd_launch_log.argtypes = [c_i32p, C.c_int]

@@ -1,5 +1,6 @@
 // capi_internal.h — what the host units of the C ABI (include/dindel_hmm.h) share: plan.cpp, batch_host.cpp (neither calls the HIP runtime),
-// launch.cpp, host_path.cpp, align_host.cpp (the haplotype alignment, self-contained); each says in its first lines what it holds.  Host work is O(bases) bookkeeping only.  All likelihood
+// launch.cpp, host_path.cpp, align_host.cpp (the haplotype alignment, self-contained), pooled_em_capi.cpp (the pooled EM's device entries;
+// pooled_em_host.cpp, its CPU evaluation, includes no HIP header and not this file); each says in its first lines what it holds.  Host work is O(bases) bookkeeping only.  All likelihood
 // arithmetic happens in the kernels; there is no CPU path for it in this library.
 #ifndef DD_CAPI_INTERNAL_H
 #define DD_CAPI_INTERNAL_H

@@ -203,6 +203,35 @@ class DeviceBatch:
         if rc != 0:
             raise RuntimeError("dd_cigars_device rc=%d: %s" % (rc, capi.last_error()))
 
+    def pooled_em(self, slots, a0=0.001, tol=1e-4, stream=None):
+        """The pooled analysis' EM loop (dd_pooled_em_device) on the `ll` of the last launch() / launch_faster(), resident in HBM (same
+        stream, behind it).  slots: pooled.pack_slots(...).  Asynchronous; returns the device tensors dict(loglik, freqs, iters, ediff),
+        which pooled_em_results() copies back."""
+        lib = capi.load()
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        nh = np.diff(self.pb.a["win_hap_off"])
+        n, f = len(slots["slot_window"]), int(slots["slot_off"][-1])
+        t_in = {k: _to_dev(slots[k], self.device) for k in ("slot_window", "slot_off", "compat")}
+        out = {"loglik": torch.zeros(max(n, 1), dtype=torch.float64, device=self.device),
+               "freqs": torch.zeros(max(f, 1), dtype=torch.float64, device=self.device),
+               "iters": torch.zeros(max(n, 1), dtype=torch.int32, device=self.device),
+               "ediff": torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)}
+        s = capi.dd_pooled_slots(n, *[t_in[k].data_ptr() for k in ("slot_window", "slot_off", "compat")])
+        r = capi.dd_pooled_result(*[out[k].data_ptr() for k in capi.POOLED_RESULT_FIELDS])
+        rc = lib.dd_pooled_em_device(C.byref(self.db), C.c_void_p(self.out["ll"].data_ptr()), C.byref(s), int(nh.max()) if len(nh) else 0,
+                                     a0, tol, C.byref(r), C.c_void_p(stream.cuda_stream))
+        if rc != 0:
+            raise RuntimeError("dd_pooled_em_device rc=%d: %s" % (rc, capi.last_error()))
+        self._pooled = (t_in, out, n, f)       # the launch reads and writes these: keep them alive
+        return out
+
+    def pooled_em_results(self):
+        """Synchronise and copy back the outputs of the last pooled_em(): dict(loglik, freqs, iters, ediff) as pooled.em returns them."""
+        torch.cuda.synchronize(self.device)
+        _, out, n, f = self._pooled
+        return {k: out[k][:(f if k == "freqs" else n)].cpu().numpy() for k in capi.POOLED_RESULT_FIELDS}
+
     def results(self):
         """Host copies (numpy) of the outputs, trimmed to their logical lengths."""
         torch.cuda.synchronize(self.device)

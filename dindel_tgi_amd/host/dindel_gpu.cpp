@@ -66,6 +66,11 @@
 //                     stops the run before any window is prepared.
 //   [--vcf F [--sampleID ID]]  after the loop PREFIX.glf.txt is converted to the VCF F as dindel_glf2vcf does with a list naming that one
 //                     file (glf_to_vcf.hpp; python/mergeOutputDiploid.py:240-317); needs --ref
+//   [--doPooled [--bayesa0 X] [--bayesType all|singlevariant|priorpersite]]  the pooled analysis (estimateHaplotypeFrequenciesBayesEM,
+//                     DInDel.cpp:411-470, :2103-2930; host/pooled_em.hpp): per window one line per (candidate variant, pool).  Alone it writes
+//                     only those lines; with --doDiploid both, the pooled lines of a window first; the likelihoods are computed once.  The
+//                     compute stage builds the windows' active sets once a batch's results are back and runs all their EM slots in one launch
+//                     (dd_pooled_em).  Defaults 0.001 and singlevariant.  --outputRealignedBAM needs --doDiploid beside it.
 //   [--timing]        one "timing:" line on stdout with the busy time of each stage
 //   [--prepareOnly]   stop after the prepare stage (no likelihoods, no calls: profiling the read selection on a GPU-less host); with --ref
 //                     in front of the haplotype stage, which needs the device
@@ -78,6 +83,7 @@
 //   [--mergeBatches N] batches already waiting when an engine becomes free ride in its launch, up to N (default 4; 2 when the per-base alignments come back)
 //   [--computeAhead N] prepared batches that may wait for the GPU ahead of the next one to leave (default max(computeThreads + 1, prepareThreads))
 //   tests and diagnostics only:
+//   [--hostEM]        --doPooled: the EM slots run through dd_pooled_em_host on the CPU instead of on the device (the same bits)
 //   [--noLookBack]    several pools: every batch starts with an empty read buffer (no replay of the windows in front of it)
 //   [--injectLateSkip I,J,...]  the reduce step of these windows throws "hapSize error." (a late skip, also under --prepareOnly)
 //   [--lateSkipsKnown] the prepare stage is told of the injected late skips in advance and resets its buffers behind them
@@ -99,6 +105,7 @@
 #include "glf_output.hpp"
 #include "glf_to_vcf.hpp"
 #include "haplotypes.hpp"
+#include "pooled_em.hpp"
 #include "realigned_bam.hpp"
 #include "window_io.hpp"
 
@@ -125,6 +132,7 @@ struct WindowTask {
         return J;
     }
 };
+struct PooledJob { PooledWindow win; PooledPlan plan; };
 struct Batch {
     long seq;                            // position in the file: batches are computed and written in this order
     // A finished batch goes back to the reader and is filled again: its windows' read vectors (one string and one vector of
@@ -132,6 +140,7 @@ struct Batch {
     std::vector<WindowTask> tasks;
     std::vector<WindowJob> jobs;
     std::vector<size_t> jobOf;
+    std::vector<PooledJob> pooled;       // --doPooled: per job, the window's active sets and what their EM slots returned (made by the compute stage)
     std::vector<int> toRelease;          // windows of the batch's previous use whose parsed haplotypes are no longer needed
     // several BAM pools: the windows in front of the batch (same chromosome, file order) whose read selection is replayed first
     struct Before { std::string tid; uint32_t leftPos, rightPos; int index; };
@@ -158,6 +167,8 @@ struct Options {
     std::vector<int> devices;            // --devices 0,1,...: the engines are dealt out over these GPUs (batches are independent: no exchange between devices)
     bool faster, oneBased, prepareOnly, quiet, timing, longWindows, longWindowsFaster, noLookBack, lateSkipsKnown, windowByWindow;
     bool realignedBAM, deviceCigars;
+    bool doPooled, doDiploid, hostEM;    // --doPooled: the pooled lines; the diploid lines too with --doDiploid, or when --doPooled is not given
+    PooledParameters pool;               // --bayesa0, --bayesType
     bool keepAlignments;                 // the per-base alignments come back from the device (--faster; --outputRealignedBAM without --deviceCigars)
     std::set<int> injectedLateSkips;
     bool discover;                       // --discover: the discovery stage writes varFile (= disc.windowsFile()) before the loop starts
@@ -192,6 +203,8 @@ const char *const kHelp =
     "            [--hostConvert]  the variants of every alignment are made on the host from its slice instead of by the variants kernel\n"
     "            --hapFile F      the haplotypes come from a file instead (W / H / V / A records); with both, --hapFile wins and these have no effect\n"
     "  model:    [--faster] [--libFile F] [--filterHaplotypes] [--outputRealignedBAM] [--varFileIsOneBased]\n"
+    "            [--doPooled]     the pooled analysis: one line per (candidate variant, pool) and window; alone it writes only those lines, with\n"
+    "                             --doDiploid both (pooled first)   [--bayesa0 X] Dirichlet parameter (0.001)   [--bayesType all|singlevariant|priorpersite]\n"
     "            [--deviceCigars]  with --outputRealignedBAM: compute the realigned reads' CIGARs on the device and bring them back instead of the\n"
     "                             per-base alignments (same files); [--cigarOpsCap N] operations kept per read (default 8), reads with more\n"
     "                             are redone on the host, which recomputes their whole window with alignments once (one window at a time:\n"
@@ -207,7 +220,7 @@ const char *const kHelp =
     "  files:    --varFile: the reference's window file; --hapFile: W / H / V / A records (host/window_io.hpp)\n";
 // the options without a value; any other --NAME takes the next argument as its value, whatever its name
 const char *const kFlags[] = {"varFileIsOneBased", "faster", "filterHaplotypes", "quiet", "doDiploid", "timing", "outputRealignedBAM", "prepareOnly", "noLookBack",
-                              "lateSkipsKnown", "windowByWindow", "longWindows", "longWindowsFaster", "deviceCigars", "changeINStoN", "hostDistribution", "hostConvert", "discover", "useLibraries", "vcfCandidatesOnly"};
+                              "lateSkipsKnown", "windowByWindow", "doPooled", "hostEM", "longWindows", "longWindowsFaster", "deviceCigars", "changeINStoN", "hostDistribution", "hostConvert", "discover", "useLibraries", "vcfCandidatesOnly"};
 
 std::vector<int> commaInts(const std::string &list)      // "3,5,,8" -> 3 5 8
 {
@@ -294,6 +307,15 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     o.noLookBack = has("noLookBack"); o.lateSkipsKnown = has("lateSkipsKnown"); o.windowByWindow = has("windowByWindow");
     o.realignedBAM = has("outputRealignedBAM") && !o.faster;                      // `params.outputRealignedBAM && params.slower`, :589
     o.deviceCigars = o.realignedBAM && has("deviceCigars");                       // modifies --outputRealignedBAM only
+    o.doPooled = has("doPooled"); o.doDiploid = has("doDiploid") || !o.doPooled; o.hostEM = has("hostEM");
+    o.pool.a0 = num("bayesa0", o.pool.a0);
+    if (has("bayesType")) o.pool.bayesType = opt["bayesType"];
+    if (o.doPooled && !knownBayesType(o.pool.bayesType)) { std::cerr << "Unknown EM option" << std::endl; return false; }          // DInDel.cpp:2287-2288
+    if (o.doPooled && !(o.pool.a0 > 0.0)) { std::cerr << "--bayesa0 must be positive\n"; exitCode = 2; return false; }
+    if (o.doPooled && !o.doDiploid && has("outputRealignedBAM")) {
+        std::cerr << "--doPooled --outputRealignedBAM needs --doDiploid: the pooled analysis' own choice of the haplotype to realign to (DInDel.cpp:498-520) is not built\n";
+        return false;
+    }
     o.keepAlignments = o.faster || (o.realignedBAM && !o.deviceCigars);           // (the --faster model's indel count, DInDel.cpp:3529, needs hpos)
     o.cigarOpsCap = std::max(1, int(num("cigarOpsCap", 8)));
     ObservationModelParameters &obs = o.obs;
@@ -362,7 +384,8 @@ private:
     void buildHaplotypes(const std::vector<WindowTask *> &tasks, IndexedFasta &fasta, int device);
     void prepareWorker(int pt);
     void computeWorker(int ct);
-    void reduceWindow(WindowTask &T, const WindowJob *J);
+    void reduceWindow(WindowTask &T, const WindowJob *J, PooledJob *P = NULL);
+    void pooledStage(std::vector<BatchPtr> &group, int device);
     void reduceBatch(Batch &B);
     void rePrepare(WindowTask &T);
     void writeBatch(Batch &B);
@@ -408,9 +431,9 @@ private:
 
     // ---- what the summary and --timing print.  Per-thread slots are written by their thread and summed after the joins. ----
     struct Counters {
-        Counters(size_t np, size_t nc) : prepareOf(np, 0.0), computeOf(nc, 0.0), packOf(nc, 0.0), deviceOf(nc, 0.0), unpackOf(nc, 0.0), readyAt(nc, 0.0),
+        Counters(size_t np, size_t nc) : prepareOf(np, 0.0), computeOf(nc, 0.0), pooledOf(nc, 0.0), packOf(nc, 0.0), deviceOf(nc, 0.0), unpackOf(nc, 0.0), readyAt(nc, 0.0),
             reduce(0.0), reduceWork(0.0), launches(0), cigarFallbacks(0), hposBytes(0), cigarBytes(0), fallbackHposBytes(0), windows(0), skipped(0), rePrepared(0) {}
-        std::vector<double> prepareOf, computeOf, packOf, deviceOf, unpackOf;
+        std::vector<double> prepareOf, computeOf, pooledOf, packOf, deviceOf, unpackOf;
         std::vector<double> readyAt;           // when each engine had its device context, arena and streams
         double reduce;                         // the writer's busy time
         std::mutex reduceWork_m; double reduceWork;     // reduceWindow time summed over the writer and its helpers
@@ -713,6 +736,11 @@ void WindowLoop::computeWorker(int ct)
                         for (size_t j = 0; j < group[g]->jobs.size(); j++) group[g]->jobs[j] = std::move(merged[at++]);
                     merged.clear();
                 }
+                if (opt.doPooled) {
+                    const TimePoint p0 = now();
+                    pooledStage(group, opt.devices[size_t(ct) % opt.devices.size()]);
+                    n.pooledOf[size_t(ct)] += seconds_since(p0);
+                }
                 n.packOf[size_t(ct)] += engine.lastPackSeconds; n.deviceOf[size_t(ct)] += engine.lastDeviceSeconds; n.unpackOf[size_t(ct)] += engine.lastUnpackSeconds;
                 n.hposBytes += (long long)engine.lastHposBytes; n.cigarBytes += (long long)engine.lastCigarBytes;
                 n.launches++;
@@ -729,9 +757,33 @@ void WindowLoop::computeWorker(int ct)
     });
 }
 
+// ---- --doPooled, compute stage: the active sets and masks of every computed window of the group, then all their EM slots in one launch
+//      (--hostEM: on the CPU).  The ll go up again from the result block: the engine's own copy on the device belongs to its call. ----
+void WindowLoop::pooledStage(std::vector<BatchPtr> &group, int device)
+{
+    std::vector<PooledPlan *> plans;
+    std::vector<const PooledWindow *> wins;
+    for (size_t g = 0; g < group.size(); g++) {
+        Batch &B = *group[g];
+        B.pooled.assign(B.jobs.size(), PooledJob());
+        for (size_t i = 0; i < B.tasks.size(); i++) {
+            if (B.jobOf[i] == size_t(-1)) continue;
+            const WindowJob &J = B.jobs[B.jobOf[i]];
+            const WindowTask &T = B.tasks[i];
+            if (!J.error.empty() || !J.result.valid() || opt.injectedLateSkips.count(T.index)) continue;
+            PooledJob &P = B.pooled[B.jobOf[i]];
+            pooledWindowOf(*T.haps, T.reads, J.result, opt.dip, P.win);
+            pooledPlan(*T.haps, P.win, T.leftPos, T.candidates, opt.dip, opt.pool.bayesType, P.plan);
+            plans.push_back(&P.plan);
+            wins.push_back(&P.win);
+        }
+    }
+    if (!plans.empty()) pooledRunEM(plans, wins, opt.pool, opt.hostEM, device, std::max(1, opt.packThreads));
+}
+
 // ---- one window's lines: diploidGLF (+ the realigned BAM), or the skipped-window line (the reduce helpers; the writer's
 //      re-preparation behind a late skip) ----
-void WindowLoop::reduceWindow(WindowTask &T, const WindowJob *J)
+void WindowLoop::reduceWindow(WindowTask &T, const WindowJob *J, PooledJob *P)
 {
     std::ostringstream os;
     OutputData local = glfData;
@@ -743,7 +795,18 @@ void WindowLoop::reduceWindow(WindowTask &T, const WindowJob *J)
                 if (!J->error.empty()) throw std::string(J->error);
                 // like the reference, diploidGLF writes its lines as it goes: if it throws half-way ("genotyping
                 // error"), the lines already written stay and the skipped-window line follows them
-                diploidGLF(*T.haps, T.reads, J->result, T.pos, T.leftPos, T.rightPos, local, T.index, T.tid, T.candidates, opt.dip, "dip");
+                if (opt.doPooled) {                                          // DInDel.cpp:411-470: in front of the diploid analysis
+                    PooledJob own;
+                    if (!P || !P->plan.ready) {                              // a window the writer re-did: its one launch here
+                        pooledWindowOf(*T.haps, T.reads, J->result, opt.dip, own.win);
+                        pooledPlan(*T.haps, own.win, T.leftPos, T.candidates, opt.dip, opt.pool.bayesType, own.plan);
+                        pooledRunEM(std::vector<PooledPlan *>(1, &own.plan), std::vector<const PooledWindow *>(1, &own.win), opt.pool, opt.hostEM, opt.devices[0], 1);
+                        P = &own;
+                    }
+                    pooledLines(*T.haps, T.reads, P->win, P->plan, T.pos, T.leftPos, T.rightPos, local, T.index, T.tid, T.candidates, opt.dip, opt.pool.bayesType,
+                                opt.bamPaths.size());
+                }
+                if (opt.doDiploid) diploidGLF(*T.haps, T.reads, J->result, T.pos, T.leftPos, T.rightPos, local, T.index, T.tid, T.candidates, opt.dip, "dip");
                 if (opt.realignedBAM) {                                      // DInDel.cpp:589-620
                     const std::pair<int, int> best = maxLikelihoodPair(*T.haps, T.reads, J->result, int(T.leftPos), T.candidates, opt.dip);
                     std::vector<CIGAR> cigars;
@@ -778,7 +841,8 @@ void WindowLoop::reduceBatch(Batch &B)
             for (;;) {
                 const size_t i = next.fetch_add(1);
                 if (i >= B.tasks.size()) break;
-                reduceWindow(B.tasks[i], (B.tasks[i].computes() && !opt.prepareOnly) ? &B.jobs[B.jobOf[i]] : NULL);
+                const bool computed = B.tasks[i].computes() && !opt.prepareOnly;
+                reduceWindow(B.tasks[i], computed ? &B.jobs[B.jobOf[i]] : NULL, computed && B.jobOf[i] < B.pooled.size() ? &B.pooled[B.jobOf[i]] : NULL);
             }
         } catch (std::exception &e) { next.store(B.tasks.size()); fail(std::string("reduce: ") + e.what()); }
         catch (...) { next.store(B.tasks.size()); fail("reduce: unknown exception"); }
@@ -864,6 +928,7 @@ void WindowLoop::writer()
             for (size_t i = 0; i < b->tasks.size(); i++) if (b->tasks[i].haps) { if (fixture) b->toRelease.push_back(b->tasks[i].index); b->tasks[i].haps = NULL; }
             b->jobs.clear();                                              // drops the batch's views: its result block can be reused
             b->jobOf.clear();
+            b->pooled.clear();
             recycled.give(b);
             n.reduce += seconds_since(t0);
         }
@@ -983,6 +1048,7 @@ void WindowLoop::report()                                 // --timing: one line;
     if (from + 1 < progress.size() && progress.back().first > progress[from].first)
         std::cout << " steady_windows_per_s=" << double(progress.back().second - progress[from].second) / (progress.back().first - progress[from].first);
     std::cout << " launches=" << n.launches.load();
+    if (opt.doPooled) std::cout << " pooled=" << sum(n.pooledOf);       // of compute: the windows' sets and masks and their EM slots
     // bytes of per-base alignments / of CIGAR arrays the window loop's engines brought back; --deviceCigars: reads redone on the host
     // and the alignment bytes those windows' recomputation brought back
     std::cout << " hpos_bytes=" << n.hposBytes.load() << " cigar_bytes=" << n.cigarBytes.load() << " cigar_host_fallbacks=" << n.cigarFallbacks.load()

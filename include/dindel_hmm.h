@@ -681,6 +681,44 @@ int dd_map_pairs(const dd_batch *b, const double *ll_host, const double *prior_h
                  const int32_t *ncand_host, double *pair_sum_out, double *posterior_out, int32_t *pairs_out,
                  double *vals_out, int device);
 
+/* ---- pooled analysis: the EM loop of estimateHaplotypeFrequenciesBayesEM (reference DInDel.cpp:2412-2543) ---------- */
+/* A slot is one (window, set of active variants): the loop runs once per slot over the window's `ll` (rl[r,h] = ll[pair(w,h,r)]) with the
+ * haplotypes the set is compatible with (:2393-2408, the caller's).  The arithmetic is csrc/pooled_math.h on the host and on the device:
+ * fp64 operations and series of its own, one order of every sum (read r in partial r mod 64, partials combined pairwise from 32 down),
+ * so every output of the three entries below is the same in every bit.  It is not the reference's libm / Boost arithmetic; DESIGN 20
+ * gives its error against exact arithmetic.
+ *   slot_window [n_slots]          window of the slot
+ *   slot_off    [n_slots + 1]      starts at 0; slot s owns compat / freqs [slot_off[s], slot_off[s + 1]), as many as its window has haplotypes
+ *   compat                         one byte per (slot, haplotype), 0 = incompatible (lpi = pi = -100)
+ * Outputs per slot: loglik (the last iteration's), freqs (exp(pi) normalised), iters (iterations run, at most 27; -1 on the device when
+ * the slot's tables do not fit its window or max_haps), ediff (the last |eOld - eNew|).  Raw addresses: host or device arrays. */
+typedef struct dd_pooled_slots {
+    int64_t n_slots;
+    const int32_t *slot_window;
+    const int64_t *slot_off;
+    const uint8_t *compat;
+} dd_pooled_slots;
+typedef struct dd_pooled_result {
+    double *loglik;                   /* [n_slots] */
+    double *freqs;                    /* [slot_off[n_slots]] */
+    int32_t *iters;                   /* [n_slots] */
+    double *ediff;                    /* [n_slots] */
+} dd_pooled_result;
+/* Device pointers, on a stream, behind any likelihood launch; asynchronous, no allocation.  Of the batch it reads n_windows, win_hap_off,
+ * win_read_off and win_pair_off.  max_haps: the most haplotypes a window of the batch has (the launch's LDS is sized from it, 536 bytes
+ * per haplotype; at most DD_POOLED_MAX_HAPS).  a0 > 0: the Dirichlet parameter (--bayesa0); tol: EMtol. */
+#define DD_POOLED_MAX_HAPS 256
+int dd_pooled_em_device(const dd_device_batch *b, const double *ll_dev, const dd_pooled_slots *s_dev, int max_haps, double a0, double tol,
+                        const dd_pooled_result *out_dev, void *stream);
+/* Host pointers: validates, copies, launches, copies back.  DD_ERR_INVALID before any launch; DD_ERR_NO_DEVICE without a GPU. */
+int dd_pooled_em(const dd_batch *b, const double *ll_host, const dd_pooled_slots *s, double a0, double tol, const dd_pooled_result *out,
+                 int device);
+/* The same loop on the CPU, no device needed: slots spread over nthreads host threads (< 1: one). */
+int dd_pooled_em_host(const dd_batch *b, const double *ll_host, const dd_pooled_slots *s, double a0, double tol, const dd_pooled_result *out,
+                      int nthreads);
+/* pooled_math.h's functions over an array (host): fn 0 = exp, 1 = log, 2 = digamma; fn 3 = addLogs over pairs x[2i], x[2i + 1]. */
+int dd_pooled_math_eval(int fn, const double *x, double *y, int64_t n);
+
 /* Launch plan the library would use for the main kernel on a batch with these maxima (no device needed):
  * out = {K positions per lane, D build (6 / 11 / 12), 1 if back-pointers go to HBM scratch else 0, waves per workgroup,
  *        read split of a haplotype, LDS bytes per workgroup, scratch bytes (low 31 bits, in KiB), waves per CU the plan expects,
