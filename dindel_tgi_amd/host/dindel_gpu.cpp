@@ -70,7 +70,14 @@
 //                     DInDel.cpp:411-470, :2103-2930; host/pooled_em.hpp): per window one line per (candidate variant, pool).  Alone it writes
 //                     only those lines; with --doDiploid both, the pooled lines of a window first; the likelihoods are computed once.  The
 //                     compute stage builds the windows' active sets once a batch's results are back and runs all their EM slots in one launch
-//                     (dd_pooled_em).  Defaults 0.001 and singlevariant.  --outputRealignedBAM needs --doDiploid beside it.
+//                     (dd_pooled_em).  Defaults 0.001 and singlevariant.  With --outputRealignedBAM and no --doDiploid a window's file holds every
+//                     read that lies on a haplotype realigned to the FIRST haplotype with the largest likelihood (DInDel.cpp:498-520; a note on
+//                     stderr says so); with --doDiploid beside it the diploid step's file, which has the same name, is the one that stays.
+//   [--pooledVcf F --numSamples N [--pooledGlf G]]  with --doPooled: after the loop PREFIX.glf.txt is converted to the VCF F as dindel_pooled2vcf
+//                     does with a list naming that one file and --numBamFiles = the run's number of BAM files (host/pooled_vcf.hpp;
+//                     python/mergeOutputPooled.py:202-575), then, with --pooledGlf, the per-pool likelihoods of the called sites go to G as
+//                     dindel_pooled2glf writes them, the BAM names being the run's paths
+//                     (python/makeGenotypeLikelihoodFilePooled.py:146-213).  Needs --ref.
 //   [--timing]        one "timing:" line on stdout with the busy time of each stage
 //   [--prepareOnly]   stop after the prepare stage (no likelihoods, no calls: profiling the read selection on a GPU-less host); with --ref
 //                     in front of the haplotype stage, which needs the device
@@ -106,6 +113,8 @@
 #include "glf_to_vcf.hpp"
 #include "haplotypes.hpp"
 #include "pooled_em.hpp"
+#include "pooled_vcf.hpp"
+#include "python_text.hpp"
 #include "realigned_bam.hpp"
 #include "window_io.hpp"
 
@@ -174,6 +183,8 @@ struct Options {
     bool discover;                       // --discover: the discovery stage writes varFile (= disc.windowsFile()) before the loop starts
     DiscoverOptions disc;
     std::string vcfFile, vcfRef, sampleID;   // --vcf F: PREFIX.glf.txt -> F after the loop, with the FASTA of --ref
+    std::string pooledVcfFile, pooledGlfFile;   // --pooledVcf F [--pooledGlf G]: PREFIX.glf.txt -> the pooled calls F (and their per-pool likelihoods G) after the loop
+    PooledVcfOptions pooledVcf;              // ... with --numSamples, the FASTA of --ref and numBamFiles = the run's number of BAM files
 };
 
 const char *const kHelp =
@@ -195,6 +206,9 @@ const char *const kHelp =
     "                             never filter them   [--minQual X] records with QUAL `.` or >= X (default 1)\n"
     "            [--vcfCandidatesOnly]  with --candidateVCF: no pass over the CIGARs of the BAM, the known sites alone\n"
     "  output:   [--vcf F]        after the loop, convert PREFIX.glf.txt to the VCF F (dindel_glf2vcf on that one file); needs --ref   [--sampleID ID]\n"
+    "            [--pooledVcf F --numSamples N]  with --doPooled: after the loop, the pooled lines of PREFIX.glf.txt become the VCF F (dindel_pooled2vcf on that\n"
+    "                             one file, --numBamFiles = the run's number of BAM files); needs --ref   [--pooledGlf G] and the called sites' likelihoods\n"
+    "                             per pool go to G (dindel_pooled2glf)\n"
     "  haplotypes: --ref FASTA (with FASTA.fai)  every window's candidate haplotypes are built in the run from the reads it selected: the block\n"
     "                             tables and the alignment to the reference on the device, one launch each per batch of windows\n"
     "            [--maxHap N]     combinations the blocks are thinned to (default 8)      [--skipMaxHap N]  a window with more haplotypes is passed\n"
@@ -312,9 +326,18 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     if (has("bayesType")) o.pool.bayesType = opt["bayesType"];
     if (o.doPooled && !knownBayesType(o.pool.bayesType)) { std::cerr << "Unknown EM option" << std::endl; return false; }          // DInDel.cpp:2287-2288
     if (o.doPooled && !(o.pool.a0 > 0.0)) { std::cerr << "--bayesa0 must be positive\n"; exitCode = 2; return false; }
-    if (o.doPooled && !o.doDiploid && has("outputRealignedBAM")) {
-        std::cerr << "--doPooled --outputRealignedBAM needs --doDiploid: the pooled analysis' own choice of the haplotype to realign to (DInDel.cpp:498-520) is not built\n";
-        return false;
+    // which of the reference's two realigned-BAM steps writes the files is easy to miss: said once, on stderr, like the reference's own notes
+    if (o.doPooled && !o.doDiploid && o.realignedBAM && !o.quiet)
+        std::cerr << "--doPooled --outputRealignedBAM without --doDiploid: the files are the pooled analysis' own (DInDel.cpp:498-520), every read on a haplotype "
+                     "realigned to the first haplotype with the largest likelihood; with --doDiploid beside it they are the diploid step's\n";
+    if (has("pooledVcf") && !o.doPooled) { std::cerr << "--pooledVcf converts the lines of the pooled analysis: it needs --doPooled\n"; return false; }
+    if (has("pooledVcf") && !has("ref")) { std::cerr << "Please specify --ref: --pooledVcf needs the reference FASTA\n"; return false; }
+    if (has("pooledVcf") && !has("numSamples")) { std::cerr << "Please specify --numSamples: --pooledVcf needs the number of samples in the pools\n"; return false; }
+    if (has("pooledGlf") && !has("pooledVcf")) { std::cerr << "--pooledGlf writes the likelihoods of the sites --pooledVcf calls: it needs --pooledVcf\n"; return false; }
+    if (has("pooledVcf")) {
+        o.pooledVcfFile = opt["pooledVcf"]; o.pooledVcf.outputFile = o.pooledVcfFile; o.pooledVcf.refFile = opt["ref"];
+        if (has("pooledGlf")) o.pooledGlfFile = opt["pooledGlf"];
+        try { o.pooledVcf.numSamples = int(pytext::pyInt(opt["numSamples"])); } catch (const std::string &e) { std::cerr << "--numSamples: " << e << "\n"; return false; }
     }
     o.keepAlignments = o.faster || (o.realignedBAM && !o.deviceCigars);           // (the --faster model's indel count, DInDel.cpp:3529, needs hpos)
     o.cigarOpsCap = std::max(1, int(num("cigarOpsCap", 8)));
@@ -379,6 +402,7 @@ class WindowLoop {
 public:
     explicit WindowLoop(const Options &options);          // set-up: throws std::string
     int run();                                            // the exit code
+    const std::vector<std::string> &bamPaths() const { return opt.bamPaths; }   // the run's BAM files (--bamFile, or the files of --bamFiles)
 private:
     void prepareWindow(ReadFetcher &fetcher, WindowTask &T);
     void buildHaplotypes(const std::vector<WindowTask *> &tasks, IndexedFasta &fasta, int device);
@@ -806,8 +830,18 @@ void WindowLoop::reduceWindow(WindowTask &T, const WindowJob *J, PooledJob *P)
                     pooledLines(*T.haps, T.reads, P->win, P->plan, T.pos, T.leftPos, T.rightPos, local, T.index, T.tid, T.candidates, opt.dip, opt.pool.bayesType,
                                 opt.bamPaths.size());
                 }
+                if (opt.doPooled && !opt.doDiploid && opt.realignedBAM) {    // DInDel.cpp:498-520: the pooled analysis' own file (with --doDiploid its step below overwrites it)
+                    std::vector<CIGAR> cigars;
+                    long fallbacks = 0;
+                    pooledRealignedCigars(*T.haps, T.reads, J->result, int(T.leftPos), cigars, [&]() { return recomputeWithAlignments(T); }, &fallbacks);
+                    n.cigarFallbacks += fallbacks;
+                    std::vector<int> onHap(T.reads.size());
+                    for (size_t r = 0; r < onHap.size(); r++) onHap[r] = J->result.onHap(r);
+                    writeRealignedBAMFile(realignedBAMFileName(opt.outputPrefix, T.index, T.tid, T.leftPos, T.rightPos, opt.rsp.minReadOverlap),
+                                          cigars, T.reads, onHap, headerBam[0]);
+                }
                 if (opt.doDiploid) diploidGLF(*T.haps, T.reads, J->result, T.pos, T.leftPos, T.rightPos, local, T.index, T.tid, T.candidates, opt.dip, "dip");
-                if (opt.realignedBAM) {                                      // DInDel.cpp:589-620
+                if (opt.realignedBAM && opt.doDiploid) {                     // DInDel.cpp:589-620
                     const std::pair<int, int> best = maxLikelihoodPair(*T.haps, T.reads, J->result, int(T.leftPos), T.candidates, opt.dip);
                     std::vector<CIGAR> cigars;
                     long fallbacks = 0;
@@ -1094,9 +1128,18 @@ int main(int argc, char **argv)
         {
             WindowLoop loop(options);
             rc = loop.run();
+            options.bamPaths = loop.bamPaths();
         }
         if (rc == 0 && !options.vcfFile.empty())
             mergeOutputFiles(std::vector<std::string>(1, options.outputPrefix + ".glf.txt"), options.sampleID, options.vcfRef, 10, options.vcfFile, 20);
+        if (rc == 0 && !options.pooledVcfFile.empty()) {                 // dindel_pooled2vcf, then dindel_pooled2glf, on the one file just written
+            const std::vector<std::string> glf(1, options.outputPrefix + ".glf.txt");
+            std::ostringstream notes;                                    // (the scripts' progress lines)
+            options.pooledVcf.numBamFiles = int(options.bamPaths.size());
+            pooledGlfToVcf(glf, options.pooledVcf, std::cerr, options.quiet ? static_cast<std::ostream &>(notes) : std::cout);
+            if (!options.pooledGlfFile.empty())
+                pooledCallsToGlf(glf, options.pooledVcfFile, options.pooledGlfFile, options.bamPaths, std::cerr, options.quiet ? static_cast<std::ostream &>(notes) : std::cout);
+        }
         return rc;
     } catch (std::string &s) {
         std::cerr << "Exception: " << s << std::endl;

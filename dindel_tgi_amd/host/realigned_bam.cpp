@@ -51,11 +51,37 @@ void realignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read>
     }
 }
 
+namespace {
+// The CIGAR of pair (h, r) from the device's result block; a read over the batch's cap (DD_CIGAR_OVERFLOW, or a pair the device did not
+// compute) on the host, from the window's alignments, which `full` keeps once they were asked for.
+CIGAR deviceCigarOf(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, size_t h, size_t r, int refSeqPos,
+                    WindowLikelihoods &full, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks)
+{
+    static const char *const thrown[] = {"", "Haplotype has not been aligned!", "Error(1)!", "Error(2)!", "Error(3)!", "Error(4)!", "How is this possible? (1)"};
+    const int st = liks.cigarStatus(h, r);
+    if (st >= DD_CIGAR_HAP_NOT_ALIGNED && st <= DD_CIGAR_IMPOSSIBLE) throw std::string(thrown[st]);
+    if (st == DD_CIGAR_OK) {
+        const uint32_t *ops = liks.cigarOps(h, r);
+        const int n = liks.cigarNumOps(h, r), off = liks.cigarRefOff(h, r);
+        CIGAR c;
+        for (int i = 0; i < n; i++) c.push_back(CIGAR::CIGOp(int(ops[i] & 15u), int(ops[i] >> 4)));
+        c.refPos = off < 0 ? -1 : refSeqPos + off;                                           // no aligned base: refPos stays -1
+        return c;
+    }
+    if (!full.valid()) {
+        if (!withAlignments) throw std::string("realignedCigars: a read needs the host getCIGAR and no alignments are at hand");
+        full = withAlignments();
+    }
+    const CIGAR c = getCIGAR(haps[h].refHpos, haps[h].size(), full.get(h, r), reads[r].size(), refSeqPos);
+    if (hostFallbacks) ++*hostFallbacks;
+    return c;
+}
+}
+
 void realignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, std::pair<int, int> pair,
                      int refSeqPos, std::vector<CIGAR> &cigars, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks)
 {
     if (!liks.hasDeviceCigars()) { realignedCigars(haps, reads, liks, pair, refSeqPos, cigars); return; }
-    static const char *const thrown[] = {"", "Haplotype has not been aligned!", "Error(1)!", "Error(2)!", "Error(3)!", "Error(4)!", "How is this possible? (1)"};
     cigars.assign(reads.size(), CIGAR());
     const size_t h1 = size_t(pair.first), h2 = size_t(pair.second);
     WindowLikelihoods full;
@@ -66,24 +92,40 @@ void realignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read>
         } else {
             if (liks.ll(h1, r) > liks.ll(h2, r)) hmax = h1; else hmax = h2;
         }
-        const int st = liks.cigarStatus(hmax, r);
-        if (st >= DD_CIGAR_HAP_NOT_ALIGNED && st <= DD_CIGAR_IMPOSSIBLE) throw std::string(thrown[st]);
-        if (st == DD_CIGAR_OK) {
-            const uint32_t *ops = liks.cigarOps(hmax, r);
-            const int n = liks.cigarNumOps(hmax, r), off = liks.cigarRefOff(hmax, r);
-            CIGAR &c = cigars[r];
-            for (int i = 0; i < n; i++) c.push_back(CIGAR::CIGOp(int(ops[i] & 15u), int(ops[i] >> 4)));
-            c.refPos = off < 0 ? -1 : refSeqPos + off;                                       // no aligned base: refPos stays -1
-            continue;
-        }
-        // DD_CIGAR_OVERFLOW (or a pair the device did not compute): this read on the host, from the window's alignments
-        if (!full.valid()) {
-            if (!withAlignments) throw std::string("realignedCigars: a read needs the host getCIGAR and no alignments are at hand");
-            full = withAlignments();
-        }
-        cigars[r] = getCIGAR(haps[hmax].refHpos, haps[hmax].size(), full.get(hmax, r), reads[r].size(), refSeqPos);
-        if (hostFallbacks) ++*hostFallbacks;
+        cigars[r] = deviceCigarOf(haps, reads, liks, hmax, r, refSeqPos, full, withAlignments, hostFallbacks);
     }
+}
+
+void pooledRealignedCigars(size_t numHaps, size_t numReads, const std::function<double(size_t, size_t)> &ll, const std::function<bool(size_t)> &onHap,
+                           const std::function<CIGAR(size_t, size_t)> &cigarOf, std::vector<CIGAR> &cigars)
+{
+    cigars.assign(numReads, CIGAR());                                                        // :502
+    for (size_t r = 0; r < numReads; r++) {
+        if (!onHap(r)) continue;                                                             // :504
+        double llmax = -HUGE_VAL;                                                            // :505-510
+        size_t hidx = 0;
+        for (size_t h = 0; h < numHaps; h++) {
+            const double l = ll(h, r);
+            if (l > llmax) { llmax = l; hidx = h; }
+        }
+        cigars[r] = cigarOf(hidx, r);                                                        // :511
+    }
+}
+
+void pooledRealignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, int refSeqPos,
+                           std::vector<CIGAR> &cigars)
+{
+    pooledRealignedCigars(haps.size(), reads.size(), [&](size_t h, size_t r) { return liks.ll(h, r); }, [&](size_t r) { return liks.onHap(r) != 0; },
+                          [&](size_t h, size_t r) { return getCIGAR(haps[h].refHpos, haps[h].size(), liks.get(h, r), reads[r].size(), refSeqPos); }, cigars);
+}
+
+void pooledRealignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, int refSeqPos,
+                           std::vector<CIGAR> &cigars, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks)
+{
+    if (!liks.hasDeviceCigars()) { pooledRealignedCigars(haps, reads, liks, refSeqPos, cigars); return; }
+    WindowLikelihoods full;
+    pooledRealignedCigars(haps.size(), reads.size(), [&](size_t h, size_t r) { return liks.ll(h, r); }, [&](size_t r) { return liks.onHap(r) != 0; },
+                          [&](size_t h, size_t r) { return deviceCigarOf(haps, reads, liks, h, r, refSeqPos, full, withAlignments, hostFallbacks); }, cigars);
 }
 
 std::string realignedBAMFileName(const std::string &prefix, int index, const std::string &tid, uint32_t leftPos, uint32_t rightPos, int minReadOverlap)

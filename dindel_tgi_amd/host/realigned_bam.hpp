@@ -34,6 +34,19 @@ void realignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read>
 void realignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, std::pair<int, int> pair,
                      int refSeqPos, std::vector<CIGAR> &cigars, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks);
 
+// The pooled analysis' own choice (DInDel.cpp:498-520): a read placed on a haplotype (onHap) is realigned to the FIRST haplotype with the
+// largest ll — strict `>` from -HUGE_VAL, so index 0 when none compares greater (all -inf, NaN), DInDel.cpp:503-512 — and gets getCIGAR's
+// CIGAR against it; a read without onHap keeps an empty CIGAR, and writeRealignedBAMFile copies its record.  Throws getCIGAR's strings.
+void pooledRealignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, int refSeqPos,
+                           std::vector<CIGAR> &cigars);
+// The same with device CIGARs, exactly as the second realignedCigars above uses them: the same status-to-throw mapping, a read over the
+// batch's cap redone on the host from `withAlignments()` and counted in *hostFallbacks.  Without device CIGARs in `liks`: the function above.
+void pooledRealignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, int refSeqPos,
+                           std::vector<CIGAR> &cigars, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks);
+// What both are made of: the choice per read from ll(h, r) and onHap(r), the CIGAR of the chosen pair from cigarOf(h, r).
+void pooledRealignedCigars(size_t numHaps, size_t numReads, const std::function<double(size_t, size_t)> &ll, const std::function<bool(size_t)> &onHap,
+                           const std::function<CIGAR(size_t, size_t)> &cigarOf, std::vector<CIGAR> &cigars);
+
 // The name the reference gives the window's file: PREFIX.ra.INDEX_TID_(leftPos+minReadOverlap)_(rightPos-minReadOverlap).bam (:614-618)
 std::string realignedBAMFileName(const std::string &prefix, int index, const std::string &tid, uint32_t leftPos, uint32_t rightPos, int minReadOverlap);
 

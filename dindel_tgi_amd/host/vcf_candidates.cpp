@@ -1,6 +1,7 @@
 // vcf_candidates.cpp — see vcf_candidates.hpp.  Line references are to the reference's python/convertVCFToDindel.py and its
 // python/utils/VCFFile.py, python/utils/Variant.py and python/utils/Fasta.py.
 #include "vcf_candidates.hpp"
+#include "python_text.hpp"
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
@@ -15,10 +16,10 @@
 
 namespace dindel {
 
-namespace {
+namespace pytext {
 
 // where the script dies: a NameError's own text, any other exception as `Type: text`
-void raise(const char *type, const std::string &text)
+void pyRaise(const char *type, const std::string &text)
 {
     if (!strcmp(type, "NameError")) throw text;
     throw std::string(type).append(": ").append(text);
@@ -69,14 +70,15 @@ long pyInt(const std::string &s)
     size_t i = (!t.empty() && (t[0] == '-' || t[0] == '+')) ? 1 : 0;
     bool ok = i < t.size();
     for (size_t k = i; k < t.size() && ok; k++) ok = t[k] >= '0' && t[k] <= '9';
-    if (!ok) raise("ValueError", std::string("invalid literal for int() with base 10: '").append(s).append("'"));
+    if (!ok) pyRaise("ValueError", std::string("invalid literal for int() with base 10: '").append(s).append("'"));
     errno = 0;
     const long v = strtol(t.c_str(), NULL, 10);
-    if (errno != 0) raise("OverflowError", std::string("integer too large for this tool: '").append(s).append("'"));
+    if (errno != 0) pyRaise("OverflowError", std::string("integer too large for this tool: '").append(s).append("'"));
     return v;
 }
 
-} // namespace
+} // namespace pytext
+using namespace pytext;
 
 double pythonFloat(const std::string &s)
 {
@@ -85,7 +87,7 @@ double pythonFloat(const std::string &s)
     for (size_t k = 0; k < t.size() && ok; k++) ok = t[k] != 'x' && t[k] != 'X' && t[k] != '(' && !strchr(kBlanks, t[k]);
     char *end = NULL;
     const double v = ok ? strtod(t.c_str(), &end) : 0.0;
-    if (!ok || end == t.c_str() || *end != '\0') raise("ValueError", std::string("could not convert string to float: ").append(s));
+    if (!ok || end == t.c_str() || *end != '\0') pyRaise("ValueError", std::string("could not convert string to float: ").append(s));
     return v;
 }
 
@@ -101,13 +103,16 @@ std::string upperNoSpaces(const std::string &s)               // string.upper(s.
     return u;
 }
 
+} // namespace
+
+namespace pytext {
 std::string ioError(const std::string &path) { return std::string("[Errno ") + std::to_string(errno) + "] " + strerror(errno) + ": '" + path + "'"; }
 
 // the whole file as bytes; a name whose extension is .gz (python/utils/VCFFile.py:95-98) through zlib, member after member
 std::string readBytes(const std::string &path)
 {
     FILE *f = fopen(path.c_str(), "rb");
-    if (!f) raise("IOError", ioError(path));
+    if (!f) pyRaise("IOError", ioError(path));
     std::string raw;
     char buf[1 << 16];
     size_t n;
@@ -122,10 +127,10 @@ std::string readBytes(const std::string &path)
     std::string text;
     z_stream z;
     memset(&z, 0, sizeof z);
-    if (inflateInit2(&z, 15 + 16) != Z_OK) raise("IOError", "zlib: inflateInit2 failed");
+    if (inflateInit2(&z, 15 + 16) != Z_OK) pyRaise("IOError", "zlib: inflateInit2 failed");
     z.next_in = reinterpret_cast<Bytef *>(const_cast<char *>(raw.data()));
     z.avail_in = uInt(raw.size());
-    if (raw.size() > size_t(0x7fffffff)) { inflateEnd(&z); raise("IOError", "compressed VCF larger than 2 GiB"); }
+    if (raw.size() > size_t(0x7fffffff)) { inflateEnd(&z); pyRaise("IOError", "compressed VCF larger than 2 GiB"); }
     bool ended = raw.empty();                                 // (no member at all: an empty file)
     while (z.avail_in > 0) {
         z.next_out = reinterpret_cast<Bytef *>(buf);
@@ -135,25 +140,28 @@ std::string readBytes(const std::string &path)
         ended = rc == Z_STREAM_END;
         if (ended) {                             // the next member, if any (zero padding behind the last one is allowed, as in gzip.py)
             while (z.avail_in > 0 && *z.next_in == 0) { z.next_in++; z.avail_in--; }
-            if (z.avail_in > 0 && inflateReset(&z) != Z_OK) { inflateEnd(&z); raise("IOError", "zlib: inflateReset failed"); }
+            if (z.avail_in > 0 && inflateReset(&z) != Z_OK) { inflateEnd(&z); pyRaise("IOError", "zlib: inflateReset failed"); }
         } else if (rc != Z_OK) {
             inflateEnd(&z);
-            raise("IOError", rc == Z_BUF_ERROR ? "Compressed file ended before the end-of-stream marker was reached" : "Not a gzipped file");
+            pyRaise("IOError", rc == Z_BUF_ERROR ? "Compressed file ended before the end-of-stream marker was reached" : "Not a gzipped file");
         }
     }
     inflateEnd(&z);
-    if (!ended) raise("IOError", "Compressed file ended before the end-of-stream marker was reached");
+    if (!ended) pyRaise("IOError", "Compressed file ended before the end-of-stream marker was reached");
     return text;
 }
+} // namespace pytext
+
+namespace {
 
 // class FastaIndex and Fasta.get, python/utils/Fasta.py:11-51
 class ScriptFasta {
 public:
     explicit ScriptFasta(const std::string &fname) : fa(fopen(fname.c_str(), "rb"))
     {
-        if (!fa) raise("IOError", ioError(fname));
+        if (!fa) pyRaise("IOError", ioError(fname));
         std::ifstream fai((fname + ".fai").c_str());
-        if (!fai.is_open()) { const std::string e = ioError(fname + ".fai"); fclose(fa); fa = NULL; raise("IOError", e); }
+        if (!fai.is_open()) { const std::string e = ioError(fname + ".fai"); fclose(fa); fa = NULL; pyRaise("IOError", e); }
         std::string line;
         try {
             while (std::getline(fai, line)) {
@@ -172,14 +180,14 @@ public:
         std::map<std::string, Target>::const_iterator it = ft.find(tid);
         if (it == ft.end()) {
             out << "KeyError:  " << tid << "\n";
-            raise("NameError", "KeyError");
+            pyRaise("NameError", "KeyError");
         }
         const Target &idx = it->second;
-        if (idx.blen == 0) raise("ZeroDivisionError", "integer division or modulo by zero");
+        if (idx.blen == 0) pyRaise("ZeroDivisionError", "integer division or modulo by zero");
         const long fpos = idx.offset + floorDiv(pos, idx.blen) * idx.llen + floorMod(pos, idx.blen);
-        if (fpos < 0) raise("IOError", "[Errno 22] Invalid argument");
+        if (fpos < 0) pyRaise("IOError", "[Errno 22] Invalid argument");
         std::string seq;
-        if (fseek(fa, fpos, SEEK_SET) != 0) raise("IOError", "[Errno 22] Invalid argument");
+        if (fseek(fa, fpos, SEEK_SET) != 0) pyRaise("IOError", "[Errno 22] Invalid argument");
         for (size_t numread = 0; numread < len;) {
             const int c = getc(fa);
             if (c == EOF) break;                              // every further read gives '' and counts: the letters come out short
@@ -204,18 +212,18 @@ public:
             const std::string line = readline();
             if (line.compare(0, 2, "##") == 0) {
                 if (line.find("fileformat") != std::string::npos) {                                       // :103-112
-                    if (line.find("VCF") == std::string::npos && line.find("vcf") == std::string::npos) raise("NameError", "Cannot determine VCF version");
+                    if (line.find("VCF") == std::string::npos && line.find("vcf") == std::string::npos) pyRaise("NameError", "Cannot determine VCF version");
                     if (line.find("v3") != std::string::npos) version = 3;
                     else if (line.find("v4") != std::string::npos || line.find("VCF4") != std::string::npos) version = 4;
-                    else raise("NameError", "Cannot determine VCF version");
+                    else pyRaise("NameError", "Cannot determine VCF version");
                 }
                 if (line.compare(0, 7, "##INFO=") == 0) { description(line, 7, info, true); infoFound = true; }   // :115-169
                 else if (line.compare(0, 9, "##FILTER=") == 0) description(line, 9, filter, false);              // :170-206
                 else if (line.compare(0, 9, "##FORMAT=") == 0) description(line, 9, format, true);               // :210-257
             } else {                                                                                      // :267: line[0] == '#' and line[1] == 'C'
-                if (line.empty()) raise("IndexError", "string index out of range");
+                if (line.empty()) pyRaise("IndexError", "string index out of range");
                 if (line[0] != '#') continue;
-                if (line.size() < 2) raise("IndexError", "string index out of range");
+                if (line.size() < 2) pyRaise("IndexError", "string index out of range");
                 if (line[1] != 'C') continue;
                 if (!infoFound) err << "WARNING: did not detect INFO fields!\n";
                 std::string headerLine;
@@ -227,7 +235,7 @@ public:
         }
         static const char *const mainLabels[] = {"CHROM", "POS", "ID", "REF", "ALT", "QUAL"};
         for (size_t k = 0; k < 6; k++)                                                                    // :280-282
-            if (!column.count(mainLabels[k])) raise("NameError", std::string("Could not find column ").append(mainLabels[k]).append(" in header of VCF file!"));
+            if (!column.count(mainLabels[k])) pyRaise("NameError", std::string("Could not find column ").append(mainLabels[k]).append(" in header of VCF file!"));
         minLen = 0;                                                                                       // :284
         for (std::map<std::string, size_t>::const_iterator it = column.begin(); it != column.end(); ++it) if (it->second > minLen) minLen = it->second;
     }
@@ -245,12 +253,12 @@ public:
         }
         // :298-302 read the main columns, then every other labelled column; :307 the INFO column, :324 the FILTER column
         for (std::map<std::string, size_t>::const_iterator it = column.begin(); it != column.end(); ++it)
-            if (it->first != "INFO" && it->first != "FILTER" && it->second >= col.size()) raise("IndexError", "list index out of range");
+            if (it->first != "INFO" && it->first != "FILTER" && it->second >= col.size()) pyRaise("IndexError", "list index out of range");
         for (const char *lab : {"INFO", "FILTER"}) {
-            if (!column.count(lab)) raise("KeyError", std::string("'").append(lab).append("'"));
-            if (column[lab] >= col.size()) raise("IndexError", "list index out of range");
+            if (!column.count(lab)) pyRaise("KeyError", std::string("'").append(lab).append("'"));
+            if (column[lab] >= col.size()) pyRaise("IndexError", "list index out of range");
         }
-        if (version == 0) raise("AttributeError", "VCFFile instance has no attribute 'version'");         // :333
+        if (version == 0) pyRaise("AttributeError", "VCFFile instance has no attribute 'version'");         // :333
         r.chrom = col[column["CHROM"]]; r.pos = col[column["POS"]]; r.ref = col[column["REF"]]; r.alt = col[column["ALT"]]; r.qual = col[column["QUAL"]];
         return true;
     }
@@ -269,10 +277,10 @@ private:
     // fields[i] of a version-4 description must be KEY=value
     std::string keyed(const std::vector<std::string> &fields, size_t i, const char *key, const std::string &line)
     {
-        if (i >= fields.size()) raise("IndexError", "list index out of range");
+        if (i >= fields.size()) pyRaise("IndexError", "list index out of range");
         const std::vector<std::string> pair = split(fields[i], '=');
-        if (upperNoSpaces(pair[0]) != key) raise("NameError", std::string("Could not find ").append(key).append(" in: ").append(line));
-        if (pair.size() < 2) raise("IndexError", "list index out of range");
+        if (upperNoSpaces(pair[0]) != key) pyRaise("NameError", std::string("Could not find ").append(key).append(" in: ").append(line));
+        if (pair.size() < 2) pyRaise("IndexError", "list index out of range");
         return pair[1];
     }
     // one ##INFO= / ##FILTER= / ##FORMAT= line; `full`: number and type are part of it
@@ -281,20 +289,20 @@ private:
         const std::string sstr = line.substr(skip);
         size_t quotes = 0;
         for (size_t i = 0; i < sstr.size(); i++) quotes += sstr[i] == '"';
-        if (quotes != 2) raise("NameError", std::string("Incomplete description: ").append(line));
-        if (version == 0) raise("AttributeError", "VCFFile instance has no attribute 'version'");
+        if (quotes != 2) pyRaise("NameError", std::string("Incomplete description: ").append(line));
+        if (version == 0) pyRaise("AttributeError", "VCFFile instance has no attribute 'version'");
         if (version < 4) {
             const std::vector<std::string> fields2 = split(split(sstr, '"')[0], ',');
             const std::string id = fields2[0];
             if (full) {
-                if (fields2.size() < 2) raise("IndexError", "list index out of range");
+                if (fields2.size() < 2) pyRaise("IndexError", "list index out of range");
                 if (fields2[1] != ".") pyInt(fields2[1]);
-                if (fields2.size() < 3) raise("IndexError", "list index out of range");
+                if (fields2.size() < 3) pyRaise("IndexError", "list index out of range");
             }
-            if (ids.count(id)) raise("NameError", std::string("VCF file already has info-id ").append(id));
+            if (ids.count(id)) pyRaise("NameError", std::string("VCF file already has info-id ").append(id));
             ids.insert(id);
         } else {
-            if (sstr[0] != '<' || sstr[sstr.size() - 1] != '>') raise("NameError", "Incorrect description");
+            if (sstr[0] != '<' || sstr[sstr.size() - 1] != '>') pyRaise("NameError", "Incorrect description");
             const std::vector<std::string> fields = split(sstr.substr(1, sstr.size() - 2), ',');
             ids.insert(keyed(fields, 0, "ID", line));
             if (full) { keyed(fields, 1, "NUMBER", line); keyed(fields, 2, "TYPE", line); keyed(fields, 3, "DESCRIPTION", line); }
@@ -324,7 +332,7 @@ Variant4 variant4(const std::string &ref, const std::string &alt)
     size_t leftMatch = 0, rightMatch = 0;
     while (leftMatch < numrb && shorter[leftMatch] == longer[leftMatch]) leftMatch++;
     while (rightMatch < numrb && shorter[numrb - 1 - rightMatch] == longer[longer.size() - 1 - rightMatch]) rightMatch++;
-    if (leftMatch == 0 || leftMatch + rightMatch < numrb) raise("NameError", "Don't think this is a proper VCF4 insertion");
+    if (leftMatch == 0 || leftMatch + rightMatch < numrb) pyRaise("NameError", "Don't think this is a proper VCF4 insertion");
     size_t leftEnd = 1;
     if (numrb - leftEnd > rightMatch) leftEnd = leftMatch;
     const size_t rightStart = numrb - leftEnd;                                            // (0: the slice runs to the end, which is the same)
@@ -337,7 +345,7 @@ Variant4 variant4(const std::string &ref, const std::string &alt)
 long convertVcfToCandidates(const VcfConvertOptions &opt, std::ostream &err, std::ostream &out)
 {
     std::ofstream fo(opt.outputFile.c_str());
-    if (!fo.is_open()) raise("IOError", ioError(opt.outputFile));
+    if (!fo.is_open()) pyRaise("IOError", ioError(opt.outputFile));
     ScriptFasta fa(opt.refFile);
     long written = 0;
     const std::vector<std::string> vcffiles = split(opt.inputFiles, ',');
@@ -361,7 +369,7 @@ long convertVcfToCandidates(const VcfConvertOptions &opt, std::ostream &err, std
         }
     }
     fo.close();
-    if (!fo) raise("IOError", std::string("error writing '").append(opt.outputFile).append("'"));
+    if (!fo) pyRaise("IOError", std::string("error writing '").append(opt.outputFile).append("'"));
     return written;
 }
 
