@@ -37,6 +37,9 @@ DD_LONG_WS_BUDGET = 512 << 20
 (DD_CIGAR_OK, DD_CIGAR_HAP_NOT_ALIGNED, DD_CIGAR_ERROR1, DD_CIGAR_ERROR2, DD_CIGAR_ERROR3, DD_CIGAR_ERROR4, DD_CIGAR_IMPOSSIBLE,
  DD_CIGAR_OVERFLOW, DD_CIGAR_NOT_COMPUTED) = range(9)
 DD_CIGAR_DEFAULT_OPS_CAP = 8
+# realigned reads (opt-in): per-read status codes beside the DD_CIGAR_* of the chosen pair, and the two rules
+DD_REALIGN_OFF_HAP, DD_REALIGN_BAD_PAIR, DD_REALIGN_NO_HAPS = 9, 10, 11
+DD_REALIGN_FIRST_MAX, DD_REALIGN_PAIR = 0, 1
 # alignHaplotypes on the device: per-pair status codes and the launch geometry record
 DD_ALIGN_OK, DD_ALIGN_EMPTY, DD_ALIGN_TOO_LONG, DD_ALIGN_BAD_REF = range(4)
 DD_ALIGN_WS_BUDGET = 512 << 20
@@ -154,6 +157,15 @@ class dd_cigar_result(C.Structure):
     _fields_ = [("n_ops", C.c_void_p), ("ops", C.c_void_p), ("ref_off", C.c_void_p), ("status", C.c_void_p)]
 
 
+REALIGN_RESULT_FIELDS = ("hap", "status", "n_ops", "ops", "ref_off")
+
+
+class dd_realign_result(C.Structure):
+    """Per read: hap, status, n_ops (int32), ops (uint32 [ops_cap]), ref_off (int32).  Raw addresses: host arrays for
+    dd_compute_likelihoods_realign, device arrays for dd_realign_device."""
+    _fields_ = [(n, C.c_void_p) for n in REALIGN_RESULT_FIELDS]
+
+
 class dd_align_batch(C.Structure):
     """References and the haplotypes aligned against them.  Raw addresses: host arrays for dd_align_haplotypes and
     dd_align_workspace_bytes, device arrays for dd_align_haplotypes_device."""
@@ -225,7 +237,7 @@ EXPORTS = ["dd_params_struct_defaults", "dd_params_cli_defaults", "dd_batch_size
            "dd_pair_sums", "dd_map_pairs_device", "dd_map_pairs", "dd_last_error", "dd_abi_version", "dd_device_count",
            "dd_screen_windows_ex", "dd_compute_likelihoods_ex", "dd_workspace_bytes_long", "dd_launch_device_long", "dd_long_launch_log",
            "dd_compute_likelihoods_faster_ex", "dd_workspace_bytes_faster_long", "dd_launch_device_faster_long", "dd_faster_long_launch_log",
-           "dd_cigars_device", "dd_compute_likelihoods_cigars",
+           "dd_cigars_device", "dd_compute_likelihoods_cigars", "dd_realign_device", "dd_compute_likelihoods_realign",
            "dd_align_haplotypes", "dd_align_workspace_bytes", "dd_align_haplotypes_device", "dd_align_last_launch",
            "dd_align_events_device", "dd_align_haplotypes_events", "dd_align_events_last_launch",
            "dd_hap_variants_device", "dd_align_haplotypes_variants", "dd_hap_variants_last_launch",
@@ -300,6 +312,9 @@ def load():
                                      C.c_int, C.c_void_p]
     lib.dd_compute_likelihoods_cigars.argtypes = [C.POINTER(dd_params), C.POINTER(dd_batch), C.POINTER(dd_result), c_i32p, c_u8p,
                                                   C.POINTER(dd_cigar_result), C.c_int, C.c_int, C.c_uint32]
+    lib.dd_realign_device.argtypes = [C.POINTER(dd_device_batch), C.c_int] + [C.c_void_p] * 8 + [C.POINTER(dd_realign_result), C.c_int, C.c_void_p]
+    lib.dd_compute_likelihoods_realign.argtypes = [C.POINTER(dd_params), C.POINTER(dd_batch), C.POINTER(dd_result), C.c_int, c_i32p, c_i32p,
+                                                   c_i32p, c_u8p, C.POINTER(dd_realign_result), C.c_int, C.c_int, C.c_uint32]
     lib.dd_align_haplotypes.argtypes = [C.POINTER(dd_align_batch), C.POINTER(dd_align_result), C.c_int]
     lib.dd_align_workspace_bytes.argtypes = [C.POINTER(dd_align_batch)]
     lib.dd_align_workspace_bytes.restype = C.c_size_t
@@ -407,6 +422,17 @@ def hpos_reference_codes(hpos):
     h = np.asarray(hpos).copy()
     h[h < DD_HPOS_INS_KEY0] = DD_HPOS_INS
     return h
+
+
+def realign_arrays(n_reads, ops_cap):
+    """Host arrays for dd_compute_likelihoods_realign: (dict(hap, status, n_ops, ops [n_reads, ops_cap], ref_off), the dd_realign_result
+    that points at them).  Keep the dict alive as long as the struct is in use."""
+    import numpy as np
+    n = max(int(n_reads), 1)
+    a = {k: np.zeros(n, np.int32) for k in ("hap", "status", "n_ops", "ref_off")}
+    a["ops"] = np.zeros((n, int(ops_cap)), np.uint32)
+    res = dd_realign_result(*[a[k].ctypes.data for k in REALIGN_RESULT_FIELDS])
+    return {k: v[:int(n_reads)] for k, v in a.items()}, res
 
 
 def cigar_ops(ops, n_ops):

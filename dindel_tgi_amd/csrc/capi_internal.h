@@ -14,6 +14,7 @@
 #include "long_kernel.h"
 #include "faster_long_kernel.h"
 #include "cigar_kernel.h"
+#include "realign_kernel.h"
 
 namespace ddh {
 constexpr size_t kCuLdsBytes = 160u * 1024u;   // LDS of one CU (gfx950)
@@ -118,6 +119,15 @@ void launch_log_clear();
 int launch_cigars_range(const dd_device_batch *b, const int16_t *hpos_dev, const int32_t *status_dev, const int32_t *hap_ref_pos_dev,
                         const uint8_t *hap_aligned_dev, const dd_cigar_result *out_dev, int ops_cap, void *stream, int64_t pair_begin,
                         int64_t pair_end);
+// what one realign launch needs besides the batch (device pointers; dd_realign_device's arguments)
+struct RealignInputs {
+    int mode;
+    const double *ll; const uint8_t *on_hap; const int32_t *win_hap_pair, *hap_n_indels;
+    const int16_t *hpos; const int32_t *status, *hap_ref_pos; const uint8_t *hap_aligned;
+};
+// the realign launch (realign_kernel.hip) over the reads [read_begin, read_end) of the batch; read_end < 0 = all of them
+int launch_realign_range(const dd_device_batch *b, const RealignInputs &in, const dd_realign_result *out_dev, int ops_cap, void *stream,
+                         int read_begin, int read_end);
 
 static_assert(DD_LONG_LOG_FIELDS == DD_FASTER_LONG_LOG_FIELDS, "one record type serves both logs");
 struct LongRec {

@@ -193,9 +193,16 @@ struct StageClock {
 };
 
 // dd_compute_likelihoods_cigars: the haplotypes' reference positions in, the pairs' CIGARs out (host pointers)
+// dd_compute_likelihoods_realign: the same inputs, the window pairs and indel counts of its PAIR mode, and per READ the chosen haplotype with
+// its CIGAR out (rl != nullptr: the per-pair arrays of `out` are then neither allocated nor filled)
+struct RealignRequest {
+    int mode; const int32_t *win_hap_pair, *hap_n_indels;
+    dd_realign_result out;
+};
 struct CigarRequest {
     const int32_t *hap_ref_pos; const uint8_t *hap_aligned;
     dd_cigar_result out; int ops_cap;
+    const RealignRequest *rl;
 };
 
 int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options = 0,
@@ -207,6 +214,11 @@ int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b,
     g_flong.log.clear();
     dd_sizes sz;
     int rc = front_checks(p, b, r, sz);
+    if (!rc && sz.n_pairs == 0 && cg && cg->rl)              // reads without haplotypes: no pair, nothing to launch, every read marked
+        for (int64_t q = 0; q < sz.n_reads; q++) {
+            const dd_realign_result &o = cg->rl->out;
+            o.hap[q] = -1; o.status[q] = DD_REALIGN_NO_HAPS; o.n_ops[q] = 0; o.ref_off[q] = -1;
+        }
     if (rc || sz.n_pairs == 0) return rc;
     // validate content
     if (!b->hap_seq || !b->read_seq || !b->read_qidx || !b->read_mqidx || !b->read_start || !b->read_flags ||
@@ -312,8 +324,10 @@ int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b,
                             (size_t)(sz.n_reads + 1) * 4 + (size_t)sz.read_bases * 2 + (size_t)sz.n_reads * 6 + n_var * 20 +
                             (size_t)sz.n_haps * 4 + (size_t)lcls.list_len * 4 + 64 + DD_TABLE_DOUBLES * 8 + 48 * 256 + (size_t)W + 256 +
                             (lib_log95.empty() ? 0 : (size_t)sz.n_reads * 9 + (lib_logprob.size() + lib_log95.size()) * 8 + (size_t)(b->n_libs + 1) * 4);
-    const size_t cigar_in = cg ? (size_t)sz.hap_bases * 4 + (size_t)sz.n_haps + 2 * 256 : 0;
-    const size_t cigar_out = cg ? np * (12 + 4 * (size_t)cg->ops_cap) + 4 * 256 : 0;
+    const RealignRequest *rl = cg ? cg->rl : nullptr;
+    const size_t nr = (size_t)sz.n_reads;
+    const size_t cigar_in = cg ? (size_t)sz.hap_bases * 4 + (size_t)sz.n_haps + 2 * 256 + (rl ? (size_t)W * 8 + (size_t)sz.n_haps * 4 + 2 * 256 : 0) : 0;
+    const size_t cigar_out = !cg ? 0 : rl ? nr * (16 + 4 * (size_t)cg->ops_cap) + 5 * 256 : np * (12 + 4 * (size_t)cg->ops_cap) + 4 * 256;
     const size_t out_bytes = np * (4 * 8 + 2 + 8 * 2 + 4) + (size_t)sz.hpos_len * 2 + 2 * (size_t)sz.var_cov_len + (size_t)sz.n_reads + 24 * 256 + cigar_out;
     const bool staged = in_bytes + cigar_in + out_bytes <= (size_t)64 << 20;    // small batch: one H2D, one D2H through the pinned mirror
     DeviceCtx &ctx = g_ctx.c;
@@ -375,6 +389,11 @@ int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b,
         if ((rc = dev.upload(&hap_ref_pos_dev, cg->hap_ref_pos, (size_t)sz.hap_bases))) return rc;
         if (cg->hap_aligned && (rc = dev.upload(&hap_aligned_dev, cg->hap_aligned, (size_t)sz.n_haps))) return rc;
     }
+    const int32_t *win_hap_pair_dev = nullptr, *hap_n_indels_dev = nullptr;
+    if (rl && rl->mode == DD_REALIGN_PAIR) {
+        if ((rc = dev.upload(&win_hap_pair_dev, rl->win_hap_pair, (size_t)W * 2))) return rc;
+        if ((rc = dev.upload(&hap_n_indels_dev, rl->hap_n_indels, (size_t)sz.n_haps))) return rc;
+    }
     if ((rc = dev.flush_uploads(ctx.s[0]))) return rc;       // staged mode: the one H2D copy
     if (!staged) HIP_TRY(hipStreamSynchronize(nullptr));     // pageable uploads went through the null stream's DMA
     clk.mark("upload");
@@ -406,13 +425,27 @@ int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b,
         if ((rc = dev.alloc(&dr.hpos, (size_t)sz.hpos_len))) return rc;
         direct.hpos = false; n_direct--;
     }
+    // a realign request reads ll and onHap on the device as well
+    if (rl && direct.ll) {
+        if ((rc = dev.alloc(&dr.ll, np))) return rc;
+        direct.ll = false; n_direct--;
+    }
+    if (rl && direct.onHap) {
+        if ((rc = dev.alloc(&dr.onHap, nr))) return rc;
+        direct.onHap = false; n_direct--;
+    }
     g_last_direct = n_direct;
     if (r->onHap && !r->offHapHMQ && (rc = dev.alloc(&dr.offHapHMQ, np))) return rc;   // onHap is derived from it
     // CIGARs: the per-base alignments are needed on the device even when the caller does not want them back (r->hpos == NULL: nothing of
     // them is copied), and the CIGAR arrays come back with the other outputs
     dd_cigar_result dcg;
     memset(&dcg, 0, sizeof(dcg));
-    if (cg) {
+    dd_realign_result drl;
+    memset(&drl, 0, sizeof(drl));
+    if (rl) {
+        if ((rc = dev.alloc(&drl.hap, nr)) || (rc = dev.alloc(&drl.status, nr)) || (rc = dev.alloc(&drl.n_ops, nr)) ||
+            (rc = dev.alloc(&drl.ref_off, nr)) || (rc = dev.alloc(&drl.ops, nr * (size_t)cg->ops_cap))) return rc;
+    } else if (cg) {
         if ((rc = dev.alloc(&dcg.n_ops, np)) || (rc = dev.alloc(&dcg.ref_off, np)) || (rc = dev.alloc(&dcg.status, np)) ||
             (rc = dev.alloc(&dcg.ops, np * (size_t)cg->ops_cap))) return rc;
     }
@@ -454,7 +487,14 @@ int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b,
         hipStream_t st = streams.s[c & 1];
         const int w0 = cw[c], w1 = cw[c + 1];
         DD_RESULT_FIELDS(DOWN)
-        if (cg && pair_off[w1] > pair_off[w0]) {
+        if (rl && b->win_read_off[w1] > b->win_read_off[w0]) {
+            const size_t q0 = (size_t)b->win_read_off[w0], n = (size_t)b->win_read_off[w1] - q0, cap = (size_t)cg->ops_cap;
+            HIP_TRY(hipMemcpyAsync(rl->out.hap + q0, drl.hap + q0, n * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(rl->out.status + q0, drl.status + q0, n * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(rl->out.n_ops + q0, drl.n_ops + q0, n * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(rl->out.ref_off + q0, drl.ref_off + q0, n * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(rl->out.ops + q0 * cap, drl.ops + q0 * cap, n * cap * 4, hipMemcpyDeviceToHost, st));
+        } else if (cg && !rl && pair_off[w1] > pair_off[w0]) {
             const size_t p0 = (size_t)pair_off[w0], n = (size_t)(pair_off[w1] - pair_off[w0]), cap = (size_t)cg->ops_cap;
             HIP_TRY(hipMemcpyAsync(cg->out.n_ops + p0, dcg.n_ops + p0, n * 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(cg->out.ref_off + p0, dcg.ref_off + p0, n * 4, hipMemcpyDeviceToHost, st));
@@ -493,7 +533,12 @@ int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b,
             if (any && (rc = long_path.launch_range(p, &db, &dr, lws[c & 1], lws_bytes, streams.s[c & 1], w0, w1, q0, q1, long_stats + long_path.n_stats * c))) return rc;
         }
         // the block's CIGARs, behind its likelihood launches on the same stream (its ops start out zero: a pair's unused slots are defined)
-        if (cg && pair_off[w1] > pair_off[w0]) {
+        // or the block's realigned reads (reads of windows without haplotypes are marked too: the launch goes by reads, not by pairs)
+        if (rl && q1 > q0) {
+            HIP_TRY(hipMemsetAsync(drl.ops + (size_t)q0 * cg->ops_cap, 0, (size_t)(q1 - q0) * cg->ops_cap * 4, streams.s[c & 1]));
+            const RealignInputs in = {rl->mode, dr.ll, dr.onHap, win_hap_pair_dev, hap_n_indels_dev, dr.hpos, dr.status, hap_ref_pos_dev, hap_aligned_dev};
+            if ((rc = launch_realign_range(&db, in, &drl, cg->ops_cap, streams.s[c & 1], q0, q1))) return rc;
+        } else if (cg && !rl && pair_off[w1] > pair_off[w0]) {
             HIP_TRY(hipMemsetAsync(dcg.ops + (size_t)pair_off[w0] * cg->ops_cap, 0, (size_t)(pair_off[w1] - pair_off[w0]) * cg->ops_cap * 4, streams.s[c & 1]));
             if ((rc = launch_cigars_range(&db, dr.hpos, dr.status, hap_ref_pos_dev, hap_aligned_dev, &dcg, cg->ops_cap, streams.s[c & 1],
                                           pair_off[w0], pair_off[w1]))) return rc;
@@ -508,7 +553,14 @@ int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b,
             if (r->f && n && !direct.f) memcpy(r->f, ctx.pinned + (reinterpret_cast<unsigned char *>(dr.f) - ctx.arena), n * sizeof(*r->f)); }
         DD_RESULT_FIELDS(BACK)
 #undef BACK
-        if (cg) {
+        if (rl) {
+            const size_t cap = (size_t)cg->ops_cap;
+            memcpy(rl->out.hap, ctx.pinned + (reinterpret_cast<unsigned char *>(drl.hap) - ctx.arena), nr * 4);
+            memcpy(rl->out.status, ctx.pinned + (reinterpret_cast<unsigned char *>(drl.status) - ctx.arena), nr * 4);
+            memcpy(rl->out.n_ops, ctx.pinned + (reinterpret_cast<unsigned char *>(drl.n_ops) - ctx.arena), nr * 4);
+            memcpy(rl->out.ref_off, ctx.pinned + (reinterpret_cast<unsigned char *>(drl.ref_off) - ctx.arena), nr * 4);
+            memcpy(rl->out.ops, ctx.pinned + (reinterpret_cast<unsigned char *>(drl.ops) - ctx.arena), nr * cap * 4);
+        } else if (cg) {
             const size_t cap = (size_t)cg->ops_cap;
             memcpy(cg->out.n_ops, ctx.pinned + (reinterpret_cast<unsigned char *>(dcg.n_ops) - ctx.arena), np * 4);
             memcpy(cg->out.ref_off, ctx.pinned + (reinterpret_cast<unsigned char *>(dcg.ref_off) - ctx.arena), np * 4);
@@ -788,7 +840,25 @@ int dd_compute_likelihoods_cigars(const dd_params *p, const dd_batch *b, dd_resu
     if (ops_cap < 1) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_cigars: ops_cap must be at least 1");
     if (!cig || !cig->n_ops || !cig->ops || !cig->ref_off || !cig->status)
         return fail(DD_ERR_INVALID, "dd_compute_likelihoods_cigars: every array of dd_cigar_result is required");
-    const CigarRequest cg = {hap_ref_pos, hap_aligned, *cig, ops_cap};
+    const CigarRequest cg = {hap_ref_pos, hap_aligned, *cig, ops_cap, nullptr};
+    return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device, options, &cg);
+}
+int dd_compute_likelihoods_realign(const dd_params *p, const dd_batch *b, dd_result *r, int mode, const int32_t *win_hap_pair,
+                                   const int32_t *hap_n_indels, const int32_t *hap_ref_pos, const uint8_t *hap_aligned,
+                                   const dd_realign_result *out, int ops_cap, int device, uint32_t options)
+{
+    if (options & ~DD_OPT_LONG_WINDOWS) return fail(DD_ERR_INVALID, "unknown option bits");
+    if (mode != DD_REALIGN_FIRST_MAX && mode != DD_REALIGN_PAIR) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign: unknown mode");
+    if (mode == DD_REALIGN_PAIR && (!win_hap_pair || !hap_n_indels))
+        return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign: DD_REALIGN_PAIR needs win_hap_pair and hap_n_indels");
+    if (!hap_ref_pos) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign: hap_ref_pos is required (Haplotype::refHpos per haplotype base)");
+    if (ops_cap < 1) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign: ops_cap must be at least 1");
+    if (!out || !out->hap || !out->status || !out->n_ops || !out->ops || !out->ref_off)
+        return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign: every array of dd_realign_result is required");
+    const RealignRequest rl = {mode, win_hap_pair, hap_n_indels, *out};
+    dd_cigar_result none;
+    memset(&none, 0, sizeof(none));
+    const CigarRequest cg = {hap_ref_pos, hap_aligned, none, ops_cap, &rl};
     return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device, options, &cg);
 }
 int dd_compute_likelihoods_faster(const dd_params *p, const dd_batch *b, dd_result *r, int device)

@@ -262,6 +262,37 @@ int launch_cigars_range(const dd_device_batch *b, const int16_t *hpos_dev, const
     return DD_SUCCESS;
 }
 
+// ---------------- realigned reads (realign_kernel.hip) ----------------
+int launch_realign_range(const dd_device_batch *b, const RealignInputs &in, const dd_realign_result *out_dev, int ops_cap, void *stream,
+                         int read_begin, int read_end)
+{
+    if (!b || !in.ll || !in.hpos || !out_dev) return fail(DD_ERR_INVALID, "dd_realign_device: null batch, ll, hpos or output block");
+    if (in.mode != DD_REALIGN_FIRST_MAX && in.mode != DD_REALIGN_PAIR) return fail(DD_ERR_INVALID, "dd_realign_device: unknown mode");
+    if (in.mode == DD_REALIGN_PAIR && (!in.win_hap_pair || !in.hap_n_indels))
+        return fail(DD_ERR_INVALID, "dd_realign_device: DD_REALIGN_PAIR needs win_hap_pair and hap_n_indels");
+    if (!in.hap_ref_pos) return fail(DD_ERR_INVALID, "dd_realign_device: hap_ref_pos is required (Haplotype::refHpos per haplotype base)");
+    if (ops_cap < 1) return fail(DD_ERR_INVALID, "dd_realign_device: ops_cap must be at least 1");
+    if (!out_dev->hap || !out_dev->status || !out_dev->n_ops || !out_dev->ops || !out_dev->ref_off)
+        return fail(DD_ERR_INVALID, "dd_realign_device: every array of dd_realign_result is required");
+    if (read_end < 0) read_end = b->n_reads;
+    if (b->n_windows <= 0 || read_end <= read_begin) return DD_SUCCESS;      // (reads of windows without haplotypes are still marked)
+    if (!b->win_hap_off || !b->win_read_off || !b->hap_seq_off || !b->read_seq_off || !b->win_pair_off || !b->win_hpos_off)
+        return fail(DD_ERR_INVALID, "dd_realign_device: the batch lacks an offset array");
+    ddc::RealignArgs A;
+    memset(&A, 0, sizeof(A));
+    ddc::CigarArgs &C = A.cig;
+    C.n_windows = b->n_windows;
+    C.win_hap_off = b->win_hap_off; C.win_read_off = b->win_read_off; C.hap_seq_off = b->hap_seq_off; C.read_seq_off = b->read_seq_off;
+    C.win_pair_off = b->win_pair_off; C.win_hpos_off = b->win_hpos_off;
+    C.hpos = in.hpos; C.pair_status = in.status; C.hap_ref_pos = in.hap_ref_pos; C.hap_aligned = in.hap_aligned;
+    C.out.n_ops = out_dev->n_ops; C.out.ops = out_dev->ops; C.out.ref_off = out_dev->ref_off; C.out.status = out_dev->status;
+    C.ops_cap = ops_cap;
+    A.mode = in.mode; A.read_begin = read_begin; A.read_end = read_end;
+    A.ll = in.ll; A.on_hap = in.on_hap; A.win_hap_pair = in.win_hap_pair; A.hap_n_indels = in.hap_n_indels; A.hap = out_dev->hap;
+    HIP_TRY(ddc::launch_realign(A, static_cast<hipStream_t>(stream)));
+    return DD_SUCCESS;
+}
+
 // ---------------- long windows: what the two long paths share (long_kernel.hip for the main model, faster_long_kernel.hip for --faster) ----------------
 // The front checks of a long launch.  1: nothing to do (empty batch or range), 0: go on, < 0: error.
 static int long_front_checks(const LongPath &lp, const dd_params *p, const dd_device_batch *b, const dd_result *r, int w_begin, int w_end)
@@ -444,6 +475,15 @@ int dd_cigars_device(const dd_device_batch *b, const int16_t *hpos_dev, const in
                      const uint8_t *hap_aligned_dev, const dd_cigar_result *out_dev, int ops_cap, void *stream)
 {   // the whole batch: the pair count is win_pair_off[n_windows], a device array, so the kernel reads its own bound there
     return launch_cigars_range(b, hpos_dev, status_dev, hap_ref_pos_dev, hap_aligned_dev, out_dev, ops_cap, stream, 0, -1);
+}
+
+int dd_realign_device(const dd_device_batch *b, int mode, const double *ll_dev, const uint8_t *on_hap_dev,
+                      const int32_t *win_hap_pair_dev, const int32_t *hap_n_indels_dev,
+                      const int16_t *hpos_dev, const int32_t *status_dev, const int32_t *hap_ref_pos_dev,
+                      const uint8_t *hap_aligned_dev, const dd_realign_result *out_dev, int ops_cap, void *stream)
+{
+    const RealignInputs in = {mode, ll_dev, on_hap_dev, win_hap_pair_dev, hap_n_indels_dev, hpos_dev, status_dev, hap_ref_pos_dev, hap_aligned_dev};
+    return launch_realign_range(b, in, out_dev, ops_cap, stream, 0, -1);
 }
 
 int dd_pair_sums_device(const dd_device_batch *b, const int64_t *win_hh_off_dev, int64_t n_slots,

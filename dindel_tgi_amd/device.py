@@ -29,7 +29,7 @@ class DeviceBatch:
     """A PackedBatch resident in HBM + the dd_device_batch that points at it."""
 
     def __init__(self, pb: PackedBatch, params: capi.dd_params, device="cuda:0", long_windows=False, long_windows_faster=False,
-                 cigars=False, ops_cap=capi.DD_CIGAR_DEFAULT_OPS_CAP, hap_ref_pos=None, hap_aligned=None):
+                 cigars=False, ops_cap=capi.DD_CIGAR_DEFAULT_OPS_CAP, hap_ref_pos=None, hap_aligned=None, realign=False, hap_n_indels=None):
         """long_windows: windows beyond the main kernels' limits (haplotypes up to 4,094 bp, reads up to 4,096 bp, and with maxLengthDel
         12..31 haplotypes over 574 bp) are computed by the long-window kernel after the main launch (dd_launch_device_long) instead of
         being marked DD_PAIR_UNSUPPORTED.  Off by default.
@@ -38,7 +38,10 @@ class DeviceBatch:
         batch is screened once, for one model: both flags together raise ValueError, and launch() on such a batch raises.
         cigars: launch_cigars() turns the pairs' hpos into CIGARs on the device (dd_cigars_device) and results() also returns cigar_n_ops,
         cigar_ops [n_pairs, ops_cap], cigar_ref_off and cigar_status.  hap_ref_pos: Haplotype::refHpos, one int32 per haplotype base
-        (laid out like hap_seq); hap_aligned: one byte per haplotype, 0 = not aligned (None = all aligned).  Off by default."""
+        (laid out like hap_seq); hap_aligned: one byte per haplotype, 0 = not aligned (None = all aligned).  Off by default.
+        realign: launch_realign() chooses the haplotype each read is realigned to and computes that pair's CIGAR alone (dd_realign_device);
+        results() also returns realign_hap, realign_status, realign_n_ops, realign_ops [n_reads, ops_cap] and realign_ref_off.  Needs
+        hap_ref_pos like cigars; hap_n_indels (Haplotype::countIndels per haplotype) is needed by the DD_REALIGN_PAIR rule only."""
         if long_windows and long_windows_faster:
             raise ValueError("long_windows and long_windows_faster screen the batch for different models: one resident batch, one screening")
         lib = capi.load()
@@ -136,9 +139,10 @@ class DeviceBatch:
         self.long_ws_bytes = int(ws_long(C.byref(params), C.byref(db))) if self.n_long else 0
         self.long_ws = torch.empty(max(self.long_ws_bytes, 8), dtype=torch.uint8, device=self.device) if self.n_long else None
         self.cigars = bool(cigars)
-        if self.cigars:
+        self.realign = bool(realign)
+        if self.cigars or self.realign:
             if hap_ref_pos is None:
-                raise ValueError("cigars=True needs hap_ref_pos (Haplotype::refHpos per haplotype base)")
+                raise ValueError("cigars=True and realign=True need hap_ref_pos (Haplotype::refHpos per haplotype base)")
             hrp = np.ascontiguousarray(hap_ref_pos, np.int32)
             if hrp.shape != (int(a["hap_seq_off"][pb.n_haps]),):
                 raise ValueError("hap_ref_pos must hold one entry per haplotype base")
@@ -151,6 +155,17 @@ class DeviceBatch:
                 if hal.shape != (pb.n_haps,):
                     raise ValueError("hap_aligned must hold one byte per haplotype")
                 t["hap_aligned"] = _to_dev(hal, self.device)
+        if self.realign:
+            if hap_n_indels is not None:
+                hni = np.ascontiguousarray(hap_n_indels, np.int32)
+                if hni.shape != (pb.n_haps,):
+                    raise ValueError("hap_n_indels must hold one entry per haplotype")
+                t["hap_n_indels"] = _to_dev(hni, self.device)
+            nread = max(pb.n_reads, 1)
+            self.rl = {k: torch.zeros(nread * (self.ops_cap if k == "ops" else 1), dtype=torch.int32, device=self.device)
+                       for k in capi.REALIGN_RESULT_FIELDS}                                                 # ops: uint32 bits
+            self.drl = capi.dd_realign_result(*[self.rl[k].data_ptr() for k in capi.REALIGN_RESULT_FIELDS])
+        if self.cigars:
             npair = max(pb.n_pairs, 1)
             self.cig = {"n_ops": torch.zeros(npair, dtype=torch.int32, device=self.device),
                         "ops": torch.zeros(npair * self.ops_cap, dtype=torch.int32, device=self.device),    # uint32 bits
@@ -203,6 +218,33 @@ class DeviceBatch:
         if rc != 0:
             raise RuntimeError("dd_cigars_device rc=%d: %s" % (rc, capi.last_error()))
 
+    def launch_realign(self, mode, win_hap_pair=None, stream=None, on_hap=True):
+        """The haplotype each read is realigned to and that pair's CIGAR, from the ll, onHap, status and hpos of the last launch() /
+        launch_faster() (same stream, behind it).  mode: capi.DD_REALIGN_FIRST_MAX, or capi.DD_REALIGN_PAIR with win_hap_pair
+        [n_windows, 2] (and hap_n_indels given to the constructor).  on_hap=False: the FIRST_MAX rule without onHap (NULL).
+        Asynchronous."""
+        if not self.realign:
+            raise RuntimeError("this batch was built without realign=True")
+        lib = capi.load()
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        pairs = None
+        if win_hap_pair is not None:
+            whp = np.ascontiguousarray(win_hap_pair, np.int32).reshape(-1)
+            if whp.shape != (2 * self.pb.n_windows,):
+                raise ValueError("win_hap_pair must hold two entries per window")
+            self._win_hap_pair = _to_dev(whp, self.device)     # the launch reads it: keep it alive
+            pairs = self._win_hap_pair.data_ptr()
+        hal = self.t["hap_aligned"].data_ptr() if "hap_aligned" in self.t else None
+        hni = self.t["hap_n_indels"].data_ptr() if "hap_n_indels" in self.t else None
+        rc = lib.dd_realign_device(C.byref(self.db), int(mode), C.c_void_p(self.out["ll"].data_ptr()),
+                                   C.c_void_p(self.out["onHap"].data_ptr() if on_hap else None), C.c_void_p(pairs), C.c_void_p(hni),
+                                   C.c_void_p(self.out["hpos"].data_ptr()), C.c_void_p(self.out["status"].data_ptr()),
+                                   C.c_void_p(self.t["hap_ref_pos"].data_ptr()), C.c_void_p(hal), C.byref(self.drl), self.ops_cap,
+                                   C.c_void_p(stream.cuda_stream))
+        if rc != 0:
+            raise RuntimeError("dd_realign_device rc=%d: %s" % (rc, capi.last_error()))
+
     def pooled_em(self, slots, a0=0.001, tol=1e-4, stream=None):
         """The pooled analysis' EM loop (dd_pooled_em_device) on the `ll` of the last launch() / launch_faster(), resident in HBM (same
         stream, behind it).  slots: pooled.pack_slots(...).  Asynchronous; returns the device tensors dict(loglik, freqs, iters, ediff),
@@ -241,4 +283,9 @@ class DeviceBatch:
             for k in ("n_ops", "ref_off", "status"):
                 res["cigar_" + k] = self.cig[k][:n].cpu().numpy()
             res["cigar_ops"] = self.cig["ops"][:n * self.ops_cap].cpu().numpy().view(np.uint32).reshape(n, self.ops_cap)
+        if self.realign:
+            n = self.pb.n_reads
+            for k in ("hap", "status", "n_ops", "ref_off"):
+                res["realign_" + k] = self.rl[k][:n].cpu().numpy()
+            res["realign_ops"] = self.rl["ops"][:n * self.ops_cap].cpu().numpy().view(np.uint32).reshape(n, self.ops_cap)
         return res

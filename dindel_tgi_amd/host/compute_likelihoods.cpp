@@ -226,7 +226,11 @@ struct BatchBlock {
     bool has_cigars; int cig_cap;                        // device CIGARs (setDeviceCigars): per pair, ops at pair * cig_cap
     RawBuf<int32_t> cig_n_ops, cig_ref_off, cig_status;
     RawBuf<uint32_t> cig_ops;
-    BatchBlock() : W(0), faster(false), has_hpos(false), has_cigars(false), cig_cap(0) {}
+    bool has_realign;                                    // device realign (setDeviceRealign): per READ, ops at read * cig_cap
+    RawBuf<int32_t> rl_hap, rl_status, rl_n_ops, rl_ref_off;
+    RawBuf<uint32_t> rl_ops;
+    RawBuf<uint8_t> on_hap;                              // ... and the device's onHap, which its rule consults
+    BatchBlock() : W(0), faster(false), has_hpos(false), has_cigars(false), cig_cap(0), has_realign(false) {}
 };
 
 struct PackScratch {
@@ -374,6 +378,49 @@ int WindowLikelihoods::cigarStatus(size_t h, size_t r) const { return blk_->cig_
 int WindowLikelihoods::cigarNumOps(size_t h, size_t r) const { return blk_->cig_n_ops[pair(h, r)]; }
 const uint32_t *WindowLikelihoods::cigarOps(size_t h, size_t r) const { return blk_->cig_ops.p + size_t(pair(h, r)) * size_t(blk_->cig_cap); }
 int WindowLikelihoods::cigarRefOff(size_t h, size_t r) const { return blk_->cig_ref_off[pair(h, r)]; }
+bool WindowLikelihoods::hasDeviceRealign() const { return blk_ && blk_->has_realign; }
+int WindowLikelihoods::realignHap(size_t r) const { return blk_->rl_hap[size_t(blk_->win_read_off[w_]) + r]; }
+int WindowLikelihoods::realignStatus(size_t r) const { return blk_->rl_status[size_t(blk_->win_read_off[w_]) + r]; }
+int WindowLikelihoods::realignNumOps(size_t r) const { return blk_->rl_n_ops[size_t(blk_->win_read_off[w_]) + r]; }
+const uint32_t *WindowLikelihoods::realignOps(size_t r) const { return blk_->rl_ops.p + (size_t(blk_->win_read_off[w_]) + r) * size_t(blk_->cig_cap); }
+int WindowLikelihoods::realignRefOff(size_t r) const { return blk_->rl_ref_off[size_t(blk_->win_read_off[w_]) + r]; }
+
+WindowLikelihoods WindowLikelihoods::handMadeRealign(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, int opsCap, const int32_t *hap,
+                                                     const int32_t *status, const int32_t *nOps, const uint32_t *ops, const int32_t *refOff,
+                                                     const int16_t *hpos)
+{
+    std::shared_ptr<BatchBlock> blk = std::make_shared<BatchBlock>();
+    BatchBlock &B = *blk;
+    const size_t H = haps.size(), Rn = reads.size(), np = H * Rn + 1, cap = size_t(opsCap < 1 ? 1 : opsCap);
+    B.W = 1; B.has_realign = hap != NULL; B.cig_cap = int(cap); B.has_hpos = hpos != NULL;
+    B.win_hap_off.assign(2, 0); B.win_hap_off[1] = int32_t(H);
+    B.win_read_off.assign(2, 0); B.win_read_off[1] = int32_t(Rn);
+    B.hap_var_off.assign(H + 1, 0);
+    B.read_seq_off.assign(Rn + 1, 0);
+    for (size_t r = 0; r < Rn; r++) B.read_seq_off[r + 1] = B.read_seq_off[r] + int32_t(reads[r].size());
+    const size_t SL = size_t(B.read_seq_off[Rn]);
+    B.pair_off.assign(2, 0); B.pair_off[1] = int64_t(H * Rn);
+    B.hpos_off.assign(2, 0); B.hpos_off[1] = int64_t(H * SL);
+    B.vc_off.assign(2, 0);
+    // every pair a plain placement without a base on the haplotype: get() then hands the given hpos through as it is
+    B.ll.reserve(np); B.llOn.reserve(np); B.llOff.reserve(np); B.mLogBQ.reserve(np); B.offHap.reserve(np); B.offHapHMQ.reserve(np);
+    B.status.reserve(np); B.numIndels.reserve(np); B.numMismatch.reserve(np); B.nBQT.reserve(np); B.nmmBQT.reserve(np);
+    B.nMMLeft.reserve(np); B.nMMRight.reserve(np); B.firstBase.reserve(np); B.lastBase.reserve(np); B.vcov.reserve(1); B.fcov.reserve(1);
+    for (size_t p = 0; p < np; p++) {
+        B.ll[p] = B.llOn[p] = B.llOff[p] = B.mLogBQ[p] = 0.0; B.offHap[p] = B.offHapHMQ[p] = 0; B.status[p] = DD_PAIR_OK;
+        B.numIndels[p] = B.numMismatch[p] = B.nBQT[p] = B.nmmBQT[p] = B.nMMLeft[p] = B.nMMRight[p] = 0; B.firstBase[p] = B.lastBase[p] = -1;
+    }
+    if (hpos) { B.hpos.reserve(H * SL + 1); memcpy(B.hpos.p, hpos, H * SL * sizeof(int16_t)); }
+    if (hap) {
+        B.rl_hap.reserve(Rn + 1); B.rl_status.reserve(Rn + 1); B.rl_n_ops.reserve(Rn + 1); B.rl_ref_off.reserve(Rn + 1); B.rl_ops.reserve(Rn * cap + 1);
+        memcpy(B.rl_hap.p, hap, Rn * 4); memcpy(B.rl_status.p, status, Rn * 4); memcpy(B.rl_n_ops.p, nOps, Rn * 4);
+        memcpy(B.rl_ref_off.p, refOff, Rn * 4); memcpy(B.rl_ops.p, ops, Rn * cap * 4);
+    }
+    WindowLikelihoods v;
+    v.blk_ = blk; v.w_ = 0; v.haps_ = &haps; v.reads_ = &reads;
+    return v;
+}
+
 int WindowLikelihoods::indelCount(size_t h, size_t r) const
 {
     const BatchBlock &B = *blk_;
@@ -482,10 +529,10 @@ MLAlignment WindowLikelihoods::get(size_t h, size_t r) const
         if (!eng_) throw std::string("WindowLikelihoods::get: batch was run without alignments and the engine is gone");
         std::vector<WindowJob> one(1);
         one[0].haps = haps_; one[0].reads = reads_; one[0].leftPos = leftPos_; one[0].rightPos = leftPos_ + 1;
-        const bool keep = eng_->keepAlignments_, cig = eng_->deviceCigars_;
-        eng_->keepAlignments_ = true; eng_->deviceCigars_ = false;
-        try { eng_->runBatch(one, blk_->faster); } catch (...) { eng_->keepAlignments_ = keep; eng_->deviceCigars_ = cig; throw; }
-        eng_->keepAlignments_ = keep; eng_->deviceCigars_ = cig;
+        const bool keep = eng_->keepAlignments_, cig = eng_->deviceCigars_, rl = eng_->deviceRealign_;
+        eng_->keepAlignments_ = true; eng_->deviceCigars_ = false; eng_->deviceRealign_ = false;
+        try { eng_->runBatch(one, blk_->faster); } catch (...) { eng_->keepAlignments_ = keep; eng_->deviceCigars_ = cig; eng_->deviceRealign_ = rl; throw; }
+        eng_->keepAlignments_ = keep; eng_->deviceCigars_ = cig; eng_->deviceRealign_ = rl;
         if (!one[0].error.empty()) throw one[0].error;
         full_ = one[0].result.blk_;
     }
@@ -572,9 +619,12 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
     bool any_eager = false;
     for (int w = 0; w < W; w++) if (jobs[w].liks) any_eager = true;
     // device CIGARs: the pairs' CIGARs come back instead of their alignments (main model, lazy jobs only)
-    B.has_cigars = deviceCigars_ && !faster && !any_eager;
+    // device realign: the reads' chosen haplotypes and CIGARs come back instead of either (main model, lazy jobs only)
+    B.has_realign = deviceRealign_ && !faster && !any_eager;
+    B.has_cigars = deviceCigars_ && !faster && !any_eager && !B.has_realign;
     B.cig_cap = cigarOpsCap_;
-    B.has_hpos = !B.has_cigars && (keepAlignments_ || any_eager);
+    B.has_hpos = !B.has_cigars && !B.has_realign && (keepAlignments_ || any_eager);
+    const bool pack_ref_pos = B.has_cigars || B.has_realign;
 
     // ---- pack (CSR), pass 1: sizes and offsets.  Per window in parallel (its haplotypes and reads are scattered objects: the pass is
     // cache misses), one serial prefix sum over the windows in between ----
@@ -650,7 +700,7 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
     S.read_qidx.reserve(size_t(n_read_bases) + 1); S.read_mqidx.resize(n_reads + 1); S.read_start.resize(n_reads + 1);
     S.read_flags.resize(n_reads + 1); S.hap_var.resize(2 * n_var + 1); S.hap_var_flank.resize(3 * n_var + 1);
     if (with_mates) { S.read_mate_pos.resize(n_reads + 1); S.read_mate_len.resize(n_reads + 1); }
-    if (B.has_cigars) { S.hap_ref_pos.resize(size_t(n_hap_bases) + 1); S.hap_aligned.resize(n_haps + 1); }
+    if (pack_ref_pos) { S.hap_ref_pos.resize(size_t(n_hap_bases) + 1); S.hap_aligned.resize(n_haps + 1); }
 
     const std::chrono::steady_clock::time_point t_pass1 = std::chrono::steady_clock::now();
     // ---- pass 2: the bytes, windows in parallel ----
@@ -665,7 +715,7 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
                 const Haplotype &H = (*J.haps)[h];
                 const int g = B.win_hap_off[w] + int(h);
                 memcpy(S.hap_seq.data() + S.hap_seq_off[size_t(g)], H.seq.data(), H.seq.size());
-                if (B.has_cigars) {                       // `hapRefPos.size() != hapSize` is getCIGAR's "Haplotype has not been aligned!"
+                if (pack_ref_pos) {                       // `hapRefPos.size() != hapSize` is getCIGAR's "Haplotype has not been aligned!"
                     const bool aligned = H.refHpos.size() == H.seq.size();
                     S.hap_aligned[size_t(g)] = aligned ? 1 : 0;
                     int32_t *hr = S.hap_ref_pos.data() + S.hap_seq_off[size_t(g)];
@@ -769,6 +819,15 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
         Cg.n_ops = B.cig_n_ops.reserve(np); Cg.ref_off = B.cig_ref_off.reserve(np); Cg.status = B.cig_status.reserve(np);
         Cg.ops = B.cig_ops.reserve(np * size_t(B.cig_cap));
     }
+    dd_realign_result Rl;
+    memset(&Rl, 0, sizeof(Rl));
+    if (B.has_realign) {
+        const size_t nr = n_reads + 1;
+        Rl.hap = B.rl_hap.reserve(nr); Rl.status = B.rl_status.reserve(nr); Rl.n_ops = B.rl_n_ops.reserve(nr); Rl.ref_off = B.rl_ref_off.reserve(nr);
+        Rl.ops = B.rl_ops.reserve(nr * size_t(B.cig_cap));
+        Rz.onHap = B.on_hap.reserve(nr);                 // the pooled rule reads it on the device
+    }
+    lastRealignBytes = B.has_realign ? n_reads * (16 + 4 * size_t(B.cig_cap)) : 0;
     lastHposBytes = B.has_hpos ? size_t(sz.hpos_len) * sizeof(int16_t) : 0;
     lastCigarBytes = B.has_cigars ? size_t(sz.n_pairs) * (12 + 4 * size_t(B.cig_cap)) : 0;
     dd_params P = to_abi(params);
@@ -777,7 +836,11 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
     if (getenv("DD_TIMING"))
         fprintf(stderr, "pack_timing: windows=%d pass1=%.2fms pass2+alloc=%.2fms\n", W, std::chrono::duration<double, std::milli>(t_pass1 - t_start).count(),
                 std::chrono::duration<double, std::milli>(t_packed - t_pass1).count());
-    if (sz.n_pairs > 0 && B.has_cigars) {
+    if (B.has_realign) {                                 // (also without pairs: reads of windows without haplotypes are marked)
+        const int rc = dd_compute_likelihoods_realign(&P, &Bt, &Rz, DD_REALIGN_FIRST_MAX, NULL, NULL, S.hap_ref_pos.data(), S.hap_aligned.data(), &Rl,
+                                                      B.cig_cap, device_, longWindows_ ? DD_OPT_LONG_WINDOWS : 0u);
+        if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_realign: ") + dd_last_error();
+    } else if (sz.n_pairs > 0 && B.has_cigars) {
         const int rc = dd_compute_likelihoods_cigars(&P, &Bt, &Rz, S.hap_ref_pos.data(), S.hap_aligned.data(), &Cg, B.cig_cap, device_,
                                                      longWindows_ ? DD_OPT_LONG_WINDOWS : 0u);
         if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_cigars: ") + dd_last_error();

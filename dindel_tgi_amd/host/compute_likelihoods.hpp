@@ -93,6 +93,20 @@ public:
     int cigarNumOps(size_t h, size_t r) const;
     const uint32_t *cigarOps(size_t h, size_t r) const;
     int cigarRefOff(size_t h, size_t r) const;
+    // Device realign (LikelihoodEngine::setDeviceRealign): per READ the haplotype the device chose for it by the pooled rule
+    // (DD_REALIGN_FIRST_MAX; -1: none) and that pair's CIGAR: status (DD_CIGAR_* of the chosen pair, or DD_REALIGN_OFF_HAP /
+    // DD_REALIGN_NO_HAPS), operation count, the first min(count, cigarOpsCap()) BAM words and the reference offset.
+    bool hasDeviceRealign() const;
+    int realignHap(size_t r) const;
+    int realignStatus(size_t r) const;
+    int realignNumOps(size_t r) const;
+    const uint32_t *realignOps(size_t r) const;
+    int realignRefOff(size_t r) const;
+    // A one-window view over hand-made realign rows (and, with hpos, hand-made per-base alignments for get(): one entry per (haplotype,
+    // read base), haplotype-major).  For tests of the consumers of these views; `haps` and `reads` must outlive it.
+    static WindowLikelihoods handMadeRealign(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, int opsCap, const int32_t *hap,
+                                             const int32_t *status, const int32_t *nOps, const uint32_t *ops, const int32_t *refOff,
+                                             const int16_t *hpos);
     // all records, as the eager path fills them
     void toLiks(std::vector<std::vector<MLAlignment> > &liks, std::vector<int> &onHap) const;
 
@@ -165,6 +179,12 @@ public:
     // eager job, and the --faster model, run as without it.  Default off.
     void setDeviceCigars(bool v, int opsCap = 8) { deviceCigars_ = v; cigarOpsCap_ = opsCap < 1 ? 1 : opsCap; }
     bool deviceCigars() const { return deviceCigars_; }
+    // true: computeLikelihoodsBatch asks for the realigned reads instead (dd_compute_likelihoods_realign, DD_REALIGN_FIRST_MAX): the device
+    // picks each read's haplotype by the pooled rule and only that pair's CIGAR comes back, 4 opsCap + 16 bytes per READ; the lazy views
+    // expose them (hasDeviceRealign()) and carry neither alignments nor per-pair CIGARs.  Wins over setDeviceCigars.  Main model, lazy jobs
+    // only: a batch with an eager job, and the --faster model, run as without it.  Default off.
+    void setDeviceRealign(bool v, int opsCap = 8) { deviceRealign_ = v; if (v) cigarOpsCap_ = opsCap < 1 ? 1 : opsCap; }
+    bool deviceRealign() const { return deviceRealign_; }
     // optional: have the calling thread's device cache (arena, staging mirror, streams) of this engine's device made now, for batches of
     // about `pairs` (haplotype, read) pairs — e.g. while the first batch is still being prepared.  Throws like the batch calls.
     void warmUp(size_t pairs);
@@ -173,6 +193,7 @@ public:
     double lastPackSeconds = 0.0, lastDeviceSeconds = 0.0, lastUnpackSeconds = 0.0;
     // bytes of per-base alignments (hpos) and of CIGAR arrays the last batch call brought back from the device
     size_t lastHposBytes = 0, lastCigarBytes = 0;
+    size_t lastRealignBytes = 0;         // ... and of the realigned reads' arrays (setDeviceRealign)
 
     // ObservationModelFBMax::reportVariants (ObservationModelFB.cpp:1351-1475) from the device's hpos: fills
     // hpos, indels, snps, align, firstBase/lastBase, counters and the covered maps.  Exposed for tests.
@@ -194,6 +215,7 @@ private:
     bool longWindows_ = false;
     bool longWindowsFaster_ = false;
     bool deviceCigars_ = false;
+    bool deviceRealign_ = false;
     int cigarOpsCap_ = 8;
     std::vector<std::shared_ptr<BatchBlock> > spare_;   // result blocks of earlier calls; one nobody references any more is reused (warm pages)
     unsigned spareNext_ = 0;

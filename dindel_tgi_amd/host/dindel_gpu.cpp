@@ -48,6 +48,12 @@
 //                     window at a time, so a small N costs a recompute per affected window — (counted in the timing line).  The files are the
 //                     same byte for byte.  The engines then merge as many batches per launch as without realigned BAMs.  No effect
 //                     without --outputRealignedBAM (main model, like that option)
+//   [--deviceRealign [--cigarOpsCap N]]  with --doPooled --outputRealignedBAM (and no --doDiploid): the device also picks the haplotype each read is
+//                     realigned to (the pooled rule is compares alone, so its choice is the host's bit for bit) and only that pair's CIGAR comes
+//                     back: 4 N + 16 bytes per READ instead of --deviceCigars' H (4 N + 12).  Reads over N operations are redone on the host as
+//                     with --deviceCigars.  The files are the same byte for byte.  Refused with --doDiploid (the files that stay are then the
+//                     diploid step's, whose haplotype pair the host computes after the batch has left the device) and with --faster; no
+//                     effect without --outputRealignedBAM.  Wins over --deviceCigars
 //   [--discover]      no --varFile: the run starts with the discovery stage (host/discover.hpp) on --devices[0] — candidate indels from the CIGARs
 //                     of --bamFile (or, with --tid NAME --region A-B, of every file of --bamFiles), each realigned on the device, to
 //                     PREFIX.variants.txt and PREFIX.libraries.txt exactly as `dindel_candidates --analysis getCIGARindels` writes them
@@ -175,7 +181,7 @@ struct Options {
     long computeAhead;
     std::vector<int> devices;            // --devices 0,1,...: the engines are dealt out over these GPUs (batches are independent: no exchange between devices)
     bool faster, oneBased, prepareOnly, quiet, timing, longWindows, longWindowsFaster, noLookBack, lateSkipsKnown, windowByWindow;
-    bool realignedBAM, deviceCigars;
+    bool realignedBAM, deviceCigars, deviceRealign;
     bool doPooled, doDiploid, hostEM;    // --doPooled: the pooled lines; the diploid lines too with --doDiploid, or when --doPooled is not given
     PooledParameters pool;               // --bayesa0, --bayesType
     bool keepAlignments;                 // the per-base alignments come back from the device (--faster; --outputRealignedBAM without --deviceCigars)
@@ -223,6 +229,9 @@ const char *const kHelp =
     "                             per-base alignments (same files); [--cigarOpsCap N] operations kept per read (default 8), reads with more\n"
     "                             are redone on the host, which recomputes their whole window with alignments once (one window at a time:\n"
     "                             a small N makes that the run's bottleneck); no effect without --outputRealignedBAM\n"
+    "            [--deviceRealign]  with --doPooled --outputRealignedBAM: the device also picks each read's haplotype (pooled rule) and brings back that\n"
+    "                             pair's CIGAR alone (same files; [--cigarOpsCap N] as above); refused with --doDiploid and with --faster; no effect\n"
+    "                             without --outputRealignedBAM\n"
     "            [--longWindows]  compute windows with a haplotype > 766 bp or a read > 1024 bp (up to 4,094 / 4,096; with --maxLengthIndel >= 12\n"
     "                             also haplotypes > 574 bp) instead of skipping them; main model only: no effect with --faster\n"
     "            [--longWindowsFaster]  with --faster: compute windows with a haplotype > 766 bp or a read > 1024 bp (up to 4,094 / 4,096) instead of\n"
@@ -234,7 +243,7 @@ const char *const kHelp =
     "  files:    --varFile: the reference's window file; --hapFile: W / H / V / A records (host/window_io.hpp)\n";
 // the options without a value; any other --NAME takes the next argument as its value, whatever its name
 const char *const kFlags[] = {"varFileIsOneBased", "faster", "filterHaplotypes", "quiet", "doDiploid", "timing", "outputRealignedBAM", "prepareOnly", "noLookBack",
-                              "lateSkipsKnown", "windowByWindow", "doPooled", "hostEM", "longWindows", "longWindowsFaster", "deviceCigars", "changeINStoN", "hostDistribution", "hostConvert", "discover", "useLibraries", "vcfCandidatesOnly"};
+                              "lateSkipsKnown", "windowByWindow", "doPooled", "hostEM", "longWindows", "longWindowsFaster", "deviceCigars", "deviceRealign", "changeINStoN", "hostDistribution", "hostConvert", "discover", "useLibraries", "vcfCandidatesOnly"};
 
 std::vector<int> commaInts(const std::string &list)      // "3,5,,8" -> 3 5 8
 {
@@ -267,6 +276,8 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     auto has = [&](const char *k) { return opt.find(k) != opt.end(); };
     auto num = [&](const char *k, double dflt) { return has(k) ? atof(opt[k].c_str()) : dflt; };
     exitCode = 1;
+    if (has("deviceRealign") && has("doDiploid")) { std::cerr << "--deviceRealign cannot be given with --doDiploid: the realigned BAMs that stay are then the diploid step's, whose haplotype pair is computed on the host\n"; return false; }
+    if (has("deviceRealign") && has("faster")) { std::cerr << "--deviceRealign cannot be given with --faster: realigned BAMs are written by the main model only\n"; return false; }
     o.discover = has("discover");
     for (const char *need : {"varFile", "outputFile"})
         if (!has(need) && !(o.discover && !strcmp(need, "varFile"))) { std::cerr << "Please specify --" << need << "\n"; return false; }
@@ -322,6 +333,9 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     o.realignedBAM = has("outputRealignedBAM") && !o.faster;                      // `params.outputRealignedBAM && params.slower`, :589
     o.deviceCigars = o.realignedBAM && has("deviceCigars");                       // modifies --outputRealignedBAM only
     o.doPooled = has("doPooled"); o.doDiploid = has("doDiploid") || !o.doPooled; o.hostEM = has("hostEM");
+    if (has("deviceRealign") && o.realignedBAM && !o.doPooled) { std::cerr << "--deviceRealign needs --doPooled: it realigns by the pooled analysis' rule\n"; return false; }
+    o.deviceRealign = o.realignedBAM && has("deviceRealign");                     // modifies --doPooled --outputRealignedBAM only
+    if (o.deviceRealign) o.deviceCigars = false;
     o.pool.a0 = num("bayesa0", o.pool.a0);
     if (has("bayesType")) o.pool.bayesType = opt["bayesType"];
     if (o.doPooled && !knownBayesType(o.pool.bayesType)) { std::cerr << "Unknown EM option" << std::endl; return false; }          // DInDel.cpp:2287-2288
@@ -339,7 +353,7 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
         if (has("pooledGlf")) o.pooledGlfFile = opt["pooledGlf"];
         try { o.pooledVcf.numSamples = int(pytext::pyInt(opt["numSamples"])); } catch (const std::string &e) { std::cerr << "--numSamples: " << e << "\n"; return false; }
     }
-    o.keepAlignments = o.faster || (o.realignedBAM && !o.deviceCigars);           // (the --faster model's indel count, DInDel.cpp:3529, needs hpos)
+    o.keepAlignments = o.faster || (o.realignedBAM && !o.deviceCigars && !o.deviceRealign);           // (the --faster model's indel count, DInDel.cpp:3529, needs hpos)
     o.cigarOpsCap = std::max(1, int(num("cigarOpsCap", 8)));
     ObservationModelParameters &obs = o.obs;
     obs.setCLIDefaultValues();
@@ -456,7 +470,7 @@ private:
     // ---- what the summary and --timing print.  Per-thread slots are written by their thread and summed after the joins. ----
     struct Counters {
         Counters(size_t np, size_t nc) : prepareOf(np, 0.0), computeOf(nc, 0.0), pooledOf(nc, 0.0), packOf(nc, 0.0), deviceOf(nc, 0.0), unpackOf(nc, 0.0), readyAt(nc, 0.0),
-            reduce(0.0), reduceWork(0.0), launches(0), cigarFallbacks(0), hposBytes(0), cigarBytes(0), fallbackHposBytes(0), windows(0), skipped(0), rePrepared(0) {}
+            reduce(0.0), reduceWork(0.0), launches(0), cigarFallbacks(0), hposBytes(0), cigarBytes(0), fallbackHposBytes(0), realignBytes(0), windows(0), skipped(0), rePrepared(0) {}
         std::vector<double> prepareOf, computeOf, pooledOf, packOf, deviceOf, unpackOf;
         std::vector<double> readyAt;           // when each engine had its device context, arena and streams
         double reduce;                         // the writer's busy time
@@ -464,6 +478,7 @@ private:
         std::atomic<long> launches;            // engine calls with at least one job
         std::atomic<long> cigarFallbacks;      // reads redone with getCIGAR on the host (--deviceCigars)
         std::atomic<long long> hposBytes, cigarBytes, fallbackHposBytes;   // what the engines brought back from the device
+        std::atomic<long long> realignBytes;   // ... of the realigned reads' arrays (--deviceRealign)
         long windows, skipped, rePrepared;     // the writer's
         std::vector<std::pair<double, long> > progress;   // the writer's: (seconds since start, windows written) after every batch
     } n;
@@ -541,6 +556,7 @@ void WindowLoop::configureStageEngine(LikelihoodEngine &engine) const
     engine.setThrowOnPositiveLikelihood(false);
     engine.setKeepAlignments(opt.keepAlignments);
     engine.setDeviceCigars(opt.deviceCigars, opt.cigarOpsCap);
+    engine.setDeviceRealign(opt.deviceRealign, opt.cigarOpsCap);
     engine.setLongWindows(opt.longWindows);
     engine.setLongWindowsFaster(opt.longWindowsFaster);
 }
@@ -766,7 +782,7 @@ void WindowLoop::computeWorker(int ct)
                     n.pooledOf[size_t(ct)] += seconds_since(p0);
                 }
                 n.packOf[size_t(ct)] += engine.lastPackSeconds; n.deviceOf[size_t(ct)] += engine.lastDeviceSeconds; n.unpackOf[size_t(ct)] += engine.lastUnpackSeconds;
-                n.hposBytes += (long long)engine.lastHposBytes; n.cigarBytes += (long long)engine.lastCigarBytes;
+                n.hposBytes += (long long)engine.lastHposBytes; n.cigarBytes += (long long)engine.lastCigarBytes; n.realignBytes += (long long)engine.lastRealignBytes;
                 n.launches++;
             }
             n.computeOf[size_t(ct)] += seconds_since(t0);
@@ -914,7 +930,7 @@ void WindowLoop::rePrepare(WindowTask &T)
         }
         one.push_back(T.job());
         if (opt.faster) redo.engine->computeLikelihoodsFasterBatch(one); else redo.engine->computeLikelihoodsBatch(one);
-        n.hposBytes += (long long)redo.engine->lastHposBytes; n.cigarBytes += (long long)redo.engine->lastCigarBytes;
+        n.hposBytes += (long long)redo.engine->lastHposBytes; n.cigarBytes += (long long)redo.engine->lastCigarBytes; n.realignBytes += (long long)redo.engine->lastRealignBytes;
     }
     reduceWindow(T, one.empty() ? NULL : &one[0]);
     redo.fetcher->windowDone(T.skipped, T.fileLeftPos);
@@ -1087,6 +1103,7 @@ void WindowLoop::report()                                 // --timing: one line;
     // and the alignment bytes those windows' recomputation brought back
     std::cout << " hpos_bytes=" << n.hposBytes.load() << " cigar_bytes=" << n.cigarBytes.load() << " cigar_host_fallbacks=" << n.cigarFallbacks.load()
               << " fallback_hpos_bytes=" << n.fallbackHposBytes.load();
+    if (opt.deviceRealign) std::cout << " realign_bytes=" << n.realignBytes.load();
     // when the first batch and the first 1 / 5 / 20 / 50 / 100 % of the windows were written (seconds since start)
     std::cout << " engines_ready_at=";
     for (size_t i = 0; i < n.readyAt.size(); i++) std::cout << (i ? "," : "") << n.readyAt[i];

@@ -120,3 +120,39 @@ extern "C" int ddh_pooled_realigned_cigars(const double *ll, int H, int R, const
         return 0;
     } catch (const std::string &) { return -1; }
 }
+
+// pooledDeviceRealignedCigars (and pooledRealignedCigars, which hands such views on to it) on a hand-made view of the realigned reads
+// (WindowLikelihoods::handMadeRealign): R reads of readLen bases, H haplotypes of hapLen bases, haplotype h on the reference at offset
+// 10 h base for base.  Per read the rows the device would deliver: hap, status, nOps, ops [R * opsCap], refOff.  hpos [H * R * readLen]
+// is what withAlignments() has at hand (haplotype-major, MLAlignment codes); NULL: nothing is at hand.  Out per read: numOps, refPos and
+// the first maxOps BAM words; *fallbacks counts the reads redone on the host.  Returns 0, or -1 with the thrown string in err.
+extern "C" int ddh_pooled_device_realigned_cigars(int H, int R, int readLen, int hapLen, int opsCap, const int32_t *hap, const int32_t *status,
+                                                  const int32_t *nOps, const uint32_t *ops, const int32_t *refOff, const int16_t *hpos, int refSeqPos,
+                                                  int *numOps, int *refPos, uint32_t *opsOut, int maxOps, long *fallbacks, char *err, int errLen)
+{
+    try {
+        std::vector<Haplotype> haps;
+        for (int h = 0; h < H; h++) {
+            haps.push_back(Haplotype(std::string(size_t(hapLen), 'A')));
+            for (int i = 0; i < hapLen; i++) haps.back().refHpos.push_back(10 * h + i);
+        }
+        std::vector<Read> reads;
+        reads.resize(size_t(R));
+        for (int r = 0; r < R; r++) { reads[size_t(r)].seq = Haplotype(std::string(size_t(readLen), 'A')); reads[size_t(r)].setAllQual(0.99); }
+        const WindowLikelihoods view = WindowLikelihoods::handMadeRealign(haps, reads, opsCap, hap, status, nOps, ops, refOff, NULL);
+        std::function<WindowLikelihoods()> withAlignments;
+        if (hpos) withAlignments = [&]() { return WindowLikelihoods::handMadeRealign(haps, reads, opsCap, NULL, NULL, NULL, NULL, NULL, hpos); };
+        std::vector<CIGAR> cigars;
+        *fallbacks = 0;
+        pooledRealignedCigars(haps, reads, view, refSeqPos, cigars, withAlignments, fallbacks);
+        for (int r = 0; r < R; r++) {
+            const CIGAR &c = cigars[size_t(r)];
+            numOps[r] = int(c.size()); refPos[r] = c.refPos;
+            for (int i = 0; i < maxOps; i++) opsOut[r * maxOps + i] = size_t(i) < c.size() ? (uint32_t(c[size_t(i)].second) << 4) | uint32_t(c[size_t(i)].first) : 0u;
+        }
+        return 0;
+    } catch (const std::string &e) {
+        if (err && errLen > 0) { strncpy(err, e.c_str(), size_t(errLen) - 1); err[errLen - 1] = 0; }
+        return -1;
+    }
+}

@@ -52,17 +52,19 @@ void realignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read>
 }
 
 namespace {
-// The CIGAR of pair (h, r) from the device's result block; a read over the batch's cap (DD_CIGAR_OVERFLOW, or a pair the device did not
-// compute) on the host, from the window's alignments, which `full` keeps once they were asked for.
-CIGAR deviceCigarOf(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, size_t h, size_t r, int refSeqPos,
-                    WindowLikelihoods &full, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks)
+// One row of a device result block — the per-pair CIGARs' (setDeviceCigars) or the realigned reads' (setDeviceRealign) — as the CIGAR of
+// pair (h, r); a read over the batch's cap (DD_CIGAR_OVERFLOW, or a pair the device did not compute) on the host, from the window's
+// alignments, which `full` keeps once they were asked for.
+struct DeviceCigarRow { int status, n; const uint32_t *ops; int refOff; };
+CIGAR cigarOfRow(const DeviceCigarRow &row, const std::vector<Haplotype> &haps, const std::vector<Read> &reads, size_t h, size_t r, int refSeqPos,
+                 WindowLikelihoods &full, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks)
 {
     static const char *const thrown[] = {"", "Haplotype has not been aligned!", "Error(1)!", "Error(2)!", "Error(3)!", "Error(4)!", "How is this possible? (1)"};
-    const int st = liks.cigarStatus(h, r);
+    const int st = row.status;
     if (st >= DD_CIGAR_HAP_NOT_ALIGNED && st <= DD_CIGAR_IMPOSSIBLE) throw std::string(thrown[st]);
     if (st == DD_CIGAR_OK) {
-        const uint32_t *ops = liks.cigarOps(h, r);
-        const int n = liks.cigarNumOps(h, r), off = liks.cigarRefOff(h, r);
+        const uint32_t *ops = row.ops;
+        const int n = row.n, off = row.refOff;
         CIGAR c;
         for (int i = 0; i < n; i++) c.push_back(CIGAR::CIGOp(int(ops[i] & 15u), int(ops[i] >> 4)));
         c.refPos = off < 0 ? -1 : refSeqPos + off;                                           // no aligned base: refPos stays -1
@@ -75,6 +77,12 @@ CIGAR deviceCigarOf(const std::vector<Haplotype> &haps, const std::vector<Read> 
     const CIGAR c = getCIGAR(haps[h].refHpos, haps[h].size(), full.get(h, r), reads[r].size(), refSeqPos);
     if (hostFallbacks) ++*hostFallbacks;
     return c;
+}
+CIGAR deviceCigarOf(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, size_t h, size_t r, int refSeqPos,
+                    WindowLikelihoods &full, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks)
+{
+    const DeviceCigarRow row = {liks.cigarStatus(h, r), liks.cigarNumOps(h, r), liks.cigarOps(h, r), liks.cigarRefOff(h, r)};
+    return cigarOfRow(row, haps, reads, h, r, refSeqPos, full, withAlignments, hostFallbacks);
 }
 }
 
@@ -122,10 +130,27 @@ void pooledRealignedCigars(const std::vector<Haplotype> &haps, const std::vector
 void pooledRealignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, int refSeqPos,
                            std::vector<CIGAR> &cigars, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks)
 {
+    if (liks.hasDeviceRealign()) { pooledDeviceRealignedCigars(haps, reads, liks, refSeqPos, cigars, withAlignments, hostFallbacks); return; }
     if (!liks.hasDeviceCigars()) { pooledRealignedCigars(haps, reads, liks, refSeqPos, cigars); return; }
     WindowLikelihoods full;
     pooledRealignedCigars(haps.size(), reads.size(), [&](size_t h, size_t r) { return liks.ll(h, r); }, [&](size_t r) { return liks.onHap(r) != 0; },
                           [&](size_t h, size_t r) { return deviceCigarOf(haps, reads, liks, h, r, refSeqPos, full, withAlignments, hostFallbacks); }, cigars);
+}
+
+void pooledDeviceRealignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, int refSeqPos,
+                                 std::vector<CIGAR> &cigars, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks)
+{
+    if (!liks.hasDeviceRealign()) throw std::string("pooledDeviceRealignedCigars: the batch was run without device realign");
+    cigars.assign(reads.size(), CIGAR());                                                    // :502
+    WindowLikelihoods full;
+    for (size_t r = 0; r < reads.size(); r++) {                                              // reads in order: a throw is the first read's that throws
+        const int st = liks.realignStatus(r);
+        if (st == DD_REALIGN_OFF_HAP || st == DD_REALIGN_NO_HAPS) continue;                  // :504 (without haplotypes no read is on one)
+        const int h = liks.realignHap(r);
+        if (st == DD_REALIGN_BAD_PAIR || h < 0 || size_t(h) >= haps.size()) throw std::string("pooledDeviceRealignedCigars: no haplotype was chosen for a read");
+        const DeviceCigarRow row = {st, liks.realignNumOps(r), liks.realignOps(r), liks.realignRefOff(r)};
+        cigars[r] = cigarOfRow(row, haps, reads, size_t(h), r, refSeqPos, full, withAlignments, hostFallbacks);   // :511
+    }
 }
 
 std::string realignedBAMFileName(const std::string &prefix, int index, const std::string &tid, uint32_t leftPos, uint32_t rightPos, int minReadOverlap)

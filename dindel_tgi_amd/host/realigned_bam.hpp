@@ -43,6 +43,13 @@ void pooledRealignedCigars(const std::vector<Haplotype> &haps, const std::vector
 // batch's cap redone on the host from `withAlignments()` and counted in *hostFallbacks.  Without device CIGARs in `liks`: the function above.
 void pooledRealignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, int refSeqPos,
                            std::vector<CIGAR> &cigars, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks);
+// The same from the realigned reads the device chose (LikelihoodEngine::setDeviceRealign, liks.hasDeviceRealign(); the function above calls
+// this for such a view): reads in order, haplotype liks.realignHap(r) and its CIGAR straight from the view.  DD_REALIGN_OFF_HAP (and a
+// window without haplotypes) leaves the empty CIGAR, a throw code raises getCIGAR's string, DD_CIGAR_OVERFLOW and DD_CIGAR_NOT_COMPUTED are
+// redone with getCIGAR for that haplotype from `withAlignments()` and counted in *hostFallbacks — the status table and the fallback are
+// the ones of the per-pair device CIGARs.  Nothing of the choice is restated here.
+void pooledDeviceRealignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, int refSeqPos,
+                                 std::vector<CIGAR> &cigars, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks);
 // What both are made of: the choice per read from ll(h, r) and onHap(r), the CIGAR of the chosen pair from cigarOf(h, r).
 void pooledRealignedCigars(size_t numHaps, size_t numReads, const std::function<double(size_t, size_t)> &ll, const std::function<bool(size_t)> &onHap,
                            const std::function<CIGAR(size_t, size_t)> &cigarOf, std::vector<CIGAR> &cigars);

@@ -451,6 +451,55 @@ int dd_cigars_device(const dd_device_batch *b, const int16_t *hpos_dev, const in
 int dd_compute_likelihoods_cigars(const dd_params *p, const dd_batch *b, dd_result *r, const int32_t *hap_ref_pos, const uint8_t *hap_aligned,
                                   const dd_cigar_result *cig, int ops_cap, int device, uint32_t options);
 
+/* ---- realigned reads: per-read haplotype choice and CIGAR on the device (opt-in) ------------ */
+/* Which haplotype a read is realigned to, and that pair's CIGAR, chosen on the device from the ll / onHap / hpos the likelihood kernels
+ * left there: 4 * ops_cap + 16 bytes per read come back instead of H * (4 * ops_cap + 12).  Both rules are compares and selects (no exp,
+ * no log) and equal the host's (host/realigned_bam.cpp) bit for bit.  Read q is read r of window w with H haplotypes and R reads;
+ * pair(h) = win_pair_off[w] + h * R + r, g(h) = win_hap_off[w] + h.
+ *   DD_REALIGN_FIRST_MAX  the pooled rule (reference DInDel.cpp:503-511): on_hap[q] == 0 (when on_hap is given) chooses nothing
+ *                         (DD_REALIGN_OFF_HAP, hap -1, n_ops 0, ref_off -1, ops row not written); otherwise the first h whose ll is
+ *                         strictly greater than the running maximum, starting from -inf; h = 0 when none compares greater (all -inf; NaN
+ *                         never compares greater)
+ *   DD_REALIGN_PAIR       the diploid rule (DInDel.cpp:596-610): h1 = win_hap_pair[2w], h2 = win_hap_pair[2w+1]; either outside [0, H)
+ *                         gives every read of the window DD_REALIGN_BAD_PAIR and hap -1.  If fabs(ll[pair(h1)] - ll[pair(h2)]) < 1e-8:
+ *                         h1 when hap_n_indels[g(h1)] < hap_n_indels[g(h2)], else h2; otherwise h1 when ll[pair(h1)] > ll[pair(h2)],
+ *                         else h2 (NaN and -inf - -inf fall to h2).  on_hap is not consulted
+ * A window with reads and no haplotype gives DD_REALIGN_NO_HAPS.  For a chosen pair, hap is its haplotype's index inside the window and
+ * status, n_ops, ops and ref_off are exactly what dd_cigars_device writes for that pair (DD_CIGAR_NOT_COMPUTED, the throw codes and
+ * DD_CIGAR_OVERFLOW included), at the read's index instead of the pair's. */
+typedef struct dd_realign_result {   /* per READ of the batch, in read order (win_read_off) */
+    int32_t  *hap;      /* [n_reads] chosen haplotype, index inside the window; -1 where none was chosen */
+    int32_t  *status;   /* [n_reads] DD_CIGAR_* of the chosen pair, or one of the DD_REALIGN_* below */
+    int32_t  *n_ops;    /* [n_reads] as dd_cigar_result.n_ops */
+    uint32_t *ops;      /* [n_reads * ops_cap] as dd_cigar_result.ops */
+    int32_t  *ref_off;  /* [n_reads] as dd_cigar_result.ref_off */
+} dd_realign_result;
+#define DD_REALIGN_OFF_HAP   9    /* FIRST_MAX mode: on_hap[read] == 0: nothing chosen, nothing walked */
+#define DD_REALIGN_BAD_PAIR 10    /* PAIR mode: the window's h1 or h2 is outside [0, H) */
+#define DD_REALIGN_NO_HAPS  11    /* the window has reads and no haplotype */
+#define DD_REALIGN_FIRST_MAX 0    /* DInDel.cpp:503-511 */
+#define DD_REALIGN_PAIR      1    /* DInDel.cpp:596-610 */
+/* Enqueue the realign launch for the whole batch on `stream`, behind the likelihood launch(es) that wrote ll, onHap, status and hpos (any
+ * of the four, as for dd_cigars_device).  All DEVICE pointers:
+ *   ll_dev            dd_result.ll
+ *   on_hap_dev        dd_result.onHap, one byte per read (FIRST_MAX; NULL = every read is on a haplotype; not read in PAIR mode)
+ *   win_hap_pair_dev  [2 * n_windows] the window's haplotype pair (PAIR mode, required there)
+ *   hap_n_indels_dev  [n_haps] Haplotype::countIndels() per haplotype of the batch (PAIR mode, required there)
+ *   hpos_dev, status_dev, hap_ref_pos_dev, hap_aligned_dev, ops_cap   as for dd_cigars_device
+ *   out_dev           device arrays, every one required
+ * Of the batch it reads what dd_cigars_device reads, and n_reads.  Asynchronous, no allocation. */
+int dd_realign_device(const dd_device_batch *b, int mode, const double *ll_dev, const uint8_t *on_hap_dev,
+                      const int32_t *win_hap_pair_dev, const int32_t *hap_n_indels_dev,
+                      const int16_t *hpos_dev, const int32_t *status_dev, const int32_t *hap_ref_pos_dev,
+                      const uint8_t *hap_aligned_dev, const dd_realign_result *out_dev, int ops_cap, void *stream);
+/* Host pointers: dd_compute_likelihoods_ex (options: 0 or DD_OPT_LONG_WINDOWS) followed by the realign launch; out's arrays (host memory)
+ * are filled.  win_hap_pair and hap_n_indels are required in PAIR mode only; FIRST_MAX consults r->onHap when the caller asks for it.
+ * r->hpos may be NULL.  Everything else as dd_compute_likelihoods_cigars. */
+int dd_compute_likelihoods_realign(const dd_params *p, const dd_batch *b, dd_result *r, int mode,
+                                   const int32_t *win_hap_pair, const int32_t *hap_n_indels,
+                                   const int32_t *hap_ref_pos, const uint8_t *hap_aligned,
+                                   const dd_realign_result *out, int ops_cap, int device, uint32_t options);
+
 /* ---- alignHaplotypes: candidate haplotypes against the window's reference sequence ---------- */
 /* The arithmetic of DetInDel::alignHaplotypes (reference DInDel.cpp:1427-1524): SeqAn's globalAlignment with
  * Score<int>(-1, -460, -100, -960) and no free end gaps, i.e. _align_gotoh / _align_gotoh_trace of seqan/graph_align/graph_align_gotoh.h,

@@ -7,7 +7,7 @@ per window drawn from the reference and one variant haplotype (a heterozygous si
     python tools/n2_pipeline_bench.py [--windows 2000] [--reads 200] [--batch 256] [--dir /tmp/n2bench] [--faster]
     python tools/n2_pipeline_bench.py --realigned [--device-cigars] [--reps 3] [--driver PATH/dindel_gpu]
 --realigned adds --outputRealignedBAM (one BAM per window next to the .glf.txt; their bytes go into the md5), --device-cigars the driver's
---deviceCigars; --driver times another build of the driver (e.g. the parent commit's) on the same files.
+--deviceCigars, --device-realign its --deviceRealign (which needs --extra=--doPooled); --driver times another build of the driver (e.g. the parent commit's) on the same files.
 """
 import argparse
 import hashlib
@@ -35,6 +35,7 @@ ap.add_argument("--vcf", action="store_true", help="afterwards: dindel_glf2vcf o
 ap.add_argument("--ragged", action="store_true", help="windows of 90-330 bp, 2-12 haplotypes, 20-400 reads of 60-150 bp each (default: uniform 120 bp / 8 / 200 x 100 bp)")
 ap.add_argument("--realigned", action="store_true", help="run with --outputRealignedBAM")
 ap.add_argument("--device-cigars", action="store_true", help="with --realigned: the driver's --deviceCigars")
+ap.add_argument("--device-realign", action="store_true", help="with --realigned and --extra=--doPooled: the driver's --deviceRealign")
 ap.add_argument("--reps", type=int, default=2, help="runs per configuration")
 ap.add_argument("--driver", default="", help="path of the dindel_gpu to time (default: this tree's)")
 ap.add_argument("--procs", type=int, default=min(16, os.cpu_count() or 1), help="processes writing the sample")
@@ -218,7 +219,7 @@ if args.sweep:
                for f in ([], ["--faster"]) for (b, c, p, r, k) in ((256, 2, 6, 6, 4), (256, 2, 8, 4, 4), (256, 2, 10, 4, 4), (128, 2, 8, 4, 4), (256, 3, 8, 4, 2))]
 else:
     configs = [["--batchWindows", str(args.batch)] + (["--faster"] if args.faster else []) + (["--outputRealignedBAM"] if args.realigned else []) +
-               (["--deviceCigars"] if args.device_cigars else []) + args.extra.split()]
+               (["--deviceCigars"] if args.device_cigars else []) + (["--deviceRealign"] if args.device_realign else []) + args.extra.split()]
 for cfg in configs:
     for rep in range(args.reps):
         for old in [f for f in os.listdir(args.dir) if f.startswith("out.ra.")]:
