@@ -1,5 +1,6 @@
-// host_path.cpp — the host-pointer entry points of the C ABI: the per-thread device arena and stream cache, validation, staging,
-// chunked double-buffered execution, and the front end for several devices of one process.
+// host_path.cpp — the host-pointer entry points of the C ABI: the per-thread device arena and stream cache; one call as a sequence of stages
+// (HostCall: check and screen, plan, list the inputs and outputs, reserve what the lists add up to, upload, cut window blocks, enqueue and
+// collect chunked and double-buffered, drain on error); and the front end for several devices of one process.
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -75,12 +76,14 @@ struct DevBuf {
     bool staged = false;
     explicit DevBuf(DeviceCtx &c) : C(c) {}
     static size_t align(size_t v) { return (v + 255u) & ~size_t(255u); }
+    // where an array of `bytes` placed behind `at` ends: alloc's own arithmetic, for a caller that adds up what it is going to place
+    static size_t end_of(size_t at, size_t bytes) { return align(at) + (bytes ? bytes : 1); }
     template <class T> int alloc(T **out, size_t n)
     {
-        const size_t off = align(used), bytes = (n ? n : 1) * sizeof(T);
-        if (off + bytes > C.arena_cap) return fail(DD_ERR_HIP, "internal: device arena under-sized");
-        used = off + bytes;
-        *out = reinterpret_cast<T *>(C.arena + off);
+        const size_t end = end_of(used, n * sizeof(T));
+        if (end > C.arena_cap) return fail(DD_ERR_HIP, "internal: device arena under-sized");   // (of last resort: callers reserve what they place)
+        *out = reinterpret_cast<T *>(C.arena + align(used));
+        used = end;
         return DD_SUCCESS;
     }
     template <class T> int upload(const T **out, const T *src, size_t n)
@@ -192,275 +195,373 @@ struct StageClock {
     ~StageClock() { if (on) fprintf(stderr, "dd_timing:%s\n", line.c_str()); }
 };
 
-// dd_compute_likelihoods_cigars: the haplotypes' reference positions in, the pairs' CIGARs out (host pointers)
-// dd_compute_likelihoods_realign: the same inputs, the window pairs and indel counts of its PAIR mode, and per READ the chosen haplotype with
-// its CIGAR out (rl != nullptr: the per-pair arrays of `out` are then neither allocated nor filled)
-struct RealignRequest {
-    int mode; const int32_t *win_hap_pair, *hap_n_indels;
-    dd_realign_result out;
+// One array of a call in the device arena: its bytes, the pointer variable that takes its device address, and for an input the host array
+// that is copied there.  A call lists every array it places before it touches the device, and the bytes it reserves are added up from those
+// lists (HostCall::end_of_all): there is no size formula to keep in step with them.
+struct ArenaSlot {
+    size_t bytes;
+    const unsigned char *src;                           // inputs: the host array (NULL: the array is only reserved)
+    void *var; void (*set)(void *var, void *dev);       // the variable, written through its own type
+    bool read_bases;                                    // read_seq / read_qidx, the two big inputs (HostCall::reserve_and_upload)
+    void point_at(const void *dev) const { set(var, const_cast<void *>(dev)); }
 };
-struct CigarRequest {
-    const int32_t *hap_ref_pos; const uint8_t *hap_aligned;
-    dd_cigar_result out; int ops_cap;
-    const RealignRequest *rl;
-};
-
-int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options = 0,
-                             const CigarRequest *cg = nullptr)
+template <class P> ArenaSlot arena_slot(P *var, size_t bytes, const void *src = nullptr, bool read_bases = false)
 {
+    return {bytes, static_cast<const unsigned char *>(src), var, [](void *v, void *dev) { *static_cast<P *>(v) = static_cast<P>(dev); }, read_bases};
+}
+
+// One output array of a call: a field of dd_result, dd_cigar_result or dd_realign_result.  Placement in the arena, the in-place decision, the
+// per-block download and the staged copy-back are written once, over the call's list of these.
+struct OutArray {
+    void *host;                  // the caller's array: part of the copy back (NULL: not asked for)
+    size_t elem;                 // bytes per element
+    ResultSpace space;           // its index space
+    size_t width;                // elements per index (ops: ops_cap)
+    bool in_place;               // page-locked caller memory is written by the kernels themselves
+    bool device_only;            // no caller array, yet a kernel of this call reads it: placed behind the copy-back region, never copied
+    ArenaSlot slot;              // its bytes, and the field of the device-side struct that takes its address
+    unsigned char *dev = nullptr;
+    bool direct = false;         // placement found `host` page-locked and device-addressable: dev is its device address
+    bool copied_back() const { return host && !direct; }
+};
+#define OUT_INDEX(f, space, in_place) OUT_##f,
+enum { DD_RESULT_FIELDS(OUT_INDEX) N_RESULT_OUTS };    // a dd_result field's place in the list
+#undef OUT_INDEX
+
+// What a CIGAR or realign entry adds to a call: inputs of its own, per window block one launch behind the likelihood launches, and output
+// arrays in one index space (per PAIR: dd_compute_likelihoods_cigars; per READ: dd_compute_likelihoods_realign, which takes the window pairs
+// and indel counts of its PAIR mode besides).
+struct ExtraRequest {
+    const int32_t *hap_ref_pos; const uint8_t *hap_aligned; int ops_cap;
+    bool realign;
+    dd_cigar_result cigars;                                                       // !realign
+    int mode; const int32_t *win_hap_pair, *hap_n_indels; dd_realign_result reads; // realign
+};
+
+// One call of a host-pointer entry.  run() is the sequence of its stages; the members are grouped by the stage that fills them.
+struct HostCall {
+    const Model model; const dd_params *const p; const dd_batch *const b; dd_result *const r; const int device; const uint32_t options;
+    const ExtraRequest *const x;
     StageClock clk;
-    launch_log_clear();
-    g_long.log.clear();
-    g_flong.log.clear();
     dd_sizes sz;
-    int rc = front_checks(p, b, r, sz);
-    if (!rc && sz.n_pairs == 0 && cg && cg->rl)              // reads without haplotypes: no pair, nothing to launch, every read marked
-        for (int64_t q = 0; q < sz.n_reads; q++) {
-            const dd_realign_result &o = cg->rl->out;
-            o.hap[q] = -1; o.status[q] = DD_REALIGN_NO_HAPS; o.n_ops[q] = 0; o.ref_off[q] = -1;
-        }
-    if (rc || sz.n_pairs == 0) return rc;
-    // validate content
-    if (!b->hap_seq || !b->read_seq || !b->read_qidx || !b->read_mqidx || !b->read_start || !b->read_flags ||
-        !b->win_hap_start || !b->qual_table || !b->mapq_table)
-        return fail(DD_ERR_INVALID, "null input array");
-    if (b->n_qual < 1 || b->n_qual > DD_MAX_QUAL_TABLE || b->n_mapq < 1 || b->n_mapq > DD_MAX_QUAL_TABLE)
-        return fail(DD_ERR_INVALID, "quality tables must hold 1..256 entries");
-    // windows whose shape the kernels do not cover are skipped one by one (DD_PAIR_UNSUPPORTED), not the batch
-    std::vector<uint8_t> win_skip((size_t)b->n_windows);
-    int32_t ok_max[2] = {0, 0};
-    if (!b->hap_seq_off || !b->read_seq_off) return fail(DD_ERR_INVALID, "null offset array");
+    // check_and_screen
+    std::vector<uint8_t> win_skip;
     uint8_t sym_lut[256];
-    const int sym_left = assign_symbols(b, sym_lut);     // > 0: more than 26 distinct non-ACGTN haplotype bytes in the batch
-    if (sym_left < 0) return sym_left;
-    clk.mark("symbols");
-    // long windows (DD_OPT_LONG_WINDOWS): win_skip holds the classes; the main kernels skip both non-zero classes, the long launch that
-    // follows each block's main launches computes class 2
-    // (DD_OPT_LONG_WINDOWS_FASTER: the same for the --faster model, with its own classes and its own kernel)
-    const bool fl_on = model == MODEL_S && (options & DD_OPT_LONG_WINDOWS_FASTER);
-    const bool long_on = (model == MODEL_FBMAXERR && (options & DD_OPT_LONG_WINDOWS)) || fl_on;
-    LongPath &long_path = fl_on ? g_flong : g_long;           // the model's long path (used only if long_on)
+    int n_skip = 0;
+    bool long_on = false;
+    LongPath *long_path = nullptr;                       // the model's long path (used only if long_on)
     int32_t long_max[4] = {0, 0, 0, 0};
-    int n_skip;
-    if (long_on) {
-        n_skip = screen_windows_ex(p, b, options, win_skip.data(), long_max, sym_lut, sym_left > 0);
-        ok_max[0] = long_max[0]; ok_max[1] = long_max[1];
-        for (int w = 0; w < b->n_windows; w++) if (win_skip[(size_t)w] == DD_WIN_LONG) n_skip++;   // (counts every window the main kernels skip)
-    } else {
-        n_skip = screen_windows(b, win_skip.data(), ok_max, sym_lut, sym_left > 0 && model == MODEL_FBMAXERR);
-    }
-    sz.max_hap_len = ok_max[0] > 0 ? ok_max[0] : 1;      // planning maxima: the windows that are computed
-    sz.max_read_len = ok_max[1] > 0 ? ok_max[1] : 1;
-    clk.mark("screen");
     std::vector<double> lib_logprob, lib_log95;
-    if (p->mapUnmappedReads && model == MODEL_FBMAXERR) {
-        if (!b->read_mate_pos || !b->read_mate_len || !b->read_lib)
-            return fail(DD_ERR_INVALID, "mapUnmappedReads needs read_mate_pos, read_mate_len and read_lib");
-        if (b->n_libs < 1 || !b->lib_off) return fail(DD_ERR_INVALID, "mapUnmappedReads needs the library tables");
-        lib_logprob.resize((size_t)(b->lib_off[b->n_libs] > 0 ? b->lib_off[b->n_libs] : 1));
-        lib_log95.resize((size_t)b->n_libs);
-        if ((rc = dd_build_library_tables(b, lib_logprob.data(), lib_log95.data()))) return rc;
-        for (int64_t q = 0; q < sz.n_reads; q++)
-            if (b->read_lib[q] >= b->n_libs) return fail(DD_ERR_INVALID, "read_lib out of range");
-    }
-    if (any_at_or_above(b->read_mqidx, (size_t)sz.n_reads, (unsigned)b->n_mapq)) return fail(DD_ERR_INVALID, "read_mqidx out of range");
-    if (any_at_or_above(b->read_qidx, (size_t)sz.read_bases, (unsigned)b->n_qual)) return fail(DD_ERR_INVALID, "read_qidx out of range");
-    for (int i = 0; i < b->n_qual; i++)
-        if (!(b->qual_table[i] >= 0.0 && b->qual_table[i] <= 1.0)) return fail(DD_ERR_INVALID, "base quality outside [0,1]");
-    for (int i = 0; i < b->n_mapq; i++)
-        if (!(b->mapq_table[i] >= 0.0 && b->mapq_table[i] < 1.0)) return fail(DD_ERR_INVALID, "mapping quality outside [0,1)");
-
-    clk.mark("validate");
-    if ((rc = use_device(device, "no HIP device: the likelihood path has no CPU fallback"))) return rc;
-
-    const int W = b->n_windows;
-    std::vector<int32_t> hap_window((size_t)sz.n_haps);
-    std::vector<int64_t> pair_off(W + 1), hpos_off(W + 1), vc_off(W + 1);
-    dd_build_index(b, hap_window.data(), pair_off.data(), hpos_off.data(), vc_off.data());
-    std::vector<double> tables(DD_TABLE_DOUBLES);
-    rc = dd_build_tables(p, b->qual_table, b->n_qual, b->mapq_table, b->n_mapq, tables.data());
-    if (rc < 0) return rc;
-
-    // ---- host-side planning first (no device work yet): launch classes and scratch size ----
-    // Ragged batches: one launch per (lane tiling of the haplotypes, read-length interval) that has work (build_launch_classes) — a single
-    // 170-bp haplotype or 250-bp read does not drag every pair of the batch onto the K = 3 / long-read build.
-    dd_length_classes lcls;
-    std::vector<int32_t> class_list;
-    memset(&lcls, 0, sizeof(lcls));
-    if (model == MODEL_FBMAXERR && !getenv("DD_NO_LENGTH_CLASSES")) {                      // env: A/B only
-        class_list.resize((size_t)sz.n_haps * DD_N_READ_CLASSES + 1);
-        if ((rc = build_launch_classes(b, n_skip ? win_skip.data() : nullptr, p, class_list.data(), &lcls))) return rc;
-    }
-    const int32_t *class_list_dev = nullptr;
-    dd_device_batch db;
-    memset(&db, 0, sizeof(db));
-    db.n_windows = W; db.n_haps = (int32_t)sz.n_haps; db.n_reads = (int32_t)sz.n_reads;
-    db.max_hap_len = sz.max_hap_len; db.max_read_len = sz.max_read_len;
-    db.n_qual = b->n_qual; db.n_mapq = b->n_mapq;
-    for (int w = 0; w < W; w++)
-        if (!win_skip[(size_t)w] && b->win_read_off[w + 1] - b->win_read_off[w] > db.max_window_reads) db.max_window_reads = b->win_read_off[w + 1] - b->win_read_off[w];
-    size_t ws_bytes = model == MODEL_S ? 0 : dd_workspace_bytes(p, &db);
-    const bool single_class = lcls.n_launches <= 1;
-    if (!single_class) {
-        db.classes = &lcls;
-        db.hap_class_list = class_list.data();             // (host pointer: only dd_workspace_bytes' class walk looks at it here)
-        const size_t w2 = dd_workspace_bytes(p, &db);
-        if (w2 > ws_bytes) ws_bytes = w2;
-        db.classes = nullptr; db.hap_class_list = nullptr;
-    }
-
-    size_t lws_bytes = 0;                                   // long path: its own workspace per stream
-    if (long_on && long_max[2] > 0) {
-        db.long_max_hap_len = long_max[2]; db.long_max_read_len = long_max[3];
-        lws_bytes = long_path.workspace_bytes(p, &db);
-        if (!lws_bytes) return fail(DD_ERR_UNSUPPORTED, "long path: no plan for this shape");
-    }
-
-    clk.mark("plan");
-    // ---- device arena (cached per host thread) ----
-    const size_t np = (size_t)sz.n_pairs;
-    const size_t n_var = b->hap_var_off ? (size_t)b->hap_var_off[sz.n_haps] : 0;
-    const size_t in_bytes = (size_t)(W + 1) * (4 + 4 + 8 + 8 + 8) + (size_t)W * 4 + (size_t)(sz.n_haps + 1) * 8 + (size_t)sz.hap_bases +
-                            (size_t)(sz.n_reads + 1) * 4 + (size_t)sz.read_bases * 2 + (size_t)sz.n_reads * 6 + n_var * 20 +
-                            (size_t)sz.n_haps * 4 + (size_t)lcls.list_len * 4 + 64 + DD_TABLE_DOUBLES * 8 + 48 * 256 + (size_t)W + 256 +
-                            (lib_log95.empty() ? 0 : (size_t)sz.n_reads * 9 + (lib_logprob.size() + lib_log95.size()) * 8 + (size_t)(b->n_libs + 1) * 4);
-    const RealignRequest *rl = cg ? cg->rl : nullptr;
-    const size_t nr = (size_t)sz.n_reads;
-    const size_t cigar_in = cg ? (size_t)sz.hap_bases * 4 + (size_t)sz.n_haps + 2 * 256 + (rl ? (size_t)W * 8 + (size_t)sz.n_haps * 4 + 2 * 256 : 0) : 0;
-    const size_t cigar_out = !cg ? 0 : rl ? nr * (16 + 4 * (size_t)cg->ops_cap) + 5 * 256 : np * (12 + 4 * (size_t)cg->ops_cap) + 4 * 256;
-    const size_t out_bytes = np * (4 * 8 + 2 + 8 * 2 + 4) + (size_t)sz.hpos_len * 2 + 2 * (size_t)sz.var_cov_len + (size_t)sz.n_reads + 24 * 256 + cigar_out;
-    const bool staged = in_bytes + cigar_in + out_bytes <= (size_t)64 << 20;    // small batch: one H2D, one D2H through the pinned mirror
+    // plan
+    int W = 0;
+    std::vector<int32_t> hap_window, class_list;
+    std::vector<int64_t> pair_off, hpos_off, vc_off;
+    std::vector<double> tables;
+    ResultIndex idx;
+    dd_length_classes lcls = {};
+    bool single_class = true;
+    dd_device_batch db = {};
+    size_t ws_bytes = 0, lws_bytes = 0;                  // per stream: the main kernels' workspace, the long path's own
+    // describe: the three lists, and the device-side variables their slots fill
+    std::vector<ArenaSlot> ins, scratch;
+    std::vector<OutArray> outs;
+    const int32_t *class_list_dev = nullptr, *hap_ref_pos_dev = nullptr, *win_hap_pair_dev = nullptr, *hap_n_indels_dev = nullptr;
+    const uint8_t *hap_aligned_dev = nullptr;
+    dd_result dr = {};
+    dd_cigar_result dcg = {};
+    dd_realign_result drl = {};
+    unsigned char *ws[2] = {nullptr, nullptr}, *lws[2] = {nullptr, nullptr};
+    unsigned long long *long_stats = nullptr;           // long_path->n_stats (2 or 4) words per window block's long launch
+    // reserve_and_upload, place_outputs
     DeviceCtx &ctx = g_ctx.c;
-    const size_t long_bytes = lws_bytes ? 2 * (lws_bytes + 256) + 32 * 64 + 256 : 0;
-    if ((rc = ctx.reserve(device, in_bytes + cigar_in + out_bytes + 2 * (ws_bytes + 256) + long_bytes, staged ? in_bytes + cigar_in + out_bytes : 0))) return rc;
-    clk.mark("reserve");
-    DevBuf dev(ctx);
-    dev.staged = staged;
-#define UP(field, n) if ((rc = dev.upload(&db.field, b->field, (size_t)(n)))) return rc
-    UP(win_hap_off, W + 1); UP(win_read_off, W + 1); UP(win_hap_start, W);
-    UP(hap_seq_off, sz.n_haps + 1); UP(hap_seq, sz.hap_bases);
-    UP(read_seq_off, sz.n_reads + 1);
-    // The two big inputs (one byte per read base each).  Large batches: only reserved here — each window block's share is copied
-    // on the block's own stream right in front of its kernels, so all but the first block's transfer hides behind the kernels of
-    // the block before.
-    const bool late_reads = !staged && sz.read_bases > 0;
-    char *d_read_seq = nullptr; uint8_t *d_read_qidx = nullptr;
-    if (late_reads) {
-        if ((rc = dev.alloc(&d_read_seq, (size_t)sz.read_bases))) return rc;
-        if ((rc = dev.alloc(&d_read_qidx, (size_t)sz.read_bases))) return rc;
-        db.read_seq = d_read_seq; db.read_qidx = d_read_qidx;
-    } else {
+    DevBuf dev{ctx};
+    bool staged = false, late_reads = false;
+    size_t out_begin = 0, out_end = 0;                   // the copy-back region of the arena
+    // cut_blocks
+    std::vector<int> cw;                                 // window boundaries of the blocks
+    int n_chunks = 1;
+
+
+    int run()
+    {
+        launch_log_clear();
+        g_long.log.clear();
+        g_flong.log.clear();
+        int rc = front_checks(p, b, r, sz);
+        if (!rc && sz.n_pairs == 0 && x && x->realign)       // reads without haplotypes: no pair, nothing to launch, every read marked
+            for (int64_t q = 0; q < sz.n_reads; q++) {
+                const dd_realign_result &o = x->reads;
+                o.hap[q] = -1; o.status[q] = DD_REALIGN_NO_HAPS; o.n_ops[q] = 0; o.ref_off[q] = -1;
+            }
+        if (rc || sz.n_pairs == 0) return rc;
+        if ((rc = check_and_screen())) return rc;
+        if ((rc = use_device(device, "no HIP device: the likelihood path has no CPU fallback"))) return rc;
+        if ((rc = plan())) return rc;
+        describe();
+        if ((rc = reserve_and_upload())) return rc;
+        if ((rc = place_outputs())) return rc;
+        cut_blocks();
+        clk.mark("outputs");
+        rc = enqueue_and_collect();
+        clk.mark("run");
+        if (rc != DD_SUCCESS) {
+            // kernels / copies already enqueued keep writing into the caller's buffers and this thread's arena: drain both
+            // streams before the error is reported, so that neither is reused while still in flight
+            const std::string msg = g_err;
+            (void)hipStreamSynchronize(ctx.s[0]);
+            (void)hipStreamSynchronize(ctx.s[1]);
+            g_err = msg;
+        }
+        return rc;
+    }
+
+    // ---- the batch's content, and which windows the kernels cover (no HIP call) ----
+    int check_and_screen()
+    {
+        int rc;
+        if (!b->hap_seq || !b->read_seq || !b->read_qidx || !b->read_mqidx || !b->read_start || !b->read_flags ||
+            !b->win_hap_start || !b->qual_table || !b->mapq_table)
+            return fail(DD_ERR_INVALID, "null input array");
+        if (b->n_qual < 1 || b->n_qual > DD_MAX_QUAL_TABLE || b->n_mapq < 1 || b->n_mapq > DD_MAX_QUAL_TABLE)
+            return fail(DD_ERR_INVALID, "quality tables must hold 1..256 entries");
+        // windows whose shape the kernels do not cover are skipped one by one (DD_PAIR_UNSUPPORTED), not the batch
+        win_skip.resize((size_t)b->n_windows);
+        int32_t ok_max[2] = {0, 0};
+        if (!b->hap_seq_off || !b->read_seq_off) return fail(DD_ERR_INVALID, "null offset array");
+        const int sym_left = assign_symbols(b, sym_lut);     // > 0: more than 26 distinct non-ACGTN haplotype bytes in the batch
+        if (sym_left < 0) return sym_left;
+        clk.mark("symbols");
+        // long windows (DD_OPT_LONG_WINDOWS): win_skip holds the classes; the main kernels skip both non-zero classes, the long launch that
+        // follows each block's main launches computes class 2
+        // (DD_OPT_LONG_WINDOWS_FASTER: the same for the --faster model, with its own classes and its own kernel)
+        const bool fl_on = model == MODEL_S && (options & DD_OPT_LONG_WINDOWS_FASTER);
+        long_on = (model == MODEL_FBMAXERR && (options & DD_OPT_LONG_WINDOWS)) || fl_on;
+        long_path = fl_on ? &g_flong : &g_long;
+        if (long_on) {
+            n_skip = screen_windows_ex(p, b, options, win_skip.data(), long_max, sym_lut, sym_left > 0);
+            ok_max[0] = long_max[0]; ok_max[1] = long_max[1];
+            for (int w = 0; w < b->n_windows; w++) if (win_skip[(size_t)w] == DD_WIN_LONG) n_skip++;   // (counts every window the main kernels skip)
+        } else {
+            n_skip = screen_windows(b, win_skip.data(), ok_max, sym_lut, sym_left > 0 && model == MODEL_FBMAXERR);
+        }
+        sz.max_hap_len = ok_max[0] > 0 ? ok_max[0] : 1;      // planning maxima: the windows that are computed
+        sz.max_read_len = ok_max[1] > 0 ? ok_max[1] : 1;
+        clk.mark("screen");
+        if (p->mapUnmappedReads && model == MODEL_FBMAXERR) {
+            if (!b->read_mate_pos || !b->read_mate_len || !b->read_lib)
+                return fail(DD_ERR_INVALID, "mapUnmappedReads needs read_mate_pos, read_mate_len and read_lib");
+            if (b->n_libs < 1 || !b->lib_off) return fail(DD_ERR_INVALID, "mapUnmappedReads needs the library tables");
+            lib_logprob.resize((size_t)(b->lib_off[b->n_libs] > 0 ? b->lib_off[b->n_libs] : 1));
+            lib_log95.resize((size_t)b->n_libs);
+            if ((rc = dd_build_library_tables(b, lib_logprob.data(), lib_log95.data()))) return rc;
+            for (int64_t q = 0; q < sz.n_reads; q++)
+                if (b->read_lib[q] >= b->n_libs) return fail(DD_ERR_INVALID, "read_lib out of range");
+        }
+        if (any_at_or_above(b->read_mqidx, (size_t)sz.n_reads, (unsigned)b->n_mapq)) return fail(DD_ERR_INVALID, "read_mqidx out of range");
+        if (any_at_or_above(b->read_qidx, (size_t)sz.read_bases, (unsigned)b->n_qual)) return fail(DD_ERR_INVALID, "read_qidx out of range");
+        for (int i = 0; i < b->n_qual; i++)
+            if (!(b->qual_table[i] >= 0.0 && b->qual_table[i] <= 1.0)) return fail(DD_ERR_INVALID, "base quality outside [0,1]");
+        for (int i = 0; i < b->n_mapq; i++)
+            if (!(b->mapq_table[i] >= 0.0 && b->mapq_table[i] < 1.0)) return fail(DD_ERR_INVALID, "mapping quality outside [0,1)");
+        clk.mark("validate");
+        return DD_SUCCESS;
+    }
+
+    // ---- host-side planning (no device work yet): index, tables, launch classes and workspace sizes ----
+    int plan()
+    {
+        int rc;
+        W = b->n_windows;
+        hap_window.resize((size_t)sz.n_haps);
+        pair_off.resize(W + 1); hpos_off.resize(W + 1); vc_off.resize(W + 1);
+        dd_build_index(b, hap_window.data(), pair_off.data(), hpos_off.data(), vc_off.data());
+        idx = {pair_off.data(), hpos_off.data(), vc_off.data(), b->win_read_off};
+        tables.resize(DD_TABLE_DOUBLES);
+        rc = dd_build_tables(p, b->qual_table, b->n_qual, b->mapq_table, b->n_mapq, tables.data());
+        if (rc < 0) return rc;
+        // Ragged batches: one launch per (lane tiling of the haplotypes, read-length interval) that has work (build_launch_classes) — a single
+        // 170-bp haplotype or 250-bp read does not drag every pair of the batch onto the K = 3 / long-read build.
+        if (model == MODEL_FBMAXERR && !getenv("DD_NO_LENGTH_CLASSES")) {                      // env: A/B only
+            class_list.resize((size_t)sz.n_haps * DD_N_READ_CLASSES + 1);
+            if ((rc = build_launch_classes(b, n_skip ? win_skip.data() : nullptr, p, class_list.data(), &lcls))) return rc;
+        }
+        db.n_windows = W; db.n_haps = (int32_t)sz.n_haps; db.n_reads = (int32_t)sz.n_reads;
+        db.max_hap_len = sz.max_hap_len; db.max_read_len = sz.max_read_len;
+        db.n_qual = b->n_qual; db.n_mapq = b->n_mapq;
+        for (int w = 0; w < W; w++)
+            if (!win_skip[(size_t)w] && b->win_read_off[w + 1] - b->win_read_off[w] > db.max_window_reads) db.max_window_reads = b->win_read_off[w + 1] - b->win_read_off[w];
+        ws_bytes = model == MODEL_S ? 0 : dd_workspace_bytes(p, &db);
+        single_class = lcls.n_launches <= 1;
+        if (!single_class) {
+            db.classes = &lcls;
+            db.hap_class_list = class_list.data();             // (host pointer: only dd_workspace_bytes' class walk looks at it here)
+            const size_t w2 = dd_workspace_bytes(p, &db);
+            if (w2 > ws_bytes) ws_bytes = w2;
+            db.classes = nullptr; db.hap_class_list = nullptr;
+        }
+        if (long_on && long_max[2] > 0) {
+            db.long_max_hap_len = long_max[2]; db.long_max_read_len = long_max[3];
+            lws_bytes = long_path->workspace_bytes(p, &db);
+            if (!lws_bytes) return fail(DD_ERR_UNSUPPORTED, "long path: no plan for this shape");
+        }
+        clk.mark("plan");
+        return DD_SUCCESS;
+    }
+
+    // ---- every array the call places in the arena, in the arena's order: inputs (the order of their copies), outputs, scratch ----
+    template <class T> void in(const T **var, const T *src, size_t n, bool read_bases = false) { ins.push_back(arena_slot(var, n * sizeof(T), src, read_bases)); }
+    template <class T> void out(T *host, T **dev_field, ResultSpace space, size_t width, bool in_place)
+    {
+        outs.push_back({host, sizeof(T), space, width, in_place, false, arena_slot(dev_field, (size_t)idx.at(space, W) * width * sizeof(T))});
+    }
+    void describe()
+    {
+        const size_t n_haps = (size_t)sz.n_haps, n_reads = (size_t)sz.n_reads;
+        const size_t n_var = b->hap_var_off ? (size_t)b->hap_var_off[sz.n_haps] : 0;
+        ins.reserve(40);
+#define IN(field, n) in(&db.field, b->field, (size_t)(n))
+        IN(win_hap_off, W + 1); IN(win_read_off, W + 1); IN(win_hap_start, W);
+        IN(hap_seq_off, n_haps + 1); IN(hap_seq, sz.hap_bases);
+        IN(read_seq_off, n_reads + 1);
+        in(&db.read_seq, b->read_seq, (size_t)sz.read_bases, true);
+        in(&db.read_qidx, b->read_qidx, (size_t)sz.read_bases, true);
+        IN(read_mqidx, n_reads); IN(read_start, n_reads); IN(read_flags, n_reads);
+        if (b->hap_var_off) {
+            IN(hap_var_off, n_haps + 1); IN(hap_var, 2 * n_var);
+            if (b->hap_var_flank) IN(hap_var_flank, 3 * n_var);
+        }
+        in(&db.hap_window, hap_window.data(), hap_window.size());
+        in(&db.win_pair_off, pair_off.data(), pair_off.size());
+        in(&db.win_hpos_off, hpos_off.data(), hpos_off.size());
+        in(&db.win_varcov_off, vc_off.data(), vc_off.size());
+        in(&db.tables, tables.data(), tables.size());
+        in(&db.sym_lut, sym_lut, (size_t)256);
+        if (n_skip > 0) in(&db.win_skip, win_skip.data(), win_skip.size());
+        if (!lib_log95.empty()) {
+            IN(read_mate_pos, n_reads); IN(read_mate_len, n_reads); IN(read_lib, n_reads); IN(lib_off, b->n_libs + 1);
+            in(&db.lib_logprob, lib_logprob.data(), lib_logprob.size());
+            in(&db.lib_log95, lib_log95.data(), lib_log95.size());
+        }
+#undef IN
+        if (!single_class) in(&class_list_dev, class_list.data(), (size_t)lcls.list_len);
+        if (x) {
+            in(&hap_ref_pos_dev, x->hap_ref_pos, (size_t)sz.hap_bases);
+            if (x->hap_aligned) in(&hap_aligned_dev, x->hap_aligned, n_haps);
+            if (x->realign && x->mode == DD_REALIGN_PAIR) {
+                in(&win_hap_pair_dev, x->win_hap_pair, (size_t)W * 2);
+                in(&hap_n_indels_dev, x->hap_n_indels, n_haps);
+            }
+        }
+
+        // Outputs: the fields of dd_result, then the request's own.  Output arrays the caller keeps in page-locked host memory that this device
+        // can address (dd_host_alloc, hipHostMalloc) are written by the kernels themselves, over the link, as the pairs finish: no staging
+        // copy in HBM and no copy afterwards.  (The runtime carries device -> host copies of this size out with a copy KERNEL:
+        // profiles/r02/hostapi_timeline.txt shows 300 ms of such kernels on the CUs beside 410 ms of HMM kernels for configs[1].)  status and
+        // offHapHMQ stay in HBM: the onHap kernel reads them back (DD_RESULT_FIELDS).
+        outs.reserve(N_RESULT_OUTS + 5);
+#define OUT(f, space, in_place) out(r->f, &dr.f, SPACE_##space, 1, in_place != 0);
+        DD_RESULT_FIELDS(OUT)
+#undef OUT
+        if (r->onHap && !r->offHapHMQ) outs[OUT_offHapHMQ].device_only = true;    // onHap is derived from it
+        if (x) {
+            // The request's launch reads hpos on the device: alignments the caller wants in page-locked memory are staged in HBM and copied back
+            // like pageable ones, instead of being read back over the link; and they are needed there even when the caller does not want them
+            // back (r->hpos == NULL: nothing of them is copied).  A realign launch reads ll and onHap on the device as well.
+            outs[OUT_hpos].in_place = false;
+            outs[OUT_hpos].device_only = !r->hpos;
+            const size_t cap = (size_t)x->ops_cap;
+#define OUT_PAIR(f, wide) out(x->cigars.f, &dcg.f, SPACE_PAIR, wide ? cap : 1, false);
+#define OUT_READ(f, wide) out(x->reads.f, &drl.f, SPACE_READ, wide ? cap : 1, false);
+            if (x->realign) {
+                outs[OUT_ll].in_place = outs[OUT_onHap].in_place = false;
+                DD_REALIGN_FIELDS(OUT_READ)
+            } else {
+                DD_CIGAR_FIELDS(OUT_PAIR)
+            }
+#undef OUT_PAIR
+#undef OUT_READ
+        }
+
+        for (int i = 0; i < 2; i++)
+            if (ws_bytes) scratch.push_back(arena_slot(&ws[i], ws_bytes));
+        if (lws_bytes) {
+            for (int i = 0; i < 2; i++) scratch.push_back(arena_slot(&lws[i], lws_bytes));
+            scratch.push_back(arena_slot(&long_stats, (size_t)4 * 64 * sizeof(*long_stats)));    // 64 blocks at most, 4 words at most
+        }
+    }
+    // where the arena ends once every array of the lists is placed behind `at`, in the order reserve_and_upload and place_outputs place them;
+    // *copy_back_end: the end of the inputs and of the outputs that are copied back (what the pinned mirror of a staged call holds)
+    size_t end_of_all(size_t at, size_t *copy_back_end) const
+    {
+        for (const ArenaSlot &s : ins) at = DevBuf::end_of(at, s.bytes);
+        for (const OutArray &o : outs) if (o.host) at = DevBuf::end_of(at, o.slot.bytes);
+        *copy_back_end = at;
+        for (const OutArray &o : outs) if (o.device_only) at = DevBuf::end_of(at, o.slot.bytes);
+        for (const ArenaSlot &s : scratch) at = DevBuf::end_of(at, s.bytes);
+        return at;
+    }
+
+    // ---- the device arena (cached per host thread) and the inputs ----
+    int reserve_and_upload()
+    {
+        int rc;
+        size_t io_bytes = 0;
+        const size_t arena_bytes = end_of_all(0, &io_bytes);
+        // small batch: one H2D, one D2H through the pinned mirror.  Every input and every output asked for counts, also those that end up read
+        // or written in place: what is page-locked is known only once the device is in use
+        staged = io_bytes <= (size_t)64 << 20;
+        if ((rc = ctx.reserve(device, arena_bytes, staged ? io_bytes : 0))) return rc;
+        clk.mark("reserve");
+        dev.staged = staged;
+        // The two big inputs (one byte per read base each).  Large batches: only reserved here — each window block's share is copied
+        // on the block's own stream right in front of its kernels, so all but the first block's transfer hides behind the kernels of
+        // the block before.
+        late_reads = !staged && sz.read_bases > 0;
         // Staged (small) batches whose two big inputs the caller keeps in page-locked, device-addressable memory (the C++ adapter packs
         // into dd_host_alloc buffers): the kernels read them in place over the link — each (read, haplotype) pair fetches its read once,
         // ~80 MB per 256-window batch at 8 haplotypes — instead of waiting for a staged copy whose blit kernels share the CUs with the
         // batch that is running (profiles/r03/window_loop_timeline.txt).  DD_ZERO_COPY_IN=0 switches it off (A/B).
         static const bool zero_copy_in = !(getenv("DD_ZERO_COPY_IN") && !strcmp(getenv("DD_ZERO_COPY_IN"), "0"));
-        const void *ms = zero_copy_in ? mapped_device_ptr(b->read_seq, (size_t)sz.read_bases) : nullptr;
-        const void *mq = zero_copy_in ? mapped_device_ptr(b->read_qidx, (size_t)sz.read_bases) : nullptr;
-        if (ms && mq) { db.read_seq = static_cast<const char *>(ms); db.read_qidx = static_cast<const uint8_t *>(mq); }
-        else { UP(read_seq, sz.read_bases); UP(read_qidx, sz.read_bases); }
+        const void *ms = zero_copy_in && !late_reads ? mapped_device_ptr(b->read_seq, (size_t)sz.read_bases) : nullptr;
+        const void *mq = zero_copy_in && !late_reads ? mapped_device_ptr(b->read_qidx, (size_t)sz.read_bases) : nullptr;
+        for (const ArenaSlot &s : ins) {
+            const unsigned char *d = nullptr;
+            if (s.read_bases && ms && mq) d = static_cast<const unsigned char *>(s.var == &db.read_seq ? ms : mq);
+            else if (s.read_bases && late_reads) rc = dev.alloc(const_cast<unsigned char **>(&d), s.bytes);
+            else rc = dev.upload(&d, s.src, s.bytes);
+            if (rc) return rc;
+            s.point_at(d);
+        }
+        if ((rc = dev.flush_uploads(ctx.s[0]))) return rc;       // staged mode: the one H2D copy
+        if (!staged) HIP_TRY(hipStreamSynchronize(nullptr));     // pageable uploads went through the null stream's DMA
+        clk.mark("upload");
+        return DD_SUCCESS;
     }
-    UP(read_mqidx, sz.n_reads); UP(read_start, sz.n_reads); UP(read_flags, sz.n_reads);
-#undef UP
-    if (b->hap_var_off) {
-        if ((rc = dev.upload(&db.hap_var_off, b->hap_var_off, (size_t)sz.n_haps + 1))) return rc;
-        if ((rc = dev.upload(&db.hap_var, b->hap_var, 2 * n_var))) return rc;
-        if (b->hap_var_flank && (rc = dev.upload(&db.hap_var_flank, b->hap_var_flank, 3 * n_var))) return rc;
-    }
-    if ((rc = dev.upload(&db.hap_window, (const int32_t *)hap_window.data(), hap_window.size()))) return rc;
-    if ((rc = dev.upload(&db.win_pair_off, (const int64_t *)pair_off.data(), pair_off.size()))) return rc;
-    if ((rc = dev.upload(&db.win_hpos_off, (const int64_t *)hpos_off.data(), hpos_off.size()))) return rc;
-    if ((rc = dev.upload(&db.win_varcov_off, (const int64_t *)vc_off.data(), vc_off.size()))) return rc;
-    if ((rc = dev.upload(&db.tables, (const double *)tables.data(), tables.size()))) return rc;
-    if ((rc = dev.upload(&db.sym_lut, (const uint8_t *)sym_lut, (size_t)256))) return rc;
-    if (n_skip > 0 && (rc = dev.upload(&db.win_skip, (const uint8_t *)win_skip.data(), win_skip.size()))) return rc;
-    if (!lib_log95.empty()) {
-        if ((rc = dev.upload(&db.read_mate_pos, b->read_mate_pos, (size_t)sz.n_reads))) return rc;
-        if ((rc = dev.upload(&db.read_mate_len, b->read_mate_len, (size_t)sz.n_reads))) return rc;
-        if ((rc = dev.upload(&db.read_lib, b->read_lib, (size_t)sz.n_reads))) return rc;
-        if ((rc = dev.upload(&db.lib_off, b->lib_off, (size_t)b->n_libs + 1))) return rc;
-        if ((rc = dev.upload(&db.lib_logprob, (const double *)lib_logprob.data(), lib_logprob.size()))) return rc;
-        if ((rc = dev.upload(&db.lib_log95, (const double *)lib_log95.data(), lib_log95.size()))) return rc;
-    }
-    if (!single_class && (rc = dev.upload(&class_list_dev, (const int32_t *)class_list.data(), (size_t)lcls.list_len))) return rc;
-    const int32_t *hap_ref_pos_dev = nullptr;
-    const uint8_t *hap_aligned_dev = nullptr;
-    if (cg) {
-        if ((rc = dev.upload(&hap_ref_pos_dev, cg->hap_ref_pos, (size_t)sz.hap_bases))) return rc;
-        if (cg->hap_aligned && (rc = dev.upload(&hap_aligned_dev, cg->hap_aligned, (size_t)sz.n_haps))) return rc;
-    }
-    const int32_t *win_hap_pair_dev = nullptr, *hap_n_indels_dev = nullptr;
-    if (rl && rl->mode == DD_REALIGN_PAIR) {
-        if ((rc = dev.upload(&win_hap_pair_dev, rl->win_hap_pair, (size_t)W * 2))) return rc;
-        if ((rc = dev.upload(&hap_n_indels_dev, rl->hap_n_indels, (size_t)sz.n_haps))) return rc;
-    }
-    if ((rc = dev.flush_uploads(ctx.s[0]))) return rc;       // staged mode: the one H2D copy
-    if (!staged) HIP_TRY(hipStreamSynchronize(nullptr));     // pageable uploads went through the null stream's DMA
-    clk.mark("upload");
 
-    dd_result dr;
-    memset(&dr, 0, sizeof(dr));
-    const size_t out_begin = DevBuf::align(dev.used);
-    // Output arrays the caller keeps in page-locked host memory that this device can address (dd_host_alloc, hipHostMalloc) are
-    // written by the kernels themselves, over the link, as the pairs finish: no staging copy in HBM and no copy afterwards.
-    // (The runtime carries device -> host copies of this size out with a copy KERNEL: profiles/r02/hostapi_timeline.txt shows
-    // 300 ms of such kernels on the CUs beside 410 ms of HMM kernels for configs[1].)  status and offHapHMQ stay in HBM: the
-    // onHap kernel reads them back.  DD_ZERO_COPY=0 switches this off (A/B).
-    static const bool zero_copy_on = !(getenv("DD_ZERO_COPY") && !strcmp(getenv("DD_ZERO_COPY"), "0"));
-    const ResultIndex idx = {pair_off.data(), hpos_off.data(), vc_off.data(), b->win_read_off};
-#define FLAG(f, space, in_place) bool f = false;
-    struct { DD_RESULT_FIELDS(FLAG) } direct;
-#undef FLAG
-    int n_direct = 0;
-#define OUT(f, space, in_place) if (r->f) { \
-        const size_t n = (size_t)idx.at(SPACE_##space, W); \
-        void *m = (in_place && zero_copy_on) ? mapped_device_ptr(r->f, n * sizeof(*r->f)) : nullptr; \
-        if (m) { dr.f = static_cast<decltype(dr.f)>(m); direct.f = true; n_direct++; } \
-        else if ((rc = dev.alloc(&dr.f, n))) return rc; }
-    DD_RESULT_FIELDS(OUT)
-#undef OUT
-    // a CIGAR request reads hpos on the device: alignments the caller wants in page-locked memory are then staged in HBM and copied back
-    // like pageable ones, instead of being read back over the link by the CIGAR kernel
-    if (cg && direct.hpos) {
-        if ((rc = dev.alloc(&dr.hpos, (size_t)sz.hpos_len))) return rc;
-        direct.hpos = false; n_direct--;
-    }
-    // a realign request reads ll and onHap on the device as well
-    if (rl && direct.ll) {
-        if ((rc = dev.alloc(&dr.ll, np))) return rc;
-        direct.ll = false; n_direct--;
-    }
-    if (rl && direct.onHap) {
-        if ((rc = dev.alloc(&dr.onHap, nr))) return rc;
-        direct.onHap = false; n_direct--;
-    }
-    g_last_direct = n_direct;
-    if (r->onHap && !r->offHapHMQ && (rc = dev.alloc(&dr.offHapHMQ, np))) return rc;   // onHap is derived from it
-    // CIGARs: the per-base alignments are needed on the device even when the caller does not want them back (r->hpos == NULL: nothing of
-    // them is copied), and the CIGAR arrays come back with the other outputs
-    dd_cigar_result dcg;
-    memset(&dcg, 0, sizeof(dcg));
-    dd_realign_result drl;
-    memset(&drl, 0, sizeof(drl));
-    if (rl) {
-        if ((rc = dev.alloc(&drl.hap, nr)) || (rc = dev.alloc(&drl.status, nr)) || (rc = dev.alloc(&drl.n_ops, nr)) ||
-            (rc = dev.alloc(&drl.ref_off, nr)) || (rc = dev.alloc(&drl.ops, nr * (size_t)cg->ops_cap))) return rc;
-    } else if (cg) {
-        if ((rc = dev.alloc(&dcg.n_ops, np)) || (rc = dev.alloc(&dcg.ref_off, np)) || (rc = dev.alloc(&dcg.status, np)) ||
-            (rc = dev.alloc(&dcg.ops, np * (size_t)cg->ops_cap))) return rc;
-    }
-    const size_t out_end = dev.used;
-    if (cg && !dr.hpos && (rc = dev.alloc(&dr.hpos, (size_t)sz.hpos_len))) return rc;   // (behind the outputs: not part of the staged copy back)
-    unsigned char *ws[2] = {nullptr, nullptr};
-    for (int i = 0; i < 2; i++)
-        if (ws_bytes && (rc = dev.alloc(&ws[i], ws_bytes))) return rc;
-    struct { hipStream_t s[2]; } streams = {{ctx.s[0], ctx.s[1]}};
-    unsigned char *lws[2] = {nullptr, nullptr};
-    unsigned long long *long_stats = nullptr;               // long_path.n_stats (2 or 4) words per window block's long launch
-    if (lws_bytes) {
-        for (int i = 0; i < 2; i++)
-            if ((rc = dev.alloc(&lws[i], lws_bytes))) return rc;
-        if ((rc = dev.alloc(&long_stats, (size_t)4 * 64))) return rc;      // 64 blocks at most, 4 words at most
+    // ---- outputs and scratch: which arrays the kernels write in place, the copy-back region, what lies behind it ----
+    int place_outputs()
+    {
+        int rc;
+        static const bool zero_copy_on = !(getenv("DD_ZERO_COPY") && !strcmp(getenv("DD_ZERO_COPY"), "0"));   // =0 switches in-place outputs off (A/B)
+        int n_direct = 0;
+        out_begin = DevBuf::align(dev.used);
+        for (OutArray &o : outs) {
+            if (!o.host) continue;
+            void *m = (o.in_place && zero_copy_on) ? mapped_device_ptr(o.host, o.slot.bytes) : nullptr;
+            if (m) { o.dev = static_cast<unsigned char *>(m); o.direct = true; n_direct++; }
+            else if ((rc = dev.alloc(&o.dev, o.slot.bytes))) return rc;
+        }
+        out_end = dev.used;
+        g_last_direct = n_direct;
+        for (OutArray &o : outs)                                 // (behind the outputs: not part of the staged copy back)
+            if (o.device_only && (rc = dev.alloc(&o.dev, o.slot.bytes))) return rc;
+        for (const OutArray &o : outs) if (o.dev) o.slot.point_at(o.dev);
+        for (const ArenaSlot &s : scratch) {
+            unsigned char *d = nullptr;
+            if ((rc = dev.alloc(&d, s.bytes))) return rc;
+            s.point_at(d);
+        }
+        return DD_SUCCESS;
     }
 
     // Chunked, double-buffered execution: contiguous window blocks alternate between two streams, and the D2H
@@ -468,125 +569,99 @@ int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b,
     // while the CUs work on the next block (with pageable user memory the copy call blocks the host thread, not
     // the GPU).  Each stream has its own back-pointer scratch.  Small (staged) batches run as one block on stream 0
     // and come back with one D2H through the pinned mirror.
-    int n_chunks = staged ? 1 : (int)((sz.n_pairs + 999999) / 1000000);
-    if (n_chunks > 64) n_chunks = 64;
-    if (n_chunks > W) n_chunks = W;
-    if (n_chunks < 1) n_chunks = 1;
-    std::vector<int> cw(n_chunks + 1, 0);      // window boundaries with ~equal pair counts
-    for (int c = 1; c < n_chunks; c++) {
-        const int64_t target = sz.n_pairs * c / n_chunks;
-        int w = cw[c - 1];
-        while (w < W && pair_off[w] < target) w++;
-        cw[c] = w;
+    void cut_blocks()
+    {
+        n_chunks = staged ? 1 : (int)((sz.n_pairs + 999999) / 1000000);
+        if (n_chunks > 64) n_chunks = 64;
+        if (n_chunks > W) n_chunks = W;
+        if (n_chunks < 1) n_chunks = 1;
+        cw.assign(n_chunks + 1, 0);                // window boundaries with ~equal pair counts
+        for (int c = 1; c < n_chunks; c++) {
+            const int64_t target = sz.n_pairs * c / n_chunks;
+            int w = cw[c - 1];
+            while (w < W && pair_off[w] < target) w++;
+            cw[c] = w;
+        }
+        cw[n_chunks] = W;
     }
-    cw[n_chunks] = W;
-#define DOWN(f, space, in_place) { \
-        const int64_t off = idx.at(SPACE_##space, w0), n = idx.at(SPACE_##space, w1) - off; \
-        if (r->f && n && !direct.f) HIP_TRY(hipMemcpyAsync(r->f + off, dr.f + off, (size_t)n * sizeof(*r->f), hipMemcpyDeviceToHost, st)); }
-    auto download = [&](int c) -> int {
-        hipStream_t st = streams.s[c & 1];
+
+    // block c's share of every output that is copied back, on the block's stream
+    int download(int c)
+    {
         const int w0 = cw[c], w1 = cw[c + 1];
-        DD_RESULT_FIELDS(DOWN)
-        if (rl && b->win_read_off[w1] > b->win_read_off[w0]) {
-            const size_t q0 = (size_t)b->win_read_off[w0], n = (size_t)b->win_read_off[w1] - q0, cap = (size_t)cg->ops_cap;
-            HIP_TRY(hipMemcpyAsync(rl->out.hap + q0, drl.hap + q0, n * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(rl->out.status + q0, drl.status + q0, n * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(rl->out.n_ops + q0, drl.n_ops + q0, n * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(rl->out.ref_off + q0, drl.ref_off + q0, n * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(rl->out.ops + q0 * cap, drl.ops + q0 * cap, n * cap * 4, hipMemcpyDeviceToHost, st));
-        } else if (cg && !rl && pair_off[w1] > pair_off[w0]) {
-            const size_t p0 = (size_t)pair_off[w0], n = (size_t)(pair_off[w1] - pair_off[w0]), cap = (size_t)cg->ops_cap;
-            HIP_TRY(hipMemcpyAsync(cg->out.n_ops + p0, dcg.n_ops + p0, n * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(cg->out.ref_off + p0, dcg.ref_off + p0, n * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(cg->out.status + p0, dcg.status + p0, n * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(cg->out.ops + p0 * cap, dcg.ops + p0 * cap, n * cap * 4, hipMemcpyDeviceToHost, st));
+        for (const OutArray &o : outs) {
+            const size_t off = (size_t)idx.at(o.space, w0) * o.width * o.elem, n = (size_t)idx.at(o.space, w1) * o.width * o.elem - off;
+            if (o.copied_back() && n) HIP_TRY(hipMemcpyAsync(static_cast<unsigned char *>(o.host) + off, o.dev + off, n, hipMemcpyDeviceToHost, ctx.s[c & 1]));
         }
         return DD_SUCCESS;
-    };
-    auto enqueue_and_collect = [&]() -> int {
-    for (int c = 0; c < n_chunks; c++) {
-        const int w0 = cw[c], w1 = cw[c + 1];
-        const int g0 = b->win_hap_off[w0], g1 = b->win_hap_off[w1], q0 = b->win_read_off[w0], q1 = b->win_read_off[w1];
-        if (late_reads && q1 > q0) {
-            const size_t s0 = (size_t)b->read_seq_off[q0], sn = (size_t)b->read_seq_off[q1] - s0;
-            HIP_TRY(hipMemcpyAsync(d_read_seq + s0, b->read_seq + s0, sn, hipMemcpyHostToDevice, streams.s[c & 1]));
-            HIP_TRY(hipMemcpyAsync(d_read_qidx + s0, b->read_qidx + s0, sn, hipMemcpyHostToDevice, streams.s[c & 1]));
-        }
-        if (single_class) {
-            rc = launch_range(model, p, &db, &dr, ws[c & 1], ws_bytes, streams.s[c & 1], g0, g1, q0, q1, n_chunks > 1);
-            if (rc) return rc;
-        } else {
-            // every launch class of this window block, then onHap once
-            for (int i = 0; i < lcls.n_launches; i++) {
-                const dd_launch_class &L = lcls.launch[i];
-                const int32_t *hl = class_list.data() + L.list_off;
-                LenClass lc = len_class_of(L, class_list_dev, i == lcls.n_launches - 1);
-                lc.list_begin = (int)(std::lower_bound(hl, hl + L.list_len, g0) - hl);
-                lc.list_end = (int)(std::lower_bound(hl, hl + L.list_len, g1) - hl);
-                rc = launch_range(model, p, &db, &dr, ws[c & 1], ws_bytes, streams.s[c & 1], g0, g1, q0, q1, n_chunks > 1, &lc);
-                if (rc) return rc;
+    }
+
+    // The request's launch for the windows [w0, w1) of a block, behind the block's likelihood launches on the same stream: the block's CIGARs
+    // (its ops start out zero: a pair's unused slots are defined), or the block's realigned reads (reads of windows without haplotypes are
+    // marked too: the launch goes by reads, not by pairs).
+    int launch_extra(hipStream_t st, int w0, int w1)
+    {
+        const ResultSpace space = x->realign ? SPACE_READ : SPACE_PAIR;
+        const int64_t lo = idx.at(space, w0), hi = idx.at(space, w1);
+        if (hi <= lo) return DD_SUCCESS;
+        HIP_TRY(hipMemsetAsync((x->realign ? drl.ops : dcg.ops) + (size_t)lo * x->ops_cap, 0, (size_t)(hi - lo) * x->ops_cap * 4, st));
+        if (!x->realign) return launch_cigars_range(&db, dr.hpos, dr.status, hap_ref_pos_dev, hap_aligned_dev, &dcg, x->ops_cap, st, lo, hi);
+        const RealignInputs in = {x->mode, dr.ll, dr.onHap, win_hap_pair_dev, hap_n_indels_dev, dr.hpos, dr.status, hap_ref_pos_dev, hap_aligned_dev};
+        return launch_realign_range(&db, in, &drl, x->ops_cap, st, (int)lo, (int)hi);
+    }
+
+    int enqueue_and_collect()
+    {
+        int rc;
+        for (int c = 0; c < n_chunks; c++) {
+            hipStream_t st = ctx.s[c & 1];
+            const int w0 = cw[c], w1 = cw[c + 1];
+            const int g0 = b->win_hap_off[w0], g1 = b->win_hap_off[w1], q0 = b->win_read_off[w0], q1 = b->win_read_off[w1];
+            if (late_reads && q1 > q0) {
+                const size_t s0 = (size_t)b->read_seq_off[q0], sn = (size_t)b->read_seq_off[q1] - s0;
+                HIP_TRY(hipMemcpyAsync(const_cast<char *>(db.read_seq) + s0, b->read_seq + s0, sn, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemcpyAsync(const_cast<uint8_t *>(db.read_qidx) + s0, b->read_qidx + s0, sn, hipMemcpyHostToDevice, st));
             }
+            if (single_class) {
+                if ((rc = launch_range(model, p, &db, &dr, ws[c & 1], ws_bytes, st, g0, g1, q0, q1, n_chunks > 1))) return rc;
+            } else {
+                // every launch class of this window block, then onHap once
+                for (int i = 0; i < lcls.n_launches; i++) {
+                    const dd_launch_class &L = lcls.launch[i];
+                    const int32_t *hl = class_list.data() + L.list_off;
+                    LenClass lc = len_class_of(L, class_list_dev, i == lcls.n_launches - 1);
+                    lc.list_begin = (int)(std::lower_bound(hl, hl + L.list_len, g0) - hl);
+                    lc.list_end = (int)(std::lower_bound(hl, hl + L.list_len, g1) - hl);
+                    if ((rc = launch_range(model, p, &db, &dr, ws[c & 1], ws_bytes, st, g0, g1, q0, q1, n_chunks > 1, &lc))) return rc;
+                }
+            }
+            if (lws_bytes) {
+                bool any = false;
+                for (int w = w0; w < w1 && !any; w++) any = win_skip[(size_t)w] == DD_WIN_LONG;
+                if (any && (rc = long_path->launch_range(p, &db, &dr, lws[c & 1], lws_bytes, st, w0, w1, q0, q1, long_stats + long_path->n_stats * c))) return rc;
+            }
+            if (x && (rc = launch_extra(st, w0, w1))) return rc;
+            if (!staged && c > 0 && (rc = download(c - 1))) return rc;
         }
-        if (lws_bytes) {
-            bool any = false;
-            for (int w = w0; w < w1 && !any; w++) any = win_skip[(size_t)w] == DD_WIN_LONG;
-            if (any && (rc = long_path.launch_range(p, &db, &dr, lws[c & 1], lws_bytes, streams.s[c & 1], w0, w1, q0, q1, long_stats + long_path.n_stats * c))) return rc;
+        if (staged) {
+            HIP_TRY(hipMemcpyAsync(ctx.pinned + out_begin, ctx.arena + out_begin, out_end - out_begin, hipMemcpyDeviceToHost, ctx.s[0]));
+            HIP_TRY(hipStreamSynchronize(ctx.s[0]));
+            for (const OutArray &o : outs)
+                if (o.copied_back() && o.slot.bytes) memcpy(o.host, ctx.pinned + (o.dev - ctx.arena), o.slot.bytes);
+        } else {
+            if ((rc = download(n_chunks - 1))) return rc;
+            HIP_TRY(hipStreamSynchronize(ctx.s[0]));
+            HIP_TRY(hipStreamSynchronize(ctx.s[1]));
         }
-        // the block's CIGARs, behind its likelihood launches on the same stream (its ops start out zero: a pair's unused slots are defined)
-        // or the block's realigned reads (reads of windows without haplotypes are marked too: the launch goes by reads, not by pairs)
-        if (rl && q1 > q0) {
-            HIP_TRY(hipMemsetAsync(drl.ops + (size_t)q0 * cg->ops_cap, 0, (size_t)(q1 - q0) * cg->ops_cap * 4, streams.s[c & 1]));
-            const RealignInputs in = {rl->mode, dr.ll, dr.onHap, win_hap_pair_dev, hap_n_indels_dev, dr.hpos, dr.status, hap_ref_pos_dev, hap_aligned_dev};
-            if ((rc = launch_realign_range(&db, in, &drl, cg->ops_cap, streams.s[c & 1], q0, q1))) return rc;
-        } else if (cg && !rl && pair_off[w1] > pair_off[w0]) {
-            HIP_TRY(hipMemsetAsync(dcg.ops + (size_t)pair_off[w0] * cg->ops_cap, 0, (size_t)(pair_off[w1] - pair_off[w0]) * cg->ops_cap * 4, streams.s[c & 1]));
-            if ((rc = launch_cigars_range(&db, dr.hpos, dr.status, hap_ref_pos_dev, hap_aligned_dev, &dcg, cg->ops_cap, streams.s[c & 1],
-                                          pair_off[w0], pair_off[w1]))) return rc;
-        }
-        if (!staged && c > 0 && (rc = download(c - 1))) return rc;
+        return DD_SUCCESS;
     }
-    if (staged) {
-        HIP_TRY(hipMemcpyAsync(ctx.pinned + out_begin, ctx.arena + out_begin, out_end - out_begin, hipMemcpyDeviceToHost, streams.s[0]));
-        HIP_TRY(hipStreamSynchronize(streams.s[0]));
-#define BACK(f, space, in_place) { \
-            const size_t n = (size_t)idx.at(SPACE_##space, W); \
-            if (r->f && n && !direct.f) memcpy(r->f, ctx.pinned + (reinterpret_cast<unsigned char *>(dr.f) - ctx.arena), n * sizeof(*r->f)); }
-        DD_RESULT_FIELDS(BACK)
-#undef BACK
-        if (rl) {
-            const size_t cap = (size_t)cg->ops_cap;
-            memcpy(rl->out.hap, ctx.pinned + (reinterpret_cast<unsigned char *>(drl.hap) - ctx.arena), nr * 4);
-            memcpy(rl->out.status, ctx.pinned + (reinterpret_cast<unsigned char *>(drl.status) - ctx.arena), nr * 4);
-            memcpy(rl->out.n_ops, ctx.pinned + (reinterpret_cast<unsigned char *>(drl.n_ops) - ctx.arena), nr * 4);
-            memcpy(rl->out.ref_off, ctx.pinned + (reinterpret_cast<unsigned char *>(drl.ref_off) - ctx.arena), nr * 4);
-            memcpy(rl->out.ops, ctx.pinned + (reinterpret_cast<unsigned char *>(drl.ops) - ctx.arena), nr * cap * 4);
-        } else if (cg) {
-            const size_t cap = (size_t)cg->ops_cap;
-            memcpy(cg->out.n_ops, ctx.pinned + (reinterpret_cast<unsigned char *>(dcg.n_ops) - ctx.arena), np * 4);
-            memcpy(cg->out.ref_off, ctx.pinned + (reinterpret_cast<unsigned char *>(dcg.ref_off) - ctx.arena), np * 4);
-            memcpy(cg->out.status, ctx.pinned + (reinterpret_cast<unsigned char *>(dcg.status) - ctx.arena), np * 4);
-            memcpy(cg->out.ops, ctx.pinned + (reinterpret_cast<unsigned char *>(dcg.ops) - ctx.arena), np * cap * 4);
-        }
-    } else {
-        if ((rc = download(n_chunks - 1))) return rc;
-        HIP_TRY(hipStreamSynchronize(streams.s[0]));
-        HIP_TRY(hipStreamSynchronize(streams.s[1]));
-    }
-    return DD_SUCCESS;
-    };
-#undef DOWN
-    clk.mark("outputs");
-    rc = enqueue_and_collect();
-    clk.mark("run");
-    if (rc != DD_SUCCESS) {
-        // kernels / copies already enqueued keep writing into the caller's buffers and this thread's arena: drain both
-        // streams before the error is reported, so that neither is reused while still in flight
-        const std::string msg = g_err;
-        (void)hipStreamSynchronize(streams.s[0]);
-        (void)hipStreamSynchronize(streams.s[1]);
-        g_err = msg;
-    }
-    return rc;
+};
+
+int compute_likelihoods_impl(Model model, const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options = 0,
+                             const ExtraRequest *x = nullptr)
+{
+    HostCall call{model, p, b, r, device, options, x};
+    return call.run();
 }
 
 // One persistent host thread per block slot: its thread_local device cache (arena, pinned mirror, streams) survives between
@@ -710,6 +785,46 @@ int compute_multi(Model model, const dd_params *p, const dd_batch *b, dd_result 
 } // namespace
 } // namespace ddh
 using namespace ddh;
+// What dd_map_pairs and dd_pair_sums start with: the batch's sizes, the device, the pair and haplotype-pair offsets, and this thread's arena
+// with the three offset arrays, hh_off and ll uploaded; more_bytes(c) is what the caller places behind them.  `nothing`: there is nothing to
+// compute (no window; needs_hap_pairs: no haplotype pair) and nothing was reserved.
+struct PairSumCall {
+    dd_sizes sz;
+    int W = 0;
+    std::vector<int64_t> pair_off, hh_off;
+    size_t ns = 0;                                      // hh_off[W]: the batch's haplotype pairs
+    dd_device_batch db = {};
+    const int64_t *hh_dev = nullptr;
+    const double *ll_dev = nullptr;
+    DevBuf dev{g_ctx.c};
+    bool nothing = true;
+};
+template <class MoreBytes>
+int pair_sum_prologue(PairSumCall &c, const dd_batch *b, const double *ll_host, bool args_given, int device, const char *no_device,
+                      bool needs_hap_pairs, MoreBytes more_bytes)
+{
+    int rc = dd_batch_sizes(b, &c.sz);
+    if (rc) return rc;
+    if (!args_given) return fail(DD_ERR_INVALID, "null argument");
+    if ((rc = use_device(device, no_device))) return rc;
+    const int W = c.W = b->n_windows;
+    if (W <= 0) return DD_SUCCESS;
+    c.pair_off.resize(W + 1); c.hh_off.resize(W + 1);
+    dd_batch_offsets(b, c.pair_off.data(), nullptr, nullptr);
+    dd_pair_sum_offsets(b, c.hh_off.data());
+    c.ns = (size_t)c.hh_off[W];
+    if (needs_hap_pairs && c.ns == 0) return DD_SUCCESS;
+    if ((rc = g_ctx.c.reserve(device, (size_t)(W + 1) * (2 * 4 + 2 * 8) + (size_t)c.sz.n_pairs * 8 + 5 * 256 + more_bytes(c), 0))) return rc;
+    c.db.n_windows = W;
+    if ((rc = c.dev.upload(&c.db.win_hap_off, b->win_hap_off, (size_t)W + 1))) return rc;
+    if ((rc = c.dev.upload(&c.db.win_read_off, b->win_read_off, (size_t)W + 1))) return rc;
+    if ((rc = c.dev.upload(&c.db.win_pair_off, (const int64_t *)c.pair_off.data(), c.pair_off.size()))) return rc;
+    if ((rc = c.dev.upload(&c.hh_dev, (const int64_t *)c.hh_off.data(), c.hh_off.size()))) return rc;
+    if ((rc = c.dev.upload(&c.ll_dev, ll_host, (size_t)c.sz.n_pairs))) return rc;
+    c.nothing = false;
+    return DD_SUCCESS;
+}
+
 extern "C" {
 int dd_last_direct_outputs(void) { return g_last_direct; }
 
@@ -744,83 +859,47 @@ int dd_device_count(void)
 int dd_map_pairs(const dd_batch *b, const double *ll_host, const double *prior_host, const uint8_t *filtered_host,
                  const int32_t *ncand_host, double *pair_sum_out, double *posterior_out, int32_t *pairs_out, double *vals_out, int device)
 {
-    dd_sizes sz;
-    int rc = dd_batch_sizes(b, &sz);
-    if (rc) return rc;
-    if (!ll_host || !prior_host || !filtered_host || !ncand_host || !pairs_out || !vals_out) return fail(DD_ERR_INVALID, "null argument");
-    if ((rc = use_device(device, "no HIP device: the genotype reduction has no CPU fallback in this library"))) return rc;
-    const int W = b->n_windows;
-    if (W <= 0) return DD_SUCCESS;
-    std::vector<int64_t> pair_off(W + 1), hh_off(W + 1);
-    dd_batch_offsets(b, pair_off.data(), nullptr, nullptr);
-    dd_pair_sum_offsets(b, hh_off.data());
-    const size_t ns = (size_t)hh_off[W];
-    DeviceCtx &ctx = g_ctx.c;
-    if ((rc = ctx.reserve(device, (size_t)(2 * (W + 1) * 4 + 2 * (W + 1) * 8 + ((size_t)sz.n_pairs + 3 * ns) * 8 + (size_t)sz.n_haps * 5 + (size_t)W * 40 + 32 * 256), 0))) return rc;
-    DevBuf dev(ctx);
-    dd_device_batch db;
-    memset(&db, 0, sizeof(db));
-    db.n_windows = W;
-    if ((rc = dev.upload(&db.win_hap_off, b->win_hap_off, (size_t)W + 1))) return rc;
-    if ((rc = dev.upload(&db.win_read_off, b->win_read_off, (size_t)W + 1))) return rc;
-    if ((rc = dev.upload(&db.win_pair_off, (const int64_t *)pair_off.data(), pair_off.size()))) return rc;
-    const int64_t *hh_dev = nullptr;
-    const double *ll_dev = nullptr, *prior_dev = nullptr;
+    PairSumCall c;
+    int rc = pair_sum_prologue(c, b, ll_host, ll_host && prior_host && filtered_host && ncand_host && pairs_out && vals_out, device,
+                               "no HIP device: the genotype reduction has no CPU fallback in this library", false,
+                               [](const PairSumCall &c) { return 3 * c.ns * 8 + (size_t)c.sz.n_haps * 5 + (size_t)c.W * 40 + 27 * 256; });
+    if (rc || c.nothing) return rc;
+    DevBuf &dev = c.dev;
+    const size_t ns = c.ns, W = (size_t)c.W;
+    const double *prior_dev = nullptr;
     const uint8_t *filt_dev = nullptr;
     const int32_t *nc_dev = nullptr;
     double *sum_dev = nullptr, *post_dev = nullptr, *vals_dev = nullptr;
     int32_t *pairs_dev = nullptr;
-    if ((rc = dev.upload(&hh_dev, (const int64_t *)hh_off.data(), hh_off.size()))) return rc;
-    if ((rc = dev.upload(&ll_dev, ll_host, (size_t)sz.n_pairs))) return rc;
     if ((rc = dev.upload(&prior_dev, prior_host, ns))) return rc;
-    if ((rc = dev.upload(&filt_dev, filtered_host, (size_t)sz.n_haps))) return rc;
-    if ((rc = dev.upload(&nc_dev, ncand_host, (size_t)sz.n_haps))) return rc;
+    if ((rc = dev.upload(&filt_dev, filtered_host, (size_t)c.sz.n_haps))) return rc;
+    if ((rc = dev.upload(&nc_dev, ncand_host, (size_t)c.sz.n_haps))) return rc;
     if ((rc = dev.alloc(&sum_dev, ns))) return rc;
     if ((rc = dev.alloc(&post_dev, ns))) return rc;
-    if ((rc = dev.alloc(&vals_dev, (size_t)3 * W))) return rc;
-    if ((rc = dev.alloc(&pairs_dev, (size_t)4 * W))) return rc;
+    if ((rc = dev.alloc(&vals_dev, 3 * W))) return rc;
+    if ((rc = dev.alloc(&pairs_dev, 4 * W))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = dd_pair_sums_device(&db, hh_dev, hh_off[W], ll_dev, sum_dev, nullptr))) return rc;
-    if ((rc = dd_map_pairs_device(&db, hh_dev, sum_dev, prior_dev, filt_dev, nc_dev, post_dev, pairs_dev, vals_dev, nullptr))) return rc;
+    if ((rc = dd_pair_sums_device(&c.db, c.hh_dev, c.hh_off[W], c.ll_dev, sum_dev, nullptr))) return rc;
+    if ((rc = dd_map_pairs_device(&c.db, c.hh_dev, sum_dev, prior_dev, filt_dev, nc_dev, post_dev, pairs_dev, vals_dev, nullptr))) return rc;
     HIP_TRY(hipDeviceSynchronize());
     if (pair_sum_out) HIP_TRY(hipMemcpy(pair_sum_out, sum_dev, ns * sizeof(double), hipMemcpyDeviceToHost));
     if (posterior_out) HIP_TRY(hipMemcpy(posterior_out, post_dev, ns * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(pairs_out, pairs_dev, (size_t)4 * W * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(vals_out, vals_dev, (size_t)3 * W * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pairs_out, pairs_dev, 4 * W * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(vals_out, vals_dev, 3 * W * sizeof(double), hipMemcpyDeviceToHost));
     return DD_SUCCESS;
 }
 
 int dd_pair_sums(const dd_batch *b, const double *ll_host, double *out_host, int device)
 {
-    dd_sizes sz;
-    int rc = dd_batch_sizes(b, &sz);
-    if (rc) return rc;
-    if (!ll_host || !out_host) return fail(DD_ERR_INVALID, "null argument");
-    if ((rc = use_device(device, "no HIP device: the genotype read-sum has no CPU fallback in this library"))) return rc;
-    const int W = b->n_windows;
-    std::vector<int64_t> pair_off(W + 1), hh_off(W + 1);
-    dd_batch_offsets(b, pair_off.data(), nullptr, nullptr);
-    dd_pair_sum_offsets(b, hh_off.data());
-    if (hh_off[W] == 0) return DD_SUCCESS;
-    DeviceCtx &ctx = g_ctx.c;
-    if ((rc = ctx.reserve(device, (size_t)(2 * (W + 1) * 4 + 2 * (W + 1) * 8 + (sz.n_pairs + hh_off[W]) * 8 + 16 * 256), 0))) return rc;
-    DevBuf dev(ctx);
-    dd_device_batch db;
-    memset(&db, 0, sizeof(db));
-    db.n_windows = W;
-    if ((rc = dev.upload(&db.win_hap_off, b->win_hap_off, (size_t)W + 1))) return rc;
-    if ((rc = dev.upload(&db.win_read_off, b->win_read_off, (size_t)W + 1))) return rc;
-    if ((rc = dev.upload(&db.win_pair_off, (const int64_t *)pair_off.data(), pair_off.size()))) return rc;
-    const int64_t *hh_dev = nullptr;
-    const double *ll_dev = nullptr;
+    PairSumCall c;
+    int rc = pair_sum_prologue(c, b, ll_host, ll_host && out_host, device, "no HIP device: the genotype read-sum has no CPU fallback in this library",
+                               true, [](const PairSumCall &c) { return c.ns * 8 + 11 * 256; });
+    if (rc || c.nothing) return rc;
     double *out_dev = nullptr;
-    if ((rc = dev.upload(&hh_dev, (const int64_t *)hh_off.data(), hh_off.size()))) return rc;
-    if ((rc = dev.upload(&ll_dev, ll_host, (size_t)sz.n_pairs))) return rc;
-    if ((rc = dev.alloc(&out_dev, (size_t)hh_off[W]))) return rc;
-    rc = dd_pair_sums_device(&db, hh_dev, hh_off[W], ll_dev, out_dev, nullptr);
-    if (rc) return rc;
+    if ((rc = c.dev.alloc(&out_dev, c.ns))) return rc;
+    if ((rc = dd_pair_sums_device(&c.db, c.hh_dev, c.hh_off[(size_t)c.W], c.ll_dev, out_dev, nullptr))) return rc;
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out_host, out_dev, (size_t)hh_off[W] * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_host, out_dev, c.ns * sizeof(double), hipMemcpyDeviceToHost));
     return DD_SUCCESS;
 }
 int dd_compute_likelihoods(const dd_params *p, const dd_batch *b, dd_result *r, int device)
@@ -840,8 +919,9 @@ int dd_compute_likelihoods_cigars(const dd_params *p, const dd_batch *b, dd_resu
     if (ops_cap < 1) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_cigars: ops_cap must be at least 1");
     if (!cig || !cig->n_ops || !cig->ops || !cig->ref_off || !cig->status)
         return fail(DD_ERR_INVALID, "dd_compute_likelihoods_cigars: every array of dd_cigar_result is required");
-    const CigarRequest cg = {hap_ref_pos, hap_aligned, *cig, ops_cap, nullptr};
-    return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device, options, &cg);
+    ExtraRequest x = {hap_ref_pos, hap_aligned, ops_cap, false};
+    x.cigars = *cig;
+    return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device, options, &x);
 }
 int dd_compute_likelihoods_realign(const dd_params *p, const dd_batch *b, dd_result *r, int mode, const int32_t *win_hap_pair,
                                    const int32_t *hap_n_indels, const int32_t *hap_ref_pos, const uint8_t *hap_aligned,
@@ -855,11 +935,9 @@ int dd_compute_likelihoods_realign(const dd_params *p, const dd_batch *b, dd_res
     if (ops_cap < 1) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign: ops_cap must be at least 1");
     if (!out || !out->hap || !out->status || !out->n_ops || !out->ops || !out->ref_off)
         return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign: every array of dd_realign_result is required");
-    const RealignRequest rl = {mode, win_hap_pair, hap_n_indels, *out};
-    dd_cigar_result none;
-    memset(&none, 0, sizeof(none));
-    const CigarRequest cg = {hap_ref_pos, hap_aligned, none, ops_cap, &rl};
-    return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device, options, &cg);
+    ExtraRequest x = {hap_ref_pos, hap_aligned, ops_cap, true};
+    x.mode = mode; x.win_hap_pair = win_hap_pair; x.hap_n_indels = hap_n_indels; x.reads = *out;
+    return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device, options, &x);
 }
 int dd_compute_likelihoods_faster(const dd_params *p, const dd_batch *b, dd_result *r, int device)
 {

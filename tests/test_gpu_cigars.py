@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from dindel_tgi_amd import capi, synth
-from dindel_tgi_amd.batch import ReadRec, Window, alloc_result, pack
+from dindel_tgi_amd.batch import ReadRec, Window, alloc_result, alloc_result_pinned, pack, result_lengths
 from dindel_tgi_amd.device import DeviceBatch
 from tests import _cigar_cases as cc
 
@@ -156,9 +156,9 @@ def test_more_pairs_than_one_round_of_the_grid():
     check(pb, hrp, hpos=hpos, launch=None)
 
 
-def host_entry(lib, pb, hrp, hal, ops_cap=8, options=0, with_hpos=False):
+def host_entry(lib, pb, hrp, hal, ops_cap=8, options=0, with_hpos=False, result=None):
     p = capi.params_cli_defaults()
-    arrs, res = alloc_result(pb)
+    arrs, res = result or alloc_result(pb)
     if not with_hpos:
         res.hpos = None
         arrs["hpos"][:] = -12345
@@ -201,6 +201,43 @@ def test_host_entry_keeps_the_alignments_on_the_device(lib):
     wantl, outl = cc.expected(pbl, hposl, hrpl, None, statusl, 8, 0)
     gotl, _ = host_entry(lib, pbl, hrpl, None, options=capi.DD_OPT_LONG_WINDOWS)
     cc.assert_equal(gotl, wantl, outl)
+
+
+def with_page_locked_results(lib, pb, entry):
+    """entry(result) with every dd_result array from dd_host_alloc (allocated as tests/test_gpu_parity.py::test_pinned_outputs_are_written_in_place
+    does) -> (what the entry filled besides, copies of the dd_result arrays, how many of them the entry let the kernels write in place, how many
+    a plain dd_compute_likelihoods call does on the same memory)."""
+    arrs, res, release = alloc_result_pinned(pb)
+    try:
+        p, b = capi.params_cli_defaults(), pb.ctypes_batch()
+        assert lib.dd_compute_likelihoods(C.byref(p), C.byref(b), C.byref(res), 0) == 0, capi.last_error()
+        plain = lib.dd_last_direct_outputs()
+        assert plain >= 10
+        for a in arrs.values():
+            a.view(np.uint8)[...] = 0x55
+        out, _ = entry((arrs, res))
+        return out, {k: a.copy() for k, a in arrs.items()}, lib.dd_last_direct_outputs(), plain
+    finally:
+        release()
+
+
+def assert_same_bytes(pb, pageable, pinned):
+    for k, n in result_lengths(pb).items():
+        assert np.array_equal(pageable[k][:n].view(np.uint8), pinned[k][:n].view(np.uint8)), k
+
+
+def test_host_entry_with_page_locked_results(lib):
+    """dd_compute_likelihoods_cigars with every dd_result array in page-locked memory: the CIGAR launch reads hpos on the device, so hpos — which
+    a plain call lets the kernels write in place — is staged in HBM and copied back; every byte equals the pageable call's."""
+    pb = synth.generate(5, H=5, R=60, L=100, hap_len=130, seed=1334, vary_read_len=True, mixed_quals=True)
+    hrp, hal = cc.batch_hap_ref_pos(pb, 77), some_unaligned(pb, 3)
+    want, pageable = host_entry(lib, pb, hrp, hal, with_hpos=True)
+    assert lib.dd_last_direct_outputs() == 0
+    got, pinned, direct, plain = with_page_locked_results(lib, pb, lambda result: host_entry(lib, pb, hrp, hal, with_hpos=True, result=result))
+    assert direct == plain - 1
+    assert_same_bytes(pb, pageable, pinned)
+    for k in want:
+        assert np.array_equal(want[k], got[k]), k
 
 
 def test_host_entry_in_window_blocks(lib):

@@ -15,6 +15,7 @@ from dindel_tgi_amd import capi, synth
 from dindel_tgi_amd.batch import ReadRec, Window, alloc_result, pack
 from dindel_tgi_amd.device import DeviceBatch
 from tests import _cigar_cases as cc
+from tests.test_gpu_cigars import assert_same_bytes, with_page_locked_results
 
 pytestmark = pytest.mark.gpu
 FILL = 0x3B3B3B3B
@@ -389,9 +390,9 @@ def test_more_reads_than_the_grid_has_wavefront_slots():
 
 
 # ---------------------------------------------------------------- the host-pointer entry
-def host_entry(lib, pb, hrp, hal, mode=FIRST_MAX, pairs=None, n_indels=None, ops_cap=8, options=0, with_hpos=False, with_on_hap=True):
+def host_entry(lib, pb, hrp, hal, mode=FIRST_MAX, pairs=None, n_indels=None, ops_cap=8, options=0, with_hpos=False, with_on_hap=True, result=None):
     p = capi.params_cli_defaults()
-    arrs, res = alloc_result(pb)
+    arrs, res = result or alloc_result(pb)
     if not with_hpos:
         res.hpos = None
         arrs["hpos"][:] = -12345
@@ -459,6 +460,23 @@ def test_host_entry_keeps_everything_else_on_the_device(lib):
     assert_same_reads(outl, gotl)
     outn, _ = host_entry(lib, pbl, hrpl, None, with_on_hap=False)                # without it the long window's reads name pairs that were not computed
     assert (outn["status"][:6] == capi.DD_CIGAR_NOT_COMPUTED).all() and (outn["status"][6:8] == capi.DD_REALIGN_NO_HAPS).all()
+
+
+def test_host_entry_with_page_locked_results(lib):
+    """dd_compute_likelihoods_realign with every dd_result array in page-locked memory: the realign launch reads hpos, ll and onHap on the
+    device, so these three — which a plain call lets the kernels write in place — are staged in HBM and copied back; every byte equals the
+    pageable call's."""
+    pb = synth.generate(5, H=5, R=60, L=100, hap_len=130, seed=1334, vary_read_len=True, mixed_quals=True)
+    hrp = cc.batch_hap_ref_pos(pb, 77)
+    hal = np.ones(pb.n_haps, np.uint8)
+    hal[3] = 0
+    want, pageable = host_entry(lib, pb, hrp, hal, with_hpos=True)
+    assert lib.dd_last_direct_outputs() == 0
+    got, pinned, direct, plain = with_page_locked_results(lib, pb, lambda result: host_entry(lib, pb, hrp, hal, with_hpos=True, result=result))
+    assert direct == plain - 3
+    assert_same_bytes(pb, pageable, pinned)
+    for k in want:
+        assert np.array_equal(want[k], got[k]), k
 
 
 def test_host_entry_in_window_blocks(lib):
