@@ -139,8 +139,9 @@ int build_launch_classes(const dd_batch *b, const uint8_t *win_skip, const dd_pa
     // launch to leave the last position idle — 64 K >= Hs + 3, i.e. up to 61 / 125 bp of the 62 / 126 the tiling holds.  One 126-bp haplotype
     // among thousands of shorter ones switched the fold off for all of them (the ragged leg's K = 2 launches).  When the haplotypes of exactly
     // the tiling's full length are few, they run apart (promote[c]): launches of their own, same tiling, not folded; the others fold.
+    const Switches sw = read_switches();
     bool promote[DD_N_HAP_CLASSES] = {false};
-    if (p && check_params(p) == DD_SUCCESS && pick_Dt(p->maxLengthDel + 1) == 6 && !getenv("DD_NO_FOLD") && !getenv("DD_NO_PROMOTE")) {
+    if (p && check_params(p) == DD_SUCCESS && pick_Dt(p->maxLengthDel + 1) == 6 && !sw.no_fold && !sw.no_promote) {
         int64_t n_fold[DD_N_HAP_CLASSES] = {0}, n_edge[DD_N_HAP_CLASSES] = {0};
         for (int w = 0; w < W; w++) {
             if (win_skip && win_skip[w]) continue;
@@ -154,7 +155,7 @@ int build_launch_classes(const dd_batch *b, const uint8_t *win_skip, const dd_pa
         for (int c = 0; c < DD_N_HAP_CLASSES; c++) used += (n_fold[c] + n_edge[c]) > 0 ? 1 : 0;
         for (int c = 0; c < DD_N_HAP_CLASSES; c++) {
             int G0 = 1, K0 = 1;
-            if (!pick_tiling(kHapClasses[c].bound, 6, G0, K0)) continue;
+            if (!pick_tiling(sw, kHapClasses[c].bound, 6, G0, K0)) continue;
             if (G0 != 1 || K0 > 2 || n_edge[c] == 0 || n_fold[c] == 0) continue;   // only the tilings that have a folded build
             // the full-length haplotypes get launches of their own (same tiling, not folded: they cost what they cost before); worth it when the
             // launch they leave behind is the bigger part — a small launch fills the chip badly
@@ -178,10 +179,10 @@ int build_launch_classes(const dd_batch *b, const uint8_t *win_skip, const dd_pa
         }
     }
     int bound[NC][DD_N_READ_CLASSES];                        // upper read length of each interval of each tiling
-    const bool one_read_class = getenv("DD_LENGTH_CLASSES") && !strcmp(getenv("DD_LENGTH_CLASSES"), "k");   // A/B: haplotype classes only
+    const bool one_read_class = sw.one_read_class;           // A/B: haplotype classes only
     for (int c = 0; c < NC; c++) {
-        int T = hmax[c] > 0 ? lds_read_threshold(p, hmax[c], b->n_qual) : 0;
-        if (getenv("DD_READ_BOUND")) T = atoi(getenv("DD_READ_BOUND"));                                    // A/B only
+        int T = hmax[c] > 0 ? lds_read_threshold(sw, p, hmax[c], b->n_qual) : 0;
+        if (sw.read_bound >= 0) T = sw.read_bound;            // A/B only
         if (T < 1 || T >= 160) T = 0;
         bound[c][0] = one_read_class ? DD_MAX_READ_LEN : (T ? T : 160);
         bound[c][1] = one_read_class ? DD_MAX_READ_LEN : 160;

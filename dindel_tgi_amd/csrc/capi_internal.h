@@ -1,4 +1,5 @@
-// capi_internal.h — what the host units of the C ABI (include/dindel_hmm.h) share: plan.cpp, batch_host.cpp (neither calls the HIP runtime),
+// capi_internal.h — what the host units of the C ABI (include/dindel_hmm.h) share: plan.cpp, batch_host.cpp (neither calls the HIP runtime
+// nor needs a kernel unit to link), long_plan.cpp (the plans of the two long-window paths, with the layouts of their kernel units),
 // launch.cpp, host_path.cpp, align_host.cpp (the haplotype alignment, self-contained), pooled_em_capi.cpp (the pooled EM's device entries;
 // pooled_em_host.cpp, its CPU evaluation, includes no HIP header and not this file); each says in its first lines what it holds.  Host work is O(bases) bookkeeping only.  All likelihood
 // arithmetic happens in the kernels; there is no CPU path for it in this library.
@@ -65,13 +66,34 @@ DD_LISTS_ALL_OF(dd_realign_result, DD_REALIGN_FIELDS);
 #undef DD_FIELD_SIZE
 
 // ---- plan.cpp ----
+// The A/B switches of plan.cpp, launch.cpp and build_launch_classes, read from the environment by read_switches() on every call (tests and
+// tools flip them inside one process).  The arithmetic takes this struct and never calls getenv itself.  The switches of host_path.cpp and
+// host/ stay where they are used; DD_LAUNCH_TIMING (launch.cpp) is read once per process.
+struct Switches {
+    bool no_half = false;               // DD_NO_HALF: whole-wavefront tilings only (test_launch_plan_rules, test_gpu_half_wave, tools/multi_round_sweep.py)
+    int reg_waves = 0;                  // DD_REG_WAVES=1..16: waves per CU of a build compiled for another occupancy (tools/host_equivalence.py); 0: the shipped builds'
+    int force_gbt = -1;                 // DD_FORCE_GBT=0/1: LDS / HBM-scratch back-pointers wherever that build fits (tools/plan_check.py, test_gpu_fuzz and others)
+    int fast_groups = 0;                // DD_FAST_GROUPS=1/2: fewer pairs per wavefront of the --faster kernel (test_gpu_faster)
+    int fast_waves = 0;                 // DD_FAST_WAVES=1..DD_WAVES: workgroup size of the --faster kernel (by hand only)
+    int64_t fast_target_blocks = 1024;  // DD_FAST_TARGET_BLOCKS: workgroups wanted before the --faster kernel splits haplotypes (by hand only)
+    bool always_ro = false;             // DD_ALWAYS_RO: KernelArgs::always_ro for the kernels (by hand only)
+    int64_t target_blocks = 4096;       // DD_TARGET_BLOCKS: workgroups wanted before haplotypes are split (by hand only)
+    bool split_no_rounds = false;       // DD_SPLIT_NO_ROUNDS: the read split without its round-fill term, the rule before round 3 (tools/README.md)
+    bool uniform_split = false;         // DD_UNIFORM_SPLIT: no per-window split in ragged batches (test_gpu_ragged)
+    int reads_per_wave = 0;             // DD_READS_PER_WAVE: cap on a wavefront's reads in ragged launches (test_gpu_ragged); 0: 12 or 24 by build
+    int dynamic = -1;                   // DD_DYNAMIC=1 / any other value: the item counter wherever it can be used / never (test_gpu_ragged, test_gpu_persistent_rounds, tools/hostapi_time.py)
+    bool no_fold = false;               // DD_NO_FOLD: no FOLD build, and no launches of their own for full-length haplotypes (test_gpu_fold_mirrored_ro, test_gpu_edge_cases)
+    bool no_promote = false;            // DD_NO_PROMOTE: full-length haplotypes stay in their tiling's launch (test_full_length_haplotypes_leave_the_folded_launch)
+    bool one_read_class = false;        // DD_LENGTH_CLASSES=k: launch classes by haplotype length only (test_gpu_ragged, tools/ragged_bench.py)
+    int read_bound = -1;                // DD_READ_BOUND: the read length that cuts a tiling's reads up to 160 bp, in place of the plan's (tools/host_equivalence.py)
+};
+Switches read_switches();
+
 struct HapClassDef { int bound, G, K; };     // haplotypes up to `bound` bp: G pairs per wavefront, K positions per lane
 extern const HapClassDef kHapClasses[DD_N_HAP_CLASSES];
 int hap_class_of(int hap_len);
-bool pick_tiling(int max_hap_len, int Dt, int &G, int &K);
+bool pick_tiling(const Switches &sw, int max_hap_len, int Dt, int &G, int &K);
 int pick_Dt(int D);
-size_t lds_layout(int K, int Dt, int Lmax, int n_qual, int waves, bool gbt, int G, ddk::KernelArgs &A);
-size_t scratch_wave_bytes(int K, int Dt, int G, int max_read_len);
 
 // the workspace starts with the item counter of the dynamic (ragged) launches; the back-pointer tiles follow
 constexpr size_t DD_WS_HEADER = 256;
@@ -79,19 +101,64 @@ constexpr size_t DD_WS_HEADER = 256;
 // Launch plan: LDS-resident back-pointers when that keeps the CU as full as the registers allow, otherwise
 // the HBM-scratch build (GBT) with a persistent grid (one scratch tile per resident wave).
 struct Plan {
-    int K, Dt, waves, waves_per_cu;
+    int K = 0, Dt = 0, waves = 0, waves_per_cu = 0;
     int G = 1;               // pairs per wavefront (2: the half-wave builds)
-    bool gbt;
+    bool gbt = false;
     bool two_waves = false;  // K = 3 / D = 6 scratch build: the variant compiled for 2 waves per SIMD (LDS keeps fewer than 12 waves on the CU anyway)
-    size_t lds, scratch_bytes;
-    unsigned grid_cap;       // 0 = one workgroup per item
+    size_t lds = 0, scratch_bytes = 0;
+    unsigned grid_cap = 0;   // 0 = one workgroup per item
 };
-int make_plan(const dd_params *p, int max_hap_len, int max_read_len, int n_qual, Plan &pl, ddk::KernelArgs &A);
-int lds_read_threshold(const dd_params *p, int max_hap_len, int n_qual);
-int waves_for_reads(int64_t units, int maxw, int per_cu);
-int64_t pick_split(int64_t n_haps, int64_t units, int waves, int64_t min_blocks, int64_t resident = 0);
-int64_t resident_workgroups(size_t lds, int waves_per_cu, int waves);
-size_t lds_layout_fast(int max_hap_len, int max_read_len, int n_qual, int &waves, int &groups, ddk::KernelArgs &A);
+int lds_read_threshold(const Switches &sw, const dd_params *p, int max_hap_len, int n_qual);
+
+// The scalars of one (haplotype-length class, read-length class) of a ragged batch: the launch is shaped for the class' own maxima
+// instead of the batch-wide ones.
+struct ClassDims {
+    bool listed = false;                 // the class has a haplotype list: the launch covers [list_begin, list_end) of it
+    int list_begin = 0, list_end = 0;
+    int max_hap_len = 0, max_read_len = 0, min_read_len = 1;
+    int max_window_reads = 0, avg_window_reads = 0;   // reads of the class per window of the list (0 = not known)
+    int avg_read_len = 0;                             // mean length of the class' reads (0 = not known)
+};
+// What a main-model or --faster launch is shaped from: scalars only, no pointer into the batch and no device.
+struct LaunchAsk {
+    const dd_params *p = nullptr;
+    int n_windows = 0, n_haps = 0, n_reads = 0, max_hap_len = 0, max_read_len = 0, n_qual = 0, max_window_reads = 0;   // of the batch
+    bool has_class = false;
+    ClassDims cls;
+    int hap_begin = 0, hap_end = -1;     // the haplotypes the launch covers; hap_end < 0: the whole batch
+    size_t workspace_bytes = 0;          // 0: no workspace
+    bool overlapping_chunks = false;     // the caller alternates chunk launches between two streams (the host-pointer path)
+};
+// Every decision of a launch.  dd_last_launch, dd_kernel_name and a dd_launch_log record are made from it (shape_last_launch,
+// shape_kernel_name, shape_log_record) and from nothing else.
+struct LaunchShape {
+    bool faster = false;                 // the --faster kernel: `groups` pairs per wavefront, no Plan
+    Plan pl;
+    int groups = 0;
+    int waves = 0;                       // waves per workgroup and its LDS bytes, after the thin-window rule
+    size_t lds = 0;
+    uint32_t lds_wave_bytes = 0, lds_shared_bytes = 0;
+    int64_t split = 0;                   // workgroups per haplotype of a window with the average number of reads
+    int reads_per_wave = 0;              // > 0: ragged windows, the kernel derives each haplotype's workgroups from its window's reads
+    int32_t item_begin = 0, n_items = 0;
+    int64_t n_launch_items = 0, grid = 0;   // items of this launch; workgroups (fewer where the grid is persistent); grid <= 0: nothing to launch
+    bool use_counter = false;            // the persistent grid draws its items from the counter at the start of the workspace
+    bool fold = false;                   // the FOLD build (hmm_kernel.hip)
+    int build = 0;                       // DD_BUILD_* bits
+    int occ = 0;                         // the build variant compiled for that many waves per SIMD (0: the build's usual occupancy)
+    int bt_rows = 0;                     // scratch builds: rows and bytes of a wavefront's back-pointer region, and where the regions start
+    uint32_t bt_wave_bytes = 0;
+    size_t scratch_off = 0;
+    int n_haps = 0, max_hap = 0, min_read = 1, max_read = 0;   // what the launch covers (the class', or the batch's)
+};
+// Fill the LDS-layout fields of A and every field of s.  Errors, in this order: make_plan's, workspace too small, batch too large.
+int shape_launch(const Switches &sw, const LaunchAsk &ask, LaunchShape &s, ddk::KernelArgs &A);
+int shape_fast(const Switches &sw, const LaunchAsk &ask, LaunchShape &s, ddk::KernelArgs &A);
+void shape_last_launch(const LaunchShape &s, int32_t out[8]);
+void shape_kernel_name(const LaunchShape &s, char *name, size_t size);
+void shape_log_record(const LaunchShape &s, int32_t v[DD_LAUNCH_LOG_FIELDS]);
+
+// ---- long_plan.cpp ----
 struct LongPlan { int K; size_t lds; unsigned grid; uint64_t off_lpoff, off_tiles, stash_off, tile_bytes, ws_bytes; };
 int long_plan(int n_windows, int max_hap_len, int max_read_len, int n_qual, LongPlan &lp, ddl::LongArgs &A);
 struct FLPlan { size_t lds; unsigned grid; uint64_t off_ioff, off_tiles, ws_bytes; };
@@ -105,14 +172,9 @@ int screen_windows_ex(const dd_params *p, const dd_batch *b, uint32_t options, u
 int build_launch_classes(const dd_batch *b, const uint8_t *win_skip, const dd_params *p, int32_t *list, dd_length_classes *out);
 
 // ---- launch.cpp ----
-// One (haplotype-length class, read-length class) of a ragged batch: the launch plan (K, LDS tile) is made for
-// the class' own maxima instead of the batch-wide ones.
-struct LenClass {
+// One launch class of a ragged batch: its scalars and the device copy of its haplotype list.
+struct LenClass : ClassDims {
     const int32_t *hap_list = nullptr;   // device: haplotype indices of the class (sorted); nullptr = all haplotypes
-    int list_begin = 0, list_end = 0;    // range of hap_list this launch covers
-    int max_hap_len = 0, max_read_len = 0, min_read_len = 1;
-    int max_window_reads = 0, avg_window_reads = 0;   // reads of the class per window of the list (0 = not known)
-    int avg_read_len = 0;                             // mean length of the class' reads (0 = not known)
     bool run_onhap = true;
 };
 // launch class L over its whole list; class_list: the device copy of the batch's class list

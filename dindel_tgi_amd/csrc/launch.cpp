@@ -1,13 +1,12 @@
-// launch.cpp — the device-pointer launchers of the C ABI: the main and --faster kernels, the two long-window paths, the genotype kernels;
-// the launch logs and the per-thread diagnostics that describe the last launch.
+// launch.cpp — the device-pointer launchers of the C ABI: the main and --faster kernels (shaped by plan.cpp's shape_launch / shape_fast: this
+// file checks, fills the arguments and enqueues), the two long-window paths, the CIGAR and realign launches, the genotype kernels; the launch
+// logs and this thread's last launch shape.
 #include "capi_internal.h"
 
 namespace ddh {
-static thread_local int32_t g_last_launch[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // per host thread, like the cache and the error string
-static thread_local char g_kernel_name[64] = "dd_hmm_kernel";
-static thread_local int g_last_fold = 0;       // the last main-model launch used the FOLD build (hmm_kernel.hip)
-static thread_local int g_last_G = 1;          // ... pairs per wavefront of that launch
-static thread_local int g_last_occ = 0;        // ... the build variant compiled for that many waves per SIMD (0 = the build's usual occupancy)
+// What this host thread launched last (main model or --faster): dd_last_launch and dd_kernel_name describe it.  Per host thread, like the
+// cache and the error string.
+static thread_local LaunchShape g_last_shape;
 
 // Launch log of the last dd_launch_device / dd_compute_likelihoods call on this host thread (dd_launch_log): one record per main-model
 // kernel launch.  With DD_LAUNCH_TIMING=1 (diagnostics) every launch is bracketed by HIP events and its duration is filled in when the
@@ -31,6 +30,21 @@ static unsigned long long *g_dbg = nullptr;
 extern "C" void dd_debug_set_stamp_buffer(void *p) { g_dbg = static_cast<unsigned long long *>(p); }   // (C linkage: the namespace does not enter its name)
 #endif
 
+// The fields KernelArgs, LongArgs and FLArgs name alike, from the batch, the parameters and the result block; what only some of them have
+// (read_flags, sym_lut, hap_window, the skip / class bytes, mate arrays, D, bMid) stays with the caller.
+template <class Args> static void fill_batch_args(Args &A, const dd_params *p, const dd_device_batch *b, const dd_result *r)
+{
+    A.n_windows = b->n_windows;
+    A.win_hap_off = b->win_hap_off; A.win_read_off = b->win_read_off; A.win_hap_start = b->win_hap_start;
+    A.hap_seq_off = b->hap_seq_off; A.hap_seq = b->hap_seq; A.hap_var_off = b->hap_var_off; A.hap_var = b->hap_var; A.hap_var_flank = b->hap_var_flank;
+    A.read_seq_off = b->read_seq_off; A.read_seq = b->read_seq; A.read_qidx = b->read_qidx; A.read_mqidx = b->read_mqidx;
+    A.read_start = b->read_start;
+    A.win_pair_off = b->win_pair_off; A.win_hpos_off = b->win_hpos_off; A.win_varcov_off = b->win_varcov_off;
+    A.tables = b->tables;
+    A.out = *r;
+    A.maxLengthDel = p->maxLengthDel; A.padCover = p->padCover; A.maxMismatch = p->maxMismatch;
+}
+
 // mapUnmappedReads: the mate arrays and library log tables of the insert-size prior, checked and handed to a main-model kernel
 // (the --faster model has no such prior)
 template <class Args> static int fill_mate_args(Args &A, const dd_device_batch *b)
@@ -42,43 +56,8 @@ template <class Args> static int fill_mate_args(Args &A, const dd_device_batch *
     return DD_SUCCESS;
 }
 
-static int launch_fast(const dd_params *p, const dd_device_batch *b, ddk::KernelArgs &A, void *stream, int hap_begin, int hap_end,
-                       int read_begin, int read_end, bool want_onhap)
-{
-    (void)p;
-    int waves = DD_WAVES, groups = 4;
-    size_t lds = lds_layout_fast(b->max_hap_len, b->max_read_len, b->n_qual, waves, groups, A);
-    if (lds > kCuLdsBytes) return fail(DD_ERR_UNSUPPORTED, "shape exceeds the LDS tile of the --faster kernel");
-    A.n_qual = b->n_qual;
-    A.fast_groups = groups;
-    int64_t target_blocks = 1024;                 // workgroups wanted before haplotypes are split (A/B: DD_FAST_TARGET_BLOCKS)
-    if (const char *e = getenv("DD_FAST_TARGET_BLOCKS")) { const long v = atol(e); if (v >= 1) target_blocks = v; }   // A/B only
-    int64_t avg_reads = (b->n_reads + b->n_windows - 1) / (b->n_windows > 0 ? b->n_windows : 1);
-    {   // thin windows: no more wavefronts per workgroup than the windows have groups of `groups` reads
-        const int w2 = waves_for_reads((avg_reads + groups - 1) / groups, waves, 8);
-        if (w2 != waves) {
-            waves = w2;
-            lds = (size_t)A.lds_shared_bytes + (size_t)waves * (groups < 4 ? groups + 1 : 4) * A.lds_wave_bytes;
-        }
-    }
-    const int64_t split = pick_split(hap_end - hap_begin, (avg_reads + groups - 1) / groups, waves, target_blocks);
-    if ((int64_t)b->n_haps * split > 0x7fffffffLL) return fail(DD_ERR_UNSUPPORTED, "batch too large for one launch");
-    A.n_split = (int32_t)split;
-    A.item_begin = (int32_t)(hap_begin * split);
-    A.n_items = (int32_t)(hap_end * split);
-    A.read_begin = read_begin; A.read_end = read_end;
-    A.hap_list = nullptr; A.len_min = 0; A.len_max = 0x7fffffff;
-    int64_t grid = (int64_t)(hap_end - hap_begin) * split;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (grid > 0) {
-        g_last_launch[0] = groups; g_last_launch[1] = 0; g_last_launch[2] = waves; g_last_launch[3] = (int32_t)lds;
-        g_last_launch[4] = (int32_t)grid; g_last_launch[5] = (int32_t)split; g_last_launch[6] = (int32_t)A.lds_wave_bytes; g_last_launch[7] = 0;
-        HIP_TRY(ddk::launch_faster(A, (unsigned)grid, waves, lds, st));
-    }
-    if (want_onhap) HIP_TRY(ddk::launch_onhap(A, st));
-    return DD_SUCCESS;
-}
-
+// Check, fill the arguments from the batch, shape the launch (plan.cpp: every decision is shape_launch's / shape_fast's), copy the shape
+// into the arguments, enqueue.
 int launch_range(Model model, const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes,
                  void *stream, int hap_begin, int hap_end, int read_begin, int read_end, bool overlapping_chunks, const LenClass *lc)
 {
@@ -88,181 +67,125 @@ int launch_range(Model model, const dd_params *p, const dd_device_batch *b, cons
     if (b->n_haps <= 0 || b->n_reads <= 0) return DD_SUCCESS;
     if (b->max_hap_len < 1 || b->max_hap_len > DD_MAX_HAP_LEN) return fail(DD_ERR_UNSUPPORTED, "haplotype length outside [1,766]");
     if (b->max_read_len < 1 || b->max_read_len > DD_MAX_READ_LEN) return fail(DD_ERR_UNSUPPORTED, "read length outside [1,1024]");
-    const int D = p->maxLengthDel + 1;
+    if (model == MODEL_S) lc = nullptr;         // the --faster model has no launch classes
+    const Switches sw = read_switches();
     ddk::KernelArgs A;
     memset(&A, 0, sizeof(A));
-    A.n_windows = b->n_windows; A.n_haps = b->n_haps; A.n_reads = b->n_reads;
-    A.win_hap_off = b->win_hap_off; A.win_read_off = b->win_read_off; A.win_hap_start = b->win_hap_start;
-    A.hap_seq_off = b->hap_seq_off; A.hap_seq = b->hap_seq; A.hap_var_off = b->hap_var_off; A.hap_var = b->hap_var; A.hap_var_flank = b->hap_var_flank;
-    A.read_seq_off = b->read_seq_off; A.read_seq = b->read_seq; A.read_qidx = b->read_qidx; A.read_mqidx = b->read_mqidx;
-    A.read_start = b->read_start; A.read_flags = b->read_flags;
-    A.hap_window = b->hap_window; A.win_pair_off = b->win_pair_off; A.win_hpos_off = b->win_hpos_off;
-    A.win_varcov_off = b->win_varcov_off; A.tables = b->tables; A.sym_lut = b->sym_lut; A.win_skip = b->win_skip;
+    fill_batch_args(A, p, b, r);
+    A.n_haps = b->n_haps; A.n_reads = b->n_reads;
+    A.read_flags = b->read_flags; A.hap_window = b->hap_window; A.sym_lut = b->sym_lut; A.win_skip = b->win_skip;
     if (p->mapUnmappedReads && model == MODEL_FBMAXERR && (rc = fill_mate_args(A, b))) return rc;
-    A.out = *r;
 #ifdef DD_STAMPS
     A.dbg = g_dbg;
 #endif
-    A.always_ro = getenv("DD_ALWAYS_RO") ? 1 : 0;
-    A.D = D; A.maxLengthDel = p->maxLengthDel; A.padCover = p->padCover; A.bMid = p->bMid; A.maxMismatch = p->maxMismatch;
-    if (model == MODEL_S) {
-        if (hap_end < 0) { hap_begin = 0; hap_end = b->n_haps; read_begin = 0; read_end = b->n_reads; }
-        return launch_fast(p, b, A, stream, hap_begin, hap_end, read_begin, read_end, r->onHap && r->offHapHMQ);
-    }
-    Plan pl;
-    const int cls_hap = lc ? lc->max_hap_len : b->max_hap_len, cls_read = lc ? lc->max_read_len : b->max_read_len;
-    rc = make_plan(p, cls_hap, cls_read, b->n_qual, pl, A);
-    if (rc) return rc;
+    A.always_ro = sw.always_ro ? 1 : 0;
+    A.D = p->maxLengthDel + 1; A.bMid = p->bMid;
     A.hap_list = lc ? lc->hap_list : nullptr;
     A.len_min = lc ? lc->min_read_len : 0;
     A.len_max = lc ? lc->max_read_len : 0x7fffffff;
-    const int K = pl.K, Dt = pl.Dt;
-    int waves = pl.waves;
-    size_t lds = pl.lds;
-    // thin windows: a wavefront works on one read at a time, so a workgroup never needs more waves than the windows have
-    // reads (tools/coverage_sweep.py: 2 reads per window ran at half the rate with idle waves in every workgroup)
-    const int64_t avg_reads_w = (lc && lc->avg_window_reads > 0) ? lc->avg_window_reads : (b->n_reads + b->n_windows - 1) / (b->n_windows > 0 ? b->n_windows : 1);
-    {
-        const int w2 = waves_for_reads((avg_reads_w + pl.G - 1) / pl.G, waves, pl.waves_per_cu);   // a wavefront takes G reads at a time
-        if (w2 != waves) {
-            waves = w2;
-            lds = lds_layout(K, Dt, cls_read, b->n_qual, waves, pl.gbt, pl.G, A);
-        }
-    }
-    if (pl.gbt) {
-        if (!workspace || workspace_bytes < pl.scratch_bytes + DD_WS_HEADER)
-            return fail(DD_ERR_INVALID, "workspace too small for this shape: allocate dd_workspace_bytes() bytes");
-        A.bt_scratch = static_cast<unsigned char *>(workspace) + DD_WS_HEADER;
-        A.bt_rows = cls_read;
-        A.bt_wave_bytes = (uint32_t)scratch_wave_bytes(K, Dt, pl.G, cls_read);
-    }
-    // enough workgroups to fill 256 CUs several times over, but keep >= 1 read per wave
-    int64_t target_blocks = 4096;
-    if (const char *e = getenv("DD_TARGET_BLOCKS")) { const long v = atol(e); if (v >= 1) target_blocks = v; }   // A/B only
-    int64_t avg_reads = avg_reads_w;
-    if (hap_end < 0) { hap_begin = 0; hap_end = b->n_haps; read_begin = 0; read_end = b->n_reads; }
-    if (lc && lc->hap_list) { hap_begin = lc->list_begin; hap_end = lc->list_end; }   // positions in the class list
-    // the split is chosen for the haplotypes THIS launch covers: a rare length class or a small window block must still
-    // spread over the chip
-    // workgroups the chip holds at once (one-shot grids; a persistent GBT grid is capped to that number below anyway)
-    int64_t resident = resident_workgroups(lds, pl.waves_per_cu, waves);
-    if (getenv("DD_SPLIT_NO_ROUNDS")) resident = 0;                            // A/B only: the rule before round 3
-    int64_t split = pick_split(hap_end - hap_begin, (avg_reads + pl.G - 1) / pl.G, waves, target_blocks, resident);
-    // Ragged windows: `split` suits a window with the average number of reads; a haplotype whose window has more gets proportionally more
-    // workgroups (the kernel derives its own count from reads_per_wave), so that a 400-read window among 100-read ones does not end the
-    // launch with one workgroup still at work; when the spread is wide the work of a wavefront is also capped (DD_READS_PER_WAVE, A/B).
-    A.reads_per_wave = 0;
-    const int max_reads = (lc && lc->max_window_reads > 0) ? lc->max_window_reads : b->max_window_reads;
-    if (max_reads > 0 && max_reads * 4 > avg_reads * 5 && !getenv("DD_UNIFORM_SPLIT")) {
-        const int64_t units = (avg_reads + pl.G - 1) / pl.G, max_units = (max_reads + pl.G - 1) / pl.G;
-        int64_t rpw = (units + waves * split - 1) / (waves * split);
-        int cap_rpw = (Dt > 7 || K >= 3) ? 24 : 12;
-        if (const char *e = getenv("DD_READS_PER_WAVE")) { const int v = atoi(e); if (v >= 1) cap_rpw = v; }
-        if (rpw > cap_rpw) rpw = cap_rpw;
-        if (rpw < 1) rpw = 1;
-        A.reads_per_wave = (int32_t)rpw;
-        split = (max_units + waves * rpw - 1) / (waves * rpw);
-        if (split < 1) split = 1;
-    }
-    A.n_split = (int32_t)split;
-    if ((int64_t)b->n_haps * split > 0x7fffffffLL) return fail(DD_ERR_UNSUPPORTED, "batch too large for one launch");
-    A.item_begin = (int32_t)(hap_begin * split);
-    A.n_items = (int32_t)(hap_end * split);
+    if (hap_end < 0) { read_begin = 0; read_end = b->n_reads; }
     A.read_begin = read_begin; A.read_end = read_end;
-    int64_t grid = (int64_t)(hap_end - hap_begin) * split;
-    if (grid <= 0) {
-        if (r->onHap && r->offHapHMQ && lc && lc->run_onhap) HIP_TRY(ddk::launch_onhap(A, static_cast<hipStream_t>(stream)));
+
+    LaunchAsk ask;
+    ask.p = p;
+    ask.n_windows = b->n_windows; ask.n_haps = b->n_haps; ask.n_reads = b->n_reads; ask.max_hap_len = b->max_hap_len; ask.max_read_len = b->max_read_len;
+    ask.n_qual = b->n_qual; ask.max_window_reads = b->max_window_reads;
+    ask.hap_begin = hap_begin; ask.hap_end = hap_end;
+    ask.workspace_bytes = workspace ? workspace_bytes : 0;
+    ask.overlapping_chunks = overlapping_chunks;
+    if (lc) { ask.has_class = true; ask.cls = *lc; ask.cls.listed = lc->hap_list != nullptr; }
+    LaunchShape s;
+    if ((rc = model == MODEL_S ? shape_fast(sw, ask, s, A) : shape_launch(sw, ask, s, A))) return rc;
+    A.n_split = (int32_t)s.split; A.reads_per_wave = s.reads_per_wave;
+    A.item_begin = s.item_begin; A.n_items = s.n_items;
+
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool want_onhap = r->onHap && r->offHapHMQ;
+    if (model == MODEL_S) {
+        A.n_qual = b->n_qual;
+        A.fast_groups = s.groups;
+        if (s.grid > 0) {
+            g_last_shape = s;
+            HIP_TRY(ddk::launch_faster(A, (unsigned)s.grid, s.waves, s.lds, st));
+        }
+        if (want_onhap) HIP_TRY(ddk::launch_onhap(A, st));
         return DD_SUCCESS;
     }
-    const int64_t n_launch_items = grid;
-    if (pl.grid_cap) {
-        // the scratch holds grid_cap x pl.waves back-pointer tiles; smaller workgroups (thin windows) may be more numerous
-        const int64_t cap = (int64_t)pl.grid_cap * pl.waves / waves;
-        if (grid > cap) grid = cap;
+    if (s.pl.gbt) {
+        A.bt_scratch = static_cast<unsigned char *>(workspace) + s.scratch_off;
+        A.bt_rows = s.bt_rows;
+        A.bt_wave_bytes = s.bt_wave_bytes;
     }
-    // More items than the chip holds workgroups: a persistent grid that draws its items from a counter.  Built for the ragged launches (items that
-    // differ 20-fold in work); at the end of round 4 it turned out to be worth as much on UNIFORM batches wherever the grid was persistent
-    // already — every HBM-scratch build ran a fixed stride, and the items of a uniform batch still differ by their reads' bMid: 3.42 -> 3.85e11 cells/s
-    // at 130 bp, 3.34 -> 3.88e11 at 80 bp, +10-18 % on every K >= 3 tiling (profiles/r04/item_counter_uniform_ab.txt) — and +0.1-1.5 % on the
-    // one-shot LDS grids (the headline build: +0.9 %), whose XCD-contiguous numbering (one L2 per window's haplotypes) it gives up.
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    A.work_counter = nullptr;
-    {
-        // (Except: the chunks of the host-pointer path alternate between two streams, and a one-shot grid lets the next chunk's workgroups move in
-        // while this one's drain; a chip-filling persistent grid holds its slots to the end — `dd_compute_likelihoods` with pageable pointers lost 7 %
-        // that way, 23.7 -> 22.0 k windows/s at configs[1].  There the LDS builds keep their one-shot grids unless the batch is ragged.)
-        const bool spread = A.reads_per_wave > 0 || (lc && lc->avg_read_len > 0 && lc->max_read_len * 4 > lc->avg_read_len * 5);
-        const char *e = getenv("DD_DYNAMIC");                                 // A/B: 0 = never (one-shot LDS grids, fixed stride on scratch builds)
-        const bool dynamic = e ? (e[0] == '1') : (pl.gbt || spread || !overlapping_chunks);
-        if (dynamic && workspace && workspace_bytes >= DD_WS_HEADER && resident > 0 && n_launch_items > resident) {
-            A.work_counter = static_cast<int32_t *>(workspace);
-            HIP_TRY(hipMemsetAsync(workspace, 0, 4, st));
-            if (grid > resident) grid = resident;
-        }
+    if (s.grid <= 0) {
+        if (want_onhap && lc && lc->run_onhap) HIP_TRY(ddk::launch_onhap(A, st));
+        return DD_SUCCESS;
     }
-    g_last_launch[0] = K; g_last_launch[1] = Dt + (pl.gbt ? 100 : 0); g_last_launch[2] = waves; g_last_launch[3] = (int32_t)lds;
-    g_last_launch[4] = (int32_t)grid; g_last_launch[5] = (int32_t)split; g_last_launch[6] = (int32_t)A.lds_wave_bytes;
-    g_last_launch[7] = (int32_t)A.lds_shared_bytes;
-    // the build with the end states folded into the generic candidate code (hmm_kernel.hip, FOLD): K <= 2 at D build 6 with LDS
-    // back-pointers, K = 2 at D build 6 with scratch back-pointers, K = 2 at D build 11 with LDS back-pointers — and every haplotype
-    // of this launch leaves position 64 K - 1 idle (numS <= 64 K - 1)
-    const bool fold_build = pl.gbt ? (K == 2 && Dt == 6) : ((K <= 2 && Dt == 6) || (K == 2 && Dt == 11));     // the builds measured to gain from it
-    const bool fold = pl.G == 1 && fold_build && 64 * K >= cls_hap + 3 && !getenv("DD_NO_FOLD");
-    g_last_fold = fold ? 1 : 0;
-    g_last_occ = (pl.gbt && pl.two_waves) ? 2 : 0;
-    const int build = (fold ? DD_BUILD_FOLD : 0) | ((pl.gbt && pl.two_waves) ? DD_BUILD_TWO_WAVES : 0) | (pl.G == 2 ? DD_BUILD_HALF : 0);
-    g_last_G = pl.G;
+    if (s.use_counter) {
+        A.work_counter = static_cast<int32_t *>(workspace);
+        HIP_TRY(hipMemsetAsync(workspace, 0, 4, st));
+    }
+    g_last_shape = s;
     LaunchRec rec;
-    {
-        const int32_t v[DD_LAUNCH_LOG_FIELDS] = {K, pl.G, Dt, pl.gbt ? 1 : 0, fold ? 1 : 0, waves, (int32_t)lds, (int32_t)grid, (int32_t)split,
-                                                 hap_end - hap_begin, cls_hap, lc ? lc->min_read_len : 1, cls_read, pl.waves_per_cu, g_last_occ, -1,
-                                                 A.work_counter ? 1 : 0, A.reads_per_wave};
-        memcpy(rec.v, v, sizeof(v));
-    }
+    shape_log_record(s, rec.v);
     static const bool timing = getenv("DD_LAUNCH_TIMING") != nullptr;
     if (timing) { HIP_TRY(hipEventCreate(&rec.e0)); HIP_TRY(hipEventCreate(&rec.e1)); HIP_TRY(hipEventRecord(rec.e0, st)); }
-    HIP_TRY(ddk::launch_hmm(K, Dt, pl.gbt, build, A, (unsigned)grid, waves, lds, st));
+    HIP_TRY(ddk::launch_hmm(s.pl.K, s.pl.Dt, s.pl.gbt, s.build, A, (unsigned)s.grid, s.waves, s.lds, st));
     if (timing) HIP_TRY(hipEventRecord(rec.e1, st));
     g_launch_log.push_back(rec);
-    if (r->onHap && r->offHapHMQ && (!lc || lc->run_onhap)) HIP_TRY(ddk::launch_onhap(A, st));
+    if (want_onhap && (!lc || lc->run_onhap)) HIP_TRY(ddk::launch_onhap(A, st));
     return DD_SUCCESS;
 }
 
 LenClass len_class_of(const dd_launch_class &L, const int32_t *class_list, bool run_onhap)
 {
     LenClass lc;
-    lc.hap_list = class_list + L.list_off; lc.list_begin = 0; lc.list_end = L.list_len;
+    lc.hap_list = class_list + L.list_off; lc.listed = true; lc.list_begin = 0; lc.list_end = L.list_len;
     lc.max_hap_len = L.max_hap_len; lc.min_read_len = L.min_read_len; lc.max_read_len = L.max_read_len;
     lc.max_window_reads = L.max_window_reads; lc.avg_window_reads = L.avg_window_reads; lc.avg_read_len = L.avg_read_len;
     lc.run_onhap = run_onhap;
     return lc;
 }
 
-// ---------------- device-side getCIGAR (cigar_kernel.hip) ----------------
+// ---------------- device-side getCIGAR (cigar_kernel.hip) and realigned reads (realign_kernel.hip) ----------------
+// What the two launches share, behind the checks of their own arguments: the rest of the front checks in their order, then the batch's
+// offset arrays and the alignment inputs into C.  every_output: no array of the result block is missing; nothing_to_do: an empty batch or
+// range.  1: nothing to do, 0: go on, < 0: error (its text starts with `who`).
+static int cigar_front(const char *who, const char *result_type, ddc::CigarArgs &C, const dd_device_batch *b, const int16_t *hpos,
+                       const int32_t *status, const int32_t *hap_ref_pos, const uint8_t *hap_aligned, int ops_cap, bool every_output, bool nothing_to_do)
+{
+    auto bad = [who](const std::string &what) { return fail(DD_ERR_INVALID, std::string(who) + ": " + what); };
+    if (!hap_ref_pos) return bad("hap_ref_pos is required (Haplotype::refHpos per haplotype base)");
+    if (ops_cap < 1) return bad("ops_cap must be at least 1");
+    if (!every_output) return bad(std::string("every array of ") + result_type + " is required");
+    if (nothing_to_do) return 1;
+    if (!b->win_hap_off || !b->win_read_off || !b->hap_seq_off || !b->read_seq_off || !b->win_pair_off || !b->win_hpos_off)
+        return bad("the batch lacks an offset array");
+    C.n_windows = b->n_windows;
+    C.win_hap_off = b->win_hap_off; C.win_read_off = b->win_read_off; C.hap_seq_off = b->hap_seq_off; C.read_seq_off = b->read_seq_off;
+    C.win_pair_off = b->win_pair_off; C.win_hpos_off = b->win_hpos_off;
+    C.hpos = hpos; C.pair_status = status; C.hap_ref_pos = hap_ref_pos; C.hap_aligned = hap_aligned;
+    C.ops_cap = ops_cap;
+    return 0;
+}
+
 int launch_cigars_range(const dd_device_batch *b, const int16_t *hpos_dev, const int32_t *status_dev, const int32_t *hap_ref_pos_dev,
                         const uint8_t *hap_aligned_dev, const dd_cigar_result *out_dev, int ops_cap, void *stream, int64_t pair_begin,
                         int64_t pair_end)
 {
     if (!b || !hpos_dev || !out_dev) return fail(DD_ERR_INVALID, "dd_cigars_device: null batch, hpos or output block");
-    if (!hap_ref_pos_dev) return fail(DD_ERR_INVALID, "dd_cigars_device: hap_ref_pos is required (Haplotype::refHpos per haplotype base)");
-    if (ops_cap < 1) return fail(DD_ERR_INVALID, "dd_cigars_device: ops_cap must be at least 1");
-    if (!out_dev->n_ops || !out_dev->ops || !out_dev->ref_off || !out_dev->status) return fail(DD_ERR_INVALID, "dd_cigars_device: every array of dd_cigar_result is required");
-    if (b->n_windows <= 0 || b->n_haps <= 0 || b->n_reads <= 0 || (pair_end >= 0 && pair_end <= pair_begin)) return DD_SUCCESS;
-    if (!b->win_hap_off || !b->win_read_off || !b->hap_seq_off || !b->read_seq_off || !b->win_pair_off || !b->win_hpos_off)
-        return fail(DD_ERR_INVALID, "dd_cigars_device: the batch lacks an offset array");
     ddc::CigarArgs A;
     memset(&A, 0, sizeof(A));
-    A.n_windows = b->n_windows; A.pair_begin = pair_begin; A.pair_end = pair_end;
-    A.win_hap_off = b->win_hap_off; A.win_read_off = b->win_read_off; A.hap_seq_off = b->hap_seq_off; A.read_seq_off = b->read_seq_off;
-    A.win_pair_off = b->win_pair_off; A.win_hpos_off = b->win_hpos_off;
-    A.hpos = hpos_dev; A.pair_status = status_dev; A.hap_ref_pos = hap_ref_pos_dev; A.hap_aligned = hap_aligned_dev;
-    A.out = *out_dev; A.ops_cap = ops_cap;
+    const int rc = cigar_front("dd_cigars_device", "dd_cigar_result", A, b, hpos_dev, status_dev, hap_ref_pos_dev, hap_aligned_dev, ops_cap,
+                               out_dev->n_ops && out_dev->ops && out_dev->ref_off && out_dev->status,
+                               b->n_windows <= 0 || b->n_haps <= 0 || b->n_reads <= 0 || (pair_end >= 0 && pair_end <= pair_begin));
+    if (rc) return rc < 0 ? rc : DD_SUCCESS;
+    A.pair_begin = pair_begin; A.pair_end = pair_end;
+    A.out = *out_dev;
     A.max_pairs = pair_end >= 0 ? pair_end - pair_begin : (int64_t)b->n_haps * b->n_reads;
     HIP_TRY(ddc::launch_cigars(A, static_cast<hipStream_t>(stream)));
     return DD_SUCCESS;
 }
 
-// ---------------- realigned reads (realign_kernel.hip) ----------------
 int launch_realign_range(const dd_device_batch *b, const RealignInputs &in, const dd_realign_result *out_dev, int ops_cap, void *stream,
                          int read_begin, int read_end)
 {
@@ -270,23 +193,14 @@ int launch_realign_range(const dd_device_batch *b, const RealignInputs &in, cons
     if (in.mode != DD_REALIGN_FIRST_MAX && in.mode != DD_REALIGN_PAIR) return fail(DD_ERR_INVALID, "dd_realign_device: unknown mode");
     if (in.mode == DD_REALIGN_PAIR && (!in.win_hap_pair || !in.hap_n_indels))
         return fail(DD_ERR_INVALID, "dd_realign_device: DD_REALIGN_PAIR needs win_hap_pair and hap_n_indels");
-    if (!in.hap_ref_pos) return fail(DD_ERR_INVALID, "dd_realign_device: hap_ref_pos is required (Haplotype::refHpos per haplotype base)");
-    if (ops_cap < 1) return fail(DD_ERR_INVALID, "dd_realign_device: ops_cap must be at least 1");
-    if (!out_dev->hap || !out_dev->status || !out_dev->n_ops || !out_dev->ops || !out_dev->ref_off)
-        return fail(DD_ERR_INVALID, "dd_realign_device: every array of dd_realign_result is required");
     if (read_end < 0) read_end = b->n_reads;
-    if (b->n_windows <= 0 || read_end <= read_begin) return DD_SUCCESS;      // (reads of windows without haplotypes are still marked)
-    if (!b->win_hap_off || !b->win_read_off || !b->hap_seq_off || !b->read_seq_off || !b->win_pair_off || !b->win_hpos_off)
-        return fail(DD_ERR_INVALID, "dd_realign_device: the batch lacks an offset array");
     ddc::RealignArgs A;
     memset(&A, 0, sizeof(A));
-    ddc::CigarArgs &C = A.cig;
-    C.n_windows = b->n_windows;
-    C.win_hap_off = b->win_hap_off; C.win_read_off = b->win_read_off; C.hap_seq_off = b->hap_seq_off; C.read_seq_off = b->read_seq_off;
-    C.win_pair_off = b->win_pair_off; C.win_hpos_off = b->win_hpos_off;
-    C.hpos = in.hpos; C.pair_status = in.status; C.hap_ref_pos = in.hap_ref_pos; C.hap_aligned = in.hap_aligned;
-    C.out.n_ops = out_dev->n_ops; C.out.ops = out_dev->ops; C.out.ref_off = out_dev->ref_off; C.out.status = out_dev->status;
-    C.ops_cap = ops_cap;
+    const int rc = cigar_front("dd_realign_device", "dd_realign_result", A.cig, b, in.hpos, in.status, in.hap_ref_pos, in.hap_aligned, ops_cap,
+                               out_dev->hap && out_dev->status && out_dev->n_ops && out_dev->ops && out_dev->ref_off,
+                               b->n_windows <= 0 || read_end <= read_begin);      // (reads of windows without haplotypes are still marked)
+    if (rc) return rc < 0 ? rc : DD_SUCCESS;
+    A.cig.out.n_ops = out_dev->n_ops; A.cig.out.ops = out_dev->ops; A.cig.out.ref_off = out_dev->ref_off; A.cig.out.status = out_dev->status;
     A.mode = in.mode; A.read_begin = read_begin; A.read_end = read_end;
     A.ll = in.ll; A.on_hap = in.on_hap; A.win_hap_pair = in.win_hap_pair; A.hap_n_indels = in.hap_n_indels; A.hap = out_dev->hap;
     HIP_TRY(ddc::launch_realign(A, static_cast<hipStream_t>(stream)));
@@ -305,7 +219,7 @@ static int long_front_checks(const LongPath &lp, const dd_params *p, const dd_de
     return 0;
 }
 
-// The fields LongArgs and FLArgs name alike, from the batch; the model's own (read_flags, sym_lut, mate / library arrays, D, bMid) stay with the caller.
+// The workspace check and the fields LongArgs and FLArgs name alike; the model's own (read_flags, sym_lut, mate / library arrays, D, bMid) stay with the caller.
 // ws_bytes: what the plan needs.  stats: the caller's device words, or NULL for the ones in the workspace header.
 template <class Args>
 static int long_fill_args(const LongPath &lp, Args &A, const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace,
@@ -313,15 +227,9 @@ static int long_fill_args(const LongPath &lp, Args &A, const dd_params *p, const
 {
     if (!workspace || workspace_bytes < ws_bytes)
         return fail(DD_ERR_INVALID, std::string("workspace too small for the ") + lp.name + ": allocate " + lp.ws_fn + "() bytes");
-    A.n_windows = b->n_windows; A.w_begin = w_begin; A.w_end = w_end; A.read_begin = read_begin; A.read_end = read_end;
-    A.win_hap_off = b->win_hap_off; A.win_read_off = b->win_read_off; A.win_hap_start = b->win_hap_start;
-    A.hap_seq_off = b->hap_seq_off; A.hap_seq = b->hap_seq; A.hap_var_off = b->hap_var_off; A.hap_var = b->hap_var; A.hap_var_flank = b->hap_var_flank;
-    A.read_seq_off = b->read_seq_off; A.read_seq = b->read_seq; A.read_qidx = b->read_qidx; A.read_mqidx = b->read_mqidx;
-    A.read_start = b->read_start;
-    A.win_pair_off = b->win_pair_off; A.win_hpos_off = b->win_hpos_off; A.win_varcov_off = b->win_varcov_off;
-    A.tables = b->tables; A.win_class = b->win_skip;
-    A.out = *r;
-    A.maxLengthDel = p->maxLengthDel; A.padCover = p->padCover; A.maxMismatch = p->maxMismatch;
+    fill_batch_args(A, p, b, r);
+    A.w_begin = w_begin; A.w_end = w_end; A.read_begin = read_begin; A.read_end = read_end;
+    A.win_class = b->win_skip;
     A.ws = static_cast<unsigned char *>(workspace);
     A.stats = stats ? stats : reinterpret_cast<unsigned long long *>(A.ws + DD_LWS_HDR_STATS);
     return DD_SUCCESS;
@@ -409,17 +317,13 @@ thread_local LongPath g_flong = {"--faster long path", "dd_workspace_bytes_faste
 using namespace ddh;
 extern "C" {
 const char *dd_kernel_name(void)
-{   // the template instance this host thread launched last, as rocprofv3 prints it (inside "void ddk::...(ddk::KernelArgs)")
-    const int K = g_last_launch[0], D = g_last_launch[1];
-    if (K > 0 && D > 0) snprintf(g_kernel_name, sizeof(g_kernel_name), "dd_hmm_kernel<%d, %d, %s, %s, %d, %d>", K, D % 100, D >= 100 ? "true" : "false", g_last_fold ? "true" : "false", g_last_occ, g_last_G);
-    else if (K > 0) snprintf(g_kernel_name, sizeof(g_kernel_name), "dd_faster_kernel");
-    return g_kernel_name;
+{   // the kernel this host thread launched last
+    static thread_local char name[64];
+    shape_kernel_name(g_last_shape, name, sizeof(name));
+    return name;
 }
 
-void dd_last_launch(int32_t out[8])
-{   // K, D build, waves per workgroup, LDS bytes per workgroup, grid, read split, LDS per wave, shared LDS
-    for (int i = 0; i < 8; i++) out[i] = g_last_launch[i];
-}
+void dd_last_launch(int32_t out[8]) { shape_last_launch(g_last_shape, out); }
 
 int dd_launch_log(int32_t *out, int max_records)
 {   // see include/dindel_hmm.h

@@ -1,5 +1,6 @@
-// plan.cpp — the launch planner of the C ABI: lane tilings, LDS carve-up, occupancy, workgroup sizes and read splits, and the plans of the
-// two long-window paths.  Pure host arithmetic: nothing here calls the HIP runtime.
+// plan.cpp — the launch planner of the C ABI: lane tilings, LDS carve-up, occupancy, workgroup sizes and read splits; the whole shape of a
+// main-model or --faster launch (shape_launch, shape_fast) and its three descriptions; the A/B switches (read_switches).  Pure host
+// arithmetic: nothing here calls the HIP runtime or needs a kernel unit to link (the plans of the long-window paths are long_plan.cpp).
 #include "capi_internal.h"
 
 namespace ddh {
@@ -18,7 +19,6 @@ using ddc::up16;
 const HapClassDef kHapClasses[DD_N_HAP_CLASSES] = {
     {30, 2, 1}, {62, 1, 1}, {94, 2, 3}, {126, 1, 2}, {158, 2, 5}, {190, 1, 3}, {222, 1, 4}, {254, 1, 4},
     {318, 1, 5}, {382, 1, 6}, {446, 1, 7}, {510, 1, 8}, {574, 1, 9}, {638, 1, 10}, {702, 1, 11}, {DD_MAX_HAP_LEN, 1, 12}};
-static bool half_wave_off() { return getenv("DD_NO_HALF") != nullptr; }   // A/B and tests: whole-wavefront tilings only
 int hap_class_of(int hap_len)
 {
     for (int c = 0; c < DD_N_HAP_CLASSES; c++)
@@ -26,14 +26,14 @@ int hap_class_of(int hap_len)
     return -1;
 }
 // tiling for a launch whose longest haplotype is max_hap_len: false if it is too long
-bool pick_tiling(int max_hap_len, int Dt, int &G, int &K)
+bool pick_tiling(const Switches &sw, int max_hap_len, int Dt, int &G, int &K)
 {
     const int c = hap_class_of(max_hap_len);
     if (c < 0) return false;
     G = kHapClasses[c].G; K = kHapClasses[c].K;
     // (the half tilings in use gain at the D = 6, 11 and 12 builds: 9-16 % at maxLengthDel 10 / 11; the D = 32 build exists for whole
     // wavefronts only, up to K = 9 — 574 bp — because a position's back-pointer takes 7 bits there)
-    if (G > 1 && (half_wave_off() || Dt > 12)) { G = 1; K = (kHapClasses[c].bound + 2 + 63) / 64; }
+    if (G > 1 && (sw.no_half || Dt > 12)) { G = 1; K = (kHapClasses[c].bound + 2 + 63) / 64; }
     if (Dt > 12 && K > 9) return false;
     return true;
 }
@@ -56,7 +56,7 @@ static uint32_t bt_word_bytes(int K, int Dt)
 }
 
 // LDS carve-up for (K, Dt, Lmax); returns total dynamic LDS bytes per workgroup
-size_t lds_layout(int K, int Dt, int Lmax, int n_qual, int waves, bool gbt, int G, ddk::KernelArgs &A)
+static size_t lds_layout(int K, int Dt, int Lmax, int n_qual, int waves, bool gbt, int G, ddk::KernelArgs &A)
 {
     const uint32_t W = 64u / (uint32_t)G;        // lanes per pair
     const uint32_t NP = W * K;
@@ -92,11 +92,11 @@ size_t lds_layout(int K, int Dt, int Lmax, int n_qual, int waves, bool gbt, int 
 }
 
 // waves per CU the register file allows for each K (kernel-resource-usage of the shipped builds)
-static int reg_limited_waves_per_cu(int K, int Dt, bool gbt, int G = 1)
+static int reg_limited_waves_per_cu(const Switches &sw, int K, int Dt, bool gbt, int G = 1)
 {
     (void)G;
     if (Dt > 12) return K <= 3 ? 12 : (K <= 6 ? 8 : 4);   // the D = 32 build keeps a lane's own positions only: 125-144 registers up to K = 3, <= 244 up to K = 6
-    if (const char *e = getenv("DD_REG_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= 16) return v; }   // A/B builds with another occupancy
+    if (sw.reg_waves) return sw.reg_waves;      // A/B builds with another occupancy
     if (K <= 2) return (Dt <= 7 || gbt) ? 12 : 8;
     if (K == 3) return (gbt && Dt <= 7) ? 12 : ((gbt || Dt <= 7) ? 8 : 4);      // round 3: the D = 6 scratch build is held to 168 VGPRs (3 waves/SIMD)
     if (K == 4) return gbt ? 8 : 4;
@@ -106,7 +106,7 @@ static int reg_limited_waves_per_cu(int K, int Dt, bool gbt, int G = 1)
 
 // bytes of one wavefront's region of the HBM scratch: its back-pointer tile + (K >= 3 or half-wave builds) the [2 K][64] doubles where
 // beta[bMid] waits for the join (hmm_kernel.hip STASH)
-size_t scratch_wave_bytes(int K, int Dt, int G, int max_read_len)
+static size_t scratch_wave_bytes(int K, int Dt, int G, int max_read_len)
 {
     const bool slim = G > 1 || K == 3 || K == 5 || (K == 4 && Dt <= 7);       // hmm_kernel.hip SLIM
     return (size_t)max_read_len * 64u * bt_word_bytes(K, Dt) + (slim ? (size_t)2 * K * 64 * 8 : 0);
@@ -127,15 +127,15 @@ template <class LdsBytes> static int most_waves_per_cu(LdsBytes lds_bytes, int c
     return best;
 }
 
-int make_plan(const dd_params *p, int max_hap_len, int max_read_len, int n_qual, Plan &pl, ddk::KernelArgs &A)
+static int make_plan(const Switches &sw, const dd_params *p, int max_hap_len, int max_read_len, int n_qual, Plan &pl, ddk::KernelArgs &A)
 {
     pl.Dt = pick_Dt(p->maxLengthDel + 1);
-    if (!pick_tiling(max_hap_len, pl.Dt, pl.G, pl.K))
+    if (!pick_tiling(sw, max_hap_len, pl.Dt, pl.G, pl.K))
         return fail(DD_ERR_UNSUPPORTED, pl.Dt > 12 ? "haplotype longer than 574 bp with maxLengthDel > 11" : "haplotype too long");
     int best[2] = {0, 0}, bw[2] = {0, 0}, cap[2] = {0, 0};
     auto lds_of = [&](bool gbt) { return [&, gbt](int wv) { ddk::KernelArgs tmp = A; return lds_layout(pl.K, pl.Dt, max_read_len, n_qual, wv, gbt, pl.G, tmp); }; };
     for (int gbt = 0; gbt < 2; gbt++) {
-        cap[gbt] = reg_limited_waves_per_cu(pl.K, pl.Dt, gbt != 0, pl.G);
+        cap[gbt] = reg_limited_waves_per_cu(sw, pl.K, pl.Dt, gbt != 0, pl.G);
         best[gbt] = most_waves_per_cu(lds_of(gbt != 0), cap[gbt], bw[gbt]);
     }
     if (pl.Dt > 12) best[0] = 0;                   // the D = 32 build keeps its back-pointers in the HBM scratch only
@@ -164,10 +164,8 @@ int make_plan(const dd_params *p, int max_hap_len, int max_read_len, int n_qual,
     // K = 2 on the D = 11 build 5-8 % at every read length the LDS tile fits.  Now: scratch for every K >= 3 and for K = 2 above D = 7.
     const bool lean_only = pl.K >= 3 || (pl.K == 2 && pl.Dt > 7);
     pl.gbt = best[0] == 0 || (lean_only && best[1] > 0) || best[0] < cap[0];
-    if (const char *f = getenv("DD_FORCE_GBT")) {                  // A/B only
-        if (f[0] == '1' && best[1] > 0) pl.gbt = true;
-        if (f[0] == '0' && best[0] > 0) pl.gbt = false;
-    }
+    if (sw.force_gbt == 1 && best[1] > 0) pl.gbt = true;          // A/B only
+    if (sw.force_gbt == 0 && best[0] > 0) pl.gbt = false;
     pl.waves = bw[pl.gbt ? 1 : 0];
     pl.waves_per_cu = best[pl.gbt ? 1 : 0];
     pl.lds = lds_layout(pl.K, pl.Dt, max_read_len, n_qual, pl.waves, pl.gbt, pl.G, A);
@@ -182,21 +180,21 @@ int make_plan(const dd_params *p, int max_hap_len, int max_read_len, int n_qual,
 }
 
 // the plan alone, for callers that launch nothing
-static int plan_only(const dd_params *p, int max_hap_len, int max_read_len, int n_qual, Plan &pl)
+static int plan_only(const Switches &sw, const dd_params *p, int max_hap_len, int max_read_len, int n_qual, Plan &pl)
 {
     ddk::KernelArgs A;
     memset(&A, 0, sizeof(A));
-    return make_plan(p, max_hap_len, max_read_len, n_qual, pl, A);
+    return make_plan(sw, p, max_hap_len, max_read_len, n_qual, pl, A);
 }
 
-int lds_read_threshold(const dd_params *p, int max_hap_len, int n_qual)
+int lds_read_threshold(const Switches &sw, const dd_params *p, int max_hap_len, int n_qual)
 {
     if (!p || check_params(p) != DD_SUCCESS) return 0;
     int lo = 0, hi = 160;                       // largest L in [1, 160] whose plan keeps the back-pointers in LDS (0: none)
     while (lo < hi) {
         const int mid = (lo + hi + 1) / 2;
         Plan pl;
-        if (plan_only(p, max_hap_len, mid, n_qual > 0 ? n_qual : 1, pl) == DD_SUCCESS && !pl.gbt) lo = mid; else hi = mid - 1;
+        if (plan_only(sw, p, max_hap_len, mid, n_qual > 0 ? n_qual : 1, pl) == DD_SUCCESS && !pl.gbt) lo = mid; else hi = mid - 1;
     }
     return lo;
 }
@@ -207,7 +205,7 @@ int lds_read_threshold(const dd_params *p, int max_hap_len, int n_qual)
 // (tools/coverage_sweep.py: 2 reads per window ran at half the rate with 4-wave workgroups).
 // per_cu: waves the build keeps on a CU — workgroups of w waves leave per_cu % w of them unused (three-wave workgroups of a build
 // held to 8 waves: 6 resident; the --faster kernel ran 10-read windows at 3.7e11 instead of 4.6e11 that way)
-int waves_for_reads(int64_t units, int maxw, int per_cu)
+static int waves_for_reads(int64_t units, int maxw, int per_cu)
 {
     if (units < 1) units = 1;
     if (per_cu < maxw) per_cu = maxw;
@@ -232,7 +230,7 @@ int waves_for_reads(int64_t units, int maxw, int per_cu)
 // wins.  Measured against the rule without the round term (DD_SPLIT_NO_ROUNDS=1, profiles/r03/split_ab.txt): 128 windows
 // +4.6 %, 512 windows +1.8 %, the other sizes within 0.5 % — workgroups do not finish in lock step, so the rounds matter
 // less than the count suggests.  resident == 0: the rounds are not modelled (the --faster kernel's callers).
-int64_t pick_split(int64_t n_haps, int64_t units, int waves, int64_t min_blocks, int64_t resident)
+static int64_t pick_split(int64_t n_haps, int64_t units, int waves, int64_t min_blocks, int64_t resident = 0)
 {
     if (units < 1) units = 1;
     if (n_haps < 1) n_haps = 1;
@@ -267,13 +265,20 @@ int64_t pick_split(int64_t n_haps, int64_t units, int waves, int64_t min_blocks,
 }
 
 // workgroups of `waves` waves and `lds` bytes the chip holds at once, for a build that keeps waves_per_cu waves on a CU
-int64_t resident_workgroups(size_t lds, int waves_per_cu, int waves)
+static int64_t resident_workgroups(size_t lds, int waves_per_cu, int waves)
 {
     return kCUs * (int64_t)std::max(1, std::min((int)(kCuLdsBytes / (lds ? lds : 1)), waves_per_cu / waves));
 }
 
+// --faster model: LDS bytes of a workgroup of `waves` waves with `groups` pairs per wavefront, from the layout in A.  Pair areas per
+// wavefront: one per concurrent pair, plus a dummy for the idle 16-lane groups when fewer than 4 fit.
+static size_t fast_lds_bytes(const ddk::KernelArgs &A, int waves, int groups)
+{
+    return (size_t)A.lds_shared_bytes + (size_t)waves * (groups < 4 ? groups + 1 : 4) * A.lds_wave_bytes;
+}
+
 // --faster model LDS: block-shared haplotype index + per-pair areas (layout in faster_kernel.hip's header)
-size_t lds_layout_fast(int max_hap_len, int max_read_len, int n_qual, int &waves, int &groups, ddk::KernelArgs &A)
+static size_t lds_layout_fast(const Switches &sw, int max_hap_len, int max_read_len, int n_qual, int &waves, int &groups, ddk::KernelArgs &A)
 {
     uint32_t off = 0;
     A.lds_off_E = off; off = up16(off + 16u * (uint32_t)(n_qual > 0 ? n_qual : 1));
@@ -291,86 +296,170 @@ size_t lds_layout_fast(int max_hap_len, int max_read_len, int n_qual, int &waves
     A.lds_off_I = po;   po = up16(po + 256u);
     A.lds_off_rdQ = po; po = up16(po + 64u);
     A.lds_wave_bytes = po;                       // bytes per PAIR area
-    const size_t cap = kCuLdsBytes;
-    // pair areas per wavefront: one per concurrent pair, plus a dummy for the idle 16-lane groups when fewer than 4 fit
-    auto areas = [](int gq) { return gq < 4 ? gq + 1 : 4; };
     groups = 4;
-    if (const char *e = getenv("DD_FAST_GROUPS")) {             // tests: exercise the fewer-pairs-per-wavefront geometry
-        const int gq = atoi(e);
-        if (gq == 1 || gq == 2) groups = gq;
-    }
-    while (groups > 1 && (size_t)off + (size_t)areas(groups) * po > cap) groups >>= 1;
+    if (sw.fast_groups) groups = sw.fast_groups;                // tests: exercise the fewer-pairs-per-wavefront geometry
+    while (groups > 1 && fast_lds_bytes(A, 1, groups) > kCuLdsBytes) groups >>= 1;
     // waves per workgroup: whatever keeps the most wavefronts resident per CU (ties: more waves share one haplotype index)
-    most_waves_per_cu([&](int wv) { return (size_t)off + (size_t)wv * areas(groups) * po; }, 8, waves);   // (8: the kernel is built for 2 waves per SIMD)
+    most_waves_per_cu([&](int wv) { return fast_lds_bytes(A, wv, groups); }, 8, waves);   // (8: the kernel is built for 2 waves per SIMD)
     if (waves < 1) waves = 1;
-    if (const char *e = getenv("DD_FAST_WAVES")) {              // A/B only
-        const int wv = atoi(e);
-        if (wv >= 1 && wv <= DD_WAVES && (size_t)off + (size_t)wv * areas(groups) * po <= cap) waves = wv;
+    if (sw.fast_waves && fast_lds_bytes(A, sw.fast_waves, groups) <= kCuLdsBytes) waves = sw.fast_waves;   // A/B only
+    return fast_lds_bytes(A, waves, groups);
+}
+
+Switches read_switches()
+{
+    Switches sw;
+    auto on = [](const char *name) { return getenv(name) != nullptr; };
+    auto num = [](const char *name) { const char *e = getenv(name); return e ? atoi(e) : 0; };
+    sw.no_half = on("DD_NO_HALF");
+    if (const int v = num("DD_REG_WAVES"); v >= 1 && v <= 16) sw.reg_waves = v;
+    if (const char *e = getenv("DD_FORCE_GBT")) sw.force_gbt = e[0] == '1' ? 1 : (e[0] == '0' ? 0 : -1);
+    if (const int v = num("DD_FAST_GROUPS"); v == 1 || v == 2) sw.fast_groups = v;
+    if (const int v = num("DD_FAST_WAVES"); v >= 1 && v <= DD_WAVES) sw.fast_waves = v;
+    if (const char *e = getenv("DD_FAST_TARGET_BLOCKS")) { const long v = atol(e); if (v >= 1) sw.fast_target_blocks = v; }
+    sw.always_ro = on("DD_ALWAYS_RO");
+    if (const char *e = getenv("DD_TARGET_BLOCKS")) { const long v = atol(e); if (v >= 1) sw.target_blocks = v; }
+    sw.split_no_rounds = on("DD_SPLIT_NO_ROUNDS");
+    sw.uniform_split = on("DD_UNIFORM_SPLIT");
+    if (const int v = num("DD_READS_PER_WAVE"); v >= 1) sw.reads_per_wave = v;
+    if (const char *e = getenv("DD_DYNAMIC")) sw.dynamic = e[0] == '1' ? 1 : 0;
+    sw.no_fold = on("DD_NO_FOLD");
+    sw.no_promote = on("DD_NO_PROMOTE");
+    if (const char *e = getenv("DD_LENGTH_CLASSES")) sw.one_read_class = !strcmp(e, "k");
+    if (on("DD_READ_BOUND")) sw.read_bound = std::max(num("DD_READ_BOUND"), 0);
+    return sw;
+}
+
+// The builds measured to gain from the fold (end states inside the generic candidate code, hmm_kernel.hip FOLD): K <= 2 at D build 6 with
+// LDS back-pointers, K = 2 at D build 6 with scratch back-pointers, K = 2 at D build 11 with LDS back-pointers.  (Not build_launch_classes'
+// "tilings that have a folded build": that one asks which haplotypes are worth a launch of their own.)
+static bool launch_has_fold_build(const Plan &pl)
+{
+    return pl.gbt ? (pl.K == 2 && pl.Dt == 6) : ((pl.K <= 2 && pl.Dt == 6) || (pl.K == 2 && pl.Dt == 11));
+}
+
+int shape_launch(const Switches &sw, const LaunchAsk &ask, LaunchShape &s, ddk::KernelArgs &A)
+{
+    s = LaunchShape();
+    const ClassDims *lc = ask.has_class ? &ask.cls : nullptr;
+    const int cls_hap = lc ? lc->max_hap_len : ask.max_hap_len, cls_read = lc ? lc->max_read_len : ask.max_read_len;
+    Plan &pl = s.pl;
+    const int rc = make_plan(sw, ask.p, cls_hap, cls_read, ask.n_qual, pl, A);
+    if (rc) return rc;
+    const int K = pl.K, Dt = pl.Dt;
+    s.waves = pl.waves;
+    s.lds = pl.lds;
+    // thin windows: a wavefront works on one read at a time, so a workgroup never needs more waves than the windows have
+    // reads (tools/coverage_sweep.py: 2 reads per window ran at half the rate with idle waves in every workgroup)
+    const int64_t avg_reads = (lc && lc->avg_window_reads > 0) ? lc->avg_window_reads : (ask.n_reads + ask.n_windows - 1) / (ask.n_windows > 0 ? ask.n_windows : 1);
+    const int64_t units = (avg_reads + pl.G - 1) / pl.G;                       // a wavefront takes G reads at a time
+    if (const int w2 = waves_for_reads(units, s.waves, pl.waves_per_cu); w2 != s.waves) {
+        s.waves = w2;
+        s.lds = lds_layout(K, Dt, cls_read, ask.n_qual, w2, pl.gbt, pl.G, A);
     }
-    return (size_t)off + (size_t)waves * areas(groups) * po;
-}
-
-// header + window list + prefix list of a long workspace (kernel_common.h): where the prefix list and the tiles start
-static uint64_t al256(uint64_t v) { return (v + 255u) & ~(uint64_t)255u; }
-static void long_list_layout(int n_windows, uint64_t &off_prefix, uint64_t &off_tiles)
-{
-    off_prefix = al256(DD_LWS_HEADER + 4 * (uint64_t)std::max(n_windows, 1));
-    off_tiles = al256(off_prefix + 8 * (uint64_t)(std::max(n_windows, 0) + 1));
-}
-
-// ---------------- long windows of the main model (long_kernel.hip) ----------------
-// Plan of a long launch: K states per thread (numS <= 256 K, K = 1, 2, 4, 8, 16), LDS, and the persistent grid: the chip's resident
-// workgroups (LDS- and register-limited: 2 per CU, 1 at K = 16), shrunk so that header + lists + one back-pointer tile per workgroup stay
-// within DD_LONG_WS_BUDGET.
-int long_plan(int n_windows, int max_hap_len, int max_read_len, int n_qual, LongPlan &lp, ddl::LongArgs &A)
-{
-    if (max_hap_len < 1 || max_hap_len > DD_LONG_MAX_HAP_LEN) return fail(DD_ERR_UNSUPPORTED, "long path: haplotype length outside [1,4094]");
-    if (max_read_len < 1 || max_read_len > DD_LONG_MAX_READ_LEN) return fail(DD_ERR_UNSUPPORTED, "long path: read length outside [1,4096]");
-    const int numS = max_hap_len + 2;
-    lp.K = 1;
-    while (DD_LONG_THREADS * lp.K < numS) lp.K *= 2;
-    A.n_qual = n_qual;
-    lp.lds = ddl::long_lds_layout(lp.K, max_read_len, A);
-    if (lp.lds + 64 > kCuLdsBytes) return fail(DD_ERR_UNSUPPORTED, "long path: LDS layout too large");
-    const unsigned per_cu = std::max(1u, std::min(lp.K >= 16 ? 1u : 2u, (unsigned)((kCuLdsBytes) / (lp.lds + 64))));
-    long_list_layout(n_windows, lp.off_lpoff, lp.off_tiles);
-    lp.stash_off = al256((uint64_t)max_read_len * DD_LONG_THREADS * lp.K);
-    lp.tile_bytes = lp.stash_off + 16 * (uint64_t)DD_LONG_THREADS * lp.K;
-    uint64_t grid = (uint64_t)kCUs * per_cu;
-    const uint64_t fit = DD_LONG_WS_BUDGET > lp.off_tiles ? (DD_LONG_WS_BUDGET - lp.off_tiles) / lp.tile_bytes : 0;
-    if (grid > fit) grid = fit;
-    if (grid < 1) grid = 1;
-    lp.grid = (unsigned)grid;
-    lp.ws_bytes = lp.off_tiles + grid * lp.tile_bytes;
+    s.lds_wave_bytes = A.lds_wave_bytes;
+    s.lds_shared_bytes = A.lds_shared_bytes;
+    if (pl.gbt) {
+        if (ask.workspace_bytes < pl.scratch_bytes + DD_WS_HEADER)
+            return fail(DD_ERR_INVALID, "workspace too small for this shape: allocate dd_workspace_bytes() bytes");
+        s.scratch_off = DD_WS_HEADER;
+        s.bt_rows = cls_read;
+        s.bt_wave_bytes = (uint32_t)scratch_wave_bytes(K, Dt, pl.G, cls_read);
+    }
+    int hap_begin = ask.hap_begin, hap_end = ask.hap_end;
+    if (hap_end < 0) { hap_begin = 0; hap_end = ask.n_haps; }
+    if (lc && lc->listed) { hap_begin = lc->list_begin; hap_end = lc->list_end; }   // positions in the class list
+    s.n_haps = hap_end - hap_begin; s.max_hap = cls_hap; s.min_read = lc ? lc->min_read_len : 1; s.max_read = cls_read;
+    // the split is chosen for the haplotypes THIS launch covers: a rare length class or a small window block must still
+    // spread over the chip; enough workgroups to fill 256 CUs several times over (target_blocks), but keep >= 1 read per wave
+    // resident: workgroups the chip holds at once (one-shot grids; a persistent GBT grid is capped to that number below anyway)
+    int64_t resident = resident_workgroups(s.lds, pl.waves_per_cu, s.waves);
+    if (sw.split_no_rounds) resident = 0;                                      // A/B only: the rule before round 3
+    s.split = pick_split(s.n_haps, units, s.waves, sw.target_blocks, resident);
+    // Ragged windows: `split` suits a window with the average number of reads; a haplotype whose window has more gets proportionally more
+    // workgroups (the kernel derives its own count from reads_per_wave), so that a 400-read window among 100-read ones does not end the
+    // launch with one workgroup still at work; when the spread is wide the work of a wavefront is also capped (DD_READS_PER_WAVE, A/B).
+    const int max_reads = (lc && lc->max_window_reads > 0) ? lc->max_window_reads : ask.max_window_reads;
+    if (max_reads > 0 && max_reads * 4 > avg_reads * 5 && !sw.uniform_split) {
+        const int64_t max_units = (max_reads + pl.G - 1) / pl.G;
+        const int64_t cap_rpw = sw.reads_per_wave ? sw.reads_per_wave : ((Dt > 7 || K >= 3) ? 24 : 12);
+        const int64_t rpw = std::max<int64_t>(1, std::min((units + s.waves * s.split - 1) / (s.waves * s.split), cap_rpw));
+        s.reads_per_wave = (int)rpw;
+        s.split = std::max<int64_t>(1, (max_units + s.waves * rpw - 1) / (s.waves * rpw));
+    }
+    if ((int64_t)ask.n_haps * s.split > 0x7fffffffLL) return fail(DD_ERR_UNSUPPORTED, "batch too large for one launch");
+    s.item_begin = (int32_t)(hap_begin * s.split);
+    s.n_items = (int32_t)(hap_end * s.split);
+    s.n_launch_items = s.grid = (int64_t)s.n_haps * s.split;
+    if (s.grid <= 0) return DD_SUCCESS;
+    if (pl.grid_cap)     // the scratch holds grid_cap x pl.waves back-pointer tiles; smaller workgroups (thin windows) may be more numerous
+        s.grid = std::min(s.grid, (int64_t)pl.grid_cap * pl.waves / s.waves);
+    // More items than the chip holds workgroups: a persistent grid that draws its items from a counter.  Built for the ragged launches (items that
+    // differ 20-fold in work); at the end of round 4 it turned out to be worth as much on UNIFORM batches wherever the grid was persistent
+    // already — every HBM-scratch build ran a fixed stride, and the items of a uniform batch still differ by their reads' bMid: 3.42 -> 3.85e11 cells/s
+    // at 130 bp, 3.34 -> 3.88e11 at 80 bp, +10-18 % on every K >= 3 tiling (profiles/r04/item_counter_uniform_ab.txt) — and +0.1-1.5 % on the
+    // one-shot LDS grids (the headline build: +0.9 %), whose XCD-contiguous numbering (one L2 per window's haplotypes) it gives up.
+    // (Except: the chunks of the host-pointer path alternate between two streams, and a one-shot grid lets the next chunk's workgroups move in
+    // while this one's drain; a chip-filling persistent grid holds its slots to the end — `dd_compute_likelihoods` with pageable pointers lost 7 %
+    // that way, 23.7 -> 22.0 k windows/s at configs[1].  There the LDS builds keep their one-shot grids unless the batch is ragged.)
+    const bool spread = s.reads_per_wave > 0 || (lc && lc->avg_read_len > 0 && lc->max_read_len * 4 > lc->avg_read_len * 5);
+    const bool dynamic = sw.dynamic >= 0 ? sw.dynamic == 1 : (pl.gbt || spread || !ask.overlapping_chunks);   // DD_DYNAMIC=0: one-shot LDS grids, fixed stride on scratch builds
+    if (dynamic && ask.workspace_bytes >= DD_WS_HEADER && resident > 0 && s.n_launch_items > resident) {
+        s.use_counter = true;
+        s.grid = std::min(s.grid, resident);
+    }
+    // the FOLD build needs every haplotype of this launch to leave position 64 K - 1 idle (numS <= 64 K - 1)
+    s.fold = pl.G == 1 && launch_has_fold_build(pl) && 64 * K >= cls_hap + 3 && !sw.no_fold;
+    s.occ = (pl.gbt && pl.two_waves) ? 2 : 0;
+    s.build = (s.fold ? DD_BUILD_FOLD : 0) | (s.occ == 2 ? DD_BUILD_TWO_WAVES : 0) | (pl.G == 2 ? DD_BUILD_HALF : 0);
     return DD_SUCCESS;
 }
 
-// ---------------- long windows of the --faster model (faster_long_kernel.hip) ----------------
-// Plan of a launch: LDS for the shape, and the persistent grid: the chip's resident workgroups (LDS-limited, at most 2 per CU: the kernel is
-// built for 2 waves per SIMD), no more than the batch can have 16-pair items, shrunk so that header + lists + 16 tiles per workgroup stay
-// within DD_FASTER_LONG_WS_BUDGET.
-int fl_plan(const dd_device_batch *b, FLPlan &fp, ddf::FLArgs &A)
+int shape_fast(const Switches &sw, const LaunchAsk &ask, LaunchShape &s, ddk::KernelArgs &A)
 {
-    const int mh = b->long_max_hap_len, mr = b->long_max_read_len;
-    if (mh < 1 || mh > DD_LONG_MAX_HAP_LEN) return fail(DD_ERR_UNSUPPORTED, "--faster long path: haplotype length outside [1,4094]");
-    if (mr < 1 || mr > DD_LONG_MAX_READ_LEN) return fail(DD_ERR_UNSUPPORTED, "--faster long path: read length outside [1,4096]");
-    A.n_qual = b->n_qual;
-    A.max_hap_len = mh; A.max_read_len = mr;
-    fp.lds = ddf::fl_lds_layout(mh, mr, A);
-    if (fp.lds + 64 > kCuLdsBytes) return fail(DD_ERR_UNSUPPORTED, "--faster long path: LDS layout too large");
-    const unsigned per_cu = std::max(1u, std::min(2u, (unsigned)((kCuLdsBytes) / (fp.lds + 64))));
-    long_list_layout(b->n_windows, fp.off_ioff, fp.off_tiles);
-    const uint64_t wg_bytes = DD_FL_PAIRS * ddf::fl_tile_layout(mh, mr, A);
-    uint64_t grid = (uint64_t)kCUs * per_cu;
-    const uint64_t items = (uint64_t)std::max(b->n_haps, 0) * (((uint64_t)std::max(b->n_reads, 0) + DD_FL_PAIRS - 1) / DD_FL_PAIRS);
-    if (grid > items) grid = items;
-    const uint64_t fit = DD_FASTER_LONG_WS_BUDGET > fp.off_tiles ? (DD_FASTER_LONG_WS_BUDGET - fp.off_tiles) / wg_bytes : 0;
-    if (grid > fit) grid = fit;
-    if (grid < 1) grid = 1;
-    fp.grid = (unsigned)grid;
-    fp.ws_bytes = fp.off_tiles + grid * wg_bytes;
-    A.off_ioff = fp.off_ioff; A.off_tiles = fp.off_tiles; A.grid = (int32_t)grid;
+    s = LaunchShape();
+    s.faster = true;
+    s.lds = lds_layout_fast(sw, ask.max_hap_len, ask.max_read_len, ask.n_qual, s.waves, s.groups, A);
+    if (s.lds > kCuLdsBytes) return fail(DD_ERR_UNSUPPORTED, "shape exceeds the LDS tile of the --faster kernel");
+    s.lds_wave_bytes = A.lds_wave_bytes;
+    const int64_t avg_reads = (ask.n_reads + ask.n_windows - 1) / (ask.n_windows > 0 ? ask.n_windows : 1);
+    const int64_t units = (avg_reads + s.groups - 1) / s.groups;
+    // thin windows: no more wavefronts per workgroup than the windows have groups of `groups` reads
+    if (const int w2 = waves_for_reads(units, s.waves, 8); w2 != s.waves) {
+        s.waves = w2;
+        s.lds = fast_lds_bytes(A, w2, s.groups);
+    }
+    int hap_begin = ask.hap_begin, hap_end = ask.hap_end;
+    if (hap_end < 0) { hap_begin = 0; hap_end = ask.n_haps; }
+    s.n_haps = hap_end - hap_begin;
+    s.split = pick_split(s.n_haps, units, s.waves, sw.fast_target_blocks);
+    if ((int64_t)ask.n_haps * s.split > 0x7fffffffLL) return fail(DD_ERR_UNSUPPORTED, "batch too large for one launch");
+    s.item_begin = (int32_t)(hap_begin * s.split);
+    s.n_items = (int32_t)(hap_end * s.split);
+    s.n_launch_items = s.grid = (int64_t)s.n_haps * s.split;
     return DD_SUCCESS;
+}
+
+void shape_last_launch(const LaunchShape &s, int32_t out[8])
+{   // K (--faster: pairs per wavefront), D build (+ 100: scratch back-pointers; --faster: 0), waves per workgroup, LDS bytes per workgroup, grid, read split,
+    // LDS per wave, shared LDS
+    const int32_t v[8] = {s.faster ? s.groups : s.pl.K, s.faster ? 0 : s.pl.Dt + (s.pl.gbt ? 100 : 0), s.waves, (int32_t)s.lds, (int32_t)s.grid,
+                          (int32_t)s.split, (int32_t)s.lds_wave_bytes, (int32_t)s.lds_shared_bytes};
+    memcpy(out, v, sizeof(v));
+}
+
+void shape_kernel_name(const LaunchShape &s, char *name, size_t size)
+{   // the template instance as rocprofv3 prints it (inside "void ddk::...(ddk::KernelArgs)"); no launch yet: the main kernel's plain name
+    if (s.faster) snprintf(name, size, "dd_faster_kernel");
+    else if (s.pl.K > 0) snprintf(name, size, "dd_hmm_kernel<%d, %d, %s, %s, %d, %d>", s.pl.K, s.pl.Dt, s.pl.gbt ? "true" : "false", s.fold ? "true" : "false", s.occ, s.pl.G);
+    else snprintf(name, size, "dd_hmm_kernel");
+}
+
+void shape_log_record(const LaunchShape &s, int32_t v[DD_LAUNCH_LOG_FIELDS])
+{   // include/dindel_hmm.h dd_launch_log; field 15, the duration, is filled in when the log is read
+    const int32_t r[DD_LAUNCH_LOG_FIELDS] = {s.pl.K, s.pl.G, s.pl.Dt, s.pl.gbt ? 1 : 0, s.fold ? 1 : 0, s.waves, (int32_t)s.lds, (int32_t)s.grid, (int32_t)s.split,
+                                             s.n_haps, s.max_hap, s.min_read, s.max_read, s.pl.waves_per_cu, s.occ, -1, s.use_counter ? 1 : 0, s.reads_per_wave};
+    memcpy(v, r, sizeof(r));
 }
 } // namespace ddh
 using namespace ddh;
@@ -379,36 +468,15 @@ size_t dd_workspace_bytes(const dd_params *p, const dd_device_batch *b)
 {
     if (!p || !b || check_params(p) != DD_SUCCESS) return 0;
     if (b->max_hap_len < 1 || b->max_read_len < 1) return 0;
+    const Switches sw = read_switches();
     Plan pl;
-    if (plan_only(p, b->max_hap_len, b->max_read_len, b->n_qual, pl) != DD_SUCCESS) return 0;
+    if (plan_only(sw, p, b->max_hap_len, b->max_read_len, b->n_qual, pl) != DD_SUCCESS) return 0;
     size_t bytes = pl.scratch_bytes;
     if (b->classes && b->hap_class_list)          // per-class launches: the largest scratch any of them needs
         for (int i = 0; i < b->classes->n_launches; i++)
-            if (plan_only(p, b->classes->launch[i].max_hap_len, b->classes->launch[i].max_read_len, b->n_qual, pl) == DD_SUCCESS)
+            if (plan_only(sw, p, b->classes->launch[i].max_hap_len, b->classes->launch[i].max_read_len, b->n_qual, pl) == DD_SUCCESS)
                 bytes = std::max(bytes, pl.scratch_bytes);
     return bytes + DD_WS_HEADER;                  // the work counter of the ragged launches in front of the back-pointer tiles
-}
-
-size_t dd_workspace_bytes_long(const dd_params *p, const dd_device_batch *b)
-{
-    (void)p;
-    if (!b || b->long_max_hap_len <= 0 || b->long_max_read_len <= 0) return 0;
-    ddl::LongArgs A;
-    memset(&A, 0, sizeof(A));
-    LongPlan lp;
-    if (long_plan(b->n_windows, b->long_max_hap_len, b->long_max_read_len, b->n_qual, lp, A)) return 0;
-    return (size_t)lp.ws_bytes;
-}
-
-size_t dd_workspace_bytes_faster_long(const dd_params *p, const dd_device_batch *b)
-{
-    (void)p;
-    if (!b || b->long_max_hap_len <= 0 || b->long_max_read_len <= 0) return 0;
-    ddf::FLArgs A;
-    memset(&A, 0, sizeof(A));
-    FLPlan fp;
-    if (fl_plan(b, fp, A)) return 0;
-    return (size_t)fp.ws_bytes;
 }
 
 int dd_plan_info(const dd_params *p, int max_hap_len, int max_read_len, int n_qual, int avg_reads, int n_haps, int32_t out[10])
@@ -418,18 +486,17 @@ int dd_plan_info(const dd_params *p, int max_hap_len, int max_read_len, int n_qu
     if (!out) return fail(DD_ERR_INVALID, "null argument");
     if (max_hap_len < 1 || max_hap_len > DD_MAX_HAP_LEN) return fail(DD_ERR_UNSUPPORTED, "haplotype length outside [1,766]");
     if (max_read_len < 1 || max_read_len > DD_MAX_READ_LEN) return fail(DD_ERR_UNSUPPORTED, "read length outside [1,1024]");
-    Plan pl;
+    // the shape of a whole-batch launch over n_haps haplotypes in windows of avg_reads reads, with all the workspace it may want
+    LaunchAsk ask;
+    ask.p = p; ask.n_windows = 1; ask.n_haps = n_haps; ask.n_reads = avg_reads; ask.max_hap_len = max_hap_len; ask.max_read_len = max_read_len;
+    ask.n_qual = n_qual; ask.workspace_bytes = ~(size_t)0;
+    LaunchShape s;
     ddk::KernelArgs A;
     memset(&A, 0, sizeof(A));
-    if ((rc = make_plan(p, max_hap_len, max_read_len, n_qual, pl, A))) return rc;
-    const int waves = waves_for_reads((avg_reads + pl.G - 1) / pl.G, pl.waves, pl.waves_per_cu);
-    out[8] = pl.G; out[9] = 0;
-    avg_reads = (avg_reads + pl.G - 1) / pl.G;   // units of work per haplotype: a wavefront takes G reads at a time
-    out[0] = pl.K; out[1] = pl.Dt; out[2] = pl.gbt ? 1 : 0; out[3] = waves;
-    out[5] = (int32_t)lds_layout(pl.K, pl.Dt, max_read_len, n_qual, waves, pl.gbt, pl.G, A);
-    out[4] = (int32_t)pick_split(n_haps, avg_reads, waves, 4096, resident_workgroups((size_t)out[5], pl.waves_per_cu, waves));
-    out[6] = (int32_t)((pl.scratch_bytes >> 10) & 0x7fffffff);
-    out[7] = pl.waves_per_cu;
+    if ((rc = shape_launch(read_switches(), ask, s, A))) return rc;
+    const int32_t v[10] = {s.pl.K, s.pl.Dt, s.pl.gbt ? 1 : 0, s.waves, (int32_t)s.split, (int32_t)s.lds, (int32_t)((s.pl.scratch_bytes >> 10) & 0x7fffffff),
+                           s.pl.waves_per_cu, s.pl.G, 0};
+    memcpy(out, v, sizeof(v));
     return DD_SUCCESS;
 }
 } // extern "C"
