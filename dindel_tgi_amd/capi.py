@@ -387,6 +387,19 @@ def _launch_log(fn, fields):
     return [dict(zip(fields, [int(v) for v in buf[i]])) for i in range(min(n, 64))]
 
 
+def last_launch_of(symbol, fields):
+    """This thread's last launch of one of the drawing kernels: the int64 record `symbol` (a dd_*_last_launch) fills, as a dict."""
+    out = (C.c_int64 * len(fields))()
+    getattr(load(), symbol)(C.byref(out))
+    return dict(zip(fields, list(out)))
+
+
+def stream_of(stream, device):
+    """`stream`, or the current torch stream of `device` when it is None."""
+    import torch
+    return stream if stream is not None else torch.cuda.current_stream(device)
+
+
 def long_launch_log():
     """Every long-window launch of the last dd_launch_device_long / dd_compute_likelihoods_ex call of this thread (dd_long_launch_log)."""
     return _launch_log(load().dd_long_launch_log, LONG_LOG_FIELDS)

@@ -7,11 +7,8 @@
 
 namespace dda {
 
-/* The event launch runs behind an alignment launch and keeps its three words in that launch's workspace header (DD_ALIGN_WS_HEADER bytes,
- * of which the alignment uses words 0 ... 2): zeroed on the stream in front of the event launch. */
-#define DD_EVENTS_HDR_COUNTER 4       /* header word: u32 pair counter of the event launch */
-#define DD_EVENTS_HDR_MAX_DRAWS 5     /* header word: most pairs one wavefront drew */
-#define DD_EVENTS_HDR_TRIPS 6         /* header word: wavefronts that left through the draw guard: 0 */
+/* The event launch runs behind an alignment launch and keeps its three words DD_EVENTS_HDR_* in that launch's workspace header
+ * (draw_header.h): zeroed on the stream in front of the event launch. */
 
 struct EventsArgs {
     int32_t n_refs, n_pairs;
@@ -25,7 +22,6 @@ struct EventsArgs {
     unsigned int *hdr;                   /* the alignment workspace's header, as u32 words */
 };
 
-unsigned events_grid(int64_t n_pairs);
 hipError_t launch_align_events(const EventsArgs &A, hipStream_t st);
 
 } // namespace dda

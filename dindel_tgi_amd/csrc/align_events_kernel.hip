@@ -112,19 +112,11 @@ __global__ void __launch_bounds__(64 * DD_ALIGN_WAVES) dd_align_events_kernel(Ev
     if (lane == 0) atomicMax(P.hdr + DD_EVENTS_HDR_MAX_DRAWS, draws);
 }
 
-unsigned events_grid(int64_t n_pairs)
-{
-    const int64_t blocks = (n_pairs + DD_ALIGN_WAVES - 1) / DD_ALIGN_WAVES;
-    return (unsigned)(blocks < 1 ? 1 : blocks > DD_ALIGN_MAX_BLOCKS ? DD_ALIGN_MAX_BLOCKS : blocks);
-}
-
 hipError_t launch_align_events(const EventsArgs &A, hipStream_t st)
 {
     if (A.n_pairs <= 0) return hipSuccess;
-    hipError_t e = hipMemsetAsync(A.hdr + DD_EVENTS_HDR_COUNTER, 0, 3 * sizeof(unsigned int), st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(dd_align_events_kernel, dim3(events_grid(A.n_pairs)), dim3(64 * DD_ALIGN_WAVES), 0, st, A);
-    return hipGetLastError();
+    return zero_and_launch(dd_align_events_kernel, persistent_grid(A.n_pairs, DD_ALIGN_WAVES, DD_ALIGN_MAX_BLOCKS), 64 * DD_ALIGN_WAVES, 0,
+                           A.hdr + DD_EVENTS_HDR_BASE, DD_DRAW_WORDS * sizeof(unsigned int), st, A);
 }
 
 } // namespace dda

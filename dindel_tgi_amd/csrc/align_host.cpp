@@ -1,7 +1,7 @@
-// align_host.cpp — host side of the haplotype-to-reference alignment (hapalign_kernel.hip): validation of a dd_align_batch, the grid /
-// workspace rule, the device-pointer launch and the host-pointer entry (its own allocations: one call per batch of windows); and the same
-// three for the indel-event extraction and for the variant extraction that run behind an alignment launch (align_events_kernel.hip,
-// hap_variants_kernel.hip).
+// align_host.cpp — host side of the haplotype-to-reference alignment (hapalign_kernel.hip) and of the indel-event and variant extraction
+// that run behind an alignment launch (align_events_kernel.hip, hap_variants_kernel.hip): validation of a dd_align_batch, the grid /
+// workspace rule, the three device-pointer launches with their launch records, and the one host-pointer entry behind dd_align_haplotypes,
+// ..._events and ..._variants: its checks and its list of arrays.  The arena, the records and the copy back are capi_internal.h's.
 #include "capi_internal.h"
 #include "hapalign_kernel.h"
 #include "align_events_kernel.h"
@@ -12,53 +12,9 @@ namespace {
 
 struct AlignShape { int64_t ref_bytes, hap_bytes; int max_ref_len, max_hap_len; };
 
-// this thread's last launch: the host-side fields, and where its two device words are (read on demand, or cached by the host entry,
-// whose workspace does not outlive the call)
-struct AlignLast { int64_t v[DD_ALIGN_LOG_FIELDS]; const unsigned char *ws; hipStream_t stream; bool have_stats; };
-thread_local AlignLast g_align_last = {{0, 0, 0, 0, 0, 0, 0, 0}, nullptr, nullptr, true};
-
-// this thread's last event launch; its device words are in the header of the alignment workspace it ran behind
-struct EventsLast { int64_t v[DD_ALIGN_EVENTS_LOG_FIELDS]; const unsigned char *ws; hipStream_t stream; bool have_stats; };
-thread_local EventsLast g_events_last = {{0, 0, 0, 0}, nullptr, nullptr, true};
-
-int read_events_stats()
-{
-    EventsLast &L = g_events_last;
-    if (L.have_stats || !L.ws) return DD_SUCCESS;
-    uint32_t hdr[3];
-    HIP_TRY(hipStreamSynchronize(L.stream));
-    HIP_TRY(hipMemcpy(hdr, L.ws + 4 * DD_EVENTS_HDR_COUNTER, sizeof(hdr), hipMemcpyDeviceToHost));
-    L.v[2] = hdr[DD_EVENTS_HDR_MAX_DRAWS - DD_EVENTS_HDR_COUNTER]; L.v[3] = hdr[DD_EVENTS_HDR_TRIPS - DD_EVENTS_HDR_COUNTER];
-    L.have_stats = true;
-    return DD_SUCCESS;
-}
-
-// this thread's last variants launch, likewise
-thread_local EventsLast g_variants_last = {{0, 0, 0, 0}, nullptr, nullptr, true};
-
-int read_variants_stats()
-{
-    EventsLast &L = g_variants_last;
-    if (L.have_stats || !L.ws) return DD_SUCCESS;
-    uint32_t hdr[3];
-    HIP_TRY(hipStreamSynchronize(L.stream));
-    HIP_TRY(hipMemcpy(hdr, L.ws + 4 * DD_VARIANTS_HDR_COUNTER, sizeof(hdr), hipMemcpyDeviceToHost));
-    L.v[2] = hdr[DD_VARIANTS_HDR_MAX_DRAWS - DD_VARIANTS_HDR_COUNTER]; L.v[3] = hdr[DD_VARIANTS_HDR_TRIPS - DD_VARIANTS_HDR_COUNTER];
-    L.have_stats = true;
-    return DD_SUCCESS;
-}
-
-int read_align_stats()
-{
-    AlignLast &L = g_align_last;
-    if (L.have_stats || !L.ws) return DD_SUCCESS;
-    uint32_t hdr[4];
-    HIP_TRY(hipStreamSynchronize(L.stream));
-    HIP_TRY(hipMemcpy(hdr, L.ws, sizeof(hdr), hipMemcpyDeviceToHost));
-    L.v[6] = hdr[DD_ALIGN_HDR_MAX_DRAWS]; L.v[7] = hdr[DD_ALIGN_HDR_TRIPS];
-    L.have_stats = true;
-    return DD_SUCCESS;
-}
+// this thread's last alignment, event and variants launch; the last two keep their words in the header of the alignment workspace they
+// ran behind (capi_internal.h: LaunchRecord)
+thread_local LaunchRecord g_align_last(DD_ALIGN_LOG_FIELDS), g_events_last(DD_ALIGN_EVENTS_LOG_FIELDS), g_variants_last(DD_ALIGN_EVENTS_LOG_FIELDS);
 
 // offsets start at 0 and never decrease; pair_ref in range.  The maxima leave out what the kernel refuses (too long).
 int check_align_batch(const dd_align_batch *b, AlignShape &s)
@@ -93,10 +49,8 @@ int check_align_batch(const dd_align_batch *b, AlignShape &s)
 // workgroups of the full grid: one wavefront per pair up to the persistent grid's size, fewer while the tiles exceed the budget
 unsigned align_full_grid(int64_t n_pairs, uint64_t tile_bytes)
 {
-    int64_t blocks = std::max<int64_t>(1, (n_pairs + DD_ALIGN_WAVES - 1) / DD_ALIGN_WAVES);
-    blocks = std::min<int64_t>(blocks, DD_ALIGN_MAX_BLOCKS);
     const int64_t fit = (int64_t)(DD_ALIGN_WS_BUDGET / (tile_bytes * DD_ALIGN_WAVES));
-    return (unsigned)std::max<int64_t>(1, std::min(blocks, fit));
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(dda::persistent_grid(n_pairs, DD_ALIGN_WAVES, DD_ALIGN_MAX_BLOCKS), fit));
 }
 
 } // namespace
@@ -139,19 +93,13 @@ int dd_align_haplotypes_device(const dd_align_batch *b, const dd_align_result *r
     A.K = (max_hap_len + 63) / 64;
     A.ws = static_cast<unsigned char *>(workspace);
     A.tile_bytes = tile;
-    const int64_t rec[DD_ALIGN_LOG_FIELDS] = {(int64_t)grid, (int64_t)grid * DD_ALIGN_WAVES, (int64_t)tile, (int64_t)dda::align_lds_bytes(A.K),
-                                              (int64_t)b->n_pairs, (int64_t)(DD_ALIGN_WS_HEADER + grid * wg_bytes), -1, -1};
-    memcpy(g_align_last.v, rec, sizeof(rec));
-    g_align_last.ws = A.ws; g_align_last.stream = static_cast<hipStream_t>(stream); g_align_last.have_stats = false;
+    g_align_last.note({(int64_t)grid, (int64_t)grid * DD_ALIGN_WAVES, (int64_t)tile, (int64_t)dda::align_lds_bytes(A.K), (int64_t)b->n_pairs,
+                       (int64_t)(DD_ALIGN_WS_HEADER + grid * wg_bytes)}, A.ws, DD_ALIGN_HDR_BASE, stream);
     HIP_TRY(dda::launch_hapalign(A, grid, static_cast<hipStream_t>(stream)));
     return DD_SUCCESS;
 }
 
-void dd_align_last_launch(int64_t out[DD_ALIGN_LOG_FIELDS])
-{
-    (void)read_align_stats();                  // a failure leaves -1 in the two device fields
-    if (out) memcpy(out, g_align_last.v, sizeof(g_align_last.v));
-}
+void dd_align_last_launch(int64_t out[DD_ALIGN_LOG_FIELDS]) { g_align_last.copy_out(out); }
 
 int dd_align_events_device(const dd_align_batch *b, const dd_align_result *r, int32_t *n_events, dd_align_events *events, int events_cap,
                            void *stream)
@@ -164,26 +112,21 @@ int dd_align_events_device(const dd_align_batch *b, const dd_align_result *r, in
     if (!b->ref_off || !b->pair_ref || !b->hap_off || !r->status || !r->ref_pos || !n_events || !events)
         return fail(DD_ERR_INVALID, "dd_align_events_device: null array");
     if (reinterpret_cast<uintptr_t>(events) & 7u) return fail(DD_ERR_INVALID, "dd_align_events_device: events must be 8-byte aligned");
-    if (!g_align_last.ws)
+    if (!g_align_last.hdr)
         return fail(DD_ERR_INVALID, "dd_align_events_device: no alignment launch of this thread to run behind (its workspace header holds the pair counter)");
     dda::EventsArgs A;
     A.n_refs = b->n_refs; A.n_pairs = b->n_pairs;
     A.ref_off = b->ref_off; A.pair_ref = b->pair_ref; A.hap_off = b->hap_off;
     A.status = r->status; A.ref_pos = r->ref_pos;
     A.n_events = n_events; A.events = events; A.events_cap = events_cap;
-    A.hdr = reinterpret_cast<unsigned int *>(const_cast<unsigned char *>(g_align_last.ws));
-    const int64_t rec[DD_ALIGN_EVENTS_LOG_FIELDS] = {(int64_t)dda::events_grid(b->n_pairs), (int64_t)b->n_pairs, -1, -1};
-    memcpy(g_events_last.v, rec, sizeof(rec));
-    g_events_last.ws = g_align_last.ws; g_events_last.stream = static_cast<hipStream_t>(stream); g_events_last.have_stats = false;
+    A.hdr = const_cast<unsigned int *>(g_align_last.hdr);
+    g_events_last.note({(int64_t)dda::persistent_grid(b->n_pairs, DD_ALIGN_WAVES, DD_ALIGN_MAX_BLOCKS), (int64_t)b->n_pairs}, A.hdr,
+                        DD_EVENTS_HDR_BASE, stream);
     HIP_TRY(dda::launch_align_events(A, static_cast<hipStream_t>(stream)));
     return DD_SUCCESS;
 }
 
-void dd_align_events_last_launch(int64_t out[DD_ALIGN_EVENTS_LOG_FIELDS])
-{
-    (void)read_events_stats();                 // a failure leaves -1 in the two device fields
-    if (out) memcpy(out, g_events_last.v, sizeof(g_events_last.v));
-}
+void dd_align_events_last_launch(int64_t out[DD_ALIGN_EVENTS_LOG_FIELDS]) { g_events_last.copy_out(out); }
 
 int dd_hap_variants_device(const dd_align_batch *b, const dd_align_result *r, dd_hap_variants_summary *summary, dd_hap_variant *variants, int cap,
                            void *stream)
@@ -196,7 +139,7 @@ int dd_hap_variants_device(const dd_align_batch *b, const dd_align_result *r, dd
         return fail(DD_ERR_INVALID, "dd_hap_variants_device: null array");
     if (reinterpret_cast<uintptr_t>(variants) & 7u) return fail(DD_ERR_INVALID, "dd_hap_variants_device: variants must be 8-byte aligned");
     if (reinterpret_cast<uintptr_t>(summary) & 3u) return fail(DD_ERR_INVALID, "dd_hap_variants_device: summary must be 4-byte aligned");
-    if (!g_align_last.ws)
+    if (!g_align_last.hdr)
         return fail(DD_ERR_INVALID, "dd_hap_variants_device: no alignment launch of this thread to run behind (its workspace header holds the pair counter)");
     dda::VariantsArgs A;
     A.n_refs = b->n_refs; A.n_pairs = b->n_pairs;
@@ -204,117 +147,84 @@ int dd_hap_variants_device(const dd_align_batch *b, const dd_align_result *r, dd
     A.pair_ref = b->pair_ref; A.hap_off = b->hap_off; A.hap_seq = reinterpret_cast<const uint8_t *>(b->hap_seq);
     A.status = r->status; A.ref_pos = r->ref_pos;
     A.summary = summary; A.variants = variants; A.cap = cap;
-    A.hdr = reinterpret_cast<unsigned int *>(const_cast<unsigned char *>(g_align_last.ws));
-    const int64_t rec[DD_ALIGN_EVENTS_LOG_FIELDS] = {(int64_t)dda::variants_grid(b->n_pairs), (int64_t)b->n_pairs, -1, -1};
-    memcpy(g_variants_last.v, rec, sizeof(rec));
-    g_variants_last.ws = g_align_last.ws; g_variants_last.stream = static_cast<hipStream_t>(stream); g_variants_last.have_stats = false;
+    A.hdr = const_cast<unsigned int *>(g_align_last.hdr);
+    g_variants_last.note({(int64_t)dda::persistent_grid(b->n_pairs, DD_ALIGN_WAVES, DD_ALIGN_MAX_BLOCKS), (int64_t)b->n_pairs}, A.hdr,
+                          DD_VARIANTS_HDR_BASE, stream);
     HIP_TRY(dda::launch_hap_variants(A, static_cast<hipStream_t>(stream)));
     return DD_SUCCESS;
 }
 
-void dd_hap_variants_last_launch(int64_t out[DD_ALIGN_EVENTS_LOG_FIELDS])
-{
-    (void)read_variants_stats();               // a failure leaves -1 in the two device fields
-    if (out) memcpy(out, g_variants_last.v, sizeof(g_variants_last.v));
-}
+void dd_hap_variants_last_launch(int64_t out[DD_ALIGN_EVENTS_LOG_FIELDS]) { g_variants_last.copy_out(out); }
 
 } // extern "C"
 
 namespace ddh {
 namespace {
 
-// the three host-pointer entries: ev = va = nullptr is dd_align_haplotypes; with events or variants the slice comes back only where the
-// caller has room for it
-struct EventsOut { int32_t *n_events; dd_align_events *events; int cap; };
-struct VariantsOut { dd_hap_variants_summary *summary; dd_hap_variant *variants; int cap; };
 
-int align_host_entry(const dd_align_batch *b, dd_align_result *r, const EventsOut *ev, int device, const VariantsOut *va = nullptr)
+// One host-pointer call: the alignment alone (dd_align_haplotypes), or with the events or the variants behind it; then the slice comes back
+// only where the caller has room for it.
+struct AlignRequest {
+    const dd_align_batch *b; dd_align_result *r; int device;
+    bool events = false;   int32_t *n_events = nullptr; dd_align_events *ev = nullptr; int events_cap = 0;
+    bool variants = false; dd_hap_variants_summary *summary = nullptr; dd_hap_variant *va = nullptr; int cap = 0;
+};
+
+int align_host_entry(const AlignRequest &q)
 {
+    const dd_align_batch *b = q.b;
+    dd_align_result *r = q.r;
     AlignShape s;
     int rc = check_align_batch(b, s);
     if (rc) return rc;
     if (!r) return fail(DD_ERR_INVALID, "null align result");
     if (b->n_pairs > 0 && (!r->score || !r->status)) return fail(DD_ERR_INVALID, "null score or status in align result");
-    if (!ev && !va && s.hap_bytes > 0 && !r->ref_pos) return fail(DD_ERR_INVALID, "null ref_pos in align result");
-    if (va) {
-        if (va->cap < 1 || va->cap > DD_HAP_VARIANTS_MAX_CAP) return fail(DD_ERR_INVALID, "cap outside 1 ... DD_HAP_VARIANTS_MAX_CAP");
-        if (b->n_pairs > 0 && (!va->summary || !va->variants)) return fail(DD_ERR_INVALID, "null summary or variants");
+    if (!q.events && !q.variants && s.hap_bytes > 0 && !r->ref_pos) return fail(DD_ERR_INVALID, "null ref_pos in align result");
+    if (q.variants) {
+        if (q.cap < 1 || q.cap > DD_HAP_VARIANTS_MAX_CAP) return fail(DD_ERR_INVALID, "cap outside 1 ... DD_HAP_VARIANTS_MAX_CAP");
+        if (b->n_pairs > 0 && (!q.summary || !q.va)) return fail(DD_ERR_INVALID, "null summary or variants");
     }
-    if (ev) {
-        if (ev->cap < 1 || ev->cap > DD_ALIGN_EVENTS_MAX_CAP) return fail(DD_ERR_INVALID, "events_cap outside 1 ... DD_ALIGN_EVENTS_MAX_CAP");
-        if (b->n_pairs > 0 && (!ev->n_events || !ev->events)) return fail(DD_ERR_INVALID, "null n_events or events");
+    if (q.events) {
+        if (q.events_cap < 1 || q.events_cap > DD_ALIGN_EVENTS_MAX_CAP) return fail(DD_ERR_INVALID, "events_cap outside 1 ... DD_ALIGN_EVENTS_MAX_CAP");
+        if (b->n_pairs > 0 && (!q.n_events || !q.ev)) return fail(DD_ERR_INVALID, "null n_events or events");
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(DD_ERR_NO_DEVICE, "no HIP device: the haplotype alignment has no CPU fallback in this library");
-    if (device < 0 || device >= ndev) return fail(DD_ERR_NO_DEVICE, "device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
+    if ((rc = use_device(q.device, "no HIP device: the haplotype alignment has no CPU fallback in this library"))) return rc;
     if (b->n_pairs == 0) return DD_SUCCESS;
 
-    // one allocation, 256-byte aligned pieces: offsets, sequences, outputs, workspace
+    // every array of the call once: offsets, sequences, outputs, workspace, and what the events or the variants add
     const size_t ws_bytes = dd_align_workspace_bytes(b);
-    const size_t P = (size_t)b->n_pairs, R = (size_t)b->n_refs;
-    const size_t ev_bytes = ev ? P * (size_t)ev->cap * sizeof(dd_align_events) : 0;
-    const size_t va_bytes = va ? P * (size_t)va->cap * sizeof(dd_hap_variant) : 0;
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255u) & ~size_t(255u); return o; };
-    const size_t o_roff = take((R + 1) * 4), o_rseq = take((size_t)s.ref_bytes), o_pref = take(P * 4), o_hoff = take((P + 1) * 4),
-                 o_hseq = take((size_t)s.hap_bytes), o_score = take(P * 4), o_status = take(P * 4), o_rpos = take((size_t)s.hap_bytes * 2),
-                 o_ws = take(ws_bytes), o_nev = take(ev ? P * 4 : 0), o_ev = take(ev_bytes),
-                 o_sum = take(va ? P * sizeof(dd_hap_variants_summary) : 0), o_va = take(va_bytes);
-    struct Mem {
-        unsigned char *p = nullptr;
-        ~Mem() { if (p) (void)hipFree(p); }
-    } mem;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&mem.p), off));
-    unsigned char *d = mem.p;
-    HIP_TRY(hipMemcpy(d + o_roff, b->ref_off, (R + 1) * 4, hipMemcpyHostToDevice));
-    if (s.ref_bytes) HIP_TRY(hipMemcpy(d + o_rseq, b->ref_seq, (size_t)s.ref_bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d + o_pref, b->pair_ref, P * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d + o_hoff, b->hap_off, (P + 1) * 4, hipMemcpyHostToDevice));
-    if (s.hap_bytes) HIP_TRY(hipMemcpy(d + o_hseq, b->hap_seq, (size_t)s.hap_bytes, hipMemcpyHostToDevice));
+    const size_t P = (size_t)b->n_pairs, R = (size_t)b->n_refs, ref_bytes = (size_t)s.ref_bytes, hap_bytes = (size_t)s.hap_bytes;
+    const size_t ev_bytes = q.events ? P * (size_t)q.events_cap * sizeof(dd_align_events) : 0;
+    const size_t va_bytes = q.variants ? P * (size_t)q.cap * sizeof(dd_hap_variant) : 0;
     dd_align_batch db = *b;
-    db.ref_off = reinterpret_cast<const int32_t *>(d + o_roff); db.ref_seq = reinterpret_cast<const char *>(d + o_rseq);
-    db.pair_ref = reinterpret_cast<const int32_t *>(d + o_pref); db.hap_off = reinterpret_cast<const int32_t *>(d + o_hoff);
-    db.hap_seq = reinterpret_cast<const char *>(d + o_hseq);
-    const dd_align_result dr = {reinterpret_cast<int32_t *>(d + o_score), reinterpret_cast<int32_t *>(d + o_status),
-                                reinterpret_cast<int16_t *>(d + o_rpos)};
-    if ((rc = dd_align_haplotypes_device(&db, &dr, s.max_ref_len, s.max_hap_len, d + o_ws, ws_bytes, nullptr))) return rc;
-    if (ev) {
+    dd_align_result dr;
+    unsigned char *ws;
+    int32_t *d_nev; dd_align_events *d_ev; dd_hap_variants_summary *d_sum; dd_hap_variant *d_va;
+    OneShotArena arena;
+    ArenaRecords records(arena, {&g_align_last, &g_variants_last, &g_events_last});
+    if ((rc = arena.place({arena_slot(&db.ref_off, (R + 1) * 4, b->ref_off), arena_slot(&db.ref_seq, ref_bytes, b->ref_seq),
+                           arena_slot(&db.pair_ref, P * 4, b->pair_ref), arena_slot(&db.hap_off, (P + 1) * 4, b->hap_off),
+                           arena_slot(&db.hap_seq, hap_bytes, b->hap_seq), arena_slot(&dr.score, P * 4), arena_slot(&dr.status, P * 4),
+                           arena_slot(&dr.ref_pos, hap_bytes * 2), arena_slot(&ws, ws_bytes), arena_slot(&d_nev, q.events ? P * 4 : 0),
+                           arena_slot(&d_ev, ev_bytes), arena_slot(&d_sum, q.variants ? P * sizeof(dd_hap_variants_summary) : 0),
+                           arena_slot(&d_va, va_bytes)})))
+        return rc;
+    if ((rc = dd_align_haplotypes_device(&db, &dr, s.max_ref_len, s.max_hap_len, ws, ws_bytes, nullptr))) return rc;
+    if (q.events) {
         // records no event reaches stay 0: the caller's array is overwritten as a whole
-        HIP_TRY(hipMemsetAsync(d + o_ev, 0, ev_bytes, nullptr));
-        rc = dd_align_events_device(&db, &dr, reinterpret_cast<int32_t *>(d + o_nev), reinterpret_cast<dd_align_events *>(d + o_ev), ev->cap, nullptr);
-        if (rc) { g_align_last.ws = nullptr; g_events_last.ws = nullptr; return rc; }
+        HIP_TRY(hipMemsetAsync(d_ev, 0, ev_bytes, nullptr));
+        if ((rc = dd_align_events_device(&db, &dr, d_nev, d_ev, q.events_cap, nullptr))) return rc;
     }
-    if (va) {
+    if (q.variants) {
         // records no variant reaches stay 0: the caller's array is overwritten as a whole
-        HIP_TRY(hipMemsetAsync(d + o_va, 0, va_bytes, nullptr));
-        rc = dd_hap_variants_device(&db, &dr, reinterpret_cast<dd_hap_variants_summary *>(d + o_sum), reinterpret_cast<dd_hap_variant *>(d + o_va), va->cap, nullptr);
-        if (rc) { g_align_last.ws = nullptr; g_variants_last.ws = nullptr; return rc; }
+        HIP_TRY(hipMemsetAsync(d_va, 0, va_bytes, nullptr));
+        if ((rc = dd_hap_variants_device(&db, &dr, d_sum, d_va, q.cap, nullptr))) return rc;
     }
     HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = read_align_stats())) return rc;  // the workspace goes with this call
-    g_align_last.ws = nullptr;
-    if (va) {
-        if ((rc = read_variants_stats())) return rc;
-        g_variants_last.ws = nullptr;
-    }
-    if (ev) {
-        if ((rc = read_events_stats())) return rc;
-        g_events_last.ws = nullptr;
-    }
-    HIP_TRY(hipMemcpy(r->score, dr.score, P * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(r->status, dr.status, P * 4, hipMemcpyDeviceToHost));
-    if (s.hap_bytes && r->ref_pos) HIP_TRY(hipMemcpy(r->ref_pos, dr.ref_pos, (size_t)s.hap_bytes * 2, hipMemcpyDeviceToHost));
-    if (ev) {
-        HIP_TRY(hipMemcpy(ev->n_events, d + o_nev, P * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(ev->events, d + o_ev, ev_bytes, hipMemcpyDeviceToHost));
-    }
-    if (va) {
-        HIP_TRY(hipMemcpy(va->summary, d + o_sum, P * sizeof(dd_hap_variants_summary), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(va->variants, d + o_va, va_bytes, hipMemcpyDeviceToHost));
-    }
-    return DD_SUCCESS;
+    if ((rc = records.read_stats())) return rc;   // the workspace goes with this call
+    return download({{r->score, dr.score, P * 4}, {r->status, dr.status, P * 4}, {r->ref_pos, dr.ref_pos, r->ref_pos ? hap_bytes * 2 : 0},
+                     {q.n_events, d_nev, q.events ? P * 4 : 0}, {q.ev, d_ev, ev_bytes},
+                     {q.summary, d_sum, q.variants ? P * sizeof(dd_hap_variants_summary) : 0}, {q.va, d_va, va_bytes}});
 }
 
 } // namespace
@@ -322,18 +232,20 @@ int align_host_entry(const dd_align_batch *b, dd_align_result *r, const EventsOu
 
 extern "C" {
 
-int dd_align_haplotypes(const dd_align_batch *b, dd_align_result *r, int device) { return align_host_entry(b, r, nullptr, device); }
+int dd_align_haplotypes(const dd_align_batch *b, dd_align_result *r, int device) { return align_host_entry({b, r, device}); }
 
 int dd_align_haplotypes_events(const dd_align_batch *b, dd_align_result *r, int32_t *n_events, dd_align_events *events, int events_cap, int device)
 {
-    const EventsOut ev = {n_events, events, events_cap};
-    return align_host_entry(b, r, &ev, device);
+    AlignRequest q = {b, r, device};
+    q.events = true; q.n_events = n_events; q.ev = events; q.events_cap = events_cap;
+    return align_host_entry(q);
 }
 
 int dd_align_haplotypes_variants(const dd_align_batch *b, dd_align_result *r, dd_hap_variants_summary *summary, dd_hap_variant *variants, int cap, int device)
 {
-    const ddh::VariantsOut va = {summary, variants, cap};
-    return align_host_entry(b, r, nullptr, device, &va);
+    AlignRequest q = {b, r, device};
+    q.variants = true; q.summary = summary; q.va = variants; q.cap = cap;
+    return align_host_entry(q);
 }
 
 } // extern "C"

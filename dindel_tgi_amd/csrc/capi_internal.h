@@ -1,14 +1,17 @@
 // capi_internal.h — what the host units of the C ABI (include/dindel_hmm.h) share: plan.cpp, batch_host.cpp (neither calls the HIP runtime
 // nor needs a kernel unit to link), long_plan.cpp (the plans of the two long-window paths, with the layouts of their kernel units),
-// launch.cpp, host_path.cpp, align_host.cpp (the haplotype alignment, self-contained), pooled_em_capi.cpp (the pooled EM's device entries;
-// pooled_em_host.cpp, its CPU evaluation, includes no HIP header and not this file); each says in its first lines what it holds.  Host work is O(bases) bookkeeping only.  All likelihood
-// arithmetic happens in the kernels; there is no CPU path for it in this library.
+// launch.cpp, host_path.cpp, align_host.cpp (the haplotype alignment with the events and variants behind it), hapdist_host.cpp (the block
+// table), pooled_em_capi.cpp (the pooled EM's device entries; pooled_em_host.cpp, its CPU evaluation, includes no HIP header and not this
+// file); each says in its first lines what it holds.  The last part of this file is what the host-pointer entries share: use_device, the
+// arena slot, the one-shot arena of the three small entries and the record of a drawing kernel's last launch.  Host work is O(bases)
+// bookkeeping only.  All likelihood arithmetic happens in the kernels; there is no CPU path for it in this library.
 #ifndef DD_CAPI_INTERNAL_H
 #define DD_CAPI_INTERNAL_H
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 #include "hmm_kernel.h"
@@ -16,6 +19,7 @@
 #include "faster_long_kernel.h"
 #include "cigar_kernel.h"
 #include "realign_kernel.h"
+#include "draw_header.h"
 
 namespace ddh {
 constexpr size_t kCuLdsBytes = 160u * 1024u;   // LDS of one CU (gfx950)
@@ -215,5 +219,134 @@ struct LongPath {
     std::vector<LongRec> log;
 };
 extern thread_local LongPath g_long, g_flong;
+
+// ---- what the host-pointer entries share (host_path.cpp and the one-shot entries of align_host.cpp, hapdist_host.cpp, pooled_em_capi.cpp) ----
+// makes `device` current; no_device: the text when the machine has none
+inline int use_device(int device, const char *no_device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(DD_ERR_NO_DEVICE, no_device);
+    if (device < 0 || device >= ndev) return fail(DD_ERR_NO_DEVICE, "device ordinal out of range");
+    HIP_TRY(hipSetDevice(device));
+    return DD_SUCCESS;
+}
+
+// One array of a call in the device arena: its bytes, the pointer variable that takes its device address, and for an input the host array
+// that is copied there.  A call lists every array it places before it touches the device, and the bytes it reserves are added up from those
+// lists (HostCall::end_of_all, arena_layout): there is no size formula to keep in step with them.
+struct ArenaSlot {
+    size_t bytes;
+    const unsigned char *src;                           // inputs: the host array (NULL: the array is only reserved)
+    void *var; void (*set)(void *var, void *dev);       // the variable, written through its own type
+    bool read_bases;                                    // read_seq / read_qidx, the two big inputs (HostCall::reserve_and_upload)
+    void point_at(const void *dev) const { set(var, const_cast<void *>(dev)); }
+};
+template <class P> ArenaSlot arena_slot(P *var, size_t bytes, const void *src = nullptr, bool read_bases = false)
+{
+    return {bytes, static_cast<const unsigned char *>(src), var, [](void *v, void *dev) { *static_cast<P *>(v) = static_cast<P>(dev); }, read_bases};
+}
+
+// The one-shot arena of the small entries (one allocation per call, freed with it).  Its layout, without a HIP call: every slot starts at a
+// multiple of 256 bytes, and an array of 0 bytes takes 1, so that it has an address of its own.  off[i]: where slot i starts; returns the total.
+inline size_t arena_layout(const std::vector<ArenaSlot> &slots, std::vector<size_t> &off)
+{
+    size_t at = 0;
+    off.clear();
+    for (const ArenaSlot &s : slots) {
+        off.push_back(at);
+        at = (at + std::max<size_t>(s.bytes, 1) + 255u) & ~size_t(255u);
+    }
+    return at;
+}
+inline void arena_point(const std::vector<ArenaSlot> &slots, const std::vector<size_t> &off, unsigned char *base)
+{
+    for (size_t i = 0; i < slots.size(); i++) slots[i].point_at(base + off[i]);
+}
+struct OneShotArena {
+    unsigned char *base = nullptr;
+    size_t bytes = 0;
+    OneShotArena() = default;
+    OneShotArena(const OneShotArena &) = delete;
+    ~OneShotArena() { if (base) (void)hipFree(base); }
+    bool holds(const void *p) const { return base && p >= base && p < base + bytes; }
+    // allocate what the slots add up to, point every slot's variable at its piece and upload the slots that have a source
+    int place(const std::vector<ArenaSlot> &slots)
+    {
+        std::vector<size_t> off;
+        bytes = arena_layout(slots, off);
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&base), bytes));
+        arena_point(slots, off, base);
+        for (size_t i = 0; i < slots.size(); i++)
+            if (slots[i].src && slots[i].bytes) HIP_TRY(hipMemcpy(base + off[i], slots[i].src, slots[i].bytes, hipMemcpyHostToDevice));
+        return DD_SUCCESS;
+    }
+};
+// the copy back: each array the caller has room for (0 bytes: none)
+struct Download { void *dst; const void *dev; size_t bytes; };
+inline int download(std::initializer_list<Download> list)
+{
+    for (const Download &d : list)
+        if (d.bytes) HIP_TRY(hipMemcpy(d.dst, d.dev, d.bytes, hipMemcpyDeviceToHost));
+    return DD_SUCCESS;
+}
+
+// This thread's last launch of a kernel whose wavefronts draw their items from a counter (draw_header.h): n int64 fields, of which the last
+// two come from the device (most draws of one wavefront, guard trips).  They are read on demand from the launch's three header words, or
+// cached by a host entry, whose workspace does not outlive the call.
+struct LaunchRecord {
+    int64_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int n;
+    const unsigned int *hdr = nullptr;   // device: the header the launch counts into (NULL: no launch yet, or its workspace is gone)
+    int base = 0;                        // the launch's first word in it
+    hipStream_t stream = nullptr;
+    bool have_stats = true;
+    explicit LaunchRecord(int n_fields) : n(n_fields) {}
+    // in front of a launch: its host-side fields (n - 2 of them), and where and behind what its device words will be
+    void note(std::initializer_list<int64_t> host_fields, const void *header, int base_word, void *st)
+    {
+        std::copy(host_fields.begin(), host_fields.end(), v);
+        v[n - 2] = v[n - 1] = -1;
+        hdr = static_cast<const unsigned int *>(header); base = base_word; stream = static_cast<hipStream_t>(st); have_stats = false;
+    }
+    int read_stats()
+    {
+        if (have_stats || !hdr) return DD_SUCCESS;
+        uint32_t w[DD_DRAW_WORDS];
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpy(w, hdr + base, sizeof(w), hipMemcpyDeviceToHost));
+        v[n - 2] = w[DD_DRAW_MAX_DRAWS]; v[n - 1] = w[DD_DRAW_TRIPS];
+        have_stats = true;
+        return DD_SUCCESS;
+    }
+    void forget() { hdr = nullptr; }     // the workspace is gone: what has been read stays
+    void copy_out(int64_t *out)          // a dd_*_last_launch
+    {
+        (void)read_stats();              // a failure leaves -1 in the two device fields
+        if (out) memcpy(out, v, (size_t)n * sizeof(*v));
+    }
+};
+// The records of the launches a host entry runs in its arena.  read_stats() caches their device words (the success path reports a failure
+// of that); on every way out of the entry the destructor does the same and then forgets the workspace.  It is made from the arena, so it
+// is declared behind it and gone before it: no record outlives the memory it points into.  A record of an earlier launch elsewhere is left alone.
+struct ArenaRecords {
+    const OneShotArena &arena;
+    std::vector<LaunchRecord *> recs;
+    ArenaRecords(const OneShotArena &a, std::initializer_list<LaunchRecord *> r) : arena(a), recs(r) {}
+    int read_stats()
+    {
+        for (LaunchRecord *r : recs)
+            if (arena.holds(r->hdr)) { const int rc = r->read_stats(); if (rc) return rc; }
+        return DD_SUCCESS;
+    }
+    ~ArenaRecords()
+    {
+        for (LaunchRecord *r : recs)
+            if (arena.holds(r->hdr)) {
+                const std::string err = g_err;           // the entry's own error text stands
+                if (r->read_stats()) g_err = err;
+                r->forget();
+            }
+    }
+};
 } // namespace ddh
 #endif

@@ -7,11 +7,8 @@
 
 namespace dda {
 
-/* The variants launch runs behind an alignment launch and keeps its three words in that launch's workspace header (DD_ALIGN_WS_HEADER
- * bytes; the alignment uses words 0 ... 2, the event launch 4 ... 6): zeroed on the stream in front of the variants launch. */
-#define DD_VARIANTS_HDR_COUNTER 8      /* header word: u32 pair counter of the variants launch */
-#define DD_VARIANTS_HDR_MAX_DRAWS 9    /* header word: most pairs one wavefront drew */
-#define DD_VARIANTS_HDR_TRIPS 10       /* header word: wavefronts that left through the draw guard: 0 */
+/* The variants launch runs behind an alignment launch and keeps its three words DD_VARIANTS_HDR_* in that launch's workspace header
+ * (draw_header.h): zeroed on the stream in front of the variants launch. */
 
 struct VariantsArgs {
     int32_t n_refs, n_pairs;
@@ -27,7 +24,6 @@ struct VariantsArgs {
     unsigned int *hdr;                   /* the alignment workspace's header, as u32 words */
 };
 
-unsigned variants_grid(int64_t n_pairs);
 hipError_t launch_hap_variants(const VariantsArgs &A, hipStream_t st);
 
 } // namespace dda

@@ -4,18 +4,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dindel_hmm.h"
+#include "draw_header.h"
 
 namespace dda {
 
 #define DD_ALIGN_WAVES 4              /* wavefronts per workgroup: one pair in flight per wavefront */
 #define DD_ALIGN_MAX_BLOCKS 2048      /* persistent grid: 256 CUs x 8 workgroups; the wavefronts draw pairs from a counter */
-#define DD_ALIGN_WS_HEADER 256        /* the workspace starts with the u32 pair counter and two u32 statistics; the trace tiles follow */
-#define DD_ALIGN_HDR_MAX_DRAWS 1      /* header word: most pairs one wavefront drew */
-#define DD_ALIGN_HDR_TRIPS 2          /* header word: wavefronts that left through the draw guard (more draws than the batch has pairs): 0 */
 #define DD_ALIGN_WS_BUDGET (512ull << 20)   /* the grid shrinks so the tiles stay within this (like DD_LONG_WS_BUDGET), never below one workgroup */
 
 /* Workspace of a launch (dd_align_workspace_bytes):
- *   [0, 256)     header: u32 pair counter, u32 most draws of one wavefront, u32 guard trips (zeroed on the stream in front of the launch)
+ *   [0, 256)     header (DD_ALIGN_WS_HEADER, draw_header.h): the alignment's three words DD_ALIGN_HDR_* and those of the launches that
+ *                run behind it; zeroed on the stream in front of the launch
  *   [256, ...)   grid x DD_ALIGN_WAVES tiles of tile_bytes: one byte per DP cell of the wavefront's current pair, stored by anti-diagonal
  *                step t = (column - 1) + (lane of the row): byte t * len2 + (row - 1); t < len1 + 63, so a tile of
  *                (max_ref_len + 64) * max_hap_len bytes holds every pair the launch admits */

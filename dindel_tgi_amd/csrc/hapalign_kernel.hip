@@ -239,9 +239,7 @@ hipError_t launch_hapalign(const AlignArgs &A, unsigned grid, hipStream_t st)
         if (e != hipSuccess) return e;
         raised.fetch_or(bit);
     }
-    if ((e = hipMemsetAsync(A.ws, 0, DD_ALIGN_WS_HEADER, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(dd_hapalign_kernel, dim3(grid), dim3(64 * DD_ALIGN_WAVES), lds, st, A);
-    return hipGetLastError();
+    return zero_and_launch(dd_hapalign_kernel, grid, 64 * DD_ALIGN_WAVES, lds, A.ws, DD_ALIGN_WS_HEADER, st, A);
 }
 
 } // namespace dda

@@ -1,6 +1,6 @@
 // hapdist_host.cpp — host side of the block table (hapdist_kernel.hip): validation of a dd_hap_batch and of the caller's capacities, the
-// capacity rule (dd_hap_blocks_offsets), the device-pointer launch and the host-pointer entry (its own allocation: one call per batch of
-// windows).
+// capacity rule (dd_hap_blocks_offsets), the device-pointer launch with its launch record, and the host-pointer entry: its checks and its
+// list of arrays.  The arena, the record and the copy back are capi_internal.h's.
 #include "capi_internal.h"
 #include "hapdist_kernel.h"
 
@@ -9,21 +9,7 @@ namespace {
 
 struct HapShape { int64_t ref_bytes, n_ops, n_bases; };
 
-// this thread's last launch; its two device words are read on demand, or cached by the host entry (whose workspace goes with the call)
-struct HapLast { int64_t v[DD_HAP_BLOCKS_LOG_FIELDS]; const unsigned char *ws; hipStream_t stream; bool have_stats; };
-thread_local HapLast g_hap_last = {{0, 0, 0, 0}, nullptr, nullptr, true};
-
-int read_hap_stats()
-{
-    HapLast &L = g_hap_last;
-    if (L.have_stats || !L.ws) return DD_SUCCESS;
-    uint32_t hdr[3];
-    HIP_TRY(hipStreamSynchronize(L.stream));
-    HIP_TRY(hipMemcpy(hdr, L.ws, sizeof(hdr), hipMemcpyDeviceToHost));
-    L.v[2] = hdr[DD_HAPDIST_HDR_MAX_DRAWS]; L.v[3] = hdr[DD_HAPDIST_HDR_TRIPS];
-    L.have_stats = true;
-    return DD_SUCCESS;
-}
+thread_local LaunchRecord g_hap_last(DD_HAP_BLOCKS_LOG_FIELDS);   // this thread's last launch (capi_internal.h)
 
 int check_offsets(const int32_t *off, int64_t n, const char *name)
 {
@@ -103,19 +89,13 @@ int dd_hap_blocks_device(const dd_hap_batch *b, const dd_hap_blocks *t, int64_t 
     A.b = *b; A.t = *t;
     A.max_blk = max_blk; A.max_ent = max_ent; A.max_ins = max_ins;
     A.hdr = static_cast<unsigned int *>(workspace);
-    const int64_t rec[DD_HAP_BLOCKS_LOG_FIELDS] = {(int64_t)dda::hapdist_grid(b->n_windows), (int64_t)b->n_windows, -1, -1};
-    memcpy(g_hap_last.v, rec, sizeof(rec));
-    g_hap_last.ws = static_cast<const unsigned char *>(workspace); g_hap_last.stream = static_cast<hipStream_t>(stream);
-    g_hap_last.have_stats = false;
+    g_hap_last.note({(int64_t)dda::persistent_grid(b->n_windows, DD_HAPDIST_WAVES, DD_HAPDIST_MAX_BLOCKS), (int64_t)b->n_windows}, workspace,
+                     DD_HAPDIST_HDR_BASE, stream);
     HIP_TRY(dda::launch_hapdist(A, static_cast<hipStream_t>(stream)));
     return DD_SUCCESS;
 }
 
-void dd_hap_blocks_last_launch(int64_t out[DD_HAP_BLOCKS_LOG_FIELDS])
-{
-    (void)read_hap_stats();                    // a failure leaves -1 in the two device fields
-    if (out) memcpy(out, g_hap_last.v, sizeof(g_hap_last.v));
-}
+void dd_hap_blocks_last_launch(int64_t out[DD_HAP_BLOCKS_LOG_FIELDS]) { g_hap_last.copy_out(out); }
 
 int dd_hap_blocks_compute(const dd_hap_batch *b, dd_hap_blocks *t, int device)
 {
@@ -137,74 +117,37 @@ int dd_hap_blocks_compute(const dd_hap_batch *b, dd_hap_blocks *t, int device)
     const size_t n_blk = (size_t)t->blk_off[W], n_ent = (size_t)t->ent_off[W], n_ins = (size_t)t->ins_off[W];
     if ((n_blk && !t->blocks) || (n_ent && !t->entries) || (n_ins && (!t->ins_ops || !t->ins_pos)))
         return fail(DD_ERR_INVALID, "null table in hap tables");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(DD_ERR_NO_DEVICE, "no HIP device: the library's block table runs on the device (host/haplotypes.cpp holds the host twin)");
-    if (device < 0 || device >= ndev) return fail(DD_ERR_NO_DEVICE, "device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
+    if ((rc = use_device(device, "no HIP device: the library's block table runs on the device (host/haplotypes.cpp holds the host twin)"))) return rc;
     if (W == 0) return DD_SUCCESS;
 
-    // one allocation, 256-byte aligned pieces: inputs, per-window outputs, tables, workspace
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255u) & ~size_t(255u); return o; };
-    const size_t o_rs = take(W * 4), o_refo = take((W + 1) * 4), o_ref = take((size_t)s.ref_bytes), o_wro = take((W + 1) * 4),
-                 o_pos = take(R * 4), o_flag = take(R * 4), o_opo = take((R + 1) * 4), o_ops = take((size_t)s.n_ops * 4),
-                 o_bo = take((R + 1) * 4), o_bases = take((size_t)s.n_bases), o_in_end = off;
-    const size_t o_win = take(6 * W * 4), o_blko = take((W + 1) * 4), o_ento = take((W + 1) * 4), o_inso = take((W + 1) * 4),
-                 o_blk = take(n_blk * 4), o_ent = take(n_ent * 8), o_iops = take(n_ins * 8), o_ipos = take(n_ins * 8),
-                 o_ws = take(DD_HAPDIST_WS_BYTES);
-    (void)o_in_end;
-    struct Mem {
-        unsigned char *p = nullptr;
-        ~Mem() { if (p) (void)hipFree(p); }
-    } mem;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&mem.p), off));
-    unsigned char *d = mem.p;
-    auto up = [d](size_t o, const void *src, size_t bytes) { return bytes ? hipMemcpy(d + o, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
-    HIP_TRY(up(o_rs, b->win_rs, W * 4));
-    HIP_TRY(up(o_refo, b->win_ref_off, (W + 1) * 4));
-    HIP_TRY(up(o_ref, b->ref_seq, (size_t)s.ref_bytes));
-    HIP_TRY(up(o_wro, b->win_read_off, (W + 1) * 4));
-    HIP_TRY(up(o_pos, b->read_pos, R * 4));
-    HIP_TRY(up(o_flag, b->read_flag, R * 4));
-    HIP_TRY(up(o_opo, b->read_op_off, (R + 1) * 4));
-    HIP_TRY(up(o_ops, b->ops, (size_t)s.n_ops * 4));
-    HIP_TRY(up(o_bo, b->read_base_off, (R + 1) * 4));
-    HIP_TRY(up(o_bases, b->bases, (size_t)s.n_bases));
-    HIP_TRY(up(o_blko, t->blk_off, (W + 1) * 4));
-    HIP_TRY(up(o_ento, t->ent_off, (W + 1) * 4));
-    HIP_TRY(up(o_inso, t->ins_off, (W + 1) * 4));
+    // every array of the call once: the batch, the capacities, and the tables, which go up as well as down (what the kernel leaves alone
+    // comes back as the caller had it), and the workspace
+    const size_t ref_bytes = (size_t)s.ref_bytes, n_ops = (size_t)s.n_ops, n_bases = (size_t)s.n_bases;
     dd_hap_batch db = *b;
-    db.win_rs = reinterpret_cast<const int32_t *>(d + o_rs); db.win_ref_off = reinterpret_cast<const int32_t *>(d + o_refo);
-    db.ref_seq = reinterpret_cast<const char *>(d + o_ref); db.win_read_off = reinterpret_cast<const int32_t *>(d + o_wro);
-    db.read_pos = reinterpret_cast<const int32_t *>(d + o_pos); db.read_flag = reinterpret_cast<const int32_t *>(d + o_flag);
-    db.read_op_off = reinterpret_cast<const int32_t *>(d + o_opo); db.ops = reinterpret_cast<const uint32_t *>(d + o_ops);
-    db.read_base_off = reinterpret_cast<const int32_t *>(d + o_bo); db.bases = reinterpret_cast<const char *>(d + o_bases);
-    int32_t *dw = reinterpret_cast<int32_t *>(d + o_win);
     dd_hap_blocks dt;
-    dt.status = dw; dt.n_blocks = dw + W; dt.n_entries = dw + 2 * W; dt.n_ins_ops = dw + 3 * W; dt.n_ins_pos = dw + 4 * W; dt.left = dw + 5 * W;
-    dt.blk_off = reinterpret_cast<const int32_t *>(d + o_blko); dt.ent_off = reinterpret_cast<const int32_t *>(d + o_ento);
-    dt.ins_off = reinterpret_cast<const int32_t *>(d + o_inso);
-    dt.blocks = reinterpret_cast<uint32_t *>(d + o_blk); dt.entries = reinterpret_cast<uint32_t *>(d + o_ent);
-    dt.ins_ops = reinterpret_cast<uint32_t *>(d + o_iops); dt.ins_pos = reinterpret_cast<uint32_t *>(d + o_ipos);
-    // what the kernel leaves alone comes back as the caller had it
-    HIP_TRY(up(o_win, t->status, W * 4)); HIP_TRY(up(o_win + W * 4, t->n_blocks, W * 4)); HIP_TRY(up(o_win + 2 * W * 4, t->n_entries, W * 4));
-    HIP_TRY(up(o_win + 3 * W * 4, t->n_ins_ops, W * 4)); HIP_TRY(up(o_win + 4 * W * 4, t->n_ins_pos, W * 4)); HIP_TRY(up(o_win + 5 * W * 4, t->left, W * 4));
-    HIP_TRY(up(o_blk, t->blocks, n_blk * 4)); HIP_TRY(up(o_ent, t->entries, n_ent * 8));
-    HIP_TRY(up(o_iops, t->ins_ops, n_ins * 8)); HIP_TRY(up(o_ipos, t->ins_pos, n_ins * 8));
-    if ((rc = dd_hap_blocks_device(&db, &dt, (int64_t)n_blk, (int64_t)n_ent, (int64_t)n_ins, d + o_ws, DD_HAPDIST_WS_BYTES, nullptr))) {
-        g_hap_last.ws = nullptr;
+    unsigned char *ws;
+    OneShotArena arena;
+    ArenaRecords records(arena, {&g_hap_last});
+    if ((rc = arena.place({arena_slot(&db.win_rs, W * 4, b->win_rs), arena_slot(&db.win_ref_off, (W + 1) * 4, b->win_ref_off),
+                           arena_slot(&db.ref_seq, ref_bytes, b->ref_seq), arena_slot(&db.win_read_off, (W + 1) * 4, b->win_read_off),
+                           arena_slot(&db.read_pos, R * 4, b->read_pos), arena_slot(&db.read_flag, R * 4, b->read_flag),
+                           arena_slot(&db.read_op_off, (R + 1) * 4, b->read_op_off), arena_slot(&db.ops, n_ops * 4, b->ops),
+                           arena_slot(&db.read_base_off, (R + 1) * 4, b->read_base_off), arena_slot(&db.bases, n_bases, b->bases),
+                           arena_slot(&dt.status, W * 4, t->status), arena_slot(&dt.n_blocks, W * 4, t->n_blocks),
+                           arena_slot(&dt.n_entries, W * 4, t->n_entries), arena_slot(&dt.n_ins_ops, W * 4, t->n_ins_ops),
+                           arena_slot(&dt.n_ins_pos, W * 4, t->n_ins_pos), arena_slot(&dt.left, W * 4, t->left),
+                           arena_slot(&dt.blk_off, (W + 1) * 4, t->blk_off), arena_slot(&dt.ent_off, (W + 1) * 4, t->ent_off),
+                           arena_slot(&dt.ins_off, (W + 1) * 4, t->ins_off), arena_slot(&dt.blocks, n_blk * 4, t->blocks),
+                           arena_slot(&dt.entries, n_ent * 8, t->entries), arena_slot(&dt.ins_ops, n_ins * 8, t->ins_ops),
+                           arena_slot(&dt.ins_pos, n_ins * 8, t->ins_pos), arena_slot(&ws, DD_HAPDIST_WS_BYTES)})))
         return rc;
-    }
+    if ((rc = dd_hap_blocks_device(&db, &dt, (int64_t)n_blk, (int64_t)n_ent, (int64_t)n_ins, ws, DD_HAPDIST_WS_BYTES, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = read_hap_stats())) return rc;    // the workspace goes with this call
-    g_hap_last.ws = nullptr;
-    auto down = [d](void *dst, size_t o, size_t bytes) { return bytes ? hipMemcpy(dst, d + o, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
-    HIP_TRY(down(t->status, o_win, W * 4)); HIP_TRY(down(t->n_blocks, o_win + W * 4, W * 4)); HIP_TRY(down(t->n_entries, o_win + 2 * W * 4, W * 4));
-    HIP_TRY(down(t->n_ins_ops, o_win + 3 * W * 4, W * 4)); HIP_TRY(down(t->n_ins_pos, o_win + 4 * W * 4, W * 4)); HIP_TRY(down(t->left, o_win + 5 * W * 4, W * 4));
-    HIP_TRY(down(t->blocks, o_blk, n_blk * 4)); HIP_TRY(down(t->entries, o_ent, n_ent * 8));
-    HIP_TRY(down(t->ins_ops, o_iops, n_ins * 8)); HIP_TRY(down(t->ins_pos, o_ipos, n_ins * 8));
-    return DD_SUCCESS;
+    if ((rc = records.read_stats())) return rc;   // the workspace goes with this call
+    return download({{t->status, dt.status, W * 4}, {t->n_blocks, dt.n_blocks, W * 4}, {t->n_entries, dt.n_entries, W * 4},
+                     {t->n_ins_ops, dt.n_ins_ops, W * 4}, {t->n_ins_pos, dt.n_ins_pos, W * 4}, {t->left, dt.left, W * 4},
+                     {t->blocks, dt.blocks, n_blk * 4}, {t->entries, dt.entries, n_ent * 8}, {t->ins_ops, dt.ins_ops, n_ins * 8},
+                     {t->ins_pos, dt.ins_pos, n_ins * 8}});
 }
 
 } // extern "C"

@@ -4,15 +4,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dindel_hmm.h"
+#include "draw_header.h"
 
 namespace dda {
 
 #define DD_HAPDIST_WAVES 4            /* wavefronts per workgroup, one window each */
 #define DD_HAPDIST_MAX_BLOCKS 512     /* workgroups of the persistent grid: two per CU */
-#define DD_HAPDIST_WS_BYTES 256       /* the workspace: a header of u32 words */
-#define DD_HAPDIST_HDR_COUNTER 0      /* header word: u32 window counter */
-#define DD_HAPDIST_HDR_MAX_DRAWS 1    /* header word: most windows one wavefront drew */
-#define DD_HAPDIST_HDR_TRIPS 2        /* header word: wavefronts that left through the draw guard: 0 */
+#define DD_HAPDIST_WS_BYTES 256       /* the workspace: a header of u32 words, of which the launch uses DD_HAPDIST_HDR_* (draw_header.h) */
 
 struct HapdistArgs {
     dd_hap_batch b;
@@ -21,7 +19,6 @@ struct HapdistArgs {
     unsigned int *hdr;
 };
 
-unsigned hapdist_grid(int64_t n_windows);
 hipError_t launch_hapdist(const HapdistArgs &A, hipStream_t st);
 
 } // namespace dda

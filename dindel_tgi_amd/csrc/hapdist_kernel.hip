@@ -286,19 +286,11 @@ __global__ void __launch_bounds__(64 * DD_HAPDIST_WAVES) dd_hapdist_kernel(Hapdi
     if (lane == 0) atomicMax(P.hdr + DD_HAPDIST_HDR_MAX_DRAWS, draws);
 }
 
-unsigned hapdist_grid(int64_t n_windows)
-{
-    const int64_t blocks = (n_windows + DD_HAPDIST_WAVES - 1) / DD_HAPDIST_WAVES;
-    return (unsigned)(blocks < 1 ? 1 : blocks > DD_HAPDIST_MAX_BLOCKS ? DD_HAPDIST_MAX_BLOCKS : blocks);
-}
-
 hipError_t launch_hapdist(const HapdistArgs &A, hipStream_t st)
 {
     if (A.b.n_windows <= 0) return hipSuccess;
-    hipError_t e = hipMemsetAsync(A.hdr, 0, DD_HAPDIST_WS_BYTES, st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(dd_hapdist_kernel, dim3(hapdist_grid(A.b.n_windows)), dim3(64 * DD_HAPDIST_WAVES), 0, st, A);
-    return hipGetLastError();
+    return zero_and_launch(dd_hapdist_kernel, persistent_grid(A.b.n_windows, DD_HAPDIST_WAVES, DD_HAPDIST_MAX_BLOCKS), 64 * DD_HAPDIST_WAVES, 0,
+                           A.hdr, DD_HAPDIST_WS_BYTES, st, A);
 }
 
 } // namespace dda

@@ -113,16 +113,6 @@ struct DevBuf {
 
 thread_local int g_last_direct = 0;     // output arrays the last host-pointer call on this thread let the kernels write in place
 
-// makes `device` current; no_device: the text when the machine has none
-int use_device(int device, const char *no_device)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(DD_ERR_NO_DEVICE, no_device);
-    if (device < 0 || device >= ndev) return fail(DD_ERR_NO_DEVICE, "device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
-    return DD_SUCCESS;
-}
-
 // The device address of [host, host + bytes) if that is page-locked host memory this device can address (dd_host_alloc, hipHostMalloc)
 // and its last byte belongs to the same registered range; else NULL.
 void *mapped_device_ptr(const void *host, size_t bytes)
@@ -194,21 +184,6 @@ struct StageClock {
     }
     ~StageClock() { if (on) fprintf(stderr, "dd_timing:%s\n", line.c_str()); }
 };
-
-// One array of a call in the device arena: its bytes, the pointer variable that takes its device address, and for an input the host array
-// that is copied there.  A call lists every array it places before it touches the device, and the bytes it reserves are added up from those
-// lists (HostCall::end_of_all): there is no size formula to keep in step with them.
-struct ArenaSlot {
-    size_t bytes;
-    const unsigned char *src;                           // inputs: the host array (NULL: the array is only reserved)
-    void *var; void (*set)(void *var, void *dev);       // the variable, written through its own type
-    bool read_bases;                                    // read_seq / read_qidx, the two big inputs (HostCall::reserve_and_upload)
-    void point_at(const void *dev) const { set(var, const_cast<void *>(dev)); }
-};
-template <class P> ArenaSlot arena_slot(P *var, size_t bytes, const void *src = nullptr, bool read_bases = false)
-{
-    return {bytes, static_cast<const unsigned char *>(src), var, [](void *v, void *dev) { *static_cast<P *>(v) = static_cast<P>(dev); }, read_bases};
-}
 
 // One output array of a call: a field of dd_result, dd_cigar_result or dd_realign_result.  Placement in the arena, the in-place decision, the
 // per-block download and the staged copy-back are written once, over the call's list of these.

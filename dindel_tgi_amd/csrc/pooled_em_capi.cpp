@@ -1,5 +1,6 @@
 // pooled_em_capi.cpp — the device entries of the pooled analysis' EM loop (pooled_em_kernel.hip): the device-pointer launch and the
-// host-pointer entry (its own allocation: one call per batch).  The CPU evaluation is pooled_em_host.cpp.
+// host-pointer entry: its checks and its list of arrays (the arena and the copy back are capi_internal.h's).  The CPU evaluation is
+// pooled_em_host.cpp.
 #include "capi_internal.h"
 #include "pooled_em_kernel.h"
 
@@ -40,49 +41,27 @@ int dd_pooled_em(const dd_batch *b, const double *ll_host, const dd_pooled_slots
         pair_off[w + 1] = pair_off[w] + (int64_t)(b->win_hap_off[w + 1] - b->win_hap_off[w]) * (b->win_read_off[w + 1] - b->win_read_off[w]);
     const size_t n_pairs = (size_t)pair_off[W];
     if (n_pairs > 0 && !ll_host) return fail(DD_ERR_INVALID, "dd_pooled_em: null ll");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(DD_ERR_NO_DEVICE, "no HIP device: dd_pooled_em runs on the device (dd_pooled_em_host is the CPU evaluation)");
-    if (device < 0 || device >= ndev) return fail(DD_ERR_NO_DEVICE, "device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
+    if ((rc = use_device(device, "no HIP device: dd_pooled_em runs on the device (dd_pooled_em_host is the CPU evaluation)"))) return rc;
     if (N == 0) return DD_SUCCESS;
     const size_t F = (size_t)s->slot_off[N];
 
-    // one allocation, 256-byte aligned pieces
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t o = off; off = (off + std::max<size_t>(bytes, 1) + 255u) & ~size_t(255u); return o; };
-    const size_t o_ho = take((W + 1) * 4), o_ro = take((W + 1) * 4), o_po = take((W + 1) * 8), o_ll = take(n_pairs * 8), o_sw = take(N * 4),
-                 o_so = take((N + 1) * 8), o_c = take(F), o_lk = take(N * 8), o_f = take(F * 8), o_it = take(N * 4), o_ed = take(N * 8);
-    struct Mem {
-        unsigned char *p = nullptr;
-        ~Mem() { if (p) (void)hipFree(p); }
-    } mem;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&mem.p), off));
-    unsigned char *d = mem.p;
-    auto up = [d](size_t o, const void *src, size_t bytes) { return bytes ? hipMemcpy(d + o, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
-    HIP_TRY(up(o_ho, b->win_hap_off, (W + 1) * 4));
-    HIP_TRY(up(o_ro, b->win_read_off, (W + 1) * 4));
-    HIP_TRY(up(o_po, pair_off.data(), (W + 1) * 8));
-    HIP_TRY(up(o_ll, ll_host, n_pairs * 8));
-    HIP_TRY(up(o_sw, s->slot_window, N * 4));
-    HIP_TRY(up(o_so, s->slot_off, (N + 1) * 8));
-    HIP_TRY(up(o_c, s->compat, F));
+    // every array of the call once: the window offsets, the likelihoods, the slot tables and the four outputs
     dd_device_batch db;
     memset(&db, 0, sizeof(db));
     db.n_windows = b->n_windows;
-    db.win_hap_off = reinterpret_cast<const int32_t *>(d + o_ho); db.win_read_off = reinterpret_cast<const int32_t *>(d + o_ro);
-    db.win_pair_off = reinterpret_cast<const int64_t *>(d + o_po);
-    dd_pooled_slots ds = {s->n_slots, reinterpret_cast<const int32_t *>(d + o_sw), reinterpret_cast<const int64_t *>(d + o_so), d + o_c};
-    dd_pooled_result dr = {reinterpret_cast<double *>(d + o_lk), reinterpret_cast<double *>(d + o_f), reinterpret_cast<int32_t *>(d + o_it),
-                           reinterpret_cast<double *>(d + o_ed)};
-    if ((rc = dd_pooled_em_device(&db, reinterpret_cast<const double *>(d + o_ll), &ds, max_haps, a0, tol, &dr, nullptr))) return rc;
+    const double *d_ll;
+    dd_pooled_slots ds = *s;
+    dd_pooled_result dr;
+    OneShotArena arena;
+    if ((rc = arena.place({arena_slot(&db.win_hap_off, (W + 1) * 4, b->win_hap_off), arena_slot(&db.win_read_off, (W + 1) * 4, b->win_read_off),
+                           arena_slot(&db.win_pair_off, (W + 1) * 8, pair_off.data()), arena_slot(&d_ll, n_pairs * 8, ll_host),
+                           arena_slot(&ds.slot_window, N * 4, s->slot_window), arena_slot(&ds.slot_off, (N + 1) * 8, s->slot_off),
+                           arena_slot(&ds.compat, F, s->compat), arena_slot(&dr.loglik, N * 8), arena_slot(&dr.freqs, F * 8),
+                           arena_slot(&dr.iters, N * 4), arena_slot(&dr.ediff, N * 8)})))
+        return rc;
+    if ((rc = dd_pooled_em_device(&db, d_ll, &ds, max_haps, a0, tol, &dr, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
-    auto down = [d](void *dst, size_t o, size_t bytes) { return bytes ? hipMemcpy(dst, d + o, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
-    HIP_TRY(down(out->loglik, o_lk, N * 8));
-    HIP_TRY(down(out->freqs, o_f, F * 8));
-    HIP_TRY(down(out->iters, o_it, N * 4));
-    HIP_TRY(down(out->ediff, o_ed, N * 8));
-    return DD_SUCCESS;
+    return download({{out->loglik, dr.loglik, N * 8}, {out->freqs, dr.freqs, F * 8}, {out->iters, dr.iters, N * 4}, {out->ediff, dr.ediff, N * 8}});
 }
 
 } // extern "C"

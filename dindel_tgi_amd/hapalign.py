@@ -51,21 +51,31 @@ def host_batch(a):
     return _struct(a, _host_addr)
 
 
+def _host_call(symbol, refs, haps, pair_ref, device, with_ref_pos, extra=(), cap=None):
+    """One host-pointer entry: pack, allocate, call, raise, slice.  extra: (key, dtype, trailing shape) of the arrays the entry takes
+    behind the result, in its argument order, followed by `cap`.  ref_pos is part of the result only with_ref_pos."""
+    a = pack(refs, haps, pair_ref)
+    n, nb = len(haps), int(a["hap_off"][-1])
+    out = {"score": np.zeros(max(n, 1), np.int32), "status": np.zeros(max(n, 1), np.int32), "ref_pos": np.zeros(max(nb, 1), np.int16)}
+    out.update({k: np.zeros((max(n, 1),) + shape, dt) for k, dt, shape in extra})
+    b = host_batch(a)
+    r = capi.dd_align_result(out["score"].ctypes.data, out["status"].ctypes.data, out["ref_pos"].ctypes.data if with_ref_pos else None)
+    args = [out[k].ctypes.data for k, _, _ in extra] + ([int(cap)] if extra else [])
+    rc = getattr(capi.load(), symbol)(C.byref(b), C.byref(r), *args, device)
+    if rc != 0:
+        raise RuntimeError("%s: %d %s" % (symbol, rc, capi.last_error()))
+    res = {k: out[k][:n] for k in ["score", "status"] + [k for k, _, _ in extra]}
+    res["hap_off"] = a["hap_off"]
+    if with_ref_pos:
+        res["ref_pos"] = out["ref_pos"][:nb]
+    return res
+
+
 def align_haplotypes(refs, haps, pair_ref, device=0):
     """Align haps[i] (bytes) globally against refs[pair_ref[i]].  Returns dict(score int32 [n], status int32 [n], ref_pos int16 laid
     out like the concatenated haplotypes, hap_off int32 [n + 1]): ref_pos[hap_off[i] + b] is the 0-based offset of the reference
     base that base b of haplotype i is paired with, or -1 - n when it faces a gap, n = the number of reference bases left of its column."""
-    lib = capi.load()
-    a = pack(refs, haps, pair_ref)
-    n = len(haps)
-    out = {"score": np.zeros(max(n, 1), np.int32), "status": np.zeros(max(n, 1), np.int32),
-           "ref_pos": np.zeros(max(int(a["hap_off"][-1]), 1), np.int16)}
-    b = host_batch(a)
-    r = capi.dd_align_result(out["score"].ctypes.data, out["status"].ctypes.data, out["ref_pos"].ctypes.data)
-    rc = lib.dd_align_haplotypes(C.byref(b), C.byref(r), device)
-    if rc != 0:
-        raise RuntimeError("dd_align_haplotypes: %d %s" % (rc, capi.last_error()))
-    return {"score": out["score"][:n], "status": out["status"][:n], "ref_pos": out["ref_pos"][:int(a["hap_off"][-1])], "hap_off": a["hap_off"]}
+    return _host_call("dd_align_haplotypes", refs, haps, pair_ref, device, True)
 
 
 EVENT_FIELDS = ("kind", "ref", "len", "hap")
@@ -75,29 +85,13 @@ def align_events(refs, haps, pair_ref, events_cap=8, device=0, with_ref_pos=Fals
     """Align like align_haplotypes and return the indel events of every pair instead of its slice: dict(score, status, n_events int32
     [n], events int16 [n, events_cap, 4] with the fields of EVENT_FIELDS, hap_off).  n_events is the true count; a pair with
     n_events > events_cap holds its first events_cap records.  with_ref_pos=True also copies the slice back (ref_pos)."""
-    lib = capi.load()
-    a = pack(refs, haps, pair_ref)
-    n, nb = len(haps), int(a["hap_off"][-1])
-    cap = max(int(events_cap), 1)
-    out = {"score": np.zeros(max(n, 1), np.int32), "status": np.zeros(max(n, 1), np.int32), "n_events": np.zeros(max(n, 1), np.int32),
-           "events": np.zeros((max(n, 1), cap, 4), np.int16), "ref_pos": np.zeros(max(nb, 1), np.int16)}
-    b = host_batch(a)
-    r = capi.dd_align_result(out["score"].ctypes.data, out["status"].ctypes.data, out["ref_pos"].ctypes.data if with_ref_pos else None)
-    rc = lib.dd_align_haplotypes_events(C.byref(b), C.byref(r), out["n_events"].ctypes.data, out["events"].ctypes.data, int(events_cap), device)
-    if rc != 0:
-        raise RuntimeError("dd_align_haplotypes_events: %d %s" % (rc, capi.last_error()))
-    res = {"score": out["score"][:n], "status": out["status"][:n], "n_events": out["n_events"][:n], "events": out["events"][:n],
-           "hap_off": a["hap_off"]}
-    if with_ref_pos:
-        res["ref_pos"] = out["ref_pos"][:nb]
-    return res
+    extra = (("n_events", np.int32, ()), ("events", np.int16, (max(int(events_cap), 1), 4)))
+    return _host_call("dd_align_haplotypes_events", refs, haps, pair_ref, device, with_ref_pos, extra, events_cap)
 
 
 def events_last_launch():
     """This thread's last event launch: dict(grid, pairs, max_draws, guard_trips) (dd_align_events_last_launch)."""
-    out = (C.c_int64 * len(capi.ALIGN_EVENTS_LOG_FIELDS))()
-    capi.load().dd_align_events_last_launch(C.byref(out))
-    return dict(zip(capi.ALIGN_EVENTS_LOG_FIELDS, list(out)))
+    return capi.last_launch_of("dd_align_events_last_launch", capi.ALIGN_EVENTS_LOG_FIELDS)
 
 
 VARIANT_FIELDS = ("kind", "key", "len", "start_read", "left_flank_hap", "right_flank_hap", "left_flank_read", "right_flank_read")
@@ -108,28 +102,13 @@ def align_variants(refs, haps, pair_ref, cap=16, device=0, with_ref_pos=False):
     """Align like align_haplotypes and return every pair's variants instead of its slice: dict(score, status, summary int32 [n, 4] with
     the fields of SUMMARY_FIELDS, variants int16 [n, cap, 8] with the fields of VARIANT_FIELDS, hap_off).  n_variants is the true count;
     a pair with more than `cap` holds its first `cap` records.  with_ref_pos=True also copies the slice back (ref_pos)."""
-    lib = capi.load()
-    a = pack(refs, haps, pair_ref)
-    n, nb = len(haps), int(a["hap_off"][-1])
-    c = max(int(cap), 1)
-    out = {"score": np.zeros(max(n, 1), np.int32), "status": np.zeros(max(n, 1), np.int32), "summary": np.zeros((max(n, 1), 4), np.int32),
-           "variants": np.zeros((max(n, 1), c, 8), np.int16), "ref_pos": np.zeros(max(nb, 1), np.int16)}
-    b = host_batch(a)
-    r = capi.dd_align_result(out["score"].ctypes.data, out["status"].ctypes.data, out["ref_pos"].ctypes.data if with_ref_pos else None)
-    rc = lib.dd_align_haplotypes_variants(C.byref(b), C.byref(r), out["summary"].ctypes.data, out["variants"].ctypes.data, int(cap), device)
-    if rc != 0:
-        raise RuntimeError("dd_align_haplotypes_variants: %d %s" % (rc, capi.last_error()))
-    res = {"score": out["score"][:n], "status": out["status"][:n], "summary": out["summary"][:n], "variants": out["variants"][:n], "hap_off": a["hap_off"]}
-    if with_ref_pos:
-        res["ref_pos"] = out["ref_pos"][:nb]
-    return res
+    extra = (("summary", np.int32, (4,)), ("variants", np.int16, (max(int(cap), 1), 8)))
+    return _host_call("dd_align_haplotypes_variants", refs, haps, pair_ref, device, with_ref_pos, extra, cap)
 
 
 def variants_last_launch():
     """This thread's last variants launch: dict(grid, pairs, max_draws, guard_trips) (dd_hap_variants_last_launch)."""
-    out = (C.c_int64 * len(capi.ALIGN_EVENTS_LOG_FIELDS))()
-    capi.load().dd_hap_variants_last_launch(C.byref(out))
-    return dict(zip(capi.ALIGN_EVENTS_LOG_FIELDS, list(out)))
+    return capi.last_launch_of("dd_hap_variants_last_launch", capi.ALIGN_EVENTS_LOG_FIELDS)
 
 
 def gapped_rows(ref, hap, ref_pos):
@@ -156,9 +135,7 @@ def gapped_rows(ref, hap, ref_pos):
 def last_launch():
     """This thread's last alignment launch: dict(grid, waves, tile_bytes, lds_block, pairs, ws_bytes, max_draws, guard_trips); the last
     two come from the workspace header (after a DeviceAlign launch the object must still be alive; the call synchronises its stream)."""
-    out = (C.c_int64 * len(capi.ALIGN_LOG_FIELDS))()
-    capi.load().dd_align_last_launch(C.byref(out))
-    return dict(zip(capi.ALIGN_LOG_FIELDS, list(out)))
+    return capi.last_launch_of("dd_align_last_launch", capi.ALIGN_LOG_FIELDS)
 
 
 class DeviceAlign:
@@ -195,8 +172,7 @@ class DeviceAlign:
 
     def launch(self, stream=None):
         """Enqueue the alignment on `stream` (a torch stream; None = the current one).  Asynchronous."""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        st = capi.stream_of(stream, self.device)
         rc = capi.load().dd_align_haplotypes_device(C.byref(self.batch), C.byref(self.result), self.max_ref_len, self.max_hap_len,
                                                     self.workspace.data_ptr(), self.ws_bytes, st.cuda_stream)
         if rc != 0:
@@ -209,24 +185,30 @@ class DeviceAlign:
         return {"score": self.score.cpu().numpy()[:self.n_pairs], "status": self.status.cpu().numpy()[:self.n_pairs],
                 "ref_pos": self.ref_pos.cpu().numpy()[:self.hap_bytes], "hap_off": self.a["hap_off"]}
 
+    def _launch_behind(self, symbol, counts, records, width, cap, stream, fill):
+        """Enqueue `symbol` (the event or the variants extraction) behind launch() on the same stream.  counts, records: the attributes
+        of its two tensors, int32 [n_pairs] + counts' shape and int16 [n_pairs, cap, width]; made on first use or when cap changes,
+        and preset (counts to 0, records to `fill`) unless fill is None."""
+        import torch
+        st = capi.stream_of(stream, self.device)
+        c, n = max(int(cap), 1), max(self.n_pairs, 1)
+        with torch.cuda.stream(st):
+            if getattr(self, records, None) is None or getattr(self, records).shape[1] != c:
+                setattr(self, counts[0], torch.zeros((n,) + counts[1], dtype=torch.int32, device=self.device))
+                setattr(self, records, torch.zeros((n, c, width), dtype=torch.int16, device=self.device))
+            if fill is not None:
+                getattr(self, counts[0]).zero_()
+                getattr(self, records).fill_(fill)
+        rc = getattr(capi.load(), symbol)(C.byref(self.batch), C.byref(self.result), getattr(self, counts[0]).data_ptr(),
+                                          getattr(self, records).data_ptr(), int(cap), st.cuda_stream)
+        if rc != 0:
+            raise RuntimeError("%s: %d %s" % (symbol, rc, capi.last_error()))
+
     def launch_events(self, events_cap=8, stream=None, fill=0):
         """Enqueue the event extraction behind launch() on the same stream: fills self.n_events (int32 [n_pairs]) and self.events
         (int16 [n_pairs, events_cap, 4]).  The kernel writes only the records it counts; the rest of self.events is preset to `fill`
         (None: left as it is, the tensors of the previous call are reused).  Asynchronous."""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        cap = max(int(events_cap), 1)
-        with torch.cuda.stream(st):
-            if getattr(self, "events", None) is None or self.events.shape[1] != cap:
-                self.n_events = torch.zeros(max(self.n_pairs, 1), dtype=torch.int32, device=self.device)
-                self.events = torch.zeros((max(self.n_pairs, 1), cap, 4), dtype=torch.int16, device=self.device)
-            if fill is not None:
-                self.n_events.zero_()
-                self.events.fill_(fill)
-        rc = capi.load().dd_align_events_device(C.byref(self.batch), C.byref(self.result), self.n_events.data_ptr(), self.events.data_ptr(),
-                                                int(events_cap), st.cuda_stream)
-        if rc != 0:
-            raise RuntimeError("dd_align_events_device: %d %s" % (rc, capi.last_error()))
+        self._launch_behind("dd_align_events_device", ("n_events", ()), "events", 4, events_cap, stream, fill)
 
     def event_results(self):
         """Synchronise and copy back n_events and events of the last launch_events()."""
@@ -238,20 +220,7 @@ class DeviceAlign:
         """Enqueue the variant extraction behind launch() on the same stream: fills self.summary (int32 [n_pairs, 4]) and self.variants
         (int16 [n_pairs, cap, 8]).  The kernel writes only the records it counts; the rest of self.variants is preset to `fill`
         (None: left as it is, the tensors of the previous call are reused).  Asynchronous."""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        c = max(int(cap), 1)
-        with torch.cuda.stream(st):
-            if getattr(self, "variants", None) is None or self.variants.shape[1] != c:
-                self.summary = torch.zeros((max(self.n_pairs, 1), 4), dtype=torch.int32, device=self.device)
-                self.variants = torch.zeros((max(self.n_pairs, 1), c, 8), dtype=torch.int16, device=self.device)
-            if fill is not None:
-                self.summary.zero_()
-                self.variants.fill_(fill)
-        rc = capi.load().dd_hap_variants_device(C.byref(self.batch), C.byref(self.result), self.summary.data_ptr(), self.variants.data_ptr(),
-                                                int(cap), st.cuda_stream)
-        if rc != 0:
-            raise RuntimeError("dd_hap_variants_device: %d %s" % (rc, capi.last_error()))
+        self._launch_behind("dd_hap_variants_device", ("summary", (4,)), "variants", 8, cap, stream, fill)
 
     def variant_results(self):
         """Synchronise and copy back summary and variants of the last launch_variants()."""

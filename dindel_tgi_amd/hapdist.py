@@ -128,9 +128,7 @@ def block_table(windows, reads, device=0, tables=None):
 def last_launch():
     """This thread's last block-table launch: dict(grid, windows, max_draws, guard_trips) (dd_hap_blocks_last_launch; after a
     DeviceBlocks launch the object must still be alive; the call synchronises its stream)."""
-    out = (C.c_int64 * len(capi.HAP_BLOCKS_LOG_FIELDS))()
-    capi.load().dd_hap_blocks_last_launch(C.byref(out))
-    return dict(zip(capi.HAP_BLOCKS_LOG_FIELDS, list(out)))
+    return capi.last_launch_of("dd_hap_blocks_last_launch", capi.HAP_BLOCKS_LOG_FIELDS)
 
 
 class DeviceBlocks:
@@ -160,8 +158,7 @@ class DeviceBlocks:
 
     def launch(self, stream=None):
         """Enqueue the kernel on `stream` (a torch stream; None = the current one).  Asynchronous."""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        st = capi.stream_of(stream, self.device)
         rc = capi.load().dd_hap_blocks_device(C.byref(self.batch), C.byref(self.tables), self.caps[0], self.caps[1], self.caps[2],
                                               self.workspace.data_ptr(), self.ws_bytes, st.cuda_stream)
         if rc != 0:
