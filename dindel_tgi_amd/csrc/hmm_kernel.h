@@ -7,6 +7,9 @@
 
 #define DD_WAVES 4   /* max wavefronts per workgroup: one per SIMD of a CU, one pair (two in the half-wave builds) in flight per wave */
 #define DD_HALF_CHUNK 256   /* half-wave builds (two pairs per wavefront): reads of a window ordered at a time (LDS keys, capi.cpp sizes them) */
+/* main kernel: the scalar outputs of a pair, stored by one lane each in the K <= 2 / D = 6 builds (hmm_kernel.hip, "outputs"): lanes 0..13
+ * dd_result's first 14 arrays in its order (ll, llOn, llOff, mLogBQ, offHap, offHapHMQ, the eight int16 counters), lane 14 status */
+#define DD_PAIR_FIELDS 15
 
 /* layout of the host-built table block (dd_build_tables) */
 enum {

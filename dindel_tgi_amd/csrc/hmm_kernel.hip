@@ -25,6 +25,7 @@
 // updateMax has a 1e-10 hysteresis, ObservationModelFB.cpp:877-888).  No MFMA: this is a max-plus
 // recurrence, not a contraction.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <atomic>
 #include "hmm_kernel.h"
@@ -288,6 +289,10 @@ __global__ void __launch_bounds__(DD_WAVES * 64, OCC ? OCC : DD_MIN_WAVES_PER_SI
     for (int i = tid; i < 256; i += nthr) shLut[i] = P.sym_lut ? P.sym_lut[i] : (unsigned char)builtin_symbol((unsigned)i);
     // pads of the wave-private rows: written once, never touched again
     if (lane == 0) { rowI[0] = NEG_INF; rowI[1 + NP] = NEG_INF; }
+    // LANE_OUT: the builds that store a pair's scalar outputs one lane per field (see "outputs" below).  The K <= 2 / D = 6 builds only: the
+    // once-per-pair code is 8 % of their instructions (K >= 3 and D >= 11 spend proportionally more in the sweeps), and in the other builds
+    // the changed register allocation brought the ROCm 7.2 spill placement fault (tools/check_exec_spills.py) back into three of them.
+    constexpr bool LANE_OUT = K <= 2 && D <= 7;
     STAMP_INIT;
 
     // ======================= loop over this workgroup's (haplotype, read-slice) items =======================
@@ -331,7 +336,6 @@ __global__ void __launch_bounds__(DD_WAVES * 64, OCC ? OCC : DD_MIN_WAVES_PER_SI
     const int numS = Hs + 2, RO = Hs + 1;
     const uint32_t hapStart = P.win_hap_start[w];
     const bool hap_ok = (P.maxLengthDel <= Hs);     // else "hapSize error." (ObservationModelFB.cpp:47)
-
     // ---- per-haplotype setup: state codes + homopolymer indel-error logs (setupTransitionProbs :1675-1703)
     for (int s = tid; s < NP + 16; s += nthr) {
         int code = DD_SYM_PAD;                       // padded state: matches nothing
@@ -689,6 +693,11 @@ __global__ void __launch_bounds__(DD_WAVES * 64, OCC ? OCC : DD_MIN_WAVES_PER_SI
                     }
                 }
             }
+            // the one-lane RO block's condition as an opaque per-read flag, like pubFlag: its mask is formed here, in front of the pass, and
+            // lives across the sweep only (formed per item it sat in a spilled scalar pair and cost two reloads per read base)
+            // (the LANE_OUT builds, whose register allocation it was measured with; the others keep the condition as it was)
+            int roFlag = (!foldRO && lane == laneRO) ? 1 : 0;
+            if constexpr (LANE_OUT) asm volatile("" : "+v"(roFlag));
             if (foldLO && lane == 63) { a[K - 1] = 0.0; in[K - 1] = 0.0; }      // beta[L-1][LO] = beta[L-1][numS] = 0, at LO's position in this pass
             if (mirRO && lane == laneRO) { a[K - 1] = 0.0; in[K - 1] = 0.0; }   // RO's copy: beta[L-1][RO] = beta[L-1][numS+RO] = 0
             auto cinc = [&](int k, int y) -> double {       // y = 1..D
@@ -808,7 +817,7 @@ __global__ void __launch_bounds__(DD_WAVES * 64, OCC ? OCC : DD_MIN_WAVES_PER_SI
                     ni[0] = dmax(d, val);
                     btb[0] = (btacc_t)(code | (take ? (1u << BP::CB) : 0u));
                 }
-                if (!foldRO && lane == laneRO) {                    // x = RO (:1741-1742, :1750, :1763-1767)
+                if (LANE_OUT ? roFlag != 0 : (!foldRO && lane == laneRO)) {   // x = RO (:1741-1742, :1750, :1763-1767)
 #pragma unroll
                     for (int k = 0; k < K; k++) {
                         if (k == kRO) {
@@ -1339,7 +1348,47 @@ __global__ void __launch_bounds__(DD_WAVES * 64, OCC ? OCC : DD_MIN_WAVES_PER_SI
             }
         }
 
-        if (lane == 0 && live) {
+        // The pair's DD_PAIR_FIELDS scalars, one lane per field, in dd_result's order.  Lane 0 (which alone holds llOff) lays the values out in the
+        // idle slice buffer, one 8-byte slot per field; lane f then reads field f's value from there and field f's POINTER straight from the
+        // kernel-argument segment (dd_result is a run of pointers: one vector load at a per-lane offset), and stores with the one store
+        // instruction of its element width.  Lanes whose pointer is NULL store nothing.  (One array at a time from lane 0 this was 127 reloads
+        // of spilled scalars and 137 other VALU instructions per pair — a null test, a pointer and a value each — and 15 pointers held in
+        // spilled scalar registers through the sweeps.)
+        if constexpr (LANE_OUT) {
+            static_assert(offsetof(dd_result, ll) == 0 && offsetof(dd_result, offHap) == 4 * 8 && offsetof(dd_result, numIndels) == 6 * 8 &&
+                          offsetof(dd_result, lastBase) == 13 * 8 && offsetof(dd_result, status) == 16 * 8 && sizeof(void *) == 8,
+                          "lane f < 14 takes dd_result's f-th pointer, lane 14 status");
+            uint64_t *slot = reinterpret_cast<uint64_t *>(rowA);           // [DD_PAIR_FIELDS]; K * AQ * 16 bytes >= 32 slots
+            if (lane == 0) {
+                int status = DD_PAIR_OK;
+                if (ll > 0.1) status = DD_PAIR_LLPOS;                         // DInDel.cpp:1722
+                else if (ll != ll || ll == NEG_INF || ll == -NEG_INF) status = DD_PAIR_NAN;   // DInDel.cpp:1732
+                double *dslot = reinterpret_cast<double *>(slot);
+                dslot[0] = ll; dslot[1] = llOn; dslot[2] = llOff; dslot[3] = mLogBQ;
+                const int small[DD_PAIR_FIELDS - 4] = {offHap ? 1 : 0, offHapHMQ ? 1 : 0, nIndel, nMis, nBQT, nmmBQT, nMML, nMMR, firstB, lastB, status};
+#pragma unroll
+                for (int f = 4; f < DD_PAIR_FIELDS; f++) reinterpret_cast<int *>(slot + f)[0] = small[f - 4];   // low bytes of the slot: what the narrower stores take
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            int f = lane;
+            asm volatile("" : "+v"(f));        // opaque: the field's masks, offset and width are formed here, once per pair, not kept in registers across the sweeps
+            if (f < DD_PAIR_FIELDS && live) {
+                typedef const unsigned char __attribute__((address_space(4))) *kernarg_bytes;
+                const kernarg_bytes ka = (kernarg_bytes)__builtin_amdgcn_kernarg_segment_ptr();   // the one kernel argument, P, starts the segment
+                const unsigned koff = (unsigned)offsetof(KernelArgs, out) + 8u * (unsigned)(f < 14 ? f : 16);
+                const uint64_t p = *reinterpret_cast<const uint64_t __attribute__((address_space(4))) *>(ka + koff);
+                const uint32_t vlo = reinterpret_cast<const uint32_t *>(slot + f)[0], vhi = reinterpret_cast<const uint32_t *>(slot + f)[1];
+                const int lw = f < 4 ? 3 : (f < 6 ? 0 : (f < 14 ? 1 : 2));                    // log2 of the element's bytes
+                unsigned char *dst = reinterpret_cast<unsigned char *>((uintptr_t)p) + ((uint64_t)pair << lw);
+                if (p != 0) {
+                    if (lw == 3) *reinterpret_cast<uint2 *>(dst) = make_uint2(vlo, vhi);
+                    else if (lw == 2) *reinterpret_cast<uint32_t *>(dst) = vlo;
+                    else if (lw == 1) *reinterpret_cast<uint16_t *>(dst) = (uint16_t)vlo;
+                    else *dst = (unsigned char)vlo;
+                }
+            }
+        } else if (lane == 0 && live) {
             int status = DD_PAIR_OK;
             if (ll > 0.1) status = DD_PAIR_LLPOS;                         // DInDel.cpp:1722
             else if (ll != ll || ll == NEG_INF || ll == -NEG_INF) status = DD_PAIR_NAN;   // DInDel.cpp:1732
