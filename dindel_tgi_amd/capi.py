@@ -40,6 +40,9 @@ DD_CIGAR_DEFAULT_OPS_CAP = 8
 # realigned reads (opt-in): per-read status codes beside the DD_CIGAR_* of the chosen pair, and the two rules
 DD_REALIGN_OFF_HAP, DD_REALIGN_BAD_PAIR, DD_REALIGN_NO_HAPS = 9, 10, 11
 DD_REALIGN_FIRST_MAX, DD_REALIGN_PAIR = 0, 1
+# the certified MAP haplotype pair of the diploid realigned reads (opt-in): per-window states and the haplotype cap
+(DD_DIPPAIR_CERTIFIED, DD_DIPPAIR_TIE, DD_DIPPAIR_NONFINITE, DD_DIPPAIR_NOT_COMPUTED, DD_DIPPAIR_NO_HAPS, DD_DIPPAIR_TOO_MANY_HAPS) = range(6)
+DD_DIPPAIR_MAX_HAPS = 128
 # alignHaplotypes on the device: per-pair status codes and the launch geometry record
 DD_ALIGN_OK, DD_ALIGN_EMPTY, DD_ALIGN_TOO_LONG, DD_ALIGN_BAD_REF = range(4)
 DD_ALIGN_WS_BUDGET = 512 << 20
@@ -166,6 +169,16 @@ class dd_realign_result(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in REALIGN_RESULT_FIELDS]
 
 
+DIPLOID_PAIR_FIELDS = ("pair", "state", "best", "gap", "margin")
+DIPLOID_PAIR_DTYPES = {"pair": "int32", "state": "int32", "best": "float64", "gap": "float64", "margin": "float64"}
+
+
+class dd_diploid_pair_result(C.Structure):
+    """Per window: pair (int32 [2]), state (int32, DD_DIPPAIR_*), best, gap, margin (double).  Raw addresses: host arrays for
+    dd_diploid_pairs_host, device arrays for dd_diploid_pairs_device."""
+    _fields_ = [(n, C.c_void_p) for n in DIPLOID_PAIR_FIELDS]
+
+
 class dd_align_batch(C.Structure):
     """References and the haplotypes aligned against them.  Raw addresses: host arrays for dd_align_haplotypes and
     dd_align_workspace_bytes, device arrays for dd_align_haplotypes_device."""
@@ -242,7 +255,8 @@ EXPORTS = ["dd_params_struct_defaults", "dd_params_cli_defaults", "dd_batch_size
            "dd_align_events_device", "dd_align_haplotypes_events", "dd_align_events_last_launch",
            "dd_hap_variants_device", "dd_align_haplotypes_variants", "dd_hap_variants_last_launch",
            "dd_hap_blocks_offsets", "dd_hap_blocks_workspace_bytes", "dd_hap_blocks_device", "dd_hap_blocks_compute", "dd_hap_blocks_last_launch",
-           "dd_pooled_em_device", "dd_pooled_em", "dd_pooled_em_host", "dd_pooled_math_eval"]
+           "dd_pooled_em_device", "dd_pooled_em", "dd_pooled_em_host", "dd_pooled_math_eval",
+           "dd_diploid_pairs_device", "dd_diploid_pairs_host", "dd_compute_likelihoods_realign_diploid"]
 
 _lib = None
 
@@ -343,6 +357,11 @@ def load():
     lib.dd_pooled_em.argtypes = [C.POINTER(dd_batch), c_f64p, C.POINTER(dd_pooled_slots), C.c_double, C.c_double, C.POINTER(dd_pooled_result), C.c_int]
     lib.dd_pooled_em_host.argtypes = lib.dd_pooled_em.argtypes
     lib.dd_pooled_math_eval.argtypes = [C.c_int, c_f64p, c_f64p, C.c_int64]
+    lib.dd_diploid_pairs_device.argtypes = [C.POINTER(dd_device_batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(dd_diploid_pair_result), C.c_void_p]
+    lib.dd_diploid_pairs_host.argtypes = [C.POINTER(dd_batch), c_f64p, c_i32p, c_f64p, C.POINTER(dd_diploid_pair_result), C.c_int]
+    lib.dd_compute_likelihoods_realign_diploid.argtypes = [C.POINTER(dd_params), C.POINTER(dd_batch), C.POINTER(dd_result), c_f64p, c_i32p, c_i32p, c_u8p,
+                                                           C.POINTER(dd_diploid_pair_result), C.POINTER(dd_realign_result), C.c_int, C.c_int, C.c_uint32]
     lib.dd_last_launch.argtypes = [C.POINTER(C.c_int32 * 8)]
     lib.dd_last_launch.restype = None
     lib.dd_launch_log.argtypes = [c_i32p, C.c_int]
@@ -446,6 +465,37 @@ def realign_arrays(n_reads, ops_cap):
     a["ops"] = np.zeros((n, int(ops_cap)), np.uint32)
     res = dd_realign_result(*[a[k].ctypes.data for k in REALIGN_RESULT_FIELDS])
     return {k: v[:int(n_reads)] for k, v in a.items()}, res
+
+
+def diploid_pair_arrays(n_windows):
+    """Host arrays for the certified MAP pair of every window: (dict(pair [n_windows, 2], state, best, gap, margin), the
+    dd_diploid_pair_result that points at them).  Keep the dict alive as long as the struct is in use."""
+    import numpy as np
+    n = max(int(n_windows), 1)
+    a = {k: np.zeros((n, 2) if k == "pair" else n, DIPLOID_PAIR_DTYPES[k]) for k in DIPLOID_PAIR_FIELDS}
+    res = dd_diploid_pair_result(*[a[k].ctypes.data for k in DIPLOID_PAIR_FIELDS])
+    return {k: v[:int(n_windows)] for k, v in a.items()}, res
+
+
+def diploid_pairs_host(win_hap_off, win_read_off, ll, prior, status=None, nthreads=1):
+    """dd_diploid_pairs_host on plain arrays: the window offsets (int32 [n_windows + 1]), ll (and status) per pair in pair order, prior laid
+    out by dd_pair_sum_offsets (H * H doubles per window).  Returns dict(pair, state, best, gap, margin)."""
+    import numpy as np
+    ho = np.ascontiguousarray(win_hap_off, np.int32)
+    ro = np.ascontiguousarray(win_read_off, np.int32)
+    ll = np.ascontiguousarray(ll, np.float64)
+    prior = np.ascontiguousarray(prior, np.float64)
+    st = None if status is None else np.ascontiguousarray(status, np.int32)
+    b = dd_batch()
+    b.n_windows = len(ho) - 1
+    b.win_hap_off = ho.ctypes.data_as(c_i32p)
+    b.win_read_off = ro.ctypes.data_as(c_i32p)
+    out, res = diploid_pair_arrays(b.n_windows)
+    rc = load().dd_diploid_pairs_host(C.byref(b), ll.ctypes.data_as(c_f64p) if ll.size else None, st.ctypes.data_as(c_i32p) if st is not None else None,
+                                      prior.ctypes.data_as(c_f64p) if prior.size else None, C.byref(res), int(nthreads))
+    if rc != 0:
+        raise RuntimeError("dd_diploid_pairs_host rc=%d: %s" % (rc, last_error()))
+    return out
 
 
 def cigar_ops(ops, n_ops):

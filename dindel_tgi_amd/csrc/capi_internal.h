@@ -56,16 +56,19 @@ enum Model { MODEL_FBMAXERR = 0 /* ObservationModelFBMaxErr, computeLikelihoods 
     X(ll, PAIR, 1) X(llOn, PAIR, 1) X(llOff, PAIR, 1) X(mLogBQ, PAIR, 1) X(offHap, PAIR, 1) X(offHapHMQ, PAIR, 0) X(numIndels, PAIR, 1) \
     X(numMismatch, PAIR, 1) X(nBQT, PAIR, 1) X(nmmBQT, PAIR, 1) X(nMMLeft, PAIR, 1) X(nMMRight, PAIR, 1) X(firstBase, PAIR, 1)     \
     X(lastBase, PAIR, 1) X(status, PAIR, 0) X(hpos, HPOS, 1) X(var_covered, VARCOV, 1) X(var_fcov, VARCOV, 1) X(onHap, READ, 1)
-enum ResultSpace { SPACE_PAIR, SPACE_HPOS, SPACE_VARCOV, SPACE_READ };
+enum ResultSpace { SPACE_PAIR, SPACE_HPOS, SPACE_VARCOV, SPACE_READ, SPACE_WINDOW /* one per window: dd_diploid_pair_result */ };
 // Every field of dd_cigar_result (one entry per PAIR) and of dd_realign_result (one per READ), in the order the host-pointer path places and
 // copies them, with the field's width: 1 = ops_cap elements per entry (ops), 0 = one.  None of them is written in place.
 #define DD_CIGAR_FIELDS(X) X(n_ops, 0) X(ref_off, 0) X(status, 0) X(ops, 1)
 #define DD_REALIGN_FIELDS(X) X(hap, 0) X(status, 0) X(n_ops, 0) X(ref_off, 0) X(ops, 1)
+// Every field of dd_diploid_pair_result (one entry per WINDOW) with its width in elements.
+#define DD_DIPPAIR_FIELDS(X) X(pair, 2) X(state, 1) X(best, 1) X(gap, 1) X(margin, 1)
 #define DD_FIELD_SIZE(f, ...) + sizeof(S::f)
 #define DD_LISTS_ALL_OF(T, FIELDS) static_assert([] { using S = T; return 0 FIELDS(DD_FIELD_SIZE); }() == sizeof(T), #FIELDS " must list every field of " #T)
 DD_LISTS_ALL_OF(dd_result, DD_RESULT_FIELDS);
 DD_LISTS_ALL_OF(dd_cigar_result, DD_CIGAR_FIELDS);
 DD_LISTS_ALL_OF(dd_realign_result, DD_REALIGN_FIELDS);
+DD_LISTS_ALL_OF(dd_diploid_pair_result, DD_DIPPAIR_FIELDS);
 #undef DD_LISTS_ALL_OF
 #undef DD_FIELD_SIZE
 

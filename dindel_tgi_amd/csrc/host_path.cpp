@@ -9,6 +9,7 @@
 #include <mutex>
 #include <thread>
 #include "capi_internal.h"
+#include "diploid_pair_kernel.h"
 
 namespace ddh {
 namespace {
@@ -131,7 +132,10 @@ void *mapped_device_ptr(const void *host, size_t bytes)
 struct ResultIndex {
     const int64_t *pair_off, *hpos_off, *varcov_off;   // dd_batch_offsets
     const int32_t *read_off;                            // the batch's win_read_off
-    int64_t at(ResultSpace s, int w) const { return s == SPACE_PAIR ? pair_off[w] : s == SPACE_HPOS ? hpos_off[w] : s == SPACE_VARCOV ? varcov_off[w] : read_off[w]; }
+    int64_t at(ResultSpace s, int w) const
+    {
+        return s == SPACE_PAIR ? pair_off[w] : s == SPACE_HPOS ? hpos_off[w] : s == SPACE_VARCOV ? varcov_off[w] : s == SPACE_WINDOW ? w : read_off[w];
+    }
 };
 
 // What a host-pointer call checks first; sz: the batch's sizes.  A batch without pairs (sz.n_pairs == 0) is finished here.
@@ -205,12 +209,14 @@ enum { DD_RESULT_FIELDS(OUT_INDEX) N_RESULT_OUTS };    // a dd_result field's pl
 
 // What a CIGAR or realign entry adds to a call: inputs of its own, per window block one launch behind the likelihood launches, and output
 // arrays in one index space (per PAIR: dd_compute_likelihoods_cigars; per READ: dd_compute_likelihoods_realign, which takes the window pairs
-// and indel counts of its PAIR mode besides).
+// and indel counts of its PAIR mode besides; dd_compute_likelihoods_realign_diploid, whose window pairs are chosen by a launch of its own in
+// front of the realign launch and stay on the device, with outputs per WINDOW besides).
 struct ExtraRequest {
     const int32_t *hap_ref_pos; const uint8_t *hap_aligned; int ops_cap;
     bool realign;
     dd_cigar_result cigars;                                                       // !realign
     int mode; const int32_t *win_hap_pair, *hap_n_indels; dd_realign_result reads; // realign
+    bool diploid; const double *prior; dd_diploid_pair_result pairs;              // realign in PAIR mode, the pairs from dd_diploid_pairs_device
 };
 
 // One call of a host-pointer entry.  run() is the sequence of its stages; the members are grouped by the stage that fills them.
@@ -230,7 +236,7 @@ struct HostCall {
     // plan
     int W = 0;
     std::vector<int32_t> hap_window, class_list;
-    std::vector<int64_t> pair_off, hpos_off, vc_off;
+    std::vector<int64_t> pair_off, hpos_off, vc_off, hh_off;   // hh_off: dd_pair_sum_offsets (a diploid request's prior table)
     std::vector<double> tables;
     ResultIndex idx;
     dd_length_classes lcls = {};
@@ -245,6 +251,9 @@ struct HostCall {
     dd_result dr = {};
     dd_cigar_result dcg = {};
     dd_realign_result drl = {};
+    dd_diploid_pair_result ddp = {};
+    const double *prior_dev = nullptr;
+    const int64_t *hh_off_dev = nullptr;
     unsigned char *ws[2] = {nullptr, nullptr}, *lws[2] = {nullptr, nullptr};
     unsigned long long *long_stats = nullptr;           // long_path->n_stats (2 or 4) words per window block's long launch
     // reserve_and_upload, place_outputs
@@ -268,6 +277,8 @@ struct HostCall {
                 const dd_realign_result &o = x->reads;
                 o.hap[q] = -1; o.status[q] = DD_REALIGN_NO_HAPS; o.n_ops[q] = 0; o.ref_off[q] = -1;
             }
+        if (!rc && sz.n_pairs == 0 && x && x->diploid)       // ... and no likelihood: the windows' pairs from the priors alone, by the CPU evaluation
+            rc = dd_diploid_pairs_host(b, nullptr, nullptr, x->prior, &x->pairs, 1);
         if (rc || sz.n_pairs == 0) return rc;
         if ((rc = check_and_screen())) return rc;
         if ((rc = use_device(device, "no HIP device: the likelihood path has no CPU fallback"))) return rc;
@@ -351,6 +362,10 @@ struct HostCall {
         pair_off.resize(W + 1); hpos_off.resize(W + 1); vc_off.resize(W + 1);
         dd_build_index(b, hap_window.data(), pair_off.data(), hpos_off.data(), vc_off.data());
         idx = {pair_off.data(), hpos_off.data(), vc_off.data(), b->win_read_off};
+        if (x && x->diploid) {
+            hh_off.resize(W + 1);
+            if ((rc = dd_pair_sum_offsets(b, hh_off.data()))) return rc;
+        }
         tables.resize(DD_TABLE_DOUBLES);
         rc = dd_build_tables(p, b->qual_table, b->n_qual, b->mapq_table, b->n_mapq, tables.data());
         if (rc < 0) return rc;
@@ -423,8 +438,12 @@ struct HostCall {
             in(&hap_ref_pos_dev, x->hap_ref_pos, (size_t)sz.hap_bases);
             if (x->hap_aligned) in(&hap_aligned_dev, x->hap_aligned, n_haps);
             if (x->realign && x->mode == DD_REALIGN_PAIR) {
-                in(&win_hap_pair_dev, x->win_hap_pair, (size_t)W * 2);
+                if (!x->diploid) in(&win_hap_pair_dev, x->win_hap_pair, (size_t)W * 2);
                 in(&hap_n_indels_dev, x->hap_n_indels, n_haps);
+            }
+            if (x->diploid) {
+                in(&hh_off_dev, hh_off.data(), hh_off.size());
+                in(&prior_dev, x->prior, (size_t)hh_off[(size_t)W]);
             }
         }
 
@@ -433,7 +452,7 @@ struct HostCall {
         // copy in HBM and no copy afterwards.  (The runtime carries device -> host copies of this size out with a copy KERNEL:
         // profiles/r02/hostapi_timeline.txt shows 300 ms of such kernels on the CUs beside 410 ms of HMM kernels for configs[1].)  status and
         // offHapHMQ stay in HBM: the onHap kernel reads them back (DD_RESULT_FIELDS).
-        outs.reserve(N_RESULT_OUTS + 5);
+        outs.reserve(N_RESULT_OUTS + 10);
 #define OUT(f, space, in_place) out(r->f, &dr.f, SPACE_##space, 1, in_place != 0);
         DD_RESULT_FIELDS(OUT)
 #undef OUT
@@ -447,14 +466,17 @@ struct HostCall {
             const size_t cap = (size_t)x->ops_cap;
 #define OUT_PAIR(f, wide) out(x->cigars.f, &dcg.f, SPACE_PAIR, wide ? cap : 1, false);
 #define OUT_READ(f, wide) out(x->reads.f, &drl.f, SPACE_READ, wide ? cap : 1, false);
+#define OUT_WINDOW(f, width) out(x->pairs.f, &ddp.f, SPACE_WINDOW, width, false);
             if (x->realign) {
                 outs[OUT_ll].in_place = outs[OUT_onHap].in_place = false;
                 DD_REALIGN_FIELDS(OUT_READ)
+                if (x->diploid) { DD_DIPPAIR_FIELDS(OUT_WINDOW) }
             } else {
                 DD_CIGAR_FIELDS(OUT_PAIR)
             }
 #undef OUT_PAIR
 #undef OUT_READ
+#undef OUT_WINDOW
         }
 
         for (int i = 0; i < 2; i++)
@@ -573,15 +595,19 @@ struct HostCall {
 
     // The request's launch for the windows [w0, w1) of a block, behind the block's likelihood launches on the same stream: the block's CIGARs
     // (its ops start out zero: a pair's unused slots are defined), or the block's realigned reads (reads of windows without haplotypes are
-    // marked too: the launch goes by reads, not by pairs).
+    // marked too: the launch goes by reads, not by pairs).  A diploid request's pair launch goes first, for the same windows: the realign
+    // launch reads the pairs where that launch left them.
     int launch_extra(hipStream_t st, int w0, int w1)
     {
+        int rc;
+        if (x->diploid && (rc = launch_diploid_pairs_range(&db, hh_off_dev, dr.ll, dr.status, prior_dev, &ddp, st, w0, w1))) return rc;
         const ResultSpace space = x->realign ? SPACE_READ : SPACE_PAIR;
         const int64_t lo = idx.at(space, w0), hi = idx.at(space, w1);
         if (hi <= lo) return DD_SUCCESS;
         HIP_TRY(hipMemsetAsync((x->realign ? drl.ops : dcg.ops) + (size_t)lo * x->ops_cap, 0, (size_t)(hi - lo) * x->ops_cap * 4, st));
         if (!x->realign) return launch_cigars_range(&db, dr.hpos, dr.status, hap_ref_pos_dev, hap_aligned_dev, &dcg, x->ops_cap, st, lo, hi);
-        const RealignInputs in = {x->mode, dr.ll, dr.onHap, win_hap_pair_dev, hap_n_indels_dev, dr.hpos, dr.status, hap_ref_pos_dev, hap_aligned_dev};
+        const RealignInputs in = {x->mode, dr.ll, dr.onHap, x->diploid ? ddp.pair : win_hap_pair_dev, hap_n_indels_dev, dr.hpos, dr.status, hap_ref_pos_dev,
+                                  hap_aligned_dev};
         return launch_realign_range(&db, in, &drl, x->ops_cap, st, (int)lo, (int)hi);
     }
 
@@ -912,6 +938,23 @@ int dd_compute_likelihoods_realign(const dd_params *p, const dd_batch *b, dd_res
         return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign: every array of dd_realign_result is required");
     ExtraRequest x = {hap_ref_pos, hap_aligned, ops_cap, true};
     x.mode = mode; x.win_hap_pair = win_hap_pair; x.hap_n_indels = hap_n_indels; x.reads = *out;
+    return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device, options, &x);
+}
+int dd_compute_likelihoods_realign_diploid(const dd_params *p, const dd_batch *b, dd_result *r, const double *prior, const int32_t *hap_n_indels,
+                                           const int32_t *hap_ref_pos, const uint8_t *hap_aligned, const dd_diploid_pair_result *pair_out,
+                                           const dd_realign_result *realign_out, int ops_cap, int device, uint32_t options)
+{
+    if (options & ~DD_OPT_LONG_WINDOWS) return fail(DD_ERR_INVALID, "unknown option bits");
+    if (!prior || !hap_n_indels) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign_diploid: prior and hap_n_indels are required");
+    if (!hap_ref_pos) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign_diploid: hap_ref_pos is required (Haplotype::refHpos per haplotype base)");
+    if (ops_cap < 1) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign_diploid: ops_cap must be at least 1");
+    if (!pair_out || !pair_out->pair || !pair_out->state || !pair_out->best || !pair_out->gap || !pair_out->margin)
+        return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign_diploid: every array of dd_diploid_pair_result is required");
+    if (!realign_out || !realign_out->hap || !realign_out->status || !realign_out->n_ops || !realign_out->ops || !realign_out->ref_off)
+        return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign_diploid: every array of dd_realign_result is required");
+    ExtraRequest x = {hap_ref_pos, hap_aligned, ops_cap, true};
+    x.mode = DD_REALIGN_PAIR; x.hap_n_indels = hap_n_indels; x.reads = *realign_out;
+    x.diploid = true; x.prior = prior; x.pairs = *pair_out;
     return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device, options, &x);
 }
 int dd_compute_likelihoods_faster(const dd_params *p, const dd_batch *b, dd_result *r, int device)

@@ -29,7 +29,8 @@ class DeviceBatch:
     """A PackedBatch resident in HBM + the dd_device_batch that points at it."""
 
     def __init__(self, pb: PackedBatch, params: capi.dd_params, device="cuda:0", long_windows=False, long_windows_faster=False,
-                 cigars=False, ops_cap=capi.DD_CIGAR_DEFAULT_OPS_CAP, hap_ref_pos=None, hap_aligned=None, realign=False, hap_n_indels=None):
+                 cigars=False, ops_cap=capi.DD_CIGAR_DEFAULT_OPS_CAP, hap_ref_pos=None, hap_aligned=None, realign=False, hap_n_indels=None,
+                 diploid_prior=None):
         """long_windows: windows beyond the main kernels' limits (haplotypes up to 4,094 bp, reads up to 4,096 bp, and with maxLengthDel
         12..31 haplotypes over 574 bp) are computed by the long-window kernel after the main launch (dd_launch_device_long) instead of
         being marked DD_PAIR_UNSUPPORTED.  Off by default.
@@ -41,7 +42,10 @@ class DeviceBatch:
         (laid out like hap_seq); hap_aligned: one byte per haplotype, 0 = not aligned (None = all aligned).  Off by default.
         realign: launch_realign() chooses the haplotype each read is realigned to and computes that pair's CIGAR alone (dd_realign_device);
         results() also returns realign_hap, realign_status, realign_n_ops, realign_ops [n_reads, ops_cap] and realign_ref_off.  Needs
-        hap_ref_pos like cigars; hap_n_indels (Haplotype::countIndels per haplotype) is needed by the DD_REALIGN_PAIR rule only."""
+        hap_ref_pos like cigars; hap_n_indels (Haplotype::countIndels per haplotype) is needed by the DD_REALIGN_PAIR rule only.
+        diploid_prior: getHaplotypePrior per haplotype pair, H * H doubles per window (dd_pair_sum_offsets' layout): launch_diploid_pairs()
+        picks and certifies every window's MAP haplotype pair on the device (dd_diploid_pairs_device); its `pair` tensor can be handed to
+        launch_realign(DD_REALIGN_PAIR, ...) as it is, and diploid_pair_results() copies the per-window outputs back."""
         if long_windows and long_windows_faster:
             raise ValueError("long_windows and long_windows_faster screen the batch for different models: one resident batch, one screening")
         lib = capi.load()
@@ -165,6 +169,19 @@ class DeviceBatch:
             self.rl = {k: torch.zeros(nread * (self.ops_cap if k == "ops" else 1), dtype=torch.int32, device=self.device)
                        for k in capi.REALIGN_RESULT_FIELDS}                                                 # ops: uint32 bits
             self.drl = capi.dd_realign_result(*[self.rl[k].data_ptr() for k in capi.REALIGN_RESULT_FIELDS])
+        self.dip = None
+        if diploid_prior is not None:
+            hh = np.zeros(pb.n_windows + 1, np.int64)
+            hh[1:] = np.cumsum(np.diff(a["win_hap_off"]).astype(np.int64) ** 2)
+            pr = np.ascontiguousarray(diploid_prior, np.float64).reshape(-1)
+            if pr.shape != (int(hh[-1]),):
+                raise ValueError("diploid_prior must hold H * H entries per window")
+            t["win_hh_off"] = _to_dev(hh, self.device)
+            t["diploid_prior"] = _to_dev(pr, self.device)
+            nwin = max(pb.n_windows, 1)
+            self.dip = {k: torch.zeros(nwin * (2 if k == "pair" else 1), dtype=_TORCH_DT[np.dtype(capi.DIPLOID_PAIR_DTYPES[k])], device=self.device)
+                        for k in capi.DIPLOID_PAIR_FIELDS}
+            self.ddip = capi.dd_diploid_pair_result(*[self.dip[k].data_ptr() for k in capi.DIPLOID_PAIR_FIELDS])
         if self.cigars:
             npair = max(pb.n_pairs, 1)
             self.cig = {"n_ops": torch.zeros(npair, dtype=torch.int32, device=self.device),
@@ -229,7 +246,12 @@ class DeviceBatch:
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
         pairs = None
-        if win_hap_pair is not None:
+        if isinstance(win_hap_pair, torch.Tensor):             # already on the device (launch_diploid_pairs' `pair`): read where it is
+            if win_hap_pair.dtype != torch.int32 or win_hap_pair.device != self.device or win_hap_pair.numel() < 2 * self.pb.n_windows:
+                raise ValueError("a device win_hap_pair must be an int32 tensor on the batch's device with two entries per window")
+            self._win_hap_pair = win_hap_pair
+            pairs = win_hap_pair.data_ptr()
+        elif win_hap_pair is not None:
             whp = np.ascontiguousarray(win_hap_pair, np.int32).reshape(-1)
             if whp.shape != (2 * self.pb.n_windows,):
                 raise ValueError("win_hap_pair must hold two entries per window")
@@ -244,6 +266,29 @@ class DeviceBatch:
                                    C.c_void_p(stream.cuda_stream))
         if rc != 0:
             raise RuntimeError("dd_realign_device rc=%d: %s" % (rc, capi.last_error()))
+
+    def launch_diploid_pairs(self, stream=None):
+        """Every window's MAP haplotype pair, chosen and certified from the ll and status of the last launch() (same stream, behind it).
+        Asynchronous; returns the device tensors dict(pair [2 * n_windows], state, best, gap, margin)."""
+        if self.dip is None:
+            raise RuntimeError("this batch was built without diploid_prior")
+        lib = capi.load()
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        rc = lib.dd_diploid_pairs_device(C.byref(self.db), C.c_void_p(self.t["win_hh_off"].data_ptr()), C.c_void_p(self.out["ll"].data_ptr()),
+                                         C.c_void_p(self.out["status"].data_ptr()), C.c_void_p(self.t["diploid_prior"].data_ptr()),
+                                         C.byref(self.ddip), C.c_void_p(stream.cuda_stream))
+        if rc != 0:
+            raise RuntimeError("dd_diploid_pairs_device rc=%d: %s" % (rc, capi.last_error()))
+        return self.dip
+
+    def diploid_pair_results(self):
+        """Synchronise and copy back the outputs of the last launch_diploid_pairs(): dict(pair [n_windows, 2], state, best, gap, margin)."""
+        torch.cuda.synchronize(self.device)
+        n = self.pb.n_windows
+        res = {k: self.dip[k][:n * (2 if k == "pair" else 1)].cpu().numpy() for k in capi.DIPLOID_PAIR_FIELDS}
+        res["pair"] = res["pair"].reshape(n, 2)
+        return res
 
     def pooled_em(self, slots, a0=0.001, tol=1e-4, stream=None):
         """The pooled analysis' EM loop (dd_pooled_em_device) on the `ll` of the last launch() / launch_faster(), resident in HBM (same

@@ -230,7 +230,10 @@ struct BatchBlock {
     RawBuf<int32_t> rl_hap, rl_status, rl_n_ops, rl_ref_off;
     RawBuf<uint32_t> rl_ops;
     RawBuf<uint8_t> on_hap;                              // ... and the device's onHap, which its rule consults
-    BatchBlock() : W(0), faster(false), has_hpos(false), has_cigars(false), cig_cap(0), has_realign(false) {}
+    bool has_pairs;                                      // device pair (setDeviceRealignDiploid): per WINDOW; the realign rows are then the diploid rule's
+    RawBuf<int32_t> dp_pair, dp_state;
+    RawBuf<double> dp_best, dp_gap, dp_margin;
+    BatchBlock() : W(0), faster(false), has_hpos(false), has_cigars(false), cig_cap(0), has_realign(false), has_pairs(false) {}
 };
 
 struct PackScratch {
@@ -241,6 +244,8 @@ struct PackScratch {
     RawBuf<uint8_t> read_qidx;           // H2D copy then runs at link speed instead of through the driver's staging buffers
     std::vector<uint8_t> read_mqidx, read_flags, read_lib;
     std::vector<int32_t> read_mate_pos, read_mate_len;
+    std::vector<double> pair_prior;      // device pair: the jobs' prior tables, one after the other
+    std::vector<int32_t> hap_n_indels;   // ... and Haplotype::countIndels per haplotype
     std::vector<int32_t> hap_ref_pos;    // device CIGARs: Haplotype::refHpos per haplotype base
     std::vector<uint8_t> hap_aligned;    // ... and whether the haplotype has one
 };
@@ -384,10 +389,13 @@ int WindowLikelihoods::realignStatus(size_t r) const { return blk_->rl_status[si
 int WindowLikelihoods::realignNumOps(size_t r) const { return blk_->rl_n_ops[size_t(blk_->win_read_off[w_]) + r]; }
 const uint32_t *WindowLikelihoods::realignOps(size_t r) const { return blk_->rl_ops.p + (size_t(blk_->win_read_off[w_]) + r) * size_t(blk_->cig_cap); }
 int WindowLikelihoods::realignRefOff(size_t r) const { return blk_->rl_ref_off[size_t(blk_->win_read_off[w_]) + r]; }
+bool WindowLikelihoods::hasDevicePair() const { return blk_ && blk_->has_pairs; }
+int WindowLikelihoods::pairState() const { return blk_->dp_state[size_t(w_)]; }
+std::pair<int, int> WindowLikelihoods::devicePair() const { return std::pair<int, int>(blk_->dp_pair[2 * size_t(w_)], blk_->dp_pair[2 * size_t(w_) + 1]); }
 
 WindowLikelihoods WindowLikelihoods::handMadeRealign(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, int opsCap, const int32_t *hap,
                                                      const int32_t *status, const int32_t *nOps, const uint32_t *ops, const int32_t *refOff,
-                                                     const int16_t *hpos)
+                                                     const int16_t *hpos, const double *ll, int pairState, const int32_t *pair)
 {
     std::shared_ptr<BatchBlock> blk = std::make_shared<BatchBlock>();
     BatchBlock &B = *blk;
@@ -409,6 +417,13 @@ WindowLikelihoods WindowLikelihoods::handMadeRealign(const std::vector<Haplotype
     for (size_t p = 0; p < np; p++) {
         B.ll[p] = B.llOn[p] = B.llOff[p] = B.mLogBQ[p] = 0.0; B.offHap[p] = B.offHapHMQ[p] = 0; B.status[p] = DD_PAIR_OK;
         B.numIndels[p] = B.numMismatch[p] = B.nBQT[p] = B.nmmBQT[p] = B.nMMLeft[p] = B.nMMRight[p] = 0; B.firstBase[p] = B.lastBase[p] = -1;
+    }
+    if (ll) memcpy(B.ll.p, ll, H * Rn * sizeof(double));
+    if (pairState >= 0) {
+        B.has_pairs = true;
+        B.dp_pair.reserve(2); B.dp_state.reserve(1); B.dp_best.reserve(1); B.dp_gap.reserve(1); B.dp_margin.reserve(1);
+        B.dp_state[0] = pairState; B.dp_pair[0] = pair ? pair[0] : -1; B.dp_pair[1] = pair ? pair[1] : -1;
+        B.dp_best[0] = B.dp_gap[0] = B.dp_margin[0] = 0.0;
     }
     if (hpos) { B.hpos.reserve(H * SL + 1); memcpy(B.hpos.p, hpos, H * SL * sizeof(int16_t)); }
     if (hap) {
@@ -529,10 +544,11 @@ MLAlignment WindowLikelihoods::get(size_t h, size_t r) const
         if (!eng_) throw std::string("WindowLikelihoods::get: batch was run without alignments and the engine is gone");
         std::vector<WindowJob> one(1);
         one[0].haps = haps_; one[0].reads = reads_; one[0].leftPos = leftPos_; one[0].rightPos = leftPos_ + 1;
-        const bool keep = eng_->keepAlignments_, cig = eng_->deviceCigars_, rl = eng_->deviceRealign_;
-        eng_->keepAlignments_ = true; eng_->deviceCigars_ = false; eng_->deviceRealign_ = false;
-        try { eng_->runBatch(one, blk_->faster); } catch (...) { eng_->keepAlignments_ = keep; eng_->deviceCigars_ = cig; eng_->deviceRealign_ = rl; throw; }
-        eng_->keepAlignments_ = keep; eng_->deviceCigars_ = cig; eng_->deviceRealign_ = rl;
+        const bool keep = eng_->keepAlignments_, cig = eng_->deviceCigars_, rl = eng_->deviceRealign_, dip = eng_->deviceRealignDiploid_;
+        eng_->keepAlignments_ = true; eng_->deviceCigars_ = false; eng_->deviceRealign_ = false; eng_->deviceRealignDiploid_ = false;
+        try { eng_->runBatch(one, blk_->faster); }
+        catch (...) { eng_->keepAlignments_ = keep; eng_->deviceCigars_ = cig; eng_->deviceRealign_ = rl; eng_->deviceRealignDiploid_ = dip; throw; }
+        eng_->keepAlignments_ = keep; eng_->deviceCigars_ = cig; eng_->deviceRealign_ = rl; eng_->deviceRealignDiploid_ = dip;
         if (!one[0].error.empty()) throw one[0].error;
         full_ = one[0].result.blk_;
     }
@@ -620,7 +636,9 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
     for (int w = 0; w < W; w++) if (jobs[w].liks) any_eager = true;
     // device CIGARs: the pairs' CIGARs come back instead of their alignments (main model, lazy jobs only)
     // device realign: the reads' chosen haplotypes and CIGARs come back instead of either (main model, lazy jobs only)
-    B.has_realign = deviceRealign_ && !faster && !any_eager;
+    // device pair: the diploid step's realigned reads — the windows' pairs chosen and certified on the device, then the rows of device realign
+    B.has_pairs = deviceRealignDiploid_ && !faster && !any_eager;
+    B.has_realign = (deviceRealign_ || deviceRealignDiploid_) && !faster && !any_eager;
     B.has_cigars = deviceCigars_ && !faster && !any_eager && !B.has_realign;
     B.cig_cap = cigarOpsCap_;
     B.has_hpos = !B.has_cigars && !B.has_realign && (keepAlignments_ || any_eager);
@@ -701,6 +719,17 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
     S.read_flags.resize(n_reads + 1); S.hap_var.resize(2 * n_var + 1); S.hap_var_flank.resize(3 * n_var + 1);
     if (with_mates) { S.read_mate_pos.resize(n_reads + 1); S.read_mate_len.resize(n_reads + 1); }
     if (pack_ref_pos) { S.hap_ref_pos.resize(size_t(n_hap_bases) + 1); S.hap_aligned.resize(n_haps + 1); }
+    if (B.has_pairs) {                                   // the prior tables in window order (H * H per window, dd_pair_sum_offsets), the indel counts
+        S.pair_prior.clear(); S.hap_n_indels.resize(n_haps + 1);
+        for (int w = 0; w < W; w++) {
+            const WindowJob &J = jobs[w];
+            const size_t H = J.haps->size();
+            if (!J.pairPrior || J.pairPrior->size() != H * H) throw std::string("setDeviceRealignDiploid: a job without its H x H pair prior table");
+            S.pair_prior.insert(S.pair_prior.end(), J.pairPrior->begin(), J.pairPrior->end());
+            for (size_t h = 0; h < H; h++) S.hap_n_indels[size_t(B.win_hap_off[w]) + h] = int32_t((*J.haps)[h].countIndels());
+        }
+        S.pair_prior.push_back(0.0);
+    }
 
     const std::chrono::steady_clock::time_point t_pass1 = std::chrono::steady_clock::now();
     // ---- pass 2: the bytes, windows in parallel ----
@@ -825,9 +854,16 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
         const size_t nr = n_reads + 1;
         Rl.hap = B.rl_hap.reserve(nr); Rl.status = B.rl_status.reserve(nr); Rl.n_ops = B.rl_n_ops.reserve(nr); Rl.ref_off = B.rl_ref_off.reserve(nr);
         Rl.ops = B.rl_ops.reserve(nr * size_t(B.cig_cap));
-        Rz.onHap = B.on_hap.reserve(nr);                 // the pooled rule reads it on the device
+        if (!B.has_pairs) Rz.onHap = B.on_hap.reserve(nr);   // the pooled rule reads it on the device
     }
-    lastRealignBytes = B.has_realign ? n_reads * (16 + 4 * size_t(B.cig_cap)) : 0;
+    dd_diploid_pair_result Dp;
+    memset(&Dp, 0, sizeof(Dp));
+    if (B.has_pairs) {
+        const size_t nw = size_t(W) + 1;
+        Dp.pair = B.dp_pair.reserve(2 * nw); Dp.state = B.dp_state.reserve(nw); Dp.best = B.dp_best.reserve(nw); Dp.gap = B.dp_gap.reserve(nw);
+        Dp.margin = B.dp_margin.reserve(nw);
+    }
+    lastRealignBytes = (B.has_realign ? n_reads * (16 + 4 * size_t(B.cig_cap)) : 0) + (B.has_pairs ? size_t(W) * 36 : 0);
     lastHposBytes = B.has_hpos ? size_t(sz.hpos_len) * sizeof(int16_t) : 0;
     lastCigarBytes = B.has_cigars ? size_t(sz.n_pairs) * (12 + 4 * size_t(B.cig_cap)) : 0;
     dd_params P = to_abi(params);
@@ -836,7 +872,13 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
     if (getenv("DD_TIMING"))
         fprintf(stderr, "pack_timing: windows=%d pass1=%.2fms pass2+alloc=%.2fms\n", W, std::chrono::duration<double, std::milli>(t_pass1 - t_start).count(),
                 std::chrono::duration<double, std::milli>(t_packed - t_pass1).count());
-    if (B.has_realign) {                                 // (also without pairs: reads of windows without haplotypes are marked)
+    if (B.has_pairs) {                                   // (also without pairs: the windows' states and the reads' marks are still due)
+        typedef int (*Entry)(const dd_params *, const dd_batch *, dd_result *, const double *, const int32_t *, const int32_t *, const uint8_t *,
+                             const dd_diploid_pair_result *, const dd_realign_result *, int, int, uint32_t);
+        const int rc = reinterpret_cast<Entry>(diploidEntry_)(&P, &Bt, &Rz, S.pair_prior.data(), S.hap_n_indels.data(), S.hap_ref_pos.data(),
+                                                              S.hap_aligned.data(), &Dp, &Rl, B.cig_cap, device_, longWindows_ ? DD_OPT_LONG_WINDOWS : 0u);
+        if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_realign_diploid: ") + dd_last_error();
+    } else if (B.has_realign) {                          // (also without pairs: reads of windows without haplotypes are marked)
         const int rc = dd_compute_likelihoods_realign(&P, &Bt, &Rz, DD_REALIGN_FIRST_MAX, NULL, NULL, S.hap_ref_pos.data(), S.hap_aligned.data(), &Rl,
                                                       B.cig_cap, device_, longWindows_ ? DD_OPT_LONG_WINDOWS : 0u);
         if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_realign: ") + dd_last_error();

@@ -25,6 +25,7 @@
 #define DINDEL_COMPUTE_LIKELIHOODS_HPP
 #include <cstdint>
 #include <memory>
+#include <utility>
 #include <vector>
 #include "dindel_types.hpp"
 
@@ -102,11 +103,19 @@ public:
     int realignNumOps(size_t r) const;
     const uint32_t *realignOps(size_t r) const;
     int realignRefOff(size_t r) const;
+    // Device pair (LikelihoodEngine::setDeviceRealignDiploid): the window's MAP haplotype pair as the device chose and certified it
+    // (dd_diploid_pairs_device): pairState() is a DD_DIPPAIR_* of include/dindel_hmm.h, devicePair() the pair when the state is
+    // DD_DIPPAIR_CERTIFIED and (-1, -1) otherwise.  The realign rows above are then the diploid rule's (DD_REALIGN_PAIR) for that pair; the
+    // reads of a window that is not certified carry DD_REALIGN_BAD_PAIR.
+    bool hasDevicePair() const;
+    int pairState() const;
+    std::pair<int, int> devicePair() const;
     // A one-window view over hand-made realign rows (and, with hpos, hand-made per-base alignments for get(): one entry per (haplotype,
     // read base), haplotype-major).  For tests of the consumers of these views; `haps` and `reads` must outlive it.
     static WindowLikelihoods handMadeRealign(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, int opsCap, const int32_t *hap,
                                              const int32_t *status, const int32_t *nOps, const uint32_t *ops, const int32_t *refOff,
-                                             const int16_t *hpos);
+                                             const int16_t *hpos, const double *ll = NULL, int pairState = -1, const int32_t *pair = NULL);
+    // ... ll (may be NULL: all 0): the pairs' likelihoods, haplotype-major; pairState >= 0: the view also carries a device pair.
     // all records, as the eager path fills them
     void toLiks(std::vector<std::vector<MLAlignment> > &liks, std::vector<int> &onHap) const;
 
@@ -123,12 +132,13 @@ private:
 };
 
 struct WindowJob {                      // one call of the reference's computeLikelihoods
-    WindowJob() : haps(NULL), reads(NULL), leftPos(0), rightPos(0), liks(NULL), onHap(NULL) {}
+    WindowJob() : haps(NULL), reads(NULL), leftPos(0), rightPos(0), liks(NULL), onHap(NULL), pairPrior(NULL) {}
     const std::vector<Haplotype> *haps;
     const std::vector<Read> *reads;
     uint32_t leftPos, rightPos;
     std::vector<std::vector<MLAlignment> > *liks;   // OUT (eager); NULL = lazy: use `result`
     std::vector<int> *onHap;                        // OUT (eager); may be NULL
+    const std::vector<double> *pairPrior;           // setDeviceRealignDiploid: getHaplotypePrior(h1, h2) at [h1 * haps->size() + h2], h1 <= h2
     WindowLikelihoods result;                       // OUT: always set (unless the window has an error)
     std::string error;                              // OUT: empty, or the string the reference would have thrown
 };
@@ -185,6 +195,13 @@ public:
     // only: a batch with an eager job, and the --faster model, run as without it.  Default off.
     void setDeviceRealign(bool v, int opsCap = 8) { deviceRealign_ = v; if (v) cigarOpsCap_ = opsCap < 1 ? 1 : opsCap; }
     bool deviceRealign() const { return deviceRealign_; }
+    // true: computeLikelihoodsBatch asks for the diploid step's realigned reads (dd_compute_likelihoods_realign_diploid): the device picks and
+    // certifies every window's MAP haplotype pair from WindowJob::pairPrior (required on every job), then each read's haplotype by the diploid
+    // rule; the views expose pairState(), devicePair() and the rows of hasDeviceRealign().  Wins over setDeviceRealign and setDeviceCigars.
+    // Main model, lazy jobs only, like them.  Default off.
+    // (Defined in device_pair.cpp, which binds the C ABI's entry: a program that stubs the C ABI without that entry and never sets this links.)
+    void setDeviceRealignDiploid(bool v, int opsCap = 8);
+    bool deviceRealignDiploid() const { return deviceRealignDiploid_; }
     // optional: have the calling thread's device cache (arena, staging mirror, streams) of this engine's device made now, for batches of
     // about `pairs` (haplotype, read) pairs — e.g. while the first batch is still being prepared.  Throws like the batch calls.
     void warmUp(size_t pairs);
@@ -216,6 +233,8 @@ private:
     bool longWindowsFaster_ = false;
     bool deviceCigars_ = false;
     bool deviceRealign_ = false;
+    bool deviceRealignDiploid_ = false;
+    void (*diploidEntry_)() = nullptr;   // dd_compute_likelihoods_realign_diploid, once setDeviceRealignDiploid has been called
     int cigarOpsCap_ = 8;
     std::vector<std::shared_ptr<BatchBlock> > spare_;   // result blocks of earlier calls; one nobody references any more is reused (warm pages)
     unsigned spareNext_ = 0;

@@ -54,6 +54,14 @@
 //                     with --deviceCigars.  The files are the same byte for byte.  Refused with --doDiploid (the files that stay are then the
 //                     diploid step's, whose haplotype pair the host computes after the batch has left the device) and with --faster; no
 //                     effect without --outputRealignedBAM.  Wins over --deviceCigars
+//   [--deviceRealignDiploid [--cigarOpsCap N]]  with --doDiploid --outputRealignedBAM: the diploid step's realigned reads from the device.  A kernel picks
+//                     every window's MAP haplotype pair (maxLikelihoodPair's argmax) from the likelihoods in HBM and the prior table the prepare stage
+//                     made, and certifies it: its sums are in another arithmetic than the host's, with a proven bound on the difference, so the pair is
+//                     the host's whenever the best value leads the runner-up by more than the bound.  The realign launch follows on the same stream; one
+//                     CIGAR per read comes back.  Windows that are not certified (ties, non-finite terms) are done on the host as without the switch and
+//                     counted (pair_uncertified=).  The files are the same byte for byte.  Refused with --faster, without --doDiploid and together with
+//                     --deviceRealign; no effect without --outputRealignedBAM; wins over --deviceCigars.  --checkDevicePair (tests): the reduce stage also
+//                     runs maxLikelihoodPair on every certified window; pair_disagreements= must be 0 or the run fails
 //   [--discover]      no --varFile: the run starts with the discovery stage (host/discover.hpp) on --devices[0] — candidate indels from the CIGARs
 //                     of --bamFile (or, with --tid NAME --region A-B, of every file of --bamFiles), each realigned on the device, to
 //                     PREFIX.variants.txt and PREFIX.libraries.txt exactly as `dindel_candidates --analysis getCIGARindels` writes them
@@ -106,6 +114,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <limits>
 #include <set>
 #include <sstream>
 #include <thread>
@@ -139,11 +148,15 @@ struct WindowTask {
     bool passedOver;                     // --ref: getHaplotypes returned true (DInDel.cpp:1569 / :1581): no likelihoods, no line, not a skipped window
     bool lateSkip;                       // skipped by the likelihood or genotyping step, i.e. after read selection (DInDel.cpp:1369-1408)
     std::string lines;                   // what the reduce stage wrote for this window
+    std::vector<double> pairPrior;       // --deviceRealignDiploid: getHaplotypePrior per haplotype pair (prepare stage), what the device's pair choice adds
+    bool havePairPrior = false;
+    long pairUncertified = 0, pairFallbackReads = 0, pairDisagreements = 0;   // ... of this window's last reduce step; the writer adds up what it writes
     bool computes() const { return !skipped && !passedOver; }    // the window reaches the likelihood step
     WindowJob job() const                // the window as the likelihood step takes it
     {
         WindowJob J;
         J.haps = haps; J.reads = &reads; J.leftPos = leftPos; J.rightPos = rightPos;
+        if (havePairPrior) J.pairPrior = &pairPrior;
         return J;
     }
 };
@@ -181,7 +194,7 @@ struct Options {
     long computeAhead;
     std::vector<int> devices;            // --devices 0,1,...: the engines are dealt out over these GPUs (batches are independent: no exchange between devices)
     bool faster, oneBased, prepareOnly, quiet, timing, longWindows, longWindowsFaster, noLookBack, lateSkipsKnown, windowByWindow;
-    bool realignedBAM, deviceCigars, deviceRealign;
+    bool realignedBAM, deviceCigars, deviceRealign, deviceRealignDiploid, checkDevicePair;
     bool doPooled, doDiploid, hostEM;    // --doPooled: the pooled lines; the diploid lines too with --doDiploid, or when --doPooled is not given
     PooledParameters pool;               // --bayesa0, --bayesType
     bool keepAlignments;                 // the per-base alignments come back from the device (--faster; --outputRealignedBAM without --deviceCigars)
@@ -232,6 +245,11 @@ const char *const kHelp =
     "            [--deviceRealign]  with --doPooled --outputRealignedBAM: the device also picks each read's haplotype (pooled rule) and brings back that\n"
     "                             pair's CIGAR alone (same files; [--cigarOpsCap N] as above); refused with --doDiploid and with --faster; no effect\n"
     "                             without --outputRealignedBAM\n"
+    "            [--deviceRealignDiploid]  with --doDiploid --outputRealignedBAM: the device picks and certifies every window's most likely haplotype\n"
+    "                             pair, then each read's haplotype by the diploid rule, and brings back that pair's CIGAR alone (same files;\n"
+    "                             [--cigarOpsCap N] as above); windows it cannot certify (ties, non-finite terms) are done on the host; refused with\n"
+    "                             --faster, without --doDiploid and with --deviceRealign; no effect without --outputRealignedBAM; wins over\n"
+    "                             --deviceCigars.  [--checkDevicePair] also choose every certified window's pair on the host and fail on a difference\n"
     "            [--longWindows]  compute windows with a haplotype > 766 bp or a read > 1024 bp (up to 4,094 / 4,096; with --maxLengthIndel >= 12\n"
     "                             also haplotypes > 574 bp) instead of skipping them; main model only: no effect with --faster\n"
     "            [--longWindowsFaster]  with --faster: compute windows with a haplotype > 766 bp or a read > 1024 bp (up to 4,094 / 4,096) instead of\n"
@@ -243,7 +261,7 @@ const char *const kHelp =
     "  files:    --varFile: the reference's window file; --hapFile: W / H / V / A records (host/window_io.hpp)\n";
 // the options without a value; any other --NAME takes the next argument as its value, whatever its name
 const char *const kFlags[] = {"varFileIsOneBased", "faster", "filterHaplotypes", "quiet", "doDiploid", "timing", "outputRealignedBAM", "prepareOnly", "noLookBack",
-                              "lateSkipsKnown", "windowByWindow", "doPooled", "hostEM", "longWindows", "longWindowsFaster", "deviceCigars", "deviceRealign", "changeINStoN", "hostDistribution", "hostConvert", "discover", "useLibraries", "vcfCandidatesOnly"};
+                              "lateSkipsKnown", "windowByWindow", "doPooled", "hostEM", "longWindows", "longWindowsFaster", "deviceCigars", "deviceRealign", "deviceRealignDiploid", "checkDevicePair", "changeINStoN", "hostDistribution", "hostConvert", "discover", "useLibraries", "vcfCandidatesOnly"};
 
 std::vector<int> commaInts(const std::string &list)      // "3,5,,8" -> 3 5 8
 {
@@ -278,6 +296,9 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     exitCode = 1;
     if (has("deviceRealign") && has("doDiploid")) { std::cerr << "--deviceRealign cannot be given with --doDiploid: the realigned BAMs that stay are then the diploid step's, whose haplotype pair is computed on the host\n"; return false; }
     if (has("deviceRealign") && has("faster")) { std::cerr << "--deviceRealign cannot be given with --faster: realigned BAMs are written by the main model only\n"; return false; }
+    if (has("deviceRealignDiploid") && has("faster")) { std::cerr << "--deviceRealignDiploid cannot be given with --faster: realigned BAMs are written by the main model only\n"; return false; }
+    if (has("deviceRealignDiploid") && has("deviceRealign")) { std::cerr << "--deviceRealignDiploid cannot be given with --deviceRealign: one realigns by the diploid step's rule, the other by the pooled analysis'\n"; return false; }
+    if (has("deviceRealignDiploid") && !has("doDiploid")) { std::cerr << "--deviceRealignDiploid needs --doDiploid: it realigns by the diploid step's rule\n"; return false; }
     o.discover = has("discover");
     for (const char *need : {"varFile", "outputFile"})
         if (!has(need) && !(o.discover && !strcmp(need, "varFile"))) { std::cerr << "Please specify --" << need << "\n"; return false; }
@@ -336,6 +357,9 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     if (has("deviceRealign") && o.realignedBAM && !o.doPooled) { std::cerr << "--deviceRealign needs --doPooled: it realigns by the pooled analysis' rule\n"; return false; }
     o.deviceRealign = o.realignedBAM && has("deviceRealign");                     // modifies --doPooled --outputRealignedBAM only
     if (o.deviceRealign) o.deviceCigars = false;
+    o.deviceRealignDiploid = o.realignedBAM && has("deviceRealignDiploid");       // modifies --doDiploid --outputRealignedBAM only
+    o.checkDevicePair = o.deviceRealignDiploid && has("checkDevicePair");
+    if (o.deviceRealignDiploid) o.deviceCigars = false;
     o.pool.a0 = num("bayesa0", o.pool.a0);
     if (has("bayesType")) o.pool.bayesType = opt["bayesType"];
     if (o.doPooled && !knownBayesType(o.pool.bayesType)) { std::cerr << "Unknown EM option" << std::endl; return false; }          // DInDel.cpp:2287-2288
@@ -353,7 +377,7 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
         if (has("pooledGlf")) o.pooledGlfFile = opt["pooledGlf"];
         try { o.pooledVcf.numSamples = int(pytext::pyInt(opt["numSamples"])); } catch (const std::string &e) { std::cerr << "--numSamples: " << e << "\n"; return false; }
     }
-    o.keepAlignments = o.faster || (o.realignedBAM && !o.deviceCigars && !o.deviceRealign);           // (the --faster model's indel count, DInDel.cpp:3529, needs hpos)
+    o.keepAlignments = o.faster || (o.realignedBAM && !o.deviceCigars && !o.deviceRealign && !o.deviceRealignDiploid);           // (the --faster model's indel count, DInDel.cpp:3529, needs hpos)
     o.cigarOpsCap = std::max(1, int(num("cigarOpsCap", 8)));
     ObservationModelParameters &obs = o.obs;
     obs.setCLIDefaultValues();
@@ -419,6 +443,7 @@ public:
     const std::vector<std::string> &bamPaths() const { return opt.bamPaths; }   // the run's BAM files (--bamFile, or the files of --bamFiles)
 private:
     void prepareWindow(ReadFetcher &fetcher, WindowTask &T);
+    void fillPairPrior(WindowTask &T) const;
     void buildHaplotypes(const std::vector<WindowTask *> &tasks, IndexedFasta &fasta, int device);
     void prepareWorker(int pt);
     void computeWorker(int ct);
@@ -478,7 +503,8 @@ private:
         std::atomic<long> launches;            // engine calls with at least one job
         std::atomic<long> cigarFallbacks;      // reads redone with getCIGAR on the host (--deviceCigars)
         std::atomic<long long> hposBytes, cigarBytes, fallbackHposBytes;   // what the engines brought back from the device
-        std::atomic<long long> realignBytes;   // ... of the realigned reads' arrays (--deviceRealign)
+        std::atomic<long long> realignBytes;   // ... of the realigned reads' arrays (--deviceRealign, --deviceRealignDiploid)
+        std::atomic<long> pairUncertified{0}, pairFallbackReads{0}, pairDisagreements{0};   // --deviceRealignDiploid, of the windows written: done on the host, reads redone there, --checkDevicePair
         long windows, skipped, rePrepared;     // the writer's
         std::vector<std::pair<double, long> > progress;   // the writer's: (seconds since start, windows written) after every batch
     } n;
@@ -557,6 +583,7 @@ void WindowLoop::configureStageEngine(LikelihoodEngine &engine) const
     engine.setKeepAlignments(opt.keepAlignments);
     engine.setDeviceCigars(opt.deviceCigars, opt.cigarOpsCap);
     engine.setDeviceRealign(opt.deviceRealign, opt.cigarOpsCap);
+    engine.setDeviceRealignDiploid(opt.deviceRealignDiploid, opt.cigarOpsCap);
     engine.setLongWindows(opt.longWindows);
     engine.setLongWindowsFaster(opt.longWindowsFaster);
 }
@@ -577,6 +604,22 @@ WindowLikelihoods WindowLoop::recomputeWithAlignments(const WindowTask &T)
     n.fallbackHposBytes += (long long)fallbackEngine->lastHposBytes;
     if (!one[0].error.empty()) throw std::string(one[0].error);
     return one[0].result;
+}
+
+// ---- --deviceRealignDiploid: the window's prior table, getHaplotypePrior per pair h1 <= h2 (it depends on the haplotypes and the candidates alone).
+//      A prior that throws leaves NaN: the device then leaves the window to the host, whose maxLikelihoodPair throws the same string where it did. ----
+void WindowLoop::fillPairPrior(WindowTask &T) const
+{
+    T.havePairPrior = false;
+    if (!opt.deviceRealignDiploid || !T.computes() || !T.haps) return;
+    const size_t H = T.haps->size();
+    T.pairPrior.assign(H * H, 0.0);
+    for (size_t h1 = 0; h1 < H; h1++)
+        for (size_t h2 = h1; h2 < H; h2++) {
+            try { T.pairPrior[h1 * H + h2] = getHaplotypePrior((*T.haps)[h1], (*T.haps)[h2], int(T.leftPos), T.candidates, opt.dip); }
+            catch (std::string &) { T.pairPrior[h1 * H + h2] = std::numeric_limits<double>::quiet_NaN(); }
+        }
+    T.havePairPrior = true;
 }
 
 // ---- one window's read selection and haplotypes (the prepare workers; the writer's re-preparation behind a late skip) ----
@@ -727,6 +770,7 @@ void WindowLoop::prepareWorker(int pt)
                 for (size_t i = 0; i < b->tasks.size(); i++) all.push_back(&b->tasks[i]);
                 buildHaplotypes(all, *fasta, opt.devices[size_t(pt) % opt.devices.size()]);
             }
+            for (size_t i = 0; i < b->tasks.size(); i++) fillPairPrior(b->tasks[i]);
             n.prepareOf[size_t(pt)] += seconds_since(t0);
             const long seq = b->seq;
             if (!toCompute.push(seq, b)) break;
@@ -828,6 +872,7 @@ void WindowLoop::reduceWindow(WindowTask &T, const WindowJob *J, PooledJob *P)
     std::ostringstream os;
     OutputData local = glfData;
     local.out = &os;
+    T.pairUncertified = T.pairFallbackReads = T.pairDisagreements = 0;
     if (T.computes()) {
         try {
             if (opt.injectedLateSkips.count(T.index)) throw std::string("hapSize error.");       // tests (--injectLateSkip)
@@ -858,10 +903,19 @@ void WindowLoop::reduceWindow(WindowTask &T, const WindowJob *J, PooledJob *P)
                 }
                 if (opt.doDiploid) diploidGLF(*T.haps, T.reads, J->result, T.pos, T.leftPos, T.rightPos, local, T.index, T.tid, T.candidates, opt.dip, "dip");
                 if (opt.realignedBAM && opt.doDiploid) {                     // DInDel.cpp:589-620
-                    const std::pair<int, int> best = maxLikelihoodPair(*T.haps, T.reads, J->result, int(T.leftPos), T.candidates, opt.dip);
                     std::vector<CIGAR> cigars;
                     long fallbacks = 0;
-                    realignedCigars(*T.haps, T.reads, J->result, best, int(T.leftPos), cigars, [&]() { return recomputeWithAlignments(T); }, &fallbacks);
+                    if (J->result.hasDevicePair()) {                         // --deviceRealignDiploid: a certified window's pair and rows are the device's
+                        long uncertified = 0;
+                        const std::pair<int, int> used = diploidDeviceRealignedCigars(*T.haps, T.reads, J->result, int(T.leftPos), T.candidates, opt.dip, int(T.leftPos),
+                                                                                     cigars, [&]() { return recomputeWithAlignments(T); }, &fallbacks, &uncertified);
+                        T.pairUncertified = uncertified; T.pairFallbackReads = fallbacks;
+                        if (opt.checkDevicePair && !uncertified &&
+                            maxLikelihoodPair(*T.haps, T.reads, J->result, int(T.leftPos), T.candidates, opt.dip) != used) T.pairDisagreements = 1;
+                    } else {
+                        const std::pair<int, int> best = maxLikelihoodPair(*T.haps, T.reads, J->result, int(T.leftPos), T.candidates, opt.dip);
+                        realignedCigars(*T.haps, T.reads, J->result, best, int(T.leftPos), cigars, [&]() { return recomputeWithAlignments(T); }, &fallbacks);
+                    }
                     n.cigarFallbacks += fallbacks;
                     std::vector<int> onHap(T.reads.size());
                     for (size_t r = 0; r < onHap.size(); r++) onHap[r] = J->result.onHap(r);
@@ -916,12 +970,13 @@ void WindowLoop::rePrepare(WindowTask &T)
         redo.fetcher.reset(new ReadFetcher(redo.bams.pointers(), libraries, opt.rsp));
     }
     if (redo.first) { redo.fetcher->newChromosome(); redo.reach = uint64_t(T.fileRightPos) + bufferSpan; redo.first = false; }   // the reset of DInDel.cpp:1404-1405
-    T.skipped = false; T.lateSkip = false; T.passedOver = false; T.message = "ok"; T.note.clear(); T.haps = NULL;
+    T.skipped = false; T.lateSkip = false; T.passedOver = false; T.message = "ok"; T.note.clear(); T.haps = NULL; T.havePairPrior = false;
     prepareWindow(*redo.fetcher, T);
     if (refMode && !opt.prepareOnly) {
         if (!redo.fasta) redo.fasta.reset(new IndexedFasta(opt.refFile));
         buildHaplotypes(std::vector<WindowTask *>(1, &T), *redo.fasta, opt.devices[0]);
     }
+    fillPairPrior(T);
     std::vector<WindowJob> one;
     if (T.computes() && !opt.prepareOnly) {
         if (!redo.engine) {
@@ -959,6 +1014,7 @@ void WindowLoop::writeBatch(Batch &B)
             n.skipped++;
         }
         glfOutput << T.lines;
+        n.pairUncertified += T.pairUncertified; n.pairFallbackReads += T.pairFallbackReads; n.pairDisagreements += T.pairDisagreements;   // of the lines written: a window re-done counts once
         n.windows++;
     }
     glfOutput.flush();
@@ -1038,7 +1094,7 @@ int WindowLoop::readWindowFile()                          // 1: the file is not 
         T.lines.clear();
         T.candidates = cand; T.tid = cand.tid; T.pos = uint32_t(cand.centerPos);
         T.fileLeftPos = T.leftPos = uint32_t(cand.leftPos); T.fileRightPos = T.rightPos = uint32_t(cand.rightPos);
-        T.haps = NULL; T.skipped = false; T.lateSkip = false; T.passedOver = false; T.message = "ok"; T.note.clear();
+        T.haps = NULL; T.skipped = false; T.lateSkip = false; T.passedOver = false; T.message = "ok"; T.note.clear(); T.havePairPrior = false;
         T.index = ++index;
         if (pooled) {
             Batch::Before W = { T.tid, T.fileLeftPos, T.fileRightPos, T.index };
@@ -1075,6 +1131,10 @@ int WindowLoop::run()
     if (!opt.quiet) std::cout << "windows: " << n.windows << " skipped: " << n.skipped << " -> " << glfFile << std::endl;
     if (!opt.quiet && n.rePrepared) std::cout << "re-prepared behind late skips: " << n.rePrepared << " windows" << std::endl;
     if (opt.timing) report();
+    if (opt.checkDevicePair && n.pairDisagreements.load() != 0) {            // --checkDevicePair: a certified pair that is not the host's fails the run
+        std::cerr << "--checkDevicePair: " << n.pairDisagreements.load() << " certified windows whose haplotype pair the host chooses differently" << std::endl;
+        return 3;
+    }
     return 0;
 }
 
@@ -1103,7 +1163,9 @@ void WindowLoop::report()                                 // --timing: one line;
     // and the alignment bytes those windows' recomputation brought back
     std::cout << " hpos_bytes=" << n.hposBytes.load() << " cigar_bytes=" << n.cigarBytes.load() << " cigar_host_fallbacks=" << n.cigarFallbacks.load()
               << " fallback_hpos_bytes=" << n.fallbackHposBytes.load();
-    if (opt.deviceRealign) std::cout << " realign_bytes=" << n.realignBytes.load();
+    if (opt.deviceRealign || opt.deviceRealignDiploid) std::cout << " realign_bytes=" << n.realignBytes.load();
+    if (opt.deviceRealignDiploid) std::cout << " pair_uncertified=" << n.pairUncertified.load() << " pair_fallback_reads=" << n.pairFallbackReads.load();
+    if (opt.checkDevicePair) std::cout << " pair_disagreements=" << n.pairDisagreements.load();
     // when the first batch and the first 1 / 5 / 20 / 50 / 100 % of the windows were written (seconds since start)
     std::cout << " engines_ready_at=";
     for (size_t i = 0; i < n.readyAt.size(); i++) std::cout << (i ? "," : "") << n.readyAt[i];

@@ -10,6 +10,7 @@
 #include "compute_likelihoods.hpp"
 #include "genotype.hpp"
 #include "cigar.hpp"
+#include "realigned_bam.hpp"
 
 using namespace dindel;
 
@@ -208,6 +209,22 @@ int ddh_aligned_variant(const char *str, int startHap, int endHap, int startRead
 }
 
 double ddh_add_logs(double l1, double l2) { return addLogs(l1, l2); }
+
+// maxLikelihoodPair's sums and argmax on a flat window: ll [nh * nr] (liks[h][r] order), prior [nh * nh].  pair_out[2]; values_out (may be
+// NULL) [nh * nh]: every pair's likelihood with prior.  Returns 0, or -1 on its throw (no pair with a finite likelihood).
+int ddh_max_likelihood_pair(int nh, int nr, const double *ll, const double *prior, int *pair_out, double *values_out)
+{
+    try {
+        std::vector<double> values;
+        const std::pair<int, int> best = maxLikelihoodPairOf(size_t(nh), size_t(nr), [&](size_t h, size_t r) { return ll[h * size_t(nr) + r]; },
+                                                             [&](size_t hp, size_t hm) { return prior[hp * size_t(nh) + hm]; }, values_out ? &values : NULL);
+        pair_out[0] = best.first; pair_out[1] = best.second;
+        if (values_out) for (size_t i = 0; i < values.size(); i++) values_out[i] = values[i];
+        return 0;
+    } catch (std::string &) {
+        return -1;
+    }
+}
 
 // N4: getCIGAR.  out_ops receives (op, len) pairs; returns the number of operations, or -(1+k) for the k-th throw string of
 // {"Haplotype has not been aligned!", "Read is not properly aligned!", "Error(1)!", "Error(2)!", "Error(3)!", "Error(4)!", "How is this possible? (1)"}

@@ -156,3 +156,41 @@ extern "C" int ddh_pooled_device_realigned_cigars(int H, int R, int readLen, int
         return -1;
     }
 }
+
+// diploidDeviceRealignedCigars on a hand-made view with a device pair: the window of ddh_pooled_device_realigned_cigars, with the pairs'
+// likelihoods ll [H * R] (haplotype-major), the device's state of the window (a DD_DIPPAIR_*) and its pair [2].  The haplotypes carry no variant
+// and there is no candidate, so every pair has the same prior: an uncertified window's pair is maxLikelihoodPair's on ll alone.  Out besides
+// the reads' CIGARs: *fallbacks (reads redone on the host), *uncertified (0 or 1), usedPair [2].  Returns 0, or -1 with the thrown string in err.
+extern "C" int ddh_diploid_device_realigned_cigars(int H, int R, int readLen, int hapLen, int opsCap, int pairState, const int32_t *pair, const double *ll,
+                                                   const int32_t *hap, const int32_t *status, const int32_t *nOps, const uint32_t *ops, const int32_t *refOff,
+                                                   const int16_t *hpos, int refSeqPos, int *numOps, int *refPos, uint32_t *opsOut, int maxOps, long *fallbacks,
+                                                   long *uncertified, int *usedPair, char *err, int errLen)
+{
+    try {
+        std::vector<Haplotype> haps;
+        for (int h = 0; h < H; h++) {
+            haps.push_back(Haplotype(std::string(size_t(hapLen), 'A')));
+            for (int i = 0; i < hapLen; i++) haps.back().refHpos.push_back(10 * h + i);
+        }
+        std::vector<Read> reads;
+        reads.resize(size_t(R));
+        for (int r = 0; r < R; r++) { reads[size_t(r)].seq = Haplotype(std::string(size_t(readLen), 'A')); reads[size_t(r)].setAllQual(0.99); }
+        const WindowLikelihoods view = WindowLikelihoods::handMadeRealign(haps, reads, opsCap, hap, status, nOps, ops, refOff, NULL, ll, pairState, pair);
+        std::function<WindowLikelihoods()> withAlignments;
+        if (hpos) withAlignments = [&]() { return WindowLikelihoods::handMadeRealign(haps, reads, opsCap, NULL, NULL, NULL, NULL, NULL, hpos, ll); };
+        std::vector<CIGAR> cigars;
+        *fallbacks = 0; *uncertified = 0;
+        const std::pair<int, int> used = diploidDeviceRealignedCigars(haps, reads, view, 0, AlignedCandidates(), DiploidParameters(), refSeqPos, cigars,
+                                                                     withAlignments, fallbacks, uncertified);
+        usedPair[0] = used.first; usedPair[1] = used.second;
+        for (int r = 0; r < R; r++) {
+            const CIGAR &c = cigars[size_t(r)];
+            numOps[r] = int(c.size()); refPos[r] = c.refPos;
+            for (int i = 0; i < maxOps; i++) opsOut[r * maxOps + i] = size_t(i) < c.size() ? (uint32_t(c[size_t(i)].second) << 4) | uint32_t(c[size_t(i)].first) : 0u;
+        }
+        return 0;
+    } catch (const std::string &e) {
+        if (err && errLen > 0) { strncpy(err, e.c_str(), size_t(errLen) - 1); err[errLen - 1] = 0; }
+        return -1;
+    }
+}

@@ -12,17 +12,18 @@ struct PairLik { double ll; int h1, h2; };
 bool byLikDescending(const PairLik &a, const PairLik &b) { return a.ll > b.ll; }             // :3826-3831
 }
 
-std::pair<int, int> maxLikelihoodPair(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks,
-                                      int leftPos, const AlignedCandidates &candidateVariants, const DiploidParameters &params)
+std::pair<int, int> maxLikelihoodPairOf(size_t lh, size_t numReads, const std::function<double(size_t, size_t)> &ll,
+                                        const std::function<double(size_t, size_t)> &prior, std::vector<double> *values)
 {
     std::vector<PairLik> likPairs;                                                           // :3767-3824 (the counters of HapPairLik are not read here)
-    const size_t lh = haps.size();
+    if (values) values->assign(lh * lh, 0.0);
     for (size_t hp = 0; hp < lh; hp++) for (size_t hm = hp; hm < lh; hm++) {
-        double ll = 0.0;
-        for (size_t r = 0; r < reads.size(); r++) ll += (addLogs(liks.ll(hp, r), liks.ll(hm, r)) + log(.5));
-        ll += getHaplotypePrior(haps[hp], haps[hm], leftPos, candidateVariants, params);     // usePrior = true at :591
-        PairLik p = { ll, int(hp), int(hm) };
+        double l = 0.0;
+        for (size_t r = 0; r < numReads; r++) l += (addLogs(ll(hp, r), ll(hm, r)) + log(.5));
+        l += prior(hp, hm);                                                                  // usePrior = true at :591
+        PairLik p = { l, int(hp), int(hm) };
         likPairs.push_back(p);
+        if (values) (*values)[hp * lh + hm] = l;
     }
     // the reference sorts its HapPairLik records with std::sort and this comparator; the order of equal likelihoods is the
     // algorithm's, which depends on the comparisons alone — the same here
@@ -32,6 +33,13 @@ std::pair<int, int> maxLikelihoodPair(const std::vector<Haplotype> &haps, const 
     for (size_t idx = 0; idx < likPairs.size(); idx++) if (likPairs[idx].ll > maxll) { maxll = likPairs[idx].ll; midx = idx; }
     if (midx == likPairs.size()) throw std::string("no haplotype pair with a finite likelihood");   // the reference reads an uninitialised index
     return std::pair<int, int>(likPairs[midx].h1, likPairs[midx].h2);
+}
+
+std::pair<int, int> maxLikelihoodPair(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks,
+                                      int leftPos, const AlignedCandidates &candidateVariants, const DiploidParameters &params)
+{
+    return maxLikelihoodPairOf(haps.size(), reads.size(), [&](size_t h, size_t r) { return liks.ll(h, r); },
+                               [&](size_t hp, size_t hm) { return getHaplotypePrior(haps[hp], haps[hm], leftPos, candidateVariants, params); }, NULL);
 }
 
 void realignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, std::pair<int, int> pair,
@@ -151,6 +159,33 @@ void pooledDeviceRealignedCigars(const std::vector<Haplotype> &haps, const std::
         const DeviceCigarRow row = {st, liks.realignNumOps(r), liks.realignOps(r), liks.realignRefOff(r)};
         cigars[r] = cigarOfRow(row, haps, reads, size_t(h), r, refSeqPos, full, withAlignments, hostFallbacks);   // :511
     }
+}
+
+std::pair<int, int> diploidDeviceRealignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, int leftPos,
+                                                 const AlignedCandidates &candidateVariants, const DiploidParameters &params, int refSeqPos,
+                                                 std::vector<CIGAR> &cigars, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks,
+                                                 long *uncertifiedWindows)
+{
+    if (!liks.hasDevicePair() || !liks.hasDeviceRealign()) throw std::string("diploidDeviceRealignedCigars: the batch was run without the device pair");
+    if (liks.pairState() != DD_DIPPAIR_CERTIFIED) {                                          // the host's window, as without the switch (:589-611)
+        if (uncertifiedWindows) ++*uncertifiedWindows;
+        const std::pair<int, int> best = maxLikelihoodPair(haps, reads, liks, leftPos, candidateVariants, params);
+        if (!withAlignments) throw std::string("diploidDeviceRealignedCigars: a window needs the host's CIGARs and no alignments are at hand");
+        const WindowLikelihoods full = withAlignments();
+        realignedCigars(haps, reads, full, best, refSeqPos, cigars);
+        return best;
+    }
+    const std::pair<int, int> pair = liks.devicePair();
+    cigars.assign(reads.size(), CIGAR());
+    WindowLikelihoods full;
+    for (size_t r = 0; r < reads.size(); r++) {                                              // reads in order: a throw is the first read's that throws
+        const int st = liks.realignStatus(r), h = liks.realignHap(r);
+        if (h < 0 || (h != pair.first && h != pair.second) || size_t(h) >= haps.size())
+            throw std::string("diploidDeviceRealignedCigars: a read of a certified window has no haplotype of its pair");
+        const DeviceCigarRow row = {st, liks.realignNumOps(r), liks.realignOps(r), liks.realignRefOff(r)};
+        cigars[r] = cigarOfRow(row, haps, reads, size_t(h), r, refSeqPos, full, withAlignments, hostFallbacks);
+    }
+    return pair;
 }
 
 std::string realignedBAMFileName(const std::string &prefix, int index, const std::string &tid, uint32_t leftPos, uint32_t rightPos, int minReadOverlap)

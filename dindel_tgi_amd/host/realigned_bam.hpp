@@ -19,6 +19,10 @@ namespace dindel {
 // All pairs take part: filterHaplotypes plays no role here.  Throws std::string if no pair has a finite likelihood.
 std::pair<int, int> maxLikelihoodPair(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks,
                                       int leftPos, const AlignedCandidates &candidateVariants, const DiploidParameters &params);
+// Its sums and argmax over lh haplotypes and numReads reads, with the likelihoods and the pair priors as functions (maxLikelihoodPair hands
+// over the window's and getHaplotypePrior).  values (may be NULL): every pair's likelihood with prior at [hp * lh + hm], hp <= hm.
+std::pair<int, int> maxLikelihoodPairOf(size_t lh, size_t numReads, const std::function<double(size_t, size_t)> &ll,
+                                        const std::function<double(size_t, size_t)> &prior, std::vector<double> *values);
 
 // One CIGAR per read against haplotype h1 or h2 of the pair, whichever explains the read better (within 1e-8: the one with fewer
 // indels, h2 on a tie) — DInDel.cpp:596-611.  Needs Haplotype::refHpos and the reads' alignments (a batch run with alignments).
@@ -53,6 +57,15 @@ void pooledDeviceRealignedCigars(const std::vector<Haplotype> &haps, const std::
 // What both are made of: the choice per read from ll(h, r) and onHap(r), the CIGAR of the chosen pair from cigarOf(h, r).
 void pooledRealignedCigars(size_t numHaps, size_t numReads, const std::function<double(size_t, size_t)> &ll, const std::function<bool(size_t)> &onHap,
                            const std::function<CIGAR(size_t, size_t)> &cigarOf, std::vector<CIGAR> &cigars);
+
+// --deviceRealignDiploid: the diploid step's CIGARs from a view with hasDevicePair().  On a window the device certified (pairState() ==
+// DD_DIPPAIR_CERTIFIED) the pair is devicePair() and each read's CIGAR the row of its realignHap(r) — nothing of the pair choice is computed
+// here; rows over the cap or not computed go through the host getCIGAR from withAlignments(), counted in *hostFallbacks.  On any other state
+// the window is the host's: maxLikelihoodPair, then realignedCigars on withAlignments(); *uncertifiedWindows is incremented.  Returns the pair used.
+std::pair<int, int> diploidDeviceRealignedCigars(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const WindowLikelihoods &liks, int leftPos,
+                                                 const AlignedCandidates &candidateVariants, const DiploidParameters &params, int refSeqPos,
+                                                 std::vector<CIGAR> &cigars, const std::function<WindowLikelihoods()> &withAlignments, long *hostFallbacks,
+                                                 long *uncertifiedWindows);
 
 // The name the reference gives the window's file: PREFIX.ra.INDEX_TID_(leftPos+minReadOverlap)_(rightPos-minReadOverlap).bam (:614-618)
 std::string realignedBAMFileName(const std::string &prefix, int index, const std::string &tid, uint32_t leftPos, uint32_t rightPos, int minReadOverlap);

@@ -500,6 +500,63 @@ int dd_compute_likelihoods_realign(const dd_params *p, const dd_batch *b, dd_res
                                    const int32_t *hap_ref_pos, const uint8_t *hap_aligned,
                                    const dd_realign_result *out, int ops_cap, int device, uint32_t options);
 
+/* ---- diploid realigned reads: the window's MAP haplotype pair, chosen and certified on the device (opt-in) ---------- */
+/* The pair DD_REALIGN_PAIR needs is maxLikelihoodPair's argmax (host/realigned_bam.cpp, reference DInDel.cpp:3767-3831) over
+ *   V[h1,h2] = sum over the window's reads, in order, of (addLogs(ll[h1,r], ll[h2,r]) + log(.5))  +  prior[h1,h2],   h1 <= h2,
+ * which the host takes in glibc arithmetic.  The device takes the same sums in csrc/pooled_math.h's arithmetic (bit-equal on host and
+ * device, not glibc's) with a bound eps on how far either evaluation can be from the exact value:
+ *   t_r = pm_add_logs(ll[h1,r], ll[h2,r]) + pm_log(0.5);  S = sum of t_r in read order;  A = sum of |t_r|;  V = S + prior[h1,h2]
+ *   eps = 2^-50 ((R + 4) A + 8 R + |prior[h1,h2]|)
+ *   best   = the first pair in row-major order (h1 <= h2) with the largest V
+ *   second = the first pair in row-major order, other than best, with the largest V among the others (equal values count)
+ *   gap    = V_best - V_second (+inf with one pair);  margin = max(eps_best, eps_second)
+ * A window is certified when gap > margin: the host's argmax is then the same pair.  Every other window is left to the host.
+ * prior[win_hh_off[w] + h1 * H + h2] = getHaplotypePrior(h1, h2), the layout of dd_map_pairs_device (dd_pair_sum_offsets).
+ * States, in the order they are tested:
+ *   DD_DIPPAIR_NO_HAPS         the window has no haplotype
+ *   DD_DIPPAIR_TOO_MANY_HAPS   more than DD_DIPPAIR_MAX_HAPS haplotypes
+ *   DD_DIPPAIR_NOT_COMPUTED    some pair of the window has status != 0
+ *   DD_DIPPAIR_NONFINITE       some ll of the window is NaN or +-inf, some V is NaN, or V_best is not finite (the host's
+ *                              addLogs(-inf, -inf) is NaN and its sort is then unspecified)
+ *   DD_DIPPAIR_TIE             gap <= margin
+ *   DD_DIPPAIR_CERTIFIED       gap > margin
+ * Per window: pair[2w], pair[2w+1] = best, or (-1, -1) in every state but DD_DIPPAIR_CERTIFIED (dd_realign_device then gives the
+ * window's reads DD_REALIGN_BAD_PAIR and walks nothing); state[w]; best[w] = V_best, gap[w], margin[w] (0 in the four states in
+ * which they were not taken).  A window without reads has V = prior. */
+typedef struct dd_diploid_pair_result {
+    int32_t *pair;      /* [2 * n_windows] */
+    int32_t *state;     /* [n_windows] DD_DIPPAIR_* */
+    double  *best;      /* [n_windows] */
+    double  *gap;       /* [n_windows] */
+    double  *margin;    /* [n_windows] */
+} dd_diploid_pair_result;
+#define DD_DIPPAIR_CERTIFIED      0
+#define DD_DIPPAIR_TIE            1
+#define DD_DIPPAIR_NONFINITE      2
+#define DD_DIPPAIR_NOT_COMPUTED   3
+#define DD_DIPPAIR_NO_HAPS        4
+#define DD_DIPPAIR_TOO_MANY_HAPS  5
+#define DD_DIPPAIR_MAX_HAPS     128
+/* Enqueue the pair launch for the whole batch on `stream`, behind the likelihood launch(es) that wrote ll_dev and status_dev.  All DEVICE
+ * pointers; status_dev may be NULL (every pair was computed), every array of out_dev is required.  Of the batch it reads n_windows,
+ * win_hap_off, win_read_off and win_pair_off.  out_dev->pair can be handed to dd_realign_device (DD_REALIGN_PAIR) on the same stream.
+ * Asynchronous, no allocation. */
+int dd_diploid_pairs_device(const dd_device_batch *b, const int64_t *win_hh_off_dev, const double *ll_dev, const int32_t *status_dev,
+                            const double *prior_dev, const dd_diploid_pair_result *out_dev, void *stream);
+/* The same function on the CPU, no device needed, every output equal to the device's in every bit: host pointers, ll and status per pair in
+ * pair order (status may be NULL), prior laid out by dd_pair_sum_offsets; windows spread over nthreads host threads (< 1: one). */
+int dd_diploid_pairs_host(const dd_batch *b, const double *ll_host, const int32_t *status_host, const double *prior_host,
+                          const dd_diploid_pair_result *out, int nthreads);
+/* Host pointers: dd_compute_likelihoods_realign in DD_REALIGN_PAIR mode with the window pairs chosen on the device — on every window block's
+ * stream the pair launch runs behind the block's likelihood launches and in front of its realign launch, which reads the pairs where they
+ * were written; the per-window arrays of pair_out (host memory) come back with the block, the reads' rows in realign_out.  A window that is
+ * not DD_DIPPAIR_CERTIFIED has the pair (-1, -1) and its reads DD_REALIGN_BAD_PAIR: the caller chooses that window's pair itself.
+ * prior [sum of H_w^2] (dd_pair_sum_offsets), hap_n_indels [n_haps] and hap_ref_pos are required; r->hpos may be NULL.  A batch without
+ * pairs gets its windows' states from the CPU evaluation (no device needed).  Everything else as dd_compute_likelihoods_realign. */
+int dd_compute_likelihoods_realign_diploid(const dd_params *p, const dd_batch *b, dd_result *r, const double *prior, const int32_t *hap_n_indels,
+                                           const int32_t *hap_ref_pos, const uint8_t *hap_aligned, const dd_diploid_pair_result *pair_out,
+                                           const dd_realign_result *realign_out, int ops_cap, int device, uint32_t options);
+
 /* ---- alignHaplotypes: candidate haplotypes against the window's reference sequence ---------- */
 /* The arithmetic of DetInDel::alignHaplotypes (reference DInDel.cpp:1427-1524): SeqAn's globalAlignment with
  * Score<int>(-1, -460, -100, -960) and no free end gaps, i.e. _align_gotoh / _align_gotoh_trace of seqan/graph_align/graph_align_gotoh.h,
