@@ -17,6 +17,13 @@ tests/test_insert_prior.py and tests/test_gpu_half_wave.py, restated with an exp
   mates     all 16 combinations of the mate flags over two libraries
   screened  a window the screen rejects (an empty read), one without reads, one without haplotypes, the hapSize-error pair (mld >= 5)
   chunk     only for half-wave tilings (G == 2 in capi.HAP_CLASSES): 300 reads of 36 / 48 / 60 bp in one window
+
+long_batch_for(hap_len, read_len, mld, wide, many) is the same batch for the long-window kernels (haplotypes up to DD_LONG_MAX_HAP_LEN): every
+window the screen can class gets one read of LONG_FORCE_LEN bp, so that it is DD_WIN_LONG whatever its haplotype length.  Its families:
+
+  long.force  the 1,025-bp read of every forced window
+  long.many   (many) one window of many short reads on two haplotypes: more pairs (or 16-pair items) than the persistent grid has workgroups
+  long.wide   (wide) one window with one 4,096-bp read: the largest back-pointer tile, hence the smallest grid the workspace budget allows
 """
 import numpy as np
 
@@ -26,6 +33,8 @@ from tests.test_insert_prior import library
 
 HAP_START = 1000
 FAMILIES = ("redo", "ties", "ends", "bytes", "quals", "flags", "mates", "screened", "chunk")
+LONG_FAMILIES = ("long.force", "long.many", "long.wide")
+LONG_FORCE_LEN, LONG_WIDE_LEN = capi.DD_MAX_READ_LEN + 1, capi.DD_LONG_MAX_READ_LEN
 REDO_MIN_LEN = 260            # as in test_low_likelihood_pairs_redo_with_ro_chain (250 bp): at Phred 2-4 the best path costs 0.4-0.65 per base
 CHUNK_READS, CHUNK_LENS = 300, (36, 48, 60)
 Q30, Q20, Q10 = (float(v) for v in phred_to_prob([30, 20, 10]))
@@ -222,20 +231,29 @@ def bytes_window(rng, hap_len, L, mld):
     return Window(HAP_START, [hap, hap2, hapN], reads)
 
 
-def scenario_windows(hap_len, read_len, mld, rng):
+def scenario_windows(hap_len, read_len, mld, rng, extra_read=None):
     """-> (windows, libraries, index): the windows, the `libraries` argument of batch.pack, and a dict from family name (and "family.part")
-    to the indices of its pairs in the packed batch (window-major, then haplotype, then read: the layout of the result arrays)."""
+    to the indices of its pairs in the packed batch (window-major, then haplotype, then read: the layout of the result arrays).
+    hap_len up to DD_LONG_MAX_HAP_LEN; above DD_MAX_HAP_LEN there is no half-wave class and hence no `chunk` family.
+    extra_read(window) -> (family, ReadRec) or None: one more read at the end of the window's reads, in a family of its own (the index
+    counts it; a family's "every read" stays the reads the family built)."""
     L = int(read_len)
-    G = next(c[1] for c in capi.HAP_CLASSES if hap_len <= c[0])
+    assert 1 <= hap_len <= capi.DD_LONG_MAX_HAP_LEN
+    G = next((c[1] for c in capi.HAP_CLASSES if hap_len <= c[0]), 1)
     libs = [library(rng, 600, 300), library(rng, 200, 80)]
     windows, index = [], {k: [] for k in FAMILIES}
     n_pairs = [0]
 
     def add(window, families):
         """families: {name: read indices within the window, or None for every read}."""
+        own = len(window.reads)
+        extra = extra_read(window) if extra_read is not None else None
+        if extra is not None:
+            window.reads.append(extra[1])
+            families = dict(families, **{extra[0]: [own]})
         H, R = len(window.haps), len(window.reads)
         for name, rs in families.items():
-            rs = range(R) if rs is None else rs
+            rs = range(own) if rs is None else rs
             index.setdefault(name, []).extend(n_pairs[0] + h * R + r for h in range(H) for r in rs)
         windows.append(window)
         n_pairs[0] += H * R
@@ -280,7 +298,7 @@ def scenario_windows(hap_len, read_len, mld, rng):
         rs = spread_reads(rng, small, 5, min(L, 30))
         add(Window(HAP_START, [small, "ACGT"], rs, hap_vars=[[(20, 22)], [(1, 2), (0, 3)]], hap_var_flanks=[[(19, 23, 1)], [(0, 3, 2), (1, 2, 1)]]),
             {"screened": None})
-        index["screened.hapsize"] = list(range(n_pairs[0] - len(rs), n_pairs[0]))
+        index["screened.hapsize"] = list(range(n_pairs[0] - len(windows[-1].reads), n_pairs[0]))   # every read on the 4-bp haplotype
 
     # ---- chunk: more reads than one ordering chunk of the half-wave builds, three lengths ----
     if G == 2:
@@ -325,7 +343,7 @@ def element_pairs(pb):
 
 def family_of(pair, index):
     """The scenario families (top-level keys) a pair belongs to, as text."""
-    names = [k for k in FAMILIES if k in index and pair in set(index[k].tolist())]
+    names = [k for k in FAMILIES + LONG_FAMILIES if k in index and pair in set(index[k].tolist())]
     return "+".join(n for n in names if n != "flags" or len(names) == 1) or "none"
 
 
@@ -398,6 +416,103 @@ def batch_for(hap_len, read_len, mld):
     from dindel_tgi_amd.batch import pack
     ws, libs, index = scenario_windows(hap_len, read_len, mld, np.random.default_rng(1000003 * mld + 1009 * read_len + hap_len))
     return pack(ws, libraries=libs), index
+
+
+def long_grid_bound(hap_len, max_read):
+    """An upper bound of the persistent grid of a long launch (long_plan.cpp long_plan): the resident workgroups — two per CU, one at K = 16,
+    of 256 CUs — or what DD_LONG_WS_BUDGET holds of back-pointer tiles.  -> (K, bound)."""
+    K = 1
+    while 256 * K < hap_len + 2:
+        K *= 2
+    tile = -(-max_read * 256 * K // 256) * 256 + 16 * 256 * K
+    return K, min(256 * (1 if K >= 16 else 2), capi.DD_LONG_WS_BUDGET // tile)
+
+
+# long_plan.cpp fl_plan at 4,096-bp reads: 16 pair areas of 8.6 KiB and the shared area leave room for one resident workgroup on each of the 256 CUs
+FASTER_LONG_WIDE_GRID_BOUND = 256
+
+
+def long_batch_for(hap_len, read_len, mld, wide=False, many=False):
+    """-> (PackedBatch, index map) of scenario_windows for the long-window kernels; a function of its arguments.
+
+    Every window that has haplotypes, has reads and has no empty read gets one more read of LONG_FORCE_LEN bp (family long.force), cut from
+    the middle of its first haplotype and padded where it overhangs: dd_screen_windows_ex then classes the window DD_WIN_LONG whatever
+    its haplotype length — the hapSize window's 80-bp haplotype included, which so runs on the K of the batch's longest haplotype.  The
+    read's base and mapping quality are already in the batch (`quals` fills the quality table).  The window with the empty read, the one
+    without reads and the one without haplotypes stay as they are.
+    many: one more window in the style of `chunk` (family long.many): short reads of CHUNK_LENS on two haplotypes, their number no multiple
+      of 16.  True: as many as bring the batch's long pairs above twice long_grid_bound at LONG_FORCE_LEN-bp reads (the grid of a launch
+      with 4,096-bp reads is no larger), so that some workgroup of dd_long_kernel takes a third pair.  "items": as many as bring the 16-pair
+      items of dd_faster_long_kernel above FASTER_LONG_WIDE_GRID_BOUND, the grid of a launch with the wide window (the oracle's time
+      grows with the pairs: no more than that).  The launch record of a GPU run shows pairs (items) > grid.
+    wide: one more window, the last (family long.wide): the first haplotype and one read of LONG_WIDE_LEN bp.  The batch without it is the
+      batch of wide=False, array for array a prefix: one oracle run serves both."""
+    from dindel_tgi_amd.batch import pack
+    assert many in (False, True, "items")
+    seed = 1000003 * mld + 1009 * read_len + hap_len
+    rng, side = np.random.default_rng(seed), np.random.default_rng(seed + 7919)
+
+    def long_read(src, n):
+        off = (len(src) - n) // 2                                                            # (negative: the read hangs over both ends)
+        return ReadRec(mutate(side, seq_at(side, src, off, n), 0.02), [Q30] * n, MQ, HAP_START + off)
+
+    def force(window):
+        if not window.haps or not window.reads or any(len(r.seq) == 0 for r in window.reads):
+            return None
+        return "long.force", long_read(window.haps[0], LONG_FORCE_LEN)
+
+    ws, libs, index = scenario_windows(hap_len, read_len, mld, rng, extra_read=force)
+    index = {k: v.tolist() for k, v in index.items()}
+    n_pairs = sum(len(w.haps) * len(w.reads) for w in ws)
+    hap = ws[0].haps[0]
+
+    def add(window, family, reads):
+        R = len(window.reads)
+        index[family] = [n_pairs + h * R + r for h in range(len(window.haps)) for r in reads]
+        ws.append(window)
+        return n_pairs + len(window.haps) * R
+
+    if many:
+        forced = [w for w in ws if force(w) is not None]
+        if many == "items":
+            items = sum(len(w.haps) * -(-len(w.reads) // 16) for w in forced)
+            n = 16 * -(-(FASTER_LONG_WIDE_GRID_BOUND + 8 - items) // 2) + 5                       # two haplotypes: 2 * ceil((n + 1) / 16) items
+        else:
+            n = -(-(2 * long_grid_bound(hap_len, LONG_FORCE_LEN)[1] + 33 - sum(len(w.haps) * len(w.reads) for w in forced)) // 2)
+        n = max(n, 37)
+        n += 1 if (n + 1) % 16 == 0 else 0                                                   # n + 1 reads with the forced one
+        alt = shorter(hap, 2, hap_len // 2, mld)
+        rs = []
+        for i in range(n):
+            src, Lr = (hap, alt)[i & 1], CHUNK_LENS[i % 3]
+            off = int(side.integers(-(Lr // 4), max(1, len(src) - Lr + Lr // 4)))
+            rs.append(ReadRec(mutate(side, seq_at(side, src, off, Lr), 0.02), [float(phred_to_prob([int(side.integers(5, 41))])[0])] * Lr, MQ,
+                              HAP_START + off))
+        w = Window(HAP_START, [hap, alt], rs + [long_read(hap, LONG_FORCE_LEN)])
+        index["long.force"] += [n_pairs + h * (n + 1) + n for h in range(2)]
+        n_pairs = add(w, "long.many", range(n))
+    if wide:
+        n_pairs = add(Window(HAP_START, [hap], [long_read(hap, LONG_WIDE_LEN)]), "long.wide", [0])
+    return pack(ws, libraries=libs), {k: np.asarray(v, np.int64) for k, v in index.items()}
+
+
+# ---- the grid of the long-window matrices ----
+# (haplotype length, read length, maxLengthDel, K of dd_long_kernel): both sides of every K bound (numS = hap + 2 <= 256 K) and both ends of
+# the range; 36-bp reads at one length per K; every K with maxLengthDel <= 11 and >= 12 (the main kernels' D = 32 threshold — the long kernel
+# loops over jump lengths at run time), the larger value on the shorter haplotype of a K: the oracle's time grows with both
+LONG_GRID = [(120, 100, 31, 1), (254, 36, 5, 1), (255, 100, 20, 2), (510, 36, 11, 2), (511, 100, 31, 4), (1022, 36, 5, 4),
+             (1023, 100, 20, 8), (2046, 36, 11, 8), (2047, 100, 20, 16), (4094, 36, 5, 16)]
+# dd_faster_long_kernel: the ends of the range, the first length beyond dd_faster_kernel's, the last K bound
+FASTER_LONG_GRID = [(120, 100, 31), (767, 100, 11), (2047, 100, 20), (4094, 36, 5)]
+# dd_faster_kernel: haplotype lengths of the scenario batches it runs (minus what hap_lengths(mld) drops)
+FASTER_HAP_LENGTHS = (30, 126, 254, 574, 766)
+
+
+def long_pairs(pb, cls):
+    """The pairs of the windows the screen classed DD_WIN_LONG, and their 16-pair items (faster_long_kernel.hip: per haplotype, 16 reads)."""
+    H, R = np.diff(pb.a["win_hap_off"]), np.diff(pb.a["win_read_off"])
+    sel = np.asarray(cls[:pb.n_windows]) == capi.DD_WIN_LONG
+    return int((H * R)[sel].sum()), int((H * -(-R // 16))[sel].sum())
 
 
 def params_for(mld, map_unmapped=1):
