@@ -43,6 +43,8 @@ DD_REALIGN_FIRST_MAX, DD_REALIGN_PAIR = 0, 1
 # the certified MAP haplotype pair of the diploid realigned reads (opt-in): per-window states and the haplotype cap
 (DD_DIPPAIR_CERTIFIED, DD_DIPPAIR_TIE, DD_DIPPAIR_NONFINITE, DD_DIPPAIR_NOT_COMPUTED, DD_DIPPAIR_NO_HAPS, DD_DIPPAIR_TOO_MANY_HAPS) = range(6)
 DD_DIPPAIR_MAX_HAPS = 128
+# the --faster model's indel-map key count (opt-in): one int16 per pair, the count or one of the two negative marks
+DD_INDEL_KEYS_CAP, DD_INDEL_KEYS_OVERFLOW, DD_INDEL_KEYS_NOT_COMPUTED = 64, -1, -2
 # alignHaplotypes on the device: per-pair status codes and the launch geometry record
 DD_ALIGN_OK, DD_ALIGN_EMPTY, DD_ALIGN_TOO_LONG, DD_ALIGN_BAD_REF = range(4)
 DD_ALIGN_WS_BUDGET = 512 << 20
@@ -256,7 +258,8 @@ EXPORTS = ["dd_params_struct_defaults", "dd_params_cli_defaults", "dd_batch_size
            "dd_hap_variants_device", "dd_align_haplotypes_variants", "dd_hap_variants_last_launch",
            "dd_hap_blocks_offsets", "dd_hap_blocks_workspace_bytes", "dd_hap_blocks_device", "dd_hap_blocks_compute", "dd_hap_blocks_last_launch",
            "dd_pooled_em_device", "dd_pooled_em", "dd_pooled_em_host", "dd_pooled_math_eval",
-           "dd_diploid_pairs_device", "dd_diploid_pairs_host", "dd_compute_likelihoods_realign_diploid"]
+           "dd_diploid_pairs_device", "dd_diploid_pairs_host", "dd_compute_likelihoods_realign_diploid",
+           "dd_indel_keys_device", "dd_indel_keys_host", "dd_compute_likelihoods_faster_keys"]
 
 _lib = None
 
@@ -362,6 +365,9 @@ def load():
     lib.dd_diploid_pairs_host.argtypes = [C.POINTER(dd_batch), c_f64p, c_i32p, c_f64p, C.POINTER(dd_diploid_pair_result), C.c_int]
     lib.dd_compute_likelihoods_realign_diploid.argtypes = [C.POINTER(dd_params), C.POINTER(dd_batch), C.POINTER(dd_result), c_f64p, c_i32p, c_i32p, c_u8p,
                                                            C.POINTER(dd_diploid_pair_result), C.POINTER(dd_realign_result), C.c_int, C.c_int, C.c_uint32]
+    lib.dd_indel_keys_device.argtypes = [C.POINTER(dd_device_batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dd_indel_keys_host.argtypes = [C.POINTER(dd_batch), c_i16p, c_i32p, c_i16p, C.c_int]
+    lib.dd_compute_likelihoods_faster_keys.argtypes = [C.POINTER(dd_params), C.POINTER(dd_batch), C.POINTER(dd_result), c_i16p, C.c_int, C.c_uint32]
     lib.dd_last_launch.argtypes = [C.POINTER(C.c_int32 * 8)]
     lib.dd_last_launch.restype = None
     lib.dd_launch_log.argtypes = [c_i32p, C.c_int]
@@ -496,6 +502,23 @@ def diploid_pairs_host(win_hap_off, win_read_off, ll, prior, status=None, nthrea
     if rc != 0:
         raise RuntimeError("dd_diploid_pairs_host rc=%d: %s" % (rc, last_error()))
     return out
+
+
+def indel_keys_host(pb, hpos, status=None, nthreads=1):
+    """dd_indel_keys_host on a PackedBatch: the --faster model's indel-map key count of every pair (int16 [n_pairs]) from hpos (int16, laid
+    out like dd_result.hpos) and, when given, the pairs' status (int32 [n_pairs])."""
+    import numpy as np
+    hp = np.ascontiguousarray(hpos, np.int16)
+    st = None if status is None else np.ascontiguousarray(status, np.int32)
+    if hp.size < pb.hpos_len or (st is not None and st.size < pb.n_pairs):
+        raise ValueError("hpos / status shorter than the batch's")
+    out = np.zeros(max(pb.n_pairs, 1), np.int16)
+    b = pb.ctypes_batch()
+    rc = load().dd_indel_keys_host(C.byref(b), hp.ctypes.data_as(c_i16p) if hp.size else None, st.ctypes.data_as(c_i32p) if st is not None else None,
+                                   out.ctypes.data_as(c_i16p), int(nthreads))
+    if rc != 0:
+        raise RuntimeError("dd_indel_keys_host rc=%d: %s" % (rc, last_error()))
+    return out[:pb.n_pairs]
 
 
 def cigar_ops(ops, n_ops):

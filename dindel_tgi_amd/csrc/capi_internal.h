@@ -2,7 +2,8 @@
 // nor needs a kernel unit to link), long_plan.cpp (the plans of the two long-window paths, with the layouts of their kernel units),
 // launch.cpp, host_path.cpp, align_host.cpp (the haplotype alignment with the events and variants behind it), hapdist_host.cpp (the block
 // table), pooled_em_capi.cpp (the pooled EM's device entries; pooled_em_host.cpp, its CPU evaluation, includes no HIP header and not this
-// file); each says in its first lines what it holds.  The last part of this file is what the host-pointer entries share: use_device, the
+// file), indel_keys_capi.cpp (the --faster model's indel-map key count: the launch and the CPU evaluation); each says in its first lines
+// what it holds.  The last part of this file is what the host-pointer entries share: use_device, the
 // arena slot, the one-shot arena of the three small entries and the record of a drawing kernel's last launch.  Host work is O(bases)
 // bookkeeping only.  All likelihood arithmetic happens in the kernels; there is no CPU path for it in this library.
 #ifndef DD_CAPI_INTERNAL_H
@@ -197,6 +198,10 @@ void launch_log_clear();
 int launch_cigars_range(const dd_device_batch *b, const int16_t *hpos_dev, const int32_t *status_dev, const int32_t *hap_ref_pos_dev,
                         const uint8_t *hap_aligned_dev, const dd_cigar_result *out_dev, int ops_cap, void *stream, int64_t pair_begin,
                         int64_t pair_end);
+// the --faster model's indel-map key count (indel_keys_kernel.hip, enqueued by indel_keys_capi.cpp) over the pairs [pair_begin, pair_end)
+// of the batch; pair_end < 0 = all of them
+int launch_indel_keys_range(const dd_device_batch *b, const int16_t *hpos_dev, const int32_t *status_dev, int16_t *out_dev, void *stream,
+                            int64_t pair_begin, int64_t pair_end);
 // what one realign launch needs besides the batch (device pointers; dd_realign_device's arguments)
 struct RealignInputs {
     int mode;

@@ -210,13 +210,15 @@ enum { DD_RESULT_FIELDS(OUT_INDEX) N_RESULT_OUTS };    // a dd_result field's pl
 // What a CIGAR or realign entry adds to a call: inputs of its own, per window block one launch behind the likelihood launches, and output
 // arrays in one index space (per PAIR: dd_compute_likelihoods_cigars; per READ: dd_compute_likelihoods_realign, which takes the window pairs
 // and indel counts of its PAIR mode besides; dd_compute_likelihoods_realign_diploid, whose window pairs are chosen by a launch of its own in
-// front of the realign launch and stay on the device, with outputs per WINDOW besides).
+// front of the realign launch and stay on the device, with outputs per WINDOW besides).  A key request (dd_compute_likelihoods_faster_keys,
+// the --faster model) has no input of its own and one output per PAIR, the indel-map key count.
 struct ExtraRequest {
     const int32_t *hap_ref_pos; const uint8_t *hap_aligned; int ops_cap;
     bool realign;
     dd_cigar_result cigars;                                                       // !realign
     int mode; const int32_t *win_hap_pair, *hap_n_indels; dd_realign_result reads; // realign
     bool diploid; const double *prior; dd_diploid_pair_result pairs;              // realign in PAIR mode, the pairs from dd_diploid_pairs_device
+    int16_t *keys;                                                                // non-NULL: a key request, and nothing of the above
 };
 
 // One call of a host-pointer entry.  run() is the sequence of its stages; the members are grouped by the stage that fills them.
@@ -254,6 +256,7 @@ struct HostCall {
     dd_diploid_pair_result ddp = {};
     const double *prior_dev = nullptr;
     const int64_t *hh_off_dev = nullptr;
+    int16_t *keys_dev = nullptr;
     unsigned char *ws[2] = {nullptr, nullptr}, *lws[2] = {nullptr, nullptr};
     unsigned long long *long_stats = nullptr;           // long_path->n_stats (2 or 4) words per window block's long launch
     // reserve_and_upload, place_outputs
@@ -434,7 +437,7 @@ struct HostCall {
         }
 #undef IN
         if (!single_class) in(&class_list_dev, class_list.data(), (size_t)lcls.list_len);
-        if (x) {
+        if (x && !x->keys) {
             in(&hap_ref_pos_dev, x->hap_ref_pos, (size_t)sz.hap_bases);
             if (x->hap_aligned) in(&hap_aligned_dev, x->hap_aligned, n_haps);
             if (x->realign && x->mode == DD_REALIGN_PAIR) {
@@ -464,6 +467,7 @@ struct HostCall {
             outs[OUT_hpos].in_place = false;
             outs[OUT_hpos].device_only = !r->hpos;
             const size_t cap = (size_t)x->ops_cap;
+            if (x->keys) out(x->keys, &keys_dev, SPACE_PAIR, 1, false);
 #define OUT_PAIR(f, wide) out(x->cigars.f, &dcg.f, SPACE_PAIR, wide ? cap : 1, false);
 #define OUT_READ(f, wide) out(x->reads.f, &drl.f, SPACE_READ, wide ? cap : 1, false);
 #define OUT_WINDOW(f, width) out(x->pairs.f, &ddp.f, SPACE_WINDOW, width, false);
@@ -471,7 +475,7 @@ struct HostCall {
                 outs[OUT_ll].in_place = outs[OUT_onHap].in_place = false;
                 DD_REALIGN_FIELDS(OUT_READ)
                 if (x->diploid) { DD_DIPPAIR_FIELDS(OUT_WINDOW) }
-            } else {
+            } else if (!x->keys) {
                 DD_CIGAR_FIELDS(OUT_PAIR)
             }
 #undef OUT_PAIR
@@ -596,10 +600,11 @@ struct HostCall {
     // The request's launch for the windows [w0, w1) of a block, behind the block's likelihood launches on the same stream: the block's CIGARs
     // (its ops start out zero: a pair's unused slots are defined), or the block's realigned reads (reads of windows without haplotypes are
     // marked too: the launch goes by reads, not by pairs).  A diploid request's pair launch goes first, for the same windows: the realign
-    // launch reads the pairs where that launch left them.
+    // launch reads the pairs where that launch left them.  A key request: the block's counts.
     int launch_extra(hipStream_t st, int w0, int w1)
     {
         int rc;
+        if (x->keys) return launch_indel_keys_range(&db, dr.hpos, dr.status, keys_dev, st, idx.at(SPACE_PAIR, w0), idx.at(SPACE_PAIR, w1));
         if (x->diploid && (rc = launch_diploid_pairs_range(&db, hh_off_dev, dr.ll, dr.status, prior_dev, &ddp, st, w0, w1))) return rc;
         const ResultSpace space = x->realign ? SPACE_READ : SPACE_PAIR;
         const int64_t lo = idx.at(space, w0), hi = idx.at(space, w1);
@@ -965,6 +970,14 @@ int dd_compute_likelihoods_faster_ex(const dd_params *p, const dd_batch *b, dd_r
 {
     if (options & ~DD_OPT_LONG_WINDOWS_FASTER) return fail(DD_ERR_INVALID, "unknown option bits");
     return compute_likelihoods_impl(MODEL_S, p, b, r, device, options);
+}
+int dd_compute_likelihoods_faster_keys(const dd_params *p, const dd_batch *b, dd_result *r, int16_t *keys_out, int device, uint32_t options)
+{
+    if (options & ~DD_OPT_LONG_WINDOWS_FASTER) return fail(DD_ERR_INVALID, "unknown option bits");
+    if (!keys_out) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_faster_keys: keys_out is required");
+    ExtraRequest x = {};
+    x.keys = keys_out;
+    return compute_likelihoods_impl(MODEL_S, p, b, r, device, options, &x);
 }
 int dd_compute_likelihoods_multi(const dd_params *p, const dd_batch *b, dd_result *r, const int *devices, int n_devices)
 {

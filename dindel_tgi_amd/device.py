@@ -30,7 +30,7 @@ class DeviceBatch:
 
     def __init__(self, pb: PackedBatch, params: capi.dd_params, device="cuda:0", long_windows=False, long_windows_faster=False,
                  cigars=False, ops_cap=capi.DD_CIGAR_DEFAULT_OPS_CAP, hap_ref_pos=None, hap_aligned=None, realign=False, hap_n_indels=None,
-                 diploid_prior=None):
+                 diploid_prior=None, indel_keys=False):
         """long_windows: windows beyond the main kernels' limits (haplotypes up to 4,094 bp, reads up to 4,096 bp, and with maxLengthDel
         12..31 haplotypes over 574 bp) are computed by the long-window kernel after the main launch (dd_launch_device_long) instead of
         being marked DD_PAIR_UNSUPPORTED.  Off by default.
@@ -45,7 +45,10 @@ class DeviceBatch:
         hap_ref_pos like cigars; hap_n_indels (Haplotype::countIndels per haplotype) is needed by the DD_REALIGN_PAIR rule only.
         diploid_prior: getHaplotypePrior per haplotype pair, H * H doubles per window (dd_pair_sum_offsets' layout): launch_diploid_pairs()
         picks and certifies every window's MAP haplotype pair on the device (dd_diploid_pairs_device); its `pair` tensor can be handed to
-        launch_realign(DD_REALIGN_PAIR, ...) as it is, and diploid_pair_results() copies the per-window outputs back."""
+        launch_realign(DD_REALIGN_PAIR, ...) as it is, and diploid_pair_results() copies the per-window outputs back.
+        indel_keys: launch_indel_keys() counts the distinct indel-map keys of every pair of the --faster model on the device
+        (dd_indel_keys_device) from the hpos of the last launch_faster(), and results() also returns indel_keys (int16 [n_pairs]: the
+        count, DD_INDEL_KEYS_OVERFLOW or DD_INDEL_KEYS_NOT_COMPUTED).  Off by default."""
         if long_windows and long_windows_faster:
             raise ValueError("long_windows and long_windows_faster screen the batch for different models: one resident batch, one screening")
         lib = capi.load()
@@ -182,6 +185,9 @@ class DeviceBatch:
             self.dip = {k: torch.zeros(nwin * (2 if k == "pair" else 1), dtype=_TORCH_DT[np.dtype(capi.DIPLOID_PAIR_DTYPES[k])], device=self.device)
                         for k in capi.DIPLOID_PAIR_FIELDS}
             self.ddip = capi.dd_diploid_pair_result(*[self.dip[k].data_ptr() for k in capi.DIPLOID_PAIR_FIELDS])
+        self.indel_keys = bool(indel_keys)
+        if self.indel_keys:
+            self.keys = torch.zeros(max(pb.n_pairs, 1), dtype=torch.int16, device=self.device)
         if self.cigars:
             npair = max(pb.n_pairs, 1)
             self.cig = {"n_ops": torch.zeros(npair, dtype=torch.int32, device=self.device),
@@ -234,6 +240,19 @@ class DeviceBatch:
                                   C.c_void_p(stream.cuda_stream))
         if rc != 0:
             raise RuntimeError("dd_cigars_device rc=%d: %s" % (rc, capi.last_error()))
+
+    def launch_indel_keys(self, stream=None):
+        """The --faster model's indel-map key count of every pair, from the hpos and status of the last launch_faster() (same stream,
+        behind it). Asynchronous."""
+        if not self.indel_keys:
+            raise RuntimeError("this batch was built without indel_keys=True")
+        lib = capi.load()
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        rc = lib.dd_indel_keys_device(C.byref(self.db), C.c_void_p(self.out["hpos"].data_ptr()), C.c_void_p(self.out["status"].data_ptr()),
+                                      C.c_void_p(self.keys.data_ptr()), C.c_void_p(stream.cuda_stream))
+        if rc != 0:
+            raise RuntimeError("dd_indel_keys_device rc=%d: %s" % (rc, capi.last_error()))
 
     def launch_realign(self, mode, win_hap_pair=None, stream=None, on_hap=True):
         """The haplotype each read is realigned to and that pair's CIGAR, from the ll, onHap, status and hpos of the last launch() /
@@ -328,6 +347,8 @@ class DeviceBatch:
             for k in ("n_ops", "ref_off", "status"):
                 res["cigar_" + k] = self.cig[k][:n].cpu().numpy()
             res["cigar_ops"] = self.cig["ops"][:n * self.ops_cap].cpu().numpy().view(np.uint32).reshape(n, self.ops_cap)
+        if self.indel_keys:
+            res["indel_keys"] = self.keys[:self.pb.n_pairs].cpu().numpy()
         if self.realign:
             n = self.pb.n_reads
             for k in ("hap", "status", "n_ops", "ref_off"):

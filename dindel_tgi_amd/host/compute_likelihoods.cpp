@@ -233,7 +233,11 @@ struct BatchBlock {
     bool has_pairs;                                      // device pair (setDeviceRealignDiploid): per WINDOW; the realign rows are then the diploid rule's
     RawBuf<int32_t> dp_pair, dp_state;
     RawBuf<double> dp_best, dp_gap, dp_margin;
-    BatchBlock() : W(0), faster(false), has_hpos(false), has_cigars(false), cig_cap(0), has_realign(false), has_pairs(false) {}
+    bool has_keys;                                       // device indel keys (setDeviceIndelKeys): per pair, the --faster model
+    RawBuf<int16_t> indel_keys;
+    int device; bool long_faster;                        // ... and what a recomputation of one of its windows needs of the engine that made it
+    BatchBlock() : W(0), faster(false), has_hpos(false), has_cigars(false), cig_cap(0), has_realign(false), has_pairs(false), has_keys(false),
+                   device(0), long_faster(false) {}
 };
 
 struct PackScratch {
@@ -436,10 +440,51 @@ WindowLikelihoods WindowLikelihoods::handMadeRealign(const std::vector<Haplotype
     return v;
 }
 
+WindowLikelihoods WindowLikelihoods::handMadeFaster(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const int16_t *hpos,
+                                                    const int16_t *keys, LikelihoodEngine *eng)
+{
+    WindowLikelihoods v = handMadeRealign(haps, reads, 1, NULL, NULL, NULL, NULL, NULL, hpos);
+    BatchBlock &B = const_cast<BatchBlock &>(*v.blk_);     // (just made, nobody else refers to it)
+    B.faster = true;
+    if (eng) { B.params = eng->params; B.device = eng->device_; B.long_faster = eng->longWindowsFaster_; }
+    if (keys) {
+        const size_t np = haps.size() * reads.size();
+        B.has_keys = true;
+        B.indel_keys.reserve(np + 1);
+        memcpy(B.indel_keys.p, keys, np * sizeof(int16_t));
+    }
+    v.eng_ = eng;
+    return v;
+}
+
+static std::atomic<long> g_indel_key_fallbacks(0);
+long LikelihoodEngine::indelKeyFallbacks() { return g_indel_key_fallbacks.load(); }
+bool WindowLikelihoods::hasDeviceIndelKeys() const { return blk_ && blk_->has_keys; }
+int WindowLikelihoods::deviceIndelKeys(size_t h, size_t r) const { return blk_->indel_keys[pair(h, r)]; }
+
 int WindowLikelihoods::indelCount(size_t h, size_t r) const
 {
     const BatchBlock &B = *blk_;
     if (!B.faster) return B.numIndels[pair(h, r)];
+    if (B.has_keys) {                      // the device walked hpos (csrc/indel_keys_kernel.h); more than 64 keys: the record, as below
+        const int v = B.indel_keys[pair(h, r)];
+        if (v >= 0) return v;
+        // The recompute-with-alignments path of get(), with an engine of its own: indelCount is called from reduce threads while the
+        // engine that made the block packs its next batch (or is gone), so that engine is not touched.
+        g_indel_key_fallbacks.fetch_add(1);
+        if (!full_) {
+            LikelihoodEngine own(B.params, B.device);
+            own.setLongWindowsFaster(B.long_faster);
+            std::vector<WindowJob> one(1);
+            one[0].haps = haps_; one[0].reads = reads_; one[0].leftPos = leftPos_; one[0].rightPos = leftPos_ + 1;
+            own.runBatch(one, true);
+            if (!one[0].error.empty()) throw one[0].error;
+            full_ = one[0].result.blk_;
+        }
+        MLAlignment ml;
+        fill_record(*full_, 0, h, r, (*haps_)[h], (*reads_)[r], ml);
+        return int(ml.indels.size());
+    }
     if (!B.has_hpos) return int(get(h, r).indels.size());
     // --faster: the size of the record's indel map needs the walk over hpos (rebuildAlignmentFaster), but not the record:
     // the keys that walk would enter — an insertion run's recorded position, a deletion's first base — counted once each
@@ -545,10 +590,12 @@ MLAlignment WindowLikelihoods::get(size_t h, size_t r) const
         std::vector<WindowJob> one(1);
         one[0].haps = haps_; one[0].reads = reads_; one[0].leftPos = leftPos_; one[0].rightPos = leftPos_ + 1;
         const bool keep = eng_->keepAlignments_, cig = eng_->deviceCigars_, rl = eng_->deviceRealign_, dip = eng_->deviceRealignDiploid_;
+        const bool ik = eng_->deviceIndelKeys_;
         eng_->keepAlignments_ = true; eng_->deviceCigars_ = false; eng_->deviceRealign_ = false; eng_->deviceRealignDiploid_ = false;
+        eng_->deviceIndelKeys_ = false;
         try { eng_->runBatch(one, blk_->faster); }
-        catch (...) { eng_->keepAlignments_ = keep; eng_->deviceCigars_ = cig; eng_->deviceRealign_ = rl; eng_->deviceRealignDiploid_ = dip; throw; }
-        eng_->keepAlignments_ = keep; eng_->deviceCigars_ = cig; eng_->deviceRealign_ = rl; eng_->deviceRealignDiploid_ = dip;
+        catch (...) { eng_->keepAlignments_ = keep; eng_->deviceCigars_ = cig; eng_->deviceRealign_ = rl; eng_->deviceRealignDiploid_ = dip; eng_->deviceIndelKeys_ = ik; throw; }
+        eng_->keepAlignments_ = keep; eng_->deviceCigars_ = cig; eng_->deviceRealign_ = rl; eng_->deviceRealignDiploid_ = dip; eng_->deviceIndelKeys_ = ik;
         if (!one[0].error.empty()) throw one[0].error;
         full_ = one[0].result.blk_;
     }
@@ -631,7 +678,7 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
     if (!scratch_) scratch_ = std::make_shared<PackScratch>();
     BatchBlock &B = *blk;
     PackScratch &S = *scratch_;
-    B.W = W; B.faster = faster; B.params = params;
+    B.W = W; B.faster = faster; B.params = params; B.device = device_; B.long_faster = longWindowsFaster_;
     bool any_eager = false;
     for (int w = 0; w < W; w++) if (jobs[w].liks) any_eager = true;
     // device CIGARs: the pairs' CIGARs come back instead of their alignments (main model, lazy jobs only)
@@ -641,7 +688,9 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
     B.has_realign = (deviceRealign_ || deviceRealignDiploid_) && !faster && !any_eager;
     B.has_cigars = deviceCigars_ && !faster && !any_eager && !B.has_realign;
     B.cig_cap = cigarOpsCap_;
-    B.has_hpos = !B.has_cigars && !B.has_realign && (keepAlignments_ || any_eager);
+    // device indel keys: the pairs' indel-map key counts come back instead of their alignments (--faster model, lazy jobs only)
+    B.has_keys = deviceIndelKeys_ && faster && !any_eager;
+    B.has_hpos = !B.has_cigars && !B.has_realign && !B.has_keys && (keepAlignments_ || any_eager);
     const bool pack_ref_pos = B.has_cigars || B.has_realign;
 
     // ---- pack (CSR), pass 1: sizes and offsets.  Per window in parallel (its haplotypes and reads are scattered objects: the pass is
@@ -866,6 +915,7 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
     lastRealignBytes = (B.has_realign ? n_reads * (16 + 4 * size_t(B.cig_cap)) : 0) + (B.has_pairs ? size_t(W) * 36 : 0);
     lastHposBytes = B.has_hpos ? size_t(sz.hpos_len) * sizeof(int16_t) : 0;
     lastCigarBytes = B.has_cigars ? size_t(sz.n_pairs) * (12 + 4 * size_t(B.cig_cap)) : 0;
+    lastIndelKeyBytes = B.has_keys ? size_t(sz.n_pairs) * sizeof(int16_t) : 0;
     dd_params P = to_abi(params);
     if (faster) P.mapUnmappedReads = 0;                 // ObservationModelS has no insert-size prior
     const std::chrono::steady_clock::time_point t_packed = std::chrono::steady_clock::now();
@@ -886,6 +936,11 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
         const int rc = dd_compute_likelihoods_cigars(&P, &Bt, &Rz, S.hap_ref_pos.data(), S.hap_aligned.data(), &Cg, B.cig_cap, device_,
                                                      longWindows_ ? DD_OPT_LONG_WINDOWS : 0u);
         if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_cigars: ") + dd_last_error();
+    } else if (sz.n_pairs > 0 && B.has_keys) {
+        typedef int (*Entry)(const dd_params *, const dd_batch *, dd_result *, int16_t *, int, uint32_t);
+        const int rc = reinterpret_cast<Entry>(indelKeysEntry_)(&P, &Bt, &Rz, B.indel_keys.reserve(np), device_,
+                                                                longWindowsFaster_ ? DD_OPT_LONG_WINDOWS_FASTER : 0u);
+        if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_faster_keys: ") + dd_last_error();
     } else if (sz.n_pairs > 0) {
         const int rc = faster ? (longWindowsFaster_ ? dd_compute_likelihoods_faster_ex(&P, &Bt, &Rz, device_, DD_OPT_LONG_WINDOWS_FASTER)
                                                     : dd_compute_likelihoods_faster(&P, &Bt, &Rz, device_))

@@ -51,7 +51,13 @@ public:
     bool offHapHMQ(size_t h, size_t r) const;
     int numIndels(size_t h, size_t r) const;      // == liks[h][r].indels.size() for the main model (one key per event)
     int indelCount(size_t h, size_t r) const;     // liks[h][r].indels.size() for either model (the --faster model leaves numIndels 0
-                                                  // and may key several events at one position): what DInDel.cpp:3529 reads
+                                                  // and may key several events at one position): what DInDel.cpp:3529 reads.  With
+                                                  // device indel keys it is the device's value; for a pair with more than 64 keys
+                                                  // the window is recomputed with alignments, by an engine of the call's own, and
+                                                  // counted (indelKeyFallbacks())
+    // Device indel keys (LikelihoodEngine::setDeviceIndelKeys): the --faster batch brought one int16 per pair back instead of the alignments
+    bool hasDeviceIndelKeys() const;
+    int deviceIndelKeys(size_t h, size_t r) const;   // the raw value: the count, DD_INDEL_KEYS_OVERFLOW or DD_INDEL_KEYS_NOT_COMPUTED
     int numMismatch(size_t h, size_t r) const;
     int nBQT(size_t h, size_t r) const;
     int nmmBQT(size_t h, size_t r) const;
@@ -116,6 +122,11 @@ public:
                                              const int32_t *status, const int32_t *nOps, const uint32_t *ops, const int32_t *refOff,
                                              const int16_t *hpos, const double *ll = NULL, int pairState = -1, const int32_t *pair = NULL);
     // ... ll (may be NULL: all 0): the pairs' likelihoods, haplotype-major; pairState >= 0: the view also carries a device pair.
+    // A one-window view of the --faster model over hand-made per-base alignments (hpos: haplotype-major, or NULL: none came back) and
+    // hand-made device indel keys (keys: one per pair, haplotype-major, or NULL).  eng: the engine get() recomputes the window with when
+    // the view has no alignments, and whose parameters and device indelCount's own recomputation takes (may be NULL: defaults, device 0).  For tests of indelCount; `haps` and `reads` must outlive it.
+    static WindowLikelihoods handMadeFaster(const std::vector<Haplotype> &haps, const std::vector<Read> &reads, const int16_t *hpos,
+                                            const int16_t *keys, LikelihoodEngine *eng = NULL);
     // all records, as the eager path fills them
     void toLiks(std::vector<std::vector<MLAlignment> > &liks, std::vector<int> &onHap) const;
 
@@ -202,6 +213,15 @@ public:
     // (Defined in device_pair.cpp, which binds the C ABI's entry: a program that stubs the C ABI without that entry and never sets this links.)
     void setDeviceRealignDiploid(bool v, int opsCap = 8);
     bool deviceRealignDiploid() const { return deviceRealignDiploid_; }
+    // true: computeLikelihoodsFasterBatch asks for the pairs' indel-map key counts (dd_compute_likelihoods_faster_keys) INSTEAD of their
+    // per-base alignments: 2 bytes per pair come back instead of 2 L, and WindowLikelihoods::indelCount returns the device's value.  get() on
+    // such a view recomputes the window with alignments, as for setKeepAlignments(false); indelCount does the same, with an engine of its
+    // own (it is called from reduce threads), and only for a pair with more than 64 distinct keys.  --faster model, lazy jobs only: a batch with an eager job, and the main model, run as without it.  Default off.
+    // (Defined in device_indel_keys.cpp, which binds the C ABI's entry, like setDeviceRealignDiploid.)
+    void setDeviceIndelKeys(bool v);
+    bool deviceIndelKeys() const { return deviceIndelKeys_; }
+    // pairs whose indelCount was recomputed with alignments because the device reported more than 64 keys (process-wide, all engines)
+    static long indelKeyFallbacks();
     // optional: have the calling thread's device cache (arena, staging mirror, streams) of this engine's device made now, for batches of
     // about `pairs` (haplotype, read) pairs — e.g. while the first batch is still being prepared.  Throws like the batch calls.
     void warmUp(size_t pairs);
@@ -211,6 +231,7 @@ public:
     // bytes of per-base alignments (hpos) and of CIGAR arrays the last batch call brought back from the device
     size_t lastHposBytes = 0, lastCigarBytes = 0;
     size_t lastRealignBytes = 0;         // ... and of the realigned reads' arrays (setDeviceRealign)
+    size_t lastIndelKeyBytes = 0;        // ... and of the indel-map key counts (setDeviceIndelKeys)
 
     // ObservationModelFBMax::reportVariants (ObservationModelFB.cpp:1351-1475) from the device's hpos: fills
     // hpos, indels, snps, align, firstBase/lastBase, counters and the covered maps.  Exposed for tests.
@@ -235,6 +256,8 @@ private:
     bool deviceRealign_ = false;
     bool deviceRealignDiploid_ = false;
     void (*diploidEntry_)() = nullptr;   // dd_compute_likelihoods_realign_diploid, once setDeviceRealignDiploid has been called
+    bool deviceIndelKeys_ = false;
+    void (*indelKeysEntry_)() = nullptr; // dd_compute_likelihoods_faster_keys, once setDeviceIndelKeys has been called
     int cigarOpsCap_ = 8;
     std::vector<std::shared_ptr<BatchBlock> > spare_;   // result blocks of earlier calls; one nobody references any more is reused (warm pages)
     unsigned spareNext_ = 0;

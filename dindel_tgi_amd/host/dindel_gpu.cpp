@@ -101,6 +101,11 @@
 //                     of being written as skipped windows; no effect with --faster
 //   [--longWindowsFaster]  the same for the --faster model (its own kernel): windows with a haplotype of 767..4,094 bp or a read of
 //                     1,025..4,096 bp are computed instead of being written as skipped windows; effective only with --faster
+//   [--deviceIndelKeys]  with --faster: the one number the window loop needs of a pair's per-base alignment under that model — the size of the
+//                     record's indel map, DInDel.cpp:3529 — is counted on the device behind the likelihood launches and 2 bytes per pair come back
+//                     instead of the alignment's 2 L; a pair with more than 64 distinct keys is recomputed on the host side with alignments
+//                     (indel_key_fallbacks= in the timing line).  PREFIX.glf.txt is the same byte for byte.  The engines then merge as many
+//                     batches per launch as the main model's.  No effect without --faster
 //   [--mergeBatches N] batches already waiting when an engine becomes free ride in its launch, up to N (default 4; 2 when the per-base alignments come back)
 //   [--computeAhead N] prepared batches that may wait for the GPU ahead of the next one to leave (default max(computeThreads + 1, prepareThreads))
 //   tests and diagnostics only:
@@ -195,9 +200,10 @@ struct Options {
     std::vector<int> devices;            // --devices 0,1,...: the engines are dealt out over these GPUs (batches are independent: no exchange between devices)
     bool faster, oneBased, prepareOnly, quiet, timing, longWindows, longWindowsFaster, noLookBack, lateSkipsKnown, windowByWindow;
     bool realignedBAM, deviceCigars, deviceRealign, deviceRealignDiploid, checkDevicePair;
+    bool deviceIndelKeys;                // --faster --deviceIndelKeys: the pairs' indel-map key counts come back instead of their alignments
     bool doPooled, doDiploid, hostEM;    // --doPooled: the pooled lines; the diploid lines too with --doDiploid, or when --doPooled is not given
     PooledParameters pool;               // --bayesa0, --bayesType
-    bool keepAlignments;                 // the per-base alignments come back from the device (--faster; --outputRealignedBAM without --deviceCigars)
+    bool keepAlignments;                 // the per-base alignments come back from the device (--faster without --deviceIndelKeys; --outputRealignedBAM without --deviceCigars)
     std::set<int> injectedLateSkips;
     bool discover;                       // --discover: the discovery stage writes varFile (= disc.windowsFile()) before the loop starts
     DiscoverOptions disc;
@@ -254,6 +260,8 @@ const char *const kHelp =
     "                             also haplotypes > 574 bp) instead of skipping them; main model only: no effect with --faster\n"
     "            [--longWindowsFaster]  with --faster: compute windows with a haplotype > 766 bp or a read > 1024 bp (up to 4,094 / 4,096) instead of\n"
     "                             skipping them; no effect without --faster\n"
+    "            [--deviceIndelKeys]  with --faster: count every pair's indel-map keys on the device and bring 2 bytes per pair back instead of its\n"
+    "                             per-base alignment (same PREFIX.glf.txt); no effect without --faster\n"
     "            [--maxRead N] [--maxReadLength N] [--minReadOverlap N] [--mapQualThreshold X] [--filterReadAux STR] [--pError X] [--pMut X] [--maxLengthIndel N]\n"
     "            [--flankRefSeq N] [--flankMaxMismatch N] [--priorSNP X] [--priorIndel X] [--capMapQualThreshold X] [--capMapQualFast X] [--maxHapReadProd N]\n"
     "  running:  [--batchWindows N] [--mergeBatches N] [--device D | --devices D0,D1,...] [--prepareThreads N] [--computeThreads N] [--packThreads N] [--reduceThreads N]\n"
@@ -261,7 +269,7 @@ const char *const kHelp =
     "  files:    --varFile: the reference's window file; --hapFile: W / H / V / A records (host/window_io.hpp)\n";
 // the options without a value; any other --NAME takes the next argument as its value, whatever its name
 const char *const kFlags[] = {"varFileIsOneBased", "faster", "filterHaplotypes", "quiet", "doDiploid", "timing", "outputRealignedBAM", "prepareOnly", "noLookBack",
-                              "lateSkipsKnown", "windowByWindow", "doPooled", "hostEM", "longWindows", "longWindowsFaster", "deviceCigars", "deviceRealign", "deviceRealignDiploid", "checkDevicePair", "changeINStoN", "hostDistribution", "hostConvert", "discover", "useLibraries", "vcfCandidatesOnly"};
+                              "lateSkipsKnown", "windowByWindow", "doPooled", "hostEM", "longWindows", "longWindowsFaster", "deviceCigars", "deviceRealign", "deviceRealignDiploid", "checkDevicePair", "deviceIndelKeys", "changeINStoN", "hostDistribution", "hostConvert", "discover", "useLibraries", "vcfCandidatesOnly"};
 
 std::vector<int> commaInts(const std::string &list)      // "3,5,,8" -> 3 5 8
 {
@@ -377,7 +385,8 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
         if (has("pooledGlf")) o.pooledGlfFile = opt["pooledGlf"];
         try { o.pooledVcf.numSamples = int(pytext::pyInt(opt["numSamples"])); } catch (const std::string &e) { std::cerr << "--numSamples: " << e << "\n"; return false; }
     }
-    o.keepAlignments = o.faster || (o.realignedBAM && !o.deviceCigars && !o.deviceRealign && !o.deviceRealignDiploid);           // (the --faster model's indel count, DInDel.cpp:3529, needs hpos)
+    o.deviceIndelKeys = o.faster && has("deviceIndelKeys");                       // modifies --faster only
+    o.keepAlignments = (o.faster && !o.deviceIndelKeys) || (o.realignedBAM && !o.deviceCigars && !o.deviceRealign && !o.deviceRealignDiploid);           // (the --faster model's indel count, DInDel.cpp:3529, needs hpos, or the device's count of its keys)
     o.cigarOpsCap = std::max(1, int(num("cigarOpsCap", 8)));
     ObservationModelParameters &obs = o.obs;
     obs.setCLIDefaultValues();
@@ -426,7 +435,8 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     // them): the host stages keep their small batches, the GPU gets the larger launches it runs better (42.5 us per window in a launch of
     // 256 windows, 41.3 in one of 1,024, and one kernel boundary instead of four)
     // (default 4; 2 when the per-base alignments come back too: the page-locked result blocks of such a launch are 0.4 GB each, and
-    // making them costs a 100,000-window run more than the launches save it; with --deviceCigars a realigned-BAM run brings none back: 4 again)
+    // making them costs a 100,000-window run more than the launches save it; with --deviceCigars a realigned-BAM run brings none back: 4 again;
+    // nor does --faster with --deviceIndelKeys)
     o.mergeBatches = std::max(1, int(num("mergeBatches", o.keepAlignments ? 2 : 4)));
     const std::vector<int> inject = commaInts(has("injectLateSkip") ? opt["injectLateSkip"] : std::string());
     o.injectedLateSkips.insert(inject.begin(), inject.end());
@@ -504,6 +514,7 @@ private:
         std::atomic<long> cigarFallbacks;      // reads redone with getCIGAR on the host (--deviceCigars)
         std::atomic<long long> hposBytes, cigarBytes, fallbackHposBytes;   // what the engines brought back from the device
         std::atomic<long long> realignBytes;   // ... of the realigned reads' arrays (--deviceRealign, --deviceRealignDiploid)
+        std::atomic<long long> indelKeyBytes{0};   // ... of the indel-map key counts (--deviceIndelKeys)
         std::atomic<long> pairUncertified{0}, pairFallbackReads{0}, pairDisagreements{0};   // --deviceRealignDiploid, of the windows written: done on the host, reads redone there, --checkDevicePair
         long windows, skipped, rePrepared;     // the writer's
         std::vector<std::pair<double, long> > progress;   // the writer's: (seconds since start, windows written) after every batch
@@ -586,6 +597,7 @@ void WindowLoop::configureStageEngine(LikelihoodEngine &engine) const
     engine.setDeviceRealignDiploid(opt.deviceRealignDiploid, opt.cigarOpsCap);
     engine.setLongWindows(opt.longWindows);
     engine.setLongWindowsFaster(opt.longWindowsFaster);
+    if (opt.deviceIndelKeys) engine.setDeviceIndelKeys(true);
 }
 
 // (c) --deviceCigars: a read's CIGAR did not fit, its window is computed once more for the per-base alignments.  The engine must bring those
@@ -827,6 +839,7 @@ void WindowLoop::computeWorker(int ct)
                 }
                 n.packOf[size_t(ct)] += engine.lastPackSeconds; n.deviceOf[size_t(ct)] += engine.lastDeviceSeconds; n.unpackOf[size_t(ct)] += engine.lastUnpackSeconds;
                 n.hposBytes += (long long)engine.lastHposBytes; n.cigarBytes += (long long)engine.lastCigarBytes; n.realignBytes += (long long)engine.lastRealignBytes;
+                n.indelKeyBytes += (long long)engine.lastIndelKeyBytes;
                 n.launches++;
             }
             n.computeOf[size_t(ct)] += seconds_since(t0);
@@ -986,6 +999,7 @@ void WindowLoop::rePrepare(WindowTask &T)
         one.push_back(T.job());
         if (opt.faster) redo.engine->computeLikelihoodsFasterBatch(one); else redo.engine->computeLikelihoodsBatch(one);
         n.hposBytes += (long long)redo.engine->lastHposBytes; n.cigarBytes += (long long)redo.engine->lastCigarBytes; n.realignBytes += (long long)redo.engine->lastRealignBytes;
+        n.indelKeyBytes += (long long)redo.engine->lastIndelKeyBytes;
     }
     reduceWindow(T, one.empty() ? NULL : &one[0]);
     redo.fetcher->windowDone(T.skipped, T.fileLeftPos);
@@ -1166,6 +1180,8 @@ void WindowLoop::report()                                 // --timing: one line;
     if (opt.deviceRealign || opt.deviceRealignDiploid) std::cout << " realign_bytes=" << n.realignBytes.load();
     if (opt.deviceRealignDiploid) std::cout << " pair_uncertified=" << n.pairUncertified.load() << " pair_fallback_reads=" << n.pairFallbackReads.load();
     if (opt.checkDevicePair) std::cout << " pair_disagreements=" << n.pairDisagreements.load();
+    // --deviceIndelKeys: bytes of key counts brought back, and pairs over 64 keys whose window was recomputed with alignments
+    if (opt.deviceIndelKeys) std::cout << " indel_key_bytes=" << n.indelKeyBytes.load() << " indel_key_fallbacks=" << LikelihoodEngine::indelKeyFallbacks();
     // when the first batch and the first 1 / 5 / 20 / 50 / 100 % of the windows were written (seconds since start)
     std::cout << " engines_ready_at=";
     for (size_t i = 0; i < n.readyAt.size(); i++) std::cout << (i ? "," : "") << n.readyAt[i];

@@ -999,4 +999,20 @@ int ddh_hash_map_order(const int *keys, int n, int *out)
     return int(order.size());
 }
 
+// ---- the --faster model's indel count, as the adapter's own walk over hpos gives it -------------------------------------------------------
+// WindowLikelihoods::indelCount of a one-pair --faster view over hp[0..L): the walk with its 64-key list, and behind it the record's indel
+// map (rebuildAlignmentFaster) when the list spills.  CPU only.  The haplotype is long enough for every position an int16 can hold.
+int ddh_indel_count_walk(const short *hp, int L)
+{
+    try {
+        std::vector<Haplotype> haps(1, Haplotype(std::string(32768, 'A')));
+        std::vector<Read> reads(1);
+        reads[0].seq.seq = std::string(size_t(L > 0 ? L : 0), 'A');
+        reads[0].qual.assign(size_t(L > 0 ? L : 0), 0.99);
+        return WindowLikelihoods::handMadeFaster(haps, reads, hp, NULL).indelCount(0, 0);
+    } catch (std::string &) {
+        return -1000;
+    }
+}
+
 } // extern "C"

@@ -825,6 +825,33 @@ int dd_pooled_em_host(const dd_batch *b, const double *ll_host, const dd_pooled_
 /* pooled_math.h's functions over an array (host): fn 0 = exp, 1 = log, 2 = digamma; fn 3 = addLogs over pairs x[2i], x[2i + 1]. */
 int dd_pooled_math_eval(int fn, const double *x, double *y, int64_t n);
 
+/* ---- the --faster model's indel-map key count on the device (opt-in) ------------------------ */
+/* The --faster model (ObservationModelS) leaves dd_result.numIndels 0; what the reference's window loop reads per pair is
+ * liks[h][r].indels.size() (DInDel.cpp:3529), the number of DISTINCT keys reportVariants enters into the record's indel map
+ * (Faster.cpp:553-661).  That number follows from the pair's hpos alone (csrc/indel_keys_kernel.h is the definition):
+ *     lhp = 1; walk b upward from 0.  hp[b] inserted (DD_HPOS_IS_INS): take the maximal run of such entries; with c its first entry the
+ *     key is DD_HPOS_INS_POS(c), or lhp when c is the bare DD_HPOS_INS; continue behind the run.  Otherwise, with c = hp[b]: c >= 0 sets
+ *     lhp = c + 1, and if also b < L-1, hp[b+1] >= 0 and hp[b+1] - c > 1 the key is c + 1; then b++.
+ * Computed on the device from the hpos the likelihood kernels left there, 2 bytes per pair come back instead of the pair's 2 L bytes of
+ * hpos.  One int16 per pair, in pair order: the count when it is at most DD_INDEL_KEYS_CAP, DD_INDEL_KEYS_OVERFLOW when there are more
+ * distinct keys, DD_INDEL_KEYS_NOT_COMPUTED for a pair whose dd_result.status is not DD_PAIR_OK (its hpos is not read).  Any int16
+ * content of hpos gives the same answer on the device and on the host. */
+#define DD_INDEL_KEYS_CAP           64
+#define DD_INDEL_KEYS_OVERFLOW      (-1)
+#define DD_INDEL_KEYS_NOT_COMPUTED  (-2)
+/* Enqueue the launch for the whole batch on `stream`, behind the likelihood launch(es) that wrote hpos_dev and status_dev (any of them:
+ * hpos is only read).  DEVICE pointers: hpos_dev (dd_result.hpos), status_dev (dd_result.status; NULL = every pair was computed), out_dev
+ * (int16 [n_pairs]).  Of the batch it reads n_windows, n_haps, n_reads, win_read_off, read_seq_off, win_pair_off and win_hpos_off.
+ * Asynchronous, no allocation, no synchronisation. */
+int dd_indel_keys_device(const dd_device_batch *b, const int16_t *hpos_dev, const int32_t *status_dev, int16_t *out_dev, void *stream);
+/* The same values on the CPU from host arrays, no device needed: pairs spread over nthreads host threads (< 1: one).  Of the batch it
+ * reads n_windows and the four offset arrays (win_hap_off, win_read_off, hap_seq_off, read_seq_off). */
+int dd_indel_keys_host(const dd_batch *b, const int16_t *hpos_host, const int32_t *status_host, int16_t *out, int nthreads);
+/* Host pointers: dd_compute_likelihoods_faster_ex (options: 0 or DD_OPT_LONG_WINDOWS_FASTER) with, per window block, the key launch behind
+ * the block's likelihood launches; keys_out (int16 [n_pairs], host memory) is filled.  r->hpos may be NULL: the per-base alignments then
+ * stay on the device — the point of this entry.  Everything else as dd_compute_likelihoods_faster_ex. */
+int dd_compute_likelihoods_faster_keys(const dd_params *p, const dd_batch *b, dd_result *r, int16_t *keys_out, int device, uint32_t options);
+
 /* Launch plan the library would use for the main kernel on a batch with these maxima (no device needed):
  * out = {K positions per lane, D build (6 / 11 / 12), 1 if back-pointers go to HBM scratch else 0, waves per workgroup,
  *        read split of a haplotype, LDS bytes per workgroup, scratch bytes (low 31 bits, in KiB), waves per CU the plan expects,
