@@ -42,6 +42,13 @@ inline int check_params(const dd_params *p)
     if (p->forceReadOnHaplotype) return fail(DD_ERR_UNSUPPORTED, "forceReadOnHaplotype is not on the production path (DInDel.cpp:1446 only)");
     if (p->maxLengthDel < 0 || p->maxLengthDel > DD_MAX_LENGTH_DEL) return fail(DD_ERR_UNSUPPORTED, "maxLengthDel outside [0,31]");
     if (!(p->pError > 0.0 && p->pError < 1.0)) return fail(DD_ERR_INVALID, "pError outside (0,1)");
+    // each of these would put a NaN into dd_build_tables' output (log of a negative number, pow of a NaN), and the kernels' dmax() is
+    // defined for non-NaN doubles only; the negated compares refuse a NaN field too
+    if (!(p->pMut >= 0.0 && p->pMut <= 1.0)) return fail(DD_ERR_INVALID, "pMut outside [0,1]");
+    if (!(p->pFirstgLO >= 0.0 && p->pFirstgLO <= 1.0)) return fail(DD_ERR_INVALID, "pFirstgLO outside [0,1]");
+    if (!(p->mapQualThreshold >= 0.0)) return fail(DD_ERR_INVALID, "mapQualThreshold negative or NaN");
+    if (!(p->capMapQualFast >= 0.0)) return fail(DD_ERR_INVALID, "capMapQualFast negative or NaN");
+    if (p->checkBaseQualThreshold != p->checkBaseQualThreshold) return fail(DD_ERR_INVALID, "checkBaseQualThreshold is NaN");
     return DD_SUCCESS;
 }
 

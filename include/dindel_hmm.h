@@ -81,7 +81,10 @@ extern "C" {
 #define DD_MAX_QUAL_TABLE   256
 #define DD_HP_TABLE          64   /* homopolymer run lengths >= 52 are all capped at 0.99            */
 
-/* Mirrors the fields of ObservationModelParameters the path reads — ObservationModel.hpp:28-99. */
+/* Mirrors the fields of ObservationModelParameters the path reads — ObservationModel.hpp:28-99.
+ * Every entry point that takes a dd_params refuses, with DD_ERR_INVALID and a dd_last_error() that names the field, a value that would put
+ * a NaN into the tables of dd_build_tables: pError outside (0,1); pMut or pFirstgLO outside [0,1]; mapQualThreshold or capMapQualFast
+ * negative; a NaN in any of these or in checkBaseQualThreshold.  (maxLengthDel outside [0,31] and forceReadOnHaplotype: DD_ERR_UNSUPPORTED.) */
 typedef struct dd_params {
     double  pError;                  /* probability of a read indel                                  */
     double  pMut;                    /* probability of a mutation in the read                        */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Long randomised GPU-vs-oracle parity campaign (both models), beyond what the test-suite budget allows.
   python tests/fuzz_campaign.py [--seconds 300] [--seed0 0]
-Every round draws a shape class, parameters and adversarial windows (tests/test_gpu_fuzz.make_windows — one round in four of
+Every round draws a shape class, parameters (one round in five: a set of tests/_param_cases.py on top) and adversarial windows (tests/test_gpu_fuzz.make_windows — one round in four of
 that kind takes the path scenarios of tests/_path_scenarios.py instead — plus synth.generate mixes), runs the C ABI and
 the oracle (16 threads) and requires bit-equality.  Prints one line per round ("kind 0s": a scenario round); exits non-zero at the first mismatch after dumping the seed."""
 import argparse
@@ -17,6 +17,7 @@ from dindel_tgi_amd.batch import pack
 from tests import _oracle
 from tests.test_gpu_fuzz import make_windows
 from tests._path_scenarios import scenario_windows
+from tests._param_cases import PARAM_SETS
 from tests.test_gpu_parity import assert_same, run_host_api
 from tests.test_gpu_faster import assert_same_faster, run_faster
 
@@ -45,6 +46,12 @@ while time.time() < t_end:
     p.capMapQualFast = float(rng.choice([45.0, 40.0, 5.0, 300.0]))
     if rng.random() < 0.15:
         p.bMid = int(rng.integers(0, 30))
+    prng = np.random.default_rng(90000 + seed)                          # (a stream of its own: the draws above and below stay what they were)
+    p.pFirstgLO = float(prng.choice([0.01, 1e-6, 0.5]))
+    p.checkBaseQualThreshold = float(prng.choice([0.95, 0.0, 0.5, 1.0]))
+    pset = str(prng.choice(list(PARAM_SETS))) if prng.random() < 0.2 else "-"   # one round in five: a set of tests/_param_cases.py on top
+    for k, v in PARAM_SETS.get(pset, {}).items():
+        setattr(p, k, v)
     if kind == 0:
         max_hap = int(rng.choice([23, 40, 62, 87, 126, 151, 190, 215, 254, 400, 755]))   # make_windows adds up to 7 inserted bases; every lane tiling incl. the half-wave ones
         if p.maxLengthDel > 11 and max_hap > 560:
@@ -125,7 +132,7 @@ while time.time() < t_end:
         print(str(e)[:2000], flush=True)
         sys.exit(1)
     pairs += pb.n_pairs
-    print("round %d seed %d kind %s pairs %d (total %d) max_hap %d max_read %d mld %d ok" %
-          (rnd, seed, "0s" if kind == 0 and scenario else kind, pb.n_pairs, pairs, pb.max_hap_len, pb.max_read_len, p.maxLengthDel), flush=True)
+    print("round %d seed %d kind %s pairs %d (total %d) max_hap %d max_read %d mld %d set %s ok" %
+          (rnd, seed, "0s" if kind == 0 and scenario else kind, pb.n_pairs, pairs, pb.max_hap_len, pb.max_read_len, p.maxLengthDel, pset), flush=True)
     rnd += 1
 print("campaign ok: %d rounds, %d pairs per model" % (rnd, pairs))

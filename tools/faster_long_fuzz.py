@@ -2,7 +2,7 @@
 """Randomised GPU-vs-oracle parity campaign of the --faster model's long-window path (DD_OPT_LONG_WINDOWS_FASTER), in the style of
 tools/long_window_fuzz.py.
   python tools/faster_long_fuzz.py [--seconds 300] [--seed0 0] [--out profiles/r06/faster_long_fuzz.json]
-Every round draws parameters (maxLengthDel 0..31, padCover, maxMismatch) and a batch that mixes long windows (haplotypes of 767..4,094 bp
+Every round draws parameters (maxLengthDel 0..31, padCover, maxMismatch; one round in five a set of tests/_param_cases.py on top) and a batch that mixes long windows (haplotypes of 767..4,094 bp
 and / or reads of 1,025..4,096 bp; reads from 36 bp) with ordinary ones, runs dd_compute_likelihoods_faster_ex and the oracle's --faster
 model (16 threads) and requires every dd_result field bit-equal.  A draw that holds a window beyond the long limits (a variant haplotype
 past 4,094 bp) is not run and counted apart.  One line per round; at the first mismatch the seed is printed and the exit code is 1."""
@@ -21,6 +21,7 @@ from dindel_tgi_amd.batch import alloc_result
 from tests import _oracle
 from tests.test_gpu_faster import assert_same_faster
 from tests.test_gpu_parity import assert_same
+from tests._param_cases import PARAM_SETS
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--seconds", type=float, default=300)
@@ -38,6 +39,10 @@ while time.time() < t_end:
     rng = np.random.default_rng(60000 + seed)
     p = capi.params_cli_defaults() if rng.random() < 0.5 else capi.params_struct_defaults()
     p.maxLengthDel = int(rng.integers(0, 32))
+    prng = np.random.default_rng(90000 + seed)                          # (a stream of its own: the other draws stay what they were)
+    pset = str(prng.choice(list(PARAM_SETS))) if prng.random() < 0.2 else "-"   # one round in five: a set of tests/_param_cases.py on top
+    for k, v in PARAM_SETS.get(pset, {}).items():
+        setattr(p, k, v)
     p.padCover = int(rng.integers(0, 6))
     p.maxMismatch = int(rng.integers(0, 4))
     kind = int(rng.integers(0, 3))
@@ -80,7 +85,7 @@ while time.time() < t_end:
     pairs += pb.n_pairs
     long_pairs += nl
     shapes.append([kind, hs, L, p.maxLengthDel, nl])
-    print("round %d seed %d kind %d hap %d read %d mld %d: %d pairs (%d long) ok" % (rounds, seed, kind, hs, L, p.maxLengthDel, pb.n_pairs, nl), flush=True)
+    print("round %d seed %d kind %d hap %d read %d mld %d set %s: %d pairs (%d long) ok" % (rounds, seed, kind, hs, L, p.maxLengthDel, pset, pb.n_pairs, nl), flush=True)
 summary = dict(ok=ok, seconds=round(time.time() - t0, 1), rounds=rounds, draws_not_run=skipped, pairs=pairs, long_pairs=long_pairs,
                max_hap=max([s[1] for s in shapes] or [0]), max_read=max([s[2] for s in shapes] or [0]),
                kinds={str(k): sum(1 for s in shapes if s[0] == k) for k in range(3)},

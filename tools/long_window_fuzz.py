@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Randomised GPU-vs-oracle parity campaign of the long-window path (DD_OPT_LONG_WINDOWS), in the style of tests/fuzz_campaign.py.
   python tools/long_window_fuzz.py [--seconds 600] [--seed0 0] [--out profiles/r05/long_window_fuzz.json]
-Every round draws parameters (maxLengthDel 0..31, padCover, maxMismatch, bMid; in a quarter of the rounds mapUnmappedReads with mate
+Every round draws parameters (maxLengthDel 0..31, padCover, maxMismatch; one round in five a set of tests/_param_cases.py on top, bMid; in a quarter of the rounds mapUnmappedReads with mate
 arrays and two insert-size libraries) and a batch that mixes long windows (haplotypes of 575..4,094 bp, reads of 36..4,096 bp) with ordinary
 ones, runs dd_compute_likelihoods_ex and the oracle (16 threads) and requires every dd_result field bit-equal.  A draw that holds a window
 the long path does not take either (a variant haplotype past 4,094 bp) is not run and counted apart.  One line per round; at the first
@@ -20,6 +20,7 @@ from dindel_tgi_amd import capi, synth
 from dindel_tgi_amd.batch import PackedBatch, alloc_result
 from tests import _oracle
 from tests.test_gpu_parity import assert_same
+from tests._param_cases import PARAM_SETS
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--seconds", type=float, default=600)
@@ -37,6 +38,10 @@ while time.time() < t_end:
     rng = np.random.default_rng(90000 + seed)
     p = capi.params_cli_defaults() if rng.random() < 0.5 else capi.params_struct_defaults()
     p.maxLengthDel = int(rng.integers(0, 32))
+    prng = np.random.default_rng(90000 + seed)                          # (a stream of its own: the other draws stay what they were)
+    pset = str(prng.choice(list(PARAM_SETS))) if prng.random() < 0.2 else "-"   # one round in five: a set of tests/_param_cases.py on top
+    for k, v in PARAM_SETS.get(pset, {}).items():
+        setattr(p, k, v)
     p.padCover = int(rng.integers(0, 6))
     p.maxMismatch = int(rng.integers(0, 4))
     p.bMid = -1 if rng.random() < 0.8 else int(rng.integers(0, 2000))
@@ -96,8 +101,8 @@ while time.time() < t_end:
     long_pairs += nl
     cells += pb.cells
     shapes.append([kind, hs, L, p.maxLengthDel, nl])
-    print("round %d seed %d kind %d hap %d read %d mld %d%s: %d pairs (%d long) ok" % (rounds, seed, kind, hs, L, p.maxLengthDel,
-          " mates" if with_mates else "", pb.n_pairs, nl), flush=True)
+    print("round %d seed %d kind %d hap %d read %d mld %d set %s%s: %d pairs (%d long) ok" % (rounds, seed, kind, hs, L, p.maxLengthDel,
+          pset, " mates" if with_mates else "", pb.n_pairs, nl), flush=True)
 summary = dict(ok=ok, seconds=round(time.time() - t0, 1), rounds=rounds, rounds_with_mates=mate_rounds, draws_not_run=skipped, pairs=pairs, long_pairs=long_pairs, cells=cells,
                max_hap=max([s[1] for s in shapes] or [0]), max_read=max([s[2] for s in shapes] or [0]),
                kinds={str(k): sum(1 for s in shapes if s[0] == k) for k in range(4)},
