@@ -94,6 +94,27 @@ __device__ __forceinline__ double dmax(double a, double b)
     return r;
 }
 
+// The hysteresis step `if (val > thr) { best = val; ch = CODE; }` (thr = best + EPS, formed by the caller so that the compiler schedules
+// the add) without a select: the compare writes EXEC, two moves run under it, the scalar unit puts the mask back.  3 VALU instructions
+// instead of compare + 3 v_cndmask_b32, and nothing on the VALU reads the compare's SGPR result, so the two wait states between a
+// VALU write of VCC and a VALU read of it are not needed.  The same ordered compare on the same operands: -inf against -inf and any
+// difference <= EPS stay "not taken".  The statement saves the CURRENT mask (the half-wave builds run it under a narrowed one); lanes
+// outside it are untouched.  v_cmpx of this target writes VCC as well: clobbered.
+// Wait states (CDNA4 ISA, "manually inserted wait states"; the compiler pads nothing inside an asm statement): the rows with a VALU write
+// of EXEC as producer have a DPP instruction (5 states) and v_readlane / v_writelane (4 states) as consumers only — the two moves inside
+// are neither, so v_cmpx -> move under the new mask needs none; the row "VALU writes SGPR/VCC -> VALU reads it" (2 states, the s_nop of the
+// select form) has no reader here; an SALU write of EXEC followed by a VALU instruction has no row (interlocked), so the code behind the
+// statement needs none for the restore.  Behind the statement three instructions already separate the v_cmpx from whatever the compiler
+// places next: a lane or DPP instruction FIRST behind it would be one state short, and a pad for that case costs half of what the step
+// gains (profiles/r11/valu_rate.txt), so instead `make check-spills` (tools/check_exec_spills.py check_cmpx) fails such a build.
+// The code must be a constant once the candidate loops are unrolled ("i"): as a register operand the compiler materialises it per step.
+__device__ __forceinline__ void take_if_above(double &best, unsigned &ch, double val, double thr, unsigned code)
+{
+    unsigned long long keep;
+    asm("s_mov_b64 %2, exec\n\tv_cmpx_gt_f64 vcc, %3, %4\n\tv_mov_b64 %0, %3\n\tv_mov_b32 %1, %5\n\ts_mov_b64 exec, %2"
+        : "+v"(best), "+v"(ch), "=&s"(keep) : "v"(val), "v"(thr), "i"(code) : "vcc");
+}
+
 // G pairs per wavefront (G = 1 or 2): a pair's states live on a group of W = 64 / G consecutive lanes.  The cross-lane steps of a pair
 // stay inside its group: xor-shuffles with offsets below W, the group's W bits of a ballot.  Control flow may diverge BETWEEN the two
 // groups of a wavefront (different reads), never inside one: every lane of a group holds the same per-read values.
@@ -293,6 +314,13 @@ __global__ void __launch_bounds__(DD_WAVES * 64, OCC ? OCC : DD_MIN_WAVES_PER_SI
     // once-per-pair code is 8 % of their instructions (K >= 3 and D >= 11 spend proportionally more in the sweeps), and in the other builds
     // the changed register allocation brought the ROCm 7.2 spill placement fault (tools/check_exec_spills.py) back into three of them.
     constexpr bool LANE_OUT = K <= 2 && D <= 7;
+    // PRED_STEP: the builds whose "> best + EPS" steps of the two sweeps are take_if_above (compare to EXEC + predicated moves) instead of
+    // compare + selects.  A family gets it only with a clean `make check-spills` and an A/B point of its own that does not lose.
+#ifdef DD_PRED_STEP_ALL   // diagnostic builds (tools/ab_build.sh): the step in every build with unrolled candidates, to A/B a family before it joins the rule
+    constexpr bool PRED_STEP = !BIGD;
+#else
+    constexpr bool PRED_STEP = K <= 2 && D <= 7 && G == 1;
+#endif
     STAMP_INIT;
 
     // ======================= loop over this workgroup's (haplotype, read-slice) items =======================
@@ -781,16 +809,22 @@ __global__ void __launch_bounds__(DD_WAVES * 64, OCC ? OCC : DD_MIN_WAVES_PER_SI
 #pragma unroll
                     for (int y = 2; y <= D; y++) {
                         const double val = (cinc(k, y) + v[k + y]) + ov[k + y];
+                        if constexpr (PRED_STEP) take_if_above(best, ch, val, best + DD_EPS, (unsigned)y << sh);
+                        else {
                         const bool take = val > best + DD_EPS;     // newIdx > destIdx: branch 1 only
                         best = take ? val : best;
                         ch = take ? ((btacc_t)y << sh) : ch;
+                        }
                     }
                     }
                     {
                         const double val = (eq + in[k]) + eInc[k]; // to inserted state numS+x (:1746-1749)
+                        if constexpr (PRED_STEP) take_if_above(best, ch, val, best + DD_EPS, 0u);
+                        else {
                         const bool take = val > best + DD_EPS;
                         best = take ? val : best;
                         ch = take ? (btacc_t)0 : ch;
+                        }
                     }
                     na[k] = best;
                     const double d = (eq + in[k]) + II;            // (:1754-1758)
@@ -964,9 +998,12 @@ __global__ void __launch_bounds__(DD_WAVES * 64, OCC ? OCC : DD_MIN_WAVES_PER_SI
                     {
                         const double ip = (k == 0) ? im1 : in[k > 0 ? k - 1 : 0];
                         const double val = (eq + ip) + eIn[k];     // from inserted state numS+x-1 (:1807-1811)
+                        if constexpr (PRED_STEP) take_if_above(best, ch, val, best + DD_EPS, 0u);
+                        else {
                         const bool take = val > best + DD_EPS;     // newIdx > destIdx: branch 1 only
                         best = take ? val : best;
                         ch = take ? (btacc_t)0 : ch;
+                        }
                     }
                     na[k] = best;
                     const double d = (eq + in[k]) + II;            // stay inserted (:1816-1820)

@@ -18,7 +18,12 @@ stands between the block's label and the instruction of the same block that swit
 straight-line `s_and_saveexec_b64 ... s_or_b64 exec, exec` region without the region having written its source (check_regions: the second form the
 fault took, two instructions in front of the restore and no label in between).  Exit status 1 if any kernel has one.  It knows these two forms, not
 the fault in general; `--broad` lists every spill store at a deeper exec nesting than its source's last write instead — candidates to
-read, false positives included, exit status 0."""
+read, false positives included, exit status 0.
+
+A second check rides along since the predicated hysteresis step (hmm_kernel.hip take_if_above: `v_cmpx` inside an inline-asm statement, which the
+compiler's hazard recognizer does not see into): a VALU write of EXEC needs 4 wait states before a v_readlane / v_writelane and 5 before a DPP
+instruction.  check_cmpx reports every such consumer that stands closer than that behind a `v_cmpx` (three instructions of the statement already
+lie between; the compiler has never placed one there, and a build in which it does fails here instead of computing wrong values)."""
 import re
 import sys
 
@@ -165,6 +170,32 @@ def check_regions(body):
     return found
 
 
+def check_cmpx(body):
+    """v_cmpx (a VALU write of EXEC) followed by v_readlane / v_writelane within 4 wait states or by a DPP instruction within 5, counted along
+    the straight listing (an instruction is one state, `s_nop N` is N + 1; a label or a branch ends the count: too far for a hazard to reach
+    in this code, where a join is followed by scalar code)."""
+    found, since, at = [], None, None
+    for l in body:
+        s = l.split(";")[0].strip()
+        if not s or (s.startswith(".") and not s.startswith(".LBB")):
+            continue
+        if s.startswith(".LBB"):
+            since = None
+            continue
+        parts = s.split(None, 1)
+        op, args = parts[0], (parts[1] if len(parts) > 1 else "")
+        if since is not None:
+            need = 4 if op in ("v_readlane_b32", "v_writelane_b32") else 5 if ("_dpp" in op or "row_" in args or "quad_perm" in args) else 0
+            if since < need:
+                found.append((at, [s], "%d wait state(s), %d needed" % (since, need)))
+            since += int(args, 0) + 1 if op == "s_nop" else 1
+            if since >= 5 or op.startswith(("s_cbranch", "s_branch")):
+                since = None
+        if op.startswith("v_cmpx"):
+            since, at = 0, s
+    return found
+
+
 def broad_scan(body):
     """--broad: every spill store that runs at a deeper exec nesting than the last write of its source register (nesting counted along the straight
     listing: `s_and_saveexec` / saved-and-narrowed `s_mov_b64 exec` open a level, `s_or_b64 exec, exec, <that mask>` closes it).  A superset of the two
@@ -182,6 +213,8 @@ def broad_scan(body):
             stack.append(ops[0]); continue
         if op == "s_mov_b64" and a.endswith(",exec"):
             last_save = ops[0]; continue
+        if op.startswith("v_cmpx") and last_save is not None and last_save not in stack:
+            stack.append(last_save); continue              # exec saved, then narrowed by a compare: closed by `s_mov_b64 exec, <that mask>`
         if op == "s_mov_b64" and a.startswith("exec,"):
             if ops[1] in stack:
                 while stack and stack[-1] != ops[1]: stack.pop()
@@ -231,9 +264,14 @@ def main():
     for path in sys.argv[1:]:
         for name, body in kernels(path):
             f = check(body) + check_regions(body)
+            h = check_cmpx(body)
+            if h:
+                print("%s: %s: %d lane / DPP instruction(s) too close behind a v_cmpx" % (path.split("/")[-1], name, len(h)))
+            if f:
+                print("%s: %s: %d block(s) with spill code in front of the exec restore" % (path.split("/")[-1], name, len(f)))
+            f += h
             if f:
                 bad += 1
-                print("%s: %s: %d block(s) with spill code in front of the exec restore" % (path.split("/")[-1], name, len(f)))
                 for block, pend, restore in f[:6]:
                     print("    %s: %s  |  %s" % (block, "; ".join(pend[:4]) + (" ..." if len(pend) > 4 else ""), restore))
     print("kernels with the pattern: %d" % bad)

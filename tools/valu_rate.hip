@@ -15,14 +15,17 @@
 #define ITER 2000
 
 // LANES < 64: the timed loop runs under an EXEC mask of the wave's first LANES lanes (what the HMM kernel's one-lane LO / RO blocks do)
-template <int OP, int LANES = 64>
+// TAKE (OPs 17-19): which lanes' compare comes out true, through the lane's threshold term — 0: none (+inf), 1: lane 0 only, 2: all (-inf)
+template <int OP, int LANES = 64, int TAKE = 0>
 __global__ void __launch_bounds__(1024) rate_kernel(double *out, unsigned long long *cyc, double seed)
 {
     double a[8], b[8];
     unsigned u[8];
     float f[8];
     for (int i = 0; i < 8; i++) { a[i] = seed * (i + 1) + threadIdx.x * 1e-9; b[i] = -seed * (i + 2); u[i] = threadIdx.x + i; f[i] = float(i) + float(seed); }
-    if (OP >= 14 && OP <= 16)
+    double eps = (TAKE == 2 || (TAKE == 1 && (threadIdx.x & 63) == 0)) ? -__builtin_huge_val() : __builtin_huge_val();
+    asm volatile("" : "+v"(eps));
+    if (OP >= 14 && OP <= 19)
         asm volatile("v_mov_b64 v[100:101], %0\n v_mov_b64 v[108:109], %1\n v_mov_b32 v106, 0\n v_mov_b32 v114, 0" : : "v"(b[0]), "v"(b[1])
                      : "v100", "v101", "v106", "v108", "v109", "v114");
     __syncthreads();
@@ -114,6 +117,29 @@ __global__ void __launch_bounds__(1024) rate_kernel(double *out, unsigned long l
                           : "vcc", "v100", "v101", "v104", "v105", "v106");
                 REP8(X)
 #undef X
+            } else if (OP == 17) {     // OP 14 with the threshold term per lane (eps, see TAKE): the select form of the step under a known take pattern
+#define X(i) asm volatile("v_add_f64 v[104:105], %0, %1\n v_add_f64 v[104:105], v[104:105], %2\n v_add_f64 v[102:103], v[100:101], %3\n" \
+                          "v_cmp_gt_f64 vcc, v[104:105], v[102:103]\n s_nop 1\n" \
+                          "v_cndmask_b32 v101, v101, v105, vcc\n v_cndmask_b32 v100, v100, v104, vcc\n v_cndmask_b32 v106, v106, %4, vcc" \
+                          : : "v"(a[1 + (i % 3)]), "v"(b[1 + (i % 5)]), "v"(b[6]), "v"(eps), "v"(u[1 + (i & 3)]) \
+                          : "vcc", "v100", "v101", "v102", "v103", "v104", "v105", "v106");
+                REP8(X)
+#undef X
+            } else if (OP == 18) {     // the same candidate with the step as compare-to-EXEC + two predicated moves (code an immediate), EXEC saved
+                                       // and restored on the scalar unit
+#define PRED_STEP(TAIL) asm volatile("v_add_f64 v[104:105], %0, %1\n v_add_f64 v[104:105], v[104:105], %2\n v_add_f64 v[102:103], v[100:101], %3\n" \
+                          "s_mov_b64 s[20:21], exec\n v_cmpx_gt_f64 vcc, v[104:105], v[102:103]\n" \
+                          "v_mov_b64 v[100:101], v[104:105]\n v_mov_b32 v106, %4\n s_mov_b64 exec, s[20:21]" TAIL \
+                          : : "v"(a[1 + (i % 3)]), "v"(b[1 + (i % 5)]), "v"(b[6]), "v"(eps), "i"(2 + i) \
+                          : "vcc", "s20", "s21", "v100", "v101", "v102", "v103", "v104", "v105", "v106");
+#define X(n) { constexpr int i = n; PRED_STEP("") }
+                REP8(X)
+#undef X
+            } else if (OP == 19) {     // OP 18 closed by one wait state (the fourth after the v_cmpx: what a v_readlane right behind the step would need)
+#define X(n) { constexpr int i = n; PRED_STEP("\n s_nop 0") }
+                REP8(X)
+#undef X
+#undef PRED_STEP
             }
         }
     }
@@ -129,7 +155,7 @@ __global__ void __launch_bounds__(1024) rate_kernel(double *out, unsigned long l
 static double *g_out = nullptr;
 static unsigned long long *g_cyc = nullptr;
 
-template <int OP, int LANES = 64> static void run(const char *name, int instr_per_x)
+template <int OP, int LANES = 64, int TAKE = 0> static void run(const char *name, int instr_per_x)
 {
     for (int w = 1; w <= 4; w++) {   // (round 2's w = 4 fault: OP 9 / OP 13 wrote u[i] through an input-only operand, so the register that also held
                                      //  threadIdx.x drifted and the final store left the buffer; every written register is an output operand now)
@@ -140,10 +166,10 @@ template <int OP, int LANES = 64> static void run(const char *name, int instr_pe
         }
         double *out = g_out;
         unsigned long long *cyc = g_cyc;
-        hipLaunchKernelGGL((rate_kernel<OP, LANES>), dim3(blocks), dim3(threads), 0, 0, out, cyc, 1.25);
+        hipLaunchKernelGGL((rate_kernel<OP, LANES, TAKE>), dim3(blocks), dim3(threads), 0, 0, out, cyc, 1.25);
         CHECK(hipGetLastError());
         CHECK(hipDeviceSynchronize());
-        hipLaunchKernelGGL((rate_kernel<OP, LANES>), dim3(blocks), dim3(threads), 0, 0, out, cyc, 1.25);
+        hipLaunchKernelGGL((rate_kernel<OP, LANES, TAKE>), dim3(blocks), dim3(threads), 0, 0, out, cyc, 1.25);
         CHECK(hipGetLastError());
         CHECK(hipDeviceSynchronize());
         std::vector<unsigned long long> h(blocks * (threads / 64));
@@ -179,6 +205,18 @@ int main()
     run<14>("Inc candidate, one chain (7)", 7);
     run<15>("Inc candidate x2, interleaved (14)", 14);
     run<16>("Dec candidate (6)", 6);
+    // the hysteresis step as compare + three selects against compare-to-EXEC + two predicated moves, by how many lanes take (figures per
+    // INSTRUCTION of the whole candidate: x 7 for the select form, x 6 for the predicated one — its two s_mov and the s_nop are not counted)
+    run<17, 64, 0>("Inc cand, selects (7), none take", 7);
+    run<17, 64, 1>("Inc cand, selects (7), lane 0", 7);
+    run<17, 64, 2>("Inc cand, selects (7), all take", 7);
+    run<18, 64, 0>("Inc cand, cmpx+moves (6), none", 6);
+    run<18, 64, 1>("Inc cand, cmpx+moves (6), lane 0", 6);
+    run<18, 64, 2>("Inc cand, cmpx+moves (6), all", 6);
+    run<19, 64, 0>("Inc cand, cmpx+moves+nop (6), none", 6);
+    run<19, 64, 1>("Inc cand, cmpx+moves+nop (6), lane 0", 6);
+    run<19, 64, 2>("Inc cand, cmpx+moves+nop (6), all", 6);
+    run<18, 32, 1>("cmpx+moves (6), lanes 0-31, lane 0", 6);
     // sparse EXEC masks: does a wave64 instruction with few enabled lanes cost less?
     run<0, 32>("v_add_f64, lanes 0-31 enabled", 1);
     run<0, 16>("v_add_f64, lanes 0-15 enabled", 1);
