@@ -562,6 +562,17 @@ struct HostCall {
             if ((rc = dev.alloc(&d, s.bytes))) return rc;
             s.point_at(d);
         }
+        // DD_POISON_OUTPUTS (debug, read per call): every dd_result array placed in the arena starts out as bytes 0x5A instead of what the
+        // thread's last call left at these offsets, so that an element no kernel of this call writes shows in the caller's copy.  Arrays
+        // written in place are the caller's to fill; the CIGAR / realign / key arrays are left alone.  The window blocks alternate between
+        // the two streams: the fill is complete before the first launch of either.
+        if (getenv("DD_POISON_OUTPUTS")) {
+            for (int i = 0; i < N_RESULT_OUTS; i++) {
+                const OutArray &o = outs[(size_t)i];
+                if (o.dev && !o.direct && o.slot.bytes) HIP_TRY(hipMemsetAsync(o.dev, 0x5A, o.slot.bytes, ctx.s[0]));
+            }
+            HIP_TRY(hipStreamSynchronize(ctx.s[0]));
+        }
         return DD_SUCCESS;
     }
 

@@ -163,7 +163,9 @@ typedef struct dd_batch {
 #define DD_READ_MATE_SAME_TID 16   /* bam->core.tid == bam->core.mtid                      */
 
 /* Per (window,hap,read) pair, in pair order.  Any output pointer may be NULL (then not written),
- * except ll and status. Mirrors MLAlignment (MLAlignment.hpp:28-76). */
+ * except ll and status. Mirrors MLAlignment (MLAlignment.hpp:28-76).  onHap is derived from offHapHMQ on the device: the
+ * device-pointer entries (dd_launch_device*) write it only when both pointers are given; the host-pointer entries keep a
+ * device copy of offHapHMQ of their own when the caller passes NULL for it. */
 typedef struct dd_result {
     double  *ll, *llOn, *llOff, *mLogBQ;
     uint8_t *offHap, *offHapHMQ;

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from dindel_tgi_amd import capi, synth
-from dindel_tgi_amd.batch import ReadRec, Window, alloc_result, pack
+from dindel_tgi_amd.batch import ReadRec, Window, pack
 from tests import _oracle
 
 pytestmark = pytest.mark.gpu
@@ -21,9 +21,12 @@ CHECKED = ["ll", "status", "offHap", "offHapHMQ", "firstBase", "lastBase", "numI
 
 
 def run_faster(lib, params, pb, device=0):
-    arrs, res = alloc_result(pb, fill=None)
+    """As tests/test_gpu_parity.run_host_api: poisoned arrays over a poisoned arena."""
+    from tests._output_ownership import alloc_poisoned, poisoned_arena
+    arrs, res = alloc_poisoned(pb)
     b = pb.ctypes_batch()
-    rc = lib.dd_compute_likelihoods_faster(C.byref(params), C.byref(b), C.byref(res), device)
+    with poisoned_arena():
+        rc = lib.dd_compute_likelihoods_faster(C.byref(params), C.byref(b), C.byref(res), device)
     assert rc == 0, capi.last_error()
     return arrs
 

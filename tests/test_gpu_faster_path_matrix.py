@@ -20,11 +20,12 @@ import numpy as np
 import pytest
 
 from dindel_tgi_amd import capi
-from dindel_tgi_amd.batch import alloc_result
 from tests import _oracle
+from tests import _output_ownership as oo
 from tests import _path_scenarios as ps
+from tests._output_ownership import Guarded, alloc_poisoned, poisoned_arena
 from tests.test_gpu_faster import assert_same_faster, run_faster
-from tests.test_gpu_long_path_matrix import Guarded, same_bytes
+from tests.test_gpu_long_path_matrix import same_bytes
 
 pytestmark = pytest.mark.gpu
 FL = capi.DD_OPT_LONG_WINDOWS_FASTER
@@ -38,9 +39,11 @@ def lib():
 
 
 def run_ex(lib, p, pb):
-    arrs, res = alloc_result(pb, fill=None)
+    """Poisoned arrays over a poisoned arena, as tests/test_gpu_faster.run_faster."""
+    arrs, res = alloc_poisoned(pb)
     b = pb.ctypes_batch()
-    rc = lib.dd_compute_likelihoods_faster_ex(C.byref(p), C.byref(b), C.byref(res), 0, FL)
+    with poisoned_arena():
+        rc = lib.dd_compute_likelihoods_faster_ex(C.byref(p), C.byref(b), C.byref(res), 0, FL)
     assert rc == 0, capi.last_error()
     return arrs
 
@@ -126,6 +129,7 @@ def test_every_path_on_the_faster_kernel(lib, monkeypatch, mld, L):
             continue
         pb, index = ps.batch_for(hl, L, mld)
         want = _oracle.batch(p, pb, nthreads=16, faster=True)
+        own = oo.must_write(pb, want, index, faster=True)    # every call below starts from poisoned buffers: what it must write, and nothing else
         tag = "dd_faster_kernel, maxLengthDel %d, %d-bp reads, haplotypes of %d bp" % (mld, L, hl)
         host = None
         for groups in (None, "2", "1"):
@@ -139,16 +143,20 @@ def test_every_path_on_the_faster_kernel(lib, monkeypatch, mld, L):
             assert int(ll[0]) == (int(groups) if groups else 4), (tag, groups, ll)     # four pair areas fit at every shape within DD_MAX_*
             seen.add(int(ll[0]))
             compare(got, want, pb, index, tag + ", %s pair areas per wavefront" % (groups or "4"))
+            oo.assert_owned(got, want, pb, own, tag + ", %s pair areas per wavefront" % (groups or "4"))
             host = host or got
         monkeypatch.delenv("DD_FAST_GROUPS", raising=False)
         dev = DeviceBatch(pb, p, "cuda:0")
         assert dev.n_skipped == 1
+        guarded = oo.GuardedDevice(dev)                      # its result tensors: poison inside 256-byte guards
         dev.launch_faster()
         torch.cuda.synchronize()
         res = dev.results()
         compare(res, want, pb, index, tag + ", device-pointer path")
         same_bytes(res, host, pb, index, tag + ", device-pointer path")
-        del dev
+        oo.assert_owned(res, want, pb, own, tag + ", device-pointer path")
+        guarded.check(tag + ", device-pointer path")
+        del guarded, dev
     assert seen == {1, 2, 4}
     WALL[("main", mld, L)] = time.time() - t0
     print("faster matrix mld %d L %d: %.1f s" % (mld, L, WALL[("main", mld, L)]))

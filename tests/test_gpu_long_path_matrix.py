@@ -21,18 +21,16 @@ import numpy as np
 import pytest
 
 from dindel_tgi_amd import capi
-from dindel_tgi_amd.batch import RESULT_DTYPES, alloc_result, result_lengths
+from dindel_tgi_amd.batch import result_lengths
 from tests import _oracle
 from tests import _path_scenarios as ps
+from tests._output_ownership import PER_ELEMENT, Guarded, alloc_poisoned, poisoned_arena
 from tests.test_gpu_parity import assert_same
 
 pytestmark = pytest.mark.gpu
 
 CASES = ps.LONG_GRID
 IDS = ["hap%d-L%d-mld%d-K%d" % c for c in CASES]
-GUARD = 256
-GUARD_BYTE, BODY_BYTE = 0xA5, 0x5A
-PER_ELEMENT = ("hpos", "var_covered", "var_fcov", "onHap")
 
 RECORDS = {}             # K -> launch records of the module's long launches
 SHORT_ON = set()         # K on which a computed haplotype shorter than 128 K bp ran
@@ -45,9 +43,11 @@ def lib():
 
 
 def run_ex(lib, p, pb):
-    arrs, res = alloc_result(pb, fill=None)
+    """Poisoned arrays over a poisoned arena, as tests/test_gpu_parity.run_host_api."""
+    arrs, res = alloc_poisoned(pb)
     b = pb.ctypes_batch()
-    rc = lib.dd_compute_likelihoods_ex(C.byref(p), C.byref(b), C.byref(res), 0, capi.DD_OPT_LONG_WINDOWS)
+    with poisoned_arena():
+        rc = lib.dd_compute_likelihoods_ex(C.byref(p), C.byref(b), C.byref(res), 0, capi.DD_OPT_LONG_WINDOWS)
     assert rc == 0, capi.last_error()
     return arrs
 
@@ -76,63 +76,6 @@ def long_record(log, pb, p, K, where, options=capi.DD_OPT_LONG_WINDOWS):
     assert len(log) == 1, (where, log)
     assert log[0]["K"] == K and log[0]["pairs"] == pairs and log[0]["ws_bytes"] <= capi.DD_LONG_WS_BUDGET, (where, log[0], pairs)
     return log[0]
-
-
-class Guarded:
-    """Every dd_result array in page-locked memory (dd_host_alloc), GUARD bytes longer at each end; the dd_result holds the interior
-    pointers.  Guards and body carry different sentinels."""
-
-    def __init__(self, lib, pb):
-        self.lib, self.n, self.raw, self.ptrs = lib, result_lengths(pb), {}, []
-        self.res = capi.dd_result()
-        for k, typ in capi.RESULT_FIELDS:
-            nbytes = max(self.n[k], 1) * np.dtype(RESULT_DTYPES[k]).itemsize
-            ptr = lib.dd_host_alloc(nbytes + 2 * GUARD)
-            assert ptr, k
-            self.ptrs.append(ptr)
-            self.raw[k] = np.frombuffer((C.c_char * (nbytes + 2 * GUARD)).from_address(ptr), dtype=np.uint8)
-            self.raw[k][...] = GUARD_BYTE
-            self.raw[k][GUARD:GUARD + nbytes] = BODY_BYTE
-            setattr(self.res, k, C.cast(C.c_void_p(ptr + GUARD), typ))
-
-    def body(self, k):
-        return self.raw[k][GUARD:len(self.raw[k]) - GUARD].view(RESULT_DTYPES[k])
-
-    def check(self, plain, pb, index, where):
-        """Both guards untouched; the body byte-equal to the pageable run `plain` — but for elements that still hold the body sentinel, and
-        those only where the pageable run shows that the library does not write them: elements of a pair whose status there is not
-        DD_PAIR_OK (the rejected window's pairs, of which the library defines five values; the hpos of a hapSize-error pair), or of no pair
-        (the onHap of a read in a window without haplotypes).  -> the number of such elements per array."""
-        status = plain["status"][:pb.n_pairs]
-        elem = ps.element_pairs(pb)
-        left = {}
-        for k, _typ in capi.RESULT_FIELDS:
-            raw = self.raw[k]
-            assert (raw[:GUARD] == GUARD_BYTE).all(), "%s: %s: the guard in front of the array was written at byte %d" % (
-                where, k, int(np.nonzero(raw[:GUARD] != GUARD_BYTE)[0][0]) - GUARD)
-            assert (raw[-GUARD:] == GUARD_BYTE).all(), "%s: %s: the guard behind the array was written at byte +%d" % (
-                where, k, int(np.nonzero(raw[-GUARD:] != GUARD_BYTE)[0][0]))
-            n, size = self.n[k], np.dtype(RESULT_DTYPES[k]).itemsize
-            if n == 0:
-                continue
-            mine = self.body(k)[:n].view(np.uint8).reshape(n, size)
-            ref = np.ascontiguousarray(plain[k][:n]).view(np.uint8).reshape(n, size)
-            differ = np.nonzero((mine != ref).any(axis=1))[0]
-            if differ.size == 0:
-                continue
-            pair = elem[k][differ] if k in PER_ELEMENT else differ
-            sentinel = (mine[differ] == BODY_BYTE).all(axis=1)
-            unwritten = (pair < 0) | (status[np.maximum(pair, 0)] != capi.DD_PAIR_OK)
-            bad = np.nonzero(~(sentinel & unwritten))[0]
-            assert bad.size == 0, "%s: %s[%d] (pair %d, family %s) is %r in place, %r through the copy" % (
-                where, k, int(differ[bad[0]]), int(pair[bad[0]]), ps.family_of(int(pair[bad[0]]), index), self.body(k)[int(differ[bad[0]])], plain[k][int(differ[bad[0]])])
-            left[k] = int(differ.size)
-        return left
-
-    def release(self):
-        self.raw.clear()
-        while self.ptrs:
-            self.lib.dd_host_free(self.ptrs.pop())
 
 
 def same_bytes(got, host, pb, index, where):

@@ -24,9 +24,13 @@ F64_KEYS = ["ll", "llOn", "llOff", "mLogBQ"]
 
 
 def run_host_api(lib, params, pb, device=0):
-    arrs, res = alloc_result(pb, fill=None)
+    """One host-pointer call into arrays full of the poison byte, over an arena whose output region starts out the same
+    (DD_POISON_OUTPUTS): an element the call does not write comes back as 0x5A5A..., not as what the last call left there."""
+    from tests._output_ownership import alloc_poisoned, poisoned_arena     # (imported here: that module's helpers import this one)
+    arrs, res = alloc_poisoned(pb)
     b = pb.ctypes_batch()
-    rc = lib.dd_compute_likelihoods(C.byref(params), C.byref(b), C.byref(res), device)
+    with poisoned_arena():
+        rc = lib.dd_compute_likelihoods(C.byref(params), C.byref(b), C.byref(res), device)
     assert rc == 0, capi.last_error()
     return arrs
 

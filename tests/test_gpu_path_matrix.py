@@ -15,6 +15,7 @@ import pytest
 
 from dindel_tgi_amd import capi
 from tests import _oracle
+from tests import _output_ownership as oo
 from tests import _path_scenarios as ps
 from tests.test_gpu_parity import assert_same, run_host_api
 from tests.test_gpu_persistent_rounds import KEYS, MODES
@@ -98,6 +99,7 @@ def test_every_path_on_every_build(lib, clean_env, mld, L, part):
         pb, index = ps.batch_for(hl, L, mld)
         p = ps.params_for(mld, 1)
         want = _oracle.batch(p, pb, nthreads=16)
+        own = oo.must_write(pb, want, index)                 # every call below starts from poisoned buffers: what it must write, and nothing else
         for env in MODES:
             for k in KEYS:
                 os.environ.pop(k, None)
@@ -105,18 +107,25 @@ def test_every_path_on_every_build(lib, clean_env, mld, L, part):
             got = run_host_api(lib, p, pb)
             log = capi.launch_log()
             record(log, pb, index)
-            compare(got, want, pb, index, log, "maxLengthDel %d, %d-bp reads, haplotypes of %d bp, environment %r" % (mld, L, hl, env))
+            where = "maxLengthDel %d, %d-bp reads, haplotypes of %d bp, environment %r" % (mld, L, hl, env)
+            compare(got, want, pb, index, log, where)
+            oo.assert_owned(got, want, pb, own, where + "; launches: " + ", ".join(ps.kernel_name(l) for l in log))
         for k in KEYS:
             os.environ.pop(k, None)
         # the device-pointer entry: per-class launches on the caller's stream, dd_screen_windows' flags resident with the batch
         dev = DeviceBatch(pb, p, "cuda:0")
         assert dev.n_skipped == 1
+        guarded = oo.GuardedDevice(dev)                      # its result tensors: poison inside 256-byte guards
         dev.launch()
         torch.cuda.synchronize()
         log = capi.launch_log()
         record(log, pb, index)
-        compare(dev.results(), want, pb, index, log, "maxLengthDel %d, %d-bp reads, haplotypes of %d bp, device-pointer path" % (mld, L, hl))
-        del dev
+        where = "maxLengthDel %d, %d-bp reads, haplotypes of %d bp, device-pointer path" % (mld, L, hl)
+        res = dev.results()
+        compare(res, want, pb, index, log, where)
+        oo.assert_owned(res, want, pb, own, where + "; launches: " + ", ".join(ps.kernel_name(l) for l in log))
+        guarded.check(where)
+        del guarded, dev
         # the same arrays with the mate prior switched off: only the mates window's pairs change (an unpaired read has no prior term)
         p0 = ps.params_for(mld, 0)
         w = int(index["mates.window"][0])
@@ -130,6 +139,7 @@ def test_every_path_on_every_build(lib, clean_env, mld, L, part):
         got = run_host_api(lib, p0, pb)
         log = capi.launch_log()
         compare(got, want0, pb, index, log, "maxLengthDel %d, %d-bp reads, haplotypes of %d bp, mapUnmappedReads 0" % (mld, L, hl))
+        oo.assert_owned(got, want0, pb, oo.must_write(pb, want0, index), "maxLengthDel %d, %d-bp reads, haplotypes of %d bp, mapUnmappedReads 0" % (mld, L, hl))
         assert (got["ll"][index["mates.usable"]] != want["ll"][index["mates.usable"]]).any()
     RAN.add((mld, L, part))
     WALL[(mld, L, part)] = time.time() - t0
