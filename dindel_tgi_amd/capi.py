@@ -45,6 +45,11 @@ DD_REALIGN_FIRST_MAX, DD_REALIGN_PAIR = 0, 1
 DD_DIPPAIR_MAX_HAPS = 128
 # the --faster model's indel-map key count (opt-in): one int16 per pair, the count or one of the two negative marks
 DD_INDEL_KEYS_CAP, DD_INDEL_KEYS_OVERFLOW, DD_INDEL_KEYS_NOT_COMPUTED = 64, -1, -2
+# audit (opt-in): the field ids of a difference record, in dd_result's comparison order, and the record of the audit's long launch
+AUDIT_FIELDS = ["status", "ll", "llOn", "llOff", "mLogBQ", "offHap", "offHapHMQ", "numIndels", "numMismatch", "nBQT", "nmmBQT", "nMMLeft",
+                "nMMRight", "firstBase", "lastBase", "hpos", "var_covered", "var_fcov"]
+DD_AUDIT_N_FIELDS = len(AUDIT_FIELDS)
+AUDIT_LOG_FIELDS = ["grid", "pairs", "max_pairs_per_wg", "ws_bytes", "K", "max_hap", "max_read", "compare_grid"]
 # alignHaplotypes on the device: per-pair status codes and the launch geometry record
 DD_ALIGN_OK, DD_ALIGN_EMPTY, DD_ALIGN_TOO_LONG, DD_ALIGN_BAD_REF = range(4)
 DD_ALIGN_WS_BUDGET = 512 << 20
@@ -241,6 +246,30 @@ class dd_pooled_result(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in POOLED_RESULT_FIELDS]
 
 
+class dd_audit_record(C.Structure):
+    """One difference of an audit: window, field (index into AUDIT_FIELDS), pair, the element's index in the primary array, both values'
+    bits zero-extended."""
+    _fields_ = [("window", C.c_int32), ("field", C.c_int32), ("pair", C.c_int64), ("index", C.c_int64),
+                ("primary_bits", C.c_uint64), ("shadow_bits", C.c_uint64)]
+
+
+class dd_audit_report(C.Structure):
+    """The header of an audit's report; max_records dd_audit_record follow it."""
+    _fields_ = [("n_pairs", C.c_int64), ("n_diff", C.c_int64), ("diff", C.c_int64 * DD_AUDIT_N_FIELDS), ("compared", C.c_int64 * DD_AUDIT_N_FIELDS)]
+
+
+class dd_audit_sizes(C.Structure):
+    _fields_ = [("n_windows", C.c_int32), ("max_hap_len", C.c_int32), ("max_read_len", C.c_int32), ("reserved", C.c_int32),
+                ("n_pairs", C.c_int64), ("hpos_len", C.c_int64), ("var_cov_len", C.c_int64)]
+
+
+class dd_audit_view(C.Structure):
+    """dd_audit_select's outputs where the comparison runs.  Raw addresses: device arrays for dd_audit_device, host arrays for
+    dd_audit_compare_host."""
+    _fields_ = [("n_windows", C.c_int32), ("n_qual", C.c_int32), ("audit_class", C.c_void_p), ("pair_off", C.c_void_p), ("hpos_off", C.c_void_p),
+                ("varcov_off", C.c_void_p), ("sizes", dd_audit_sizes)]
+
+
 class dd_device_result(C.Structure):
     """dd_result with raw device addresses (same layout: every member is a pointer)."""
     _fields_ = [(n, C.c_void_p) for n, _ in RESULT_FIELDS]
@@ -259,7 +288,9 @@ EXPORTS = ["dd_params_struct_defaults", "dd_params_cli_defaults", "dd_batch_size
            "dd_hap_blocks_offsets", "dd_hap_blocks_workspace_bytes", "dd_hap_blocks_device", "dd_hap_blocks_compute", "dd_hap_blocks_last_launch",
            "dd_pooled_em_device", "dd_pooled_em", "dd_pooled_em_host", "dd_pooled_math_eval",
            "dd_diploid_pairs_device", "dd_diploid_pairs_host", "dd_compute_likelihoods_realign_diploid",
-           "dd_indel_keys_device", "dd_indel_keys_host", "dd_compute_likelihoods_faster_keys"]
+           "dd_indel_keys_device", "dd_indel_keys_host", "dd_compute_likelihoods_faster_keys",
+           "dd_audit_select", "dd_audit_workspace_bytes", "dd_audit_device", "dd_audit_last_launch", "dd_audit_compare_host",
+           "dd_compute_likelihoods_audit", "dd_audit_inject_next"]
 
 _lib = None
 
@@ -368,6 +399,20 @@ def load():
     lib.dd_indel_keys_device.argtypes = [C.POINTER(dd_device_batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.dd_indel_keys_host.argtypes = [C.POINTER(dd_batch), c_i16p, c_i32p, c_i16p, C.c_int]
     lib.dd_compute_likelihoods_faster_keys.argtypes = [C.POINTER(dd_params), C.POINTER(dd_batch), C.POINTER(dd_result), c_i16p, C.c_int, C.c_uint32]
+    lib.dd_audit_select.argtypes = [C.POINTER(dd_params), C.POINTER(dd_batch), c_u8p, C.c_uint64, C.c_int32, c_u8p, c_i64p, c_i64p, c_i64p,
+                                    C.POINTER(dd_audit_sizes)]
+    lib.dd_audit_workspace_bytes.argtypes = [C.POINTER(dd_params), C.POINTER(dd_audit_view)]
+    lib.dd_audit_workspace_bytes.restype = C.c_size_t
+    lib.dd_audit_device.argtypes = [C.POINTER(dd_params), C.POINTER(dd_device_batch), C.POINTER(dd_device_result), C.POINTER(dd_audit_view),
+                                    C.POINTER(dd_device_result), C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.dd_audit_last_launch.argtypes = [C.POINTER(C.c_int64 * len(AUDIT_LOG_FIELDS))]
+    lib.dd_audit_last_launch.restype = None
+    lib.dd_audit_compare_host.argtypes = [C.POINTER(dd_batch), C.POINTER(dd_result), C.POINTER(dd_audit_view), C.POINTER(dd_result), C.c_void_p,
+                                          C.c_int64]
+    lib.dd_compute_likelihoods_audit.argtypes = [C.POINTER(dd_params), C.POINTER(dd_batch), C.POINTER(dd_result), C.c_int, C.c_uint32, C.c_uint64,
+                                                 C.c_int32, C.c_void_p, C.c_int64]
+    lib.dd_audit_inject_next.argtypes = [C.c_int]
+    lib.dd_audit_inject_next.restype = None
     lib.dd_last_launch.argtypes = [C.POINTER(C.c_int32 * 8)]
     lib.dd_last_launch.restype = None
     lib.dd_launch_log.argtypes = [c_i32p, C.c_int]
@@ -519,6 +564,76 @@ def indel_keys_host(pb, hpos, status=None, nthreads=1):
     if rc != 0:
         raise RuntimeError("dd_indel_keys_host rc=%d: %s" % (rc, last_error()))
     return out[:pb.n_pairs]
+
+
+class AuditSample:
+    """dd_audit_select on a PackedBatch: audit_class (uint8 [n_windows]), pair_off / hpos_off / varcov_off (int64 [n_windows + 1]), sizes
+    (dd_audit_sizes), n_eligible, and `chosen`, the chosen windows' indices.  view() points a dd_audit_view at the host arrays (keep the
+    sample alive while it is in use)."""
+
+    def __init__(self, params, pb, n_want, seed=0, win_class=None):
+        import numpy as np
+        W = pb.n_windows
+        self.n_windows, self.n_qual = W, int(pb.ctypes_batch().n_qual)
+        self.audit_class = np.zeros(max(W, 1), np.uint8)
+        self.pair_off, self.hpos_off, self.varcov_off = (np.zeros(W + 1, np.int64) for _ in range(3))
+        self.sizes = dd_audit_sizes()
+        wc = None if win_class is None else np.ascontiguousarray(win_class, np.uint8)
+        b = pb.ctypes_batch()
+        rc = load().dd_audit_select(C.byref(params), C.byref(b), wc.ctypes.data_as(c_u8p) if wc is not None else None, int(seed) & (2 ** 64 - 1),
+                                    int(n_want), self.audit_class.ctypes.data_as(c_u8p), self.pair_off.ctypes.data_as(c_i64p),
+                                    self.hpos_off.ctypes.data_as(c_i64p), self.varcov_off.ctypes.data_as(c_i64p), C.byref(self.sizes))
+        if rc < 0:
+            raise RuntimeError("dd_audit_select rc=%d: %s" % (rc, last_error()))
+        self.n_eligible = rc
+        self.audit_class = self.audit_class[:W]
+        self.chosen = np.nonzero(self.audit_class == DD_WIN_LONG)[0]
+
+    def view(self, addresses=None):
+        """A dd_audit_view of the host arrays, or of `addresses` = (audit_class, pair_off, hpos_off, varcov_off) raw device addresses."""
+        if addresses is None:
+            addresses = [a.ctypes.data for a in (self.audit_class, self.pair_off, self.hpos_off, self.varcov_off)]
+        return dd_audit_view(self.n_windows, self.n_qual, *addresses, self.sizes)
+
+
+def audit_report_buffer(max_records):
+    """Host memory for a report with room for max_records records (uint8 array, 8-byte aligned)."""
+    import numpy as np
+    return np.zeros((C.sizeof(dd_audit_report) + int(max_records) * C.sizeof(dd_audit_record) + 7) // 8, np.int64).view(np.uint8)
+
+
+def audit_report(buf, max_records):
+    """A report's bytes (numpy uint8) as dict(n_pairs, n_diff, diff {field: count}, compared {field: count}, records [dict(window, field
+    name, pair, index, primary_bits, shadow_bits)]): the first min(n_diff, max_records) records."""
+    import numpy as np
+    raw = np.ascontiguousarray(buf).view(np.uint8)
+    hdr = dd_audit_report.from_buffer_copy(raw[:C.sizeof(dd_audit_report)].tobytes())
+    n = min(int(hdr.n_diff), int(max_records))
+    recs = []
+    for i in range(n):
+        at = C.sizeof(dd_audit_report) + i * C.sizeof(dd_audit_record)
+        r = dd_audit_record.from_buffer_copy(raw[at:at + C.sizeof(dd_audit_record)].tobytes())
+        recs.append(dict(window=int(r.window), field=AUDIT_FIELDS[r.field] if 0 <= r.field < DD_AUDIT_N_FIELDS else int(r.field), pair=int(r.pair),
+                         index=int(r.index), primary_bits=int(r.primary_bits), shadow_bits=int(r.shadow_bits)))
+    return dict(n_pairs=int(hdr.n_pairs), n_diff=int(hdr.n_diff), diff={k: int(hdr.diff[i]) for i, k in enumerate(AUDIT_FIELDS)},
+                compared={k: int(hdr.compared[i]) for i, k in enumerate(AUDIT_FIELDS)}, records=recs)
+
+
+def audit_compare_host(pb, primary, sample, shadow, max_records=64):
+    """dd_audit_compare_host: `primary` and `shadow` are dd_result structs over host arrays (batch.alloc_result's second value, or one built
+    by hand with NULL fields); returns audit_report's dict."""
+    buf = audit_report_buffer(max_records)
+    b = pb.ctypes_batch()
+    v = sample.view()
+    rc = load().dd_audit_compare_host(C.byref(b), C.byref(primary), C.byref(v), C.byref(shadow), buf.ctypes.data, int(max_records))
+    if rc != 0:
+        raise RuntimeError("dd_audit_compare_host rc=%d: %s" % (rc, last_error()))
+    return audit_report(buf, max_records)
+
+
+def audit_last_launch():
+    """The audit's long launch of this thread's last dd_audit_device / dd_compute_likelihoods_audit call (dd_audit_last_launch)."""
+    return last_launch_of("dd_audit_last_launch", AUDIT_LOG_FIELDS)
 
 
 def cigar_ops(ops, n_ops):

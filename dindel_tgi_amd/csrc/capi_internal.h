@@ -2,7 +2,8 @@
 // nor needs a kernel unit to link), long_plan.cpp (the plans of the two long-window paths, with the layouts of their kernel units),
 // launch.cpp, host_path.cpp, align_host.cpp (the haplotype alignment with the events and variants behind it), hapdist_host.cpp (the block
 // table), pooled_em_capi.cpp (the pooled EM's device entries; pooled_em_host.cpp, its CPU evaluation, includes no HIP header and not this
-// file), indel_keys_capi.cpp (the --faster model's indel-map key count: the launch and the CPU evaluation); each says in its first lines
+// file), indel_keys_capi.cpp (the --faster model's indel-map key count: the launch and the CPU evaluation), audit_host.cpp (an audit's sample and
+// the CPU evaluation of its comparison: no HIP runtime call either) and audit_capi.cpp (its device entries); each says in its first lines
 // what it holds.  The last part of this file is what the host-pointer entries share: use_device, the
 // arena slot, the one-shot arena of the three small entries and the record of a drawing kernel's last launch.  Host work is O(bases)
 // bookkeeping only.  All likelihood arithmetic happens in the kernels; there is no CPU path for it in this library.
@@ -21,6 +22,7 @@
 #include "cigar_kernel.h"
 #include "realign_kernel.h"
 #include "draw_header.h"
+#include "audit_kernel.h"
 
 namespace ddh {
 constexpr size_t kCuLdsBytes = 160u * 1024u;   // LDS of one CU (gfx950)
@@ -218,6 +220,18 @@ struct RealignInputs {
 // the realign launch (realign_kernel.hip) over the reads [read_begin, read_end) of the batch; read_end < 0 = all of them
 int launch_realign_range(const dd_device_batch *b, const RealignInputs &in, const dd_realign_result *out_dev, int ops_cap, void *stream,
                          int read_begin, int read_end);
+
+// ---- audit_host.cpp, audit_capi.cpp ----
+// what the entries that take a dd_audit_view check about it; the comparison's geometry from a host batch (primary_off takes the primary's offsets)
+int check_audit_view(const char *who, const dd_audit_view *v, int n_windows);
+int audit_geometry_host(const dd_batch *b, const dd_audit_view *view, std::vector<int64_t> &primary_off, au_geometry &G);
+// The audit of the chosen windows in [w_begin, w_end) (their reads: [read_begin, read_end)), enqueued on `stream` behind the likelihood
+// launches of those windows: the long launch into `shadow`, then the comparison, which ADDS its counts to report_dev's header (the caller
+// zeroes it) and draws its record slots from there.  j_begin, j_end: view->pair_off[w_begin], [w_end] (a device array: the caller knows
+// them).  stats: two device words the long launch counts into, or NULL for the workspace header's.
+int launch_audit_range(const dd_params *p, const dd_device_batch *b, const dd_result *primary, const dd_audit_view *view, const dd_result *shadow,
+                       void *report_dev, int64_t max_records, void *workspace, size_t workspace_bytes, void *stream, int w_begin, int w_end,
+                       int read_begin, int read_end, int64_t j_begin, int64_t j_end, unsigned long long *stats);
 
 static_assert(DD_LONG_LOG_FIELDS == DD_FASTER_LONG_LOG_FIELDS, "one record type serves both logs");
 struct LongRec {

@@ -219,7 +219,14 @@ struct ExtraRequest {
     int mode; const int32_t *win_hap_pair, *hap_n_indels; dd_realign_result reads; // realign
     bool diploid; const double *prior; dd_diploid_pair_result pairs;              // realign in PAIR mode, the pairs from dd_diploid_pairs_device
     int16_t *keys;                                                                // non-NULL: a key request, and nothing of the above
+    // An audit request (dd_compute_likelihoods_audit, the main model) has nothing of the above either: a sample of the batch's windows, chosen
+    // once, is recomputed per window block by the long-window kernel into a shadow as large as the sample and compared on the device with the
+    // block's results; one report for the call comes back.
+    bool audit; uint64_t audit_seed; int32_t audit_want; void *audit_report; int64_t audit_max_records;
 };
+
+// test hook (dd_audit_inject_next): the window whose first pair's ll has one bit inverted in front of this thread's next audit, -1 = none
+thread_local int g_audit_inject = -1;
 
 // One call of a host-pointer entry.  run() is the sequence of its stages; the members are grouped by the stage that fills them.
 struct HostCall {
@@ -257,6 +264,17 @@ struct HostCall {
     const double *prior_dev = nullptr;
     const int64_t *hh_off_dev = nullptr;
     int16_t *keys_dev = nullptr;
+    // an audit request: the sample (plan), its device copies, the shadow, the report, per stream a workspace, per block two stats words
+    std::vector<uint8_t> audit_class;
+    std::vector<int64_t> au_pair_off, au_hpos_off, au_vc_off;
+    dd_audit_view au_view = {};                          // device addresses once the inputs are placed
+    bool audit_on = false;
+    size_t aws_bytes = 0;
+    dd_result shadow = {};
+    unsigned char *report_dev = nullptr, *aws[2] = {nullptr, nullptr};
+    unsigned long long *audit_stats = nullptr;
+    int inject_window = -1;
+    double inject_ll[2] = {0.0, 0.0};                    // the value as it was, and with its lowest bit inverted
     unsigned char *ws[2] = {nullptr, nullptr}, *lws[2] = {nullptr, nullptr};
     unsigned long long *long_stats = nullptr;           // long_path->n_stats (2 or 4) words per window block's long launch
     // reserve_and_upload, place_outputs
@@ -392,6 +410,21 @@ struct HostCall {
             if (w2 > ws_bytes) ws_bytes = w2;
             db.classes = nullptr; db.hap_class_list = nullptr;
         }
+        if (x && x->audit) {
+            // the sample, once for the whole batch; every window block audits its own chosen windows
+            audit_class.resize((size_t)std::max(W, 1)); au_pair_off.resize(W + 1); au_hpos_off.resize(W + 1); au_vc_off.resize(W + 1);
+            rc = dd_audit_select(p, b, n_skip ? win_skip.data() : nullptr, x->audit_seed, x->audit_want, audit_class.data(), au_pair_off.data(),
+                                 au_hpos_off.data(), au_vc_off.data(), &au_view.sizes);
+            if (rc < 0) return rc;
+            au_view.n_windows = W; au_view.n_qual = b->n_qual;
+            audit_on = au_view.sizes.n_pairs > 0;
+            if (audit_on) {
+                aws_bytes = dd_audit_workspace_bytes(p, &au_view);
+                if (!aws_bytes) return fail(DD_ERR_UNSUPPORTED, "audit: no long-window plan for the sample's shape");
+            }
+            inject_window = g_audit_inject;
+            g_audit_inject = -1;
+        }
         if (long_on && long_max[2] > 0) {
             db.long_max_hap_len = long_max[2]; db.long_max_read_len = long_max[3];
             lws_bytes = long_path->workspace_bytes(p, &db);
@@ -437,7 +470,13 @@ struct HostCall {
         }
 #undef IN
         if (!single_class) in(&class_list_dev, class_list.data(), (size_t)lcls.list_len);
-        if (x && !x->keys) {
+        if (audit_on) {
+            in(&au_view.audit_class, audit_class.data(), audit_class.size());
+            in(&au_view.pair_off, au_pair_off.data(), au_pair_off.size());
+            in(&au_view.hpos_off, au_hpos_off.data(), au_hpos_off.size());
+            in(&au_view.varcov_off, au_vc_off.data(), au_vc_off.size());
+        }
+        if (x && !x->keys && !x->audit) {
             in(&hap_ref_pos_dev, x->hap_ref_pos, (size_t)sz.hap_bases);
             if (x->hap_aligned) in(&hap_aligned_dev, x->hap_aligned, n_haps);
             if (x->realign && x->mode == DD_REALIGN_PAIR) {
@@ -460,7 +499,11 @@ struct HostCall {
         DD_RESULT_FIELDS(OUT)
 #undef OUT
         if (r->onHap && !r->offHapHMQ) outs[OUT_offHapHMQ].device_only = true;    // onHap is derived from it
-        if (x) {
+        if (x && x->audit) {
+            // The comparison reads every result array on the device: arrays the caller keeps in page-locked memory are staged in HBM and copied
+            // back like pageable ones, instead of being read back over the link.  An array the caller does not ask for is not compared.
+            for (int i = 0; i < N_RESULT_OUTS; i++) outs[(size_t)i].in_place = false;
+        } else if (x) {
             // The request's launch reads hpos on the device: alignments the caller wants in page-locked memory are staged in HBM and copied back
             // like pageable ones, instead of being read back over the link; and they are needed there even when the caller does not want them
             // back (r->hpos == NULL: nothing of them is copied).  A realign launch reads ll and onHap on the device as well.
@@ -489,7 +532,21 @@ struct HostCall {
             for (int i = 0; i < 2; i++) scratch.push_back(arena_slot(&lws[i], lws_bytes));
             scratch.push_back(arena_slot(&long_stats, (size_t)4 * 64 * sizeof(*long_stats)));    // 64 blocks at most, 4 words at most
         }
+        if (audit_on) {
+            // the shadow: every array the comparison can use, as large as the sample; the caller sees none of it
+            const dd_audit_sizes &as = au_view.sizes;
+#define SHADOW(f, space, in_place)                                                                                                   \
+            if (OUT_##f != OUT_onHap && dr_wanted(OUT_##f))                                                                               \
+                scratch.push_back(arena_slot(&shadow.f, sizeof(*shadow.f) * (size_t)(SPACE_##space == SPACE_PAIR ? as.n_pairs : SPACE_##space == SPACE_HPOS ? as.hpos_len : as.var_cov_len)));
+            DD_RESULT_FIELDS(SHADOW)
+#undef SHADOW
+            scratch.push_back(arena_slot(&report_dev, DD_AUDIT_REPORT_BYTES(x->audit_max_records)));
+            for (int i = 0; i < 2; i++) scratch.push_back(arena_slot(&aws[i], aws_bytes));
+            scratch.push_back(arena_slot(&audit_stats, (size_t)2 * 64 * sizeof(*audit_stats)));
+        }
     }
+    // an audit's shadow holds the arrays the call itself has on the device (the caller's, and offHapHMQ when onHap is derived from it)
+    bool dr_wanted(int i) const { return outs[(size_t)i].host || outs[(size_t)i].device_only; }
     // where the arena ends once every array of the lists is placed behind `at`, in the order reserve_and_upload and place_outputs place them;
     // *copy_back_end: the end of the inputs and of the outputs that are copied back (what the pinned mirror of a staged call holds)
     size_t end_of_all(size_t at, size_t *copy_back_end) const
@@ -612,9 +669,10 @@ struct HostCall {
     // (its ops start out zero: a pair's unused slots are defined), or the block's realigned reads (reads of windows without haplotypes are
     // marked too: the launch goes by reads, not by pairs).  A diploid request's pair launch goes first, for the same windows: the realign
     // launch reads the pairs where that launch left them.  A key request: the block's counts.
-    int launch_extra(hipStream_t st, int w0, int w1)
+    int launch_extra(hipStream_t st, int c, int w0, int w1)
     {
         int rc;
+        if (x->audit) return audit_on ? launch_audit_block(st, c, w0, w1) : DD_SUCCESS;
         if (x->keys) return launch_indel_keys_range(&db, dr.hpos, dr.status, keys_dev, st, idx.at(SPACE_PAIR, w0), idx.at(SPACE_PAIR, w1));
         if (x->diploid && (rc = launch_diploid_pairs_range(&db, hh_off_dev, dr.ll, dr.status, prior_dev, &ddp, st, w0, w1))) return rc;
         const ResultSpace space = x->realign ? SPACE_READ : SPACE_PAIR;
@@ -627,9 +685,36 @@ struct HostCall {
         return launch_realign_range(&db, in, &drl, x->ops_cap, st, (int)lo, (int)hi);
     }
 
+    // An audit request's launches for the chosen windows of [w0, w1).  The test hook inverts the lowest bit of the device copy of ll of
+    // window inject_window's first pair in front of them and puts the value back behind them: the audit sees it, the caller's results do not.
+    int launch_audit_block(hipStream_t st, int c, int w0, int w1)
+    {
+        const int64_t j0 = au_pair_off[(size_t)w0], j1 = au_pair_off[(size_t)w1];
+        if (j1 <= j0) return DD_SUCCESS;
+        const bool inject = inject_window >= w0 && inject_window < w1 && pair_off[(size_t)inject_window + 1] > pair_off[(size_t)inject_window];
+        double *target = inject ? dr.ll + pair_off[(size_t)inject_window] : nullptr;
+        if (inject) {
+            HIP_TRY(hipMemcpyAsync(&inject_ll[0], target, sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            uint64_t bits;
+            memcpy(&bits, &inject_ll[0], sizeof(bits));
+            bits ^= 1ull;
+            memcpy(&inject_ll[1], &bits, sizeof(bits));
+            HIP_TRY(hipMemcpyAsync(target, &inject_ll[1], sizeof(double), hipMemcpyHostToDevice, st));
+        }
+        const int rc = launch_audit_range(p, &db, &dr, &au_view, &shadow, report_dev, x->audit_max_records, aws[c & 1], aws_bytes, st, w0, w1,
+                                          b->win_read_off[w0], b->win_read_off[w1], j0, j1, audit_stats + 2 * c);
+        if (inject) HIP_TRY(hipMemcpyAsync(target, &inject_ll[0], sizeof(double), hipMemcpyHostToDevice, st));     // also when the launch failed
+        return rc;
+    }
+
     int enqueue_and_collect()
     {
         int rc;
+        if (audit_on) {                                      // one report for the call: zero before a block of either stream adds to it
+            HIP_TRY(hipMemsetAsync(report_dev, 0, DD_AUDIT_REPORT_BYTES(x->audit_max_records), ctx.s[0]));     // the records too: unused slots come back zero
+            HIP_TRY(hipStreamSynchronize(ctx.s[0]));
+        }
         for (int c = 0; c < n_chunks; c++) {
             hipStream_t st = ctx.s[c & 1];
             const int w0 = cw[c], w1 = cw[c + 1];
@@ -657,7 +742,7 @@ struct HostCall {
                 for (int w = w0; w < w1 && !any; w++) any = win_skip[(size_t)w] == DD_WIN_LONG;
                 if (any && (rc = long_path->launch_range(p, &db, &dr, lws[c & 1], lws_bytes, st, w0, w1, q0, q1, long_stats + long_path->n_stats * c))) return rc;
             }
-            if (x && (rc = launch_extra(st, w0, w1))) return rc;
+            if (x && (rc = launch_extra(st, c, w0, w1))) return rc;
             if (!staged && c > 0 && (rc = download(c - 1))) return rc;
         }
         if (staged) {
@@ -670,6 +755,7 @@ struct HostCall {
             HIP_TRY(hipStreamSynchronize(ctx.s[0]));
             HIP_TRY(hipStreamSynchronize(ctx.s[1]));
         }
+        if (audit_on) HIP_TRY(hipMemcpy(x->audit_report, report_dev, DD_AUDIT_REPORT_BYTES(x->audit_max_records), hipMemcpyDeviceToHost));
         return DD_SUCCESS;
     }
 };
@@ -990,6 +1076,19 @@ int dd_compute_likelihoods_faster_keys(const dd_params *p, const dd_batch *b, dd
     x.keys = keys_out;
     return compute_likelihoods_impl(MODEL_S, p, b, r, device, options, &x);
 }
+int dd_compute_likelihoods_audit(const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options, uint64_t seed, int32_t n_want,
+                                 void *report, int64_t max_records)
+{
+    if (options & ~DD_OPT_LONG_WINDOWS) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_audit: unknown option bits (the --faster model takes no audit)");
+    if (!report) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_audit: report is required");
+    if (max_records < 0) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_audit: negative max_records");
+    memset(report, 0, DD_AUDIT_REPORT_BYTES(max_records));   // a batch without pairs, or nothing chosen: an empty report
+    ExtraRequest x = {};
+    x.audit = true; x.audit_seed = seed; x.audit_want = n_want; x.audit_report = report; x.audit_max_records = max_records;
+    return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device, options, &x);
+}
+// test hook, see include/dindel_hmm.h
+void dd_audit_inject_next(int window) { g_audit_inject = window; }
 int dd_compute_likelihoods_multi(const dd_params *p, const dd_batch *b, dd_result *r, const int *devices, int n_devices)
 {
     return compute_multi(MODEL_FBMAXERR, p, b, r, devices, n_devices);

@@ -30,7 +30,7 @@ class DeviceBatch:
 
     def __init__(self, pb: PackedBatch, params: capi.dd_params, device="cuda:0", long_windows=False, long_windows_faster=False,
                  cigars=False, ops_cap=capi.DD_CIGAR_DEFAULT_OPS_CAP, hap_ref_pos=None, hap_aligned=None, realign=False, hap_n_indels=None,
-                 diploid_prior=None, indel_keys=False):
+                 diploid_prior=None, indel_keys=False, audit=0, audit_seed=0, audit_max_records=256):
         """long_windows: windows beyond the main kernels' limits (haplotypes up to 4,094 bp, reads up to 4,096 bp, and with maxLengthDel
         12..31 haplotypes over 574 bp) are computed by the long-window kernel after the main launch (dd_launch_device_long) instead of
         being marked DD_PAIR_UNSUPPORTED.  Off by default.
@@ -48,7 +48,11 @@ class DeviceBatch:
         launch_realign(DD_REALIGN_PAIR, ...) as it is, and diploid_pair_results() copies the per-window outputs back.
         indel_keys: launch_indel_keys() counts the distinct indel-map keys of every pair of the --faster model on the device
         (dd_indel_keys_device) from the hpos of the last launch_faster(), and results() also returns indel_keys (int16 [n_pairs]: the
-        count, DD_INDEL_KEYS_OVERFLOW or DD_INDEL_KEYS_NOT_COMPUTED).  Off by default."""
+        count, DD_INDEL_KEYS_OVERFLOW or DD_INDEL_KEYS_NOT_COMPUTED).  Off by default.
+        audit: that many of the batch's ordinary windows (chosen once, with audit_seed: dd_audit_select) are recomputed by the long-window
+        kernel into shadow tensors as large as the sample and compared bit for bit on the device with what launch() left in HBM:
+        launch_audit() behind launch(), audit_results() for the counts, the first audit_max_records differences and the shadow.  Main
+        model only (ValueError with long_windows_faster).  0 = off."""
         if long_windows and long_windows_faster:
             raise ValueError("long_windows and long_windows_faster screen the batch for different models: one resident batch, one screening")
         lib = capi.load()
@@ -188,6 +192,26 @@ class DeviceBatch:
         self.indel_keys = bool(indel_keys)
         if self.indel_keys:
             self.keys = torch.zeros(max(pb.n_pairs, 1), dtype=torch.int16, device=self.device)
+        self.audit = None
+        if audit and int(audit) > 0:
+            if self.long_windows_faster:
+                raise ValueError("audit checks the main model against its long-window kernel: not with long_windows_faster")
+            smp = capi.AuditSample(params, pb, int(audit), audit_seed, skip[:pb.n_windows] if self.n_skipped else None)
+            self.audit = smp
+            self.audit_max_records = int(audit_max_records)
+            at = [_to_dev(a, self.device) for a in (smp.audit_class, smp.pair_off, smp.hpos_off, smp.varcov_off)]
+            self._audit_t = at
+            self.audit_view = smp.view([x.data_ptr() for x in at])
+            sn = {"hpos": smp.sizes.hpos_len, "var_covered": smp.sizes.var_cov_len, "var_fcov": smp.sizes.var_cov_len, "onHap": 0}
+            self._shadow_n = {k: int(sn.get(k, smp.sizes.n_pairs)) for k, _ in capi.RESULT_FIELDS}
+            self.shadow = {k: torch.zeros(max(self._shadow_n[k], 1), dtype=_TORCH_DT[np.dtype(RESULT_DTYPES[k])], device=self.device)
+                           for k, _ in capi.RESULT_FIELDS if k != "onHap"}
+            self.dshadow = capi.dd_device_result()
+            for k, v in self.shadow.items():
+                setattr(self.dshadow, k, v.data_ptr())
+            self.audit_report_t = torch.zeros(len(capi.audit_report_buffer(self.audit_max_records)) // 8, dtype=torch.int64, device=self.device)
+            self.audit_ws_bytes = int(lib.dd_audit_workspace_bytes(C.byref(params), C.byref(self.audit_view)))
+            self.audit_ws = torch.empty(max(self.audit_ws_bytes, 8), dtype=torch.uint8, device=self.device)
         if self.cigars:
             npair = max(pb.n_pairs, 1)
             self.cig = {"n_ops": torch.zeros(npair, dtype=torch.int32, device=self.device),
@@ -253,6 +277,29 @@ class DeviceBatch:
                                       C.c_void_p(self.keys.data_ptr()), C.c_void_p(stream.cuda_stream))
         if rc != 0:
             raise RuntimeError("dd_indel_keys_device rc=%d: %s" % (rc, capi.last_error()))
+
+    def launch_audit(self, stream=None):
+        """The audit of the sample, from what the last launch() left in the result tensors (same stream, behind it): the long-window
+        launch into the shadow tensors, then the comparison into the report. Asynchronous."""
+        if self.audit is None:
+            raise RuntimeError("this batch was built without audit=N")
+        lib = capi.load()
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        rc = lib.dd_audit_device(C.byref(self.params), C.byref(self.db), C.byref(self.dr), C.byref(self.audit_view), C.byref(self.dshadow),
+                                 C.c_void_p(self.audit_report_t.data_ptr()), self.audit_max_records, C.c_void_p(self.audit_ws.data_ptr()),
+                                 self.audit_ws_bytes, C.c_void_p(stream.cuda_stream))
+        if rc != 0:
+            raise RuntimeError("dd_audit_device rc=%d: %s" % (rc, capi.last_error()))
+
+    def audit_results(self):
+        """Synchronise and copy back the last launch_audit(): capi.audit_report's dict (n_pairs, n_diff, diff and compared per field,
+        records) with `shadow`, the shadow arrays trimmed to the sample's lengths, and `sample`, the capi.AuditSample."""
+        torch.cuda.synchronize(self.device)
+        rep = capi.audit_report(self.audit_report_t.cpu().numpy().view(np.uint8), self.audit_max_records)
+        rep["shadow"] = {k: v[:self._shadow_n[k]].cpu().numpy() for k, v in self.shadow.items()}
+        rep["sample"] = self.audit
+        return rep
 
     def launch_realign(self, mode, win_hap_pair=None, stream=None, on_hap=True):
         """The haplotype each read is realigned to and that pair's CIGAR, from the ll, onHap, status and hpos of the last launch() /

@@ -916,6 +916,7 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
     lastHposBytes = B.has_hpos ? size_t(sz.hpos_len) * sizeof(int16_t) : 0;
     lastCigarBytes = B.has_cigars ? size_t(sz.n_pairs) * (12 + 4 * size_t(B.cig_cap)) : 0;
     lastIndelKeyBytes = B.has_keys ? size_t(sz.n_pairs) * sizeof(int16_t) : 0;
+    auditReport_ = AuditReport();
     dd_params P = to_abi(params);
     if (faster) P.mapUnmappedReads = 0;                 // ObservationModelS has no insert-size prior
     const std::chrono::steady_clock::time_point t_packed = std::chrono::steady_clock::now();
@@ -941,6 +942,9 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
         const int rc = reinterpret_cast<Entry>(indelKeysEntry_)(&P, &Bt, &Rz, B.indel_keys.reserve(np), device_,
                                                                 longWindowsFaster_ ? DD_OPT_LONG_WINDOWS_FASTER : 0u);
         if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_faster_keys: ") + dd_last_error();
+    } else if (sz.n_pairs > 0 && !faster && audit_ > 0 && auditCall_) {
+        const int rc = auditCall_(*this, &P, &Bt, &Rz, longWindows_ ? DD_OPT_LONG_WINDOWS : 0u);
+        if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_audit: ") + dd_last_error();
     } else if (sz.n_pairs > 0) {
         const int rc = faster ? (longWindowsFaster_ ? dd_compute_likelihoods_faster_ex(&P, &Bt, &Rz, device_, DD_OPT_LONG_WINDOWS_FASTER)
                                                     : dd_compute_likelihoods_faster(&P, &Bt, &Rz, device_))

@@ -222,6 +222,25 @@ public:
     bool deviceIndelKeys() const { return deviceIndelKeys_; }
     // pairs whose indelCount was recomputed with alignments because the device reported more than 64 keys (process-wide, all engines)
     static long indelKeyFallbacks();
+    // Audit (main model): every computeLikelihoodsBatch call that goes through the plain likelihood entry has windowsPerCall of its windows
+    // (0 = off) recomputed by the long-window kernel and compared with the main kernels' results on the device
+    // (dd_compute_likelihoods_audit; the sample is a function of `seed` and the batch).  The results of the call are what they are without
+    // it; auditReport() is the last such call's report.  Calls that ask for device CIGARs, realigned reads or the diploid pair, and the
+    // --faster model, take no audit: their report is empty.  Default off.
+    // (Defined in device_audit.cpp, which binds the C ABI's entries, like setDeviceIndelKeys.)
+    struct AuditDifference { int job, field; long long pair /* inside the job's window */, index; unsigned long long primaryBits, shadowBits; };
+    struct AuditReport {
+        long long windows = 0, pairs = 0, mismatches = 0;     // windows and pairs compared; differences found (all of them)
+        std::vector<AuditDifference> differences;             // the first 64 of them
+    };
+    void setAudit(int windowsPerCall, unsigned long long seed);
+    int audit() const { return audit_; }
+    const AuditReport &auditReport() const { return auditReport_; }
+    static const char *auditFieldName(int field);
+    // test hook: the next audited call inverts one bit of the device copy of ll of job `job`'s first pair in front of the audit (of the
+    // first audited window if that job is not in the sample) and restores it behind it: a caller's handling of a difference can be tested
+    // without anything going wrong on the device
+    void setAuditInject(int job) { auditInject_ = job; }
     // optional: have the calling thread's device cache (arena, staging mirror, streams) of this engine's device made now, for batches of
     // about `pairs` (haplotype, read) pairs — e.g. while the first batch is still being prepared.  Throws like the batch calls.
     void warmUp(size_t pairs);
@@ -258,6 +277,11 @@ private:
     void (*diploidEntry_)() = nullptr;   // dd_compute_likelihoods_realign_diploid, once setDeviceRealignDiploid has been called
     bool deviceIndelKeys_ = false;
     void (*indelKeysEntry_)() = nullptr; // dd_compute_likelihoods_faster_keys, once setDeviceIndelKeys has been called
+    int audit_ = 0, auditInject_ = -1;
+    unsigned long long auditSeed_ = 0;
+    AuditReport auditReport_;
+    static int auditedCall(LikelihoodEngine &E, const void *params, const void *batch, void *result, unsigned options);
+    int (*auditCall_)(LikelihoodEngine &, const void *, const void *, void *, unsigned) = nullptr;   // auditedCall, once setAudit has been called
     int cigarOpsCap_ = 8;
     std::vector<std::shared_ptr<BatchBlock> > spare_;   // result blocks of earlier calls; one nobody references any more is reused (warm pages)
     unsigned spareNext_ = 0;

@@ -101,6 +101,13 @@
 //                     of being written as skipped windows; no effect with --faster
 //   [--longWindowsFaster]  the same for the --faster model (its own kernel): windows with a haplotype of 767..4,094 bp or a read of
 //                     1,025..4,096 bp are computed instead of being written as skipped windows; effective only with --faster
+//   [--audit N [--auditSeed S]]  main model: in every launch N of its ordinary windows (a seeded sample with every kernel build of the launch in
+//                     it) are recomputed by the long-window kernel and compared on the device, bit for bit, with what the main kernels wrote
+//                     (dd_compute_likelihoods_audit).  The output files are written as without the flag.  Every difference is printed to
+//                     stderr (window line, tid, position, pair, field, both values); the timing line gains audit_windows=, audit_pairs= and
+//                     audit_mismatches=; a run with any difference ends with exit status 3.  Refused with --faster (that model's long kernel
+//                     shares its main kernel's text: no independent check); launches that ask for device CIGARs or realigned reads
+//                     (--deviceCigars, --deviceRealign, --deviceRealignDiploid) take no audit
 //   [--deviceIndelKeys]  with --faster: the one number the window loop needs of a pair's per-base alignment under that model — the size of the
 //                     record's indel map, DInDel.cpp:3529 — is counted on the device behind the likelihood launches and 2 bytes per pair come back
 //                     instead of the alignment's 2 L; a pair with more than 64 distinct keys is recomputed on the host side with alignments
@@ -112,6 +119,9 @@
 //   [--hostEM]        --doPooled: the EM slots run through dd_pooled_em_host on the CPU instead of on the device (the same bits)
 //   [--noLookBack]    several pools: every batch starts with an empty read buffer (no replay of the windows in front of it)
 //   [--injectLateSkip I,J,...]  the reduce step of these windows throws "hapSize error." (a late skip, also under --prepareOnly)
+//   [--auditInject W] with --audit: one bit of the device copy of ll of window W's first pair (W: the window's line in the window file, from 1)
+//                     is inverted in front of that window's audit and restored behind it, if the audit chose the window: the mismatch path
+//                     without anything going wrong on the GPU (the output files are not affected)
 //   [--lateSkipsKnown] the prepare stage is told of the injected late skips in advance and resets its buffers behind them
 #include <atomic>
 #include <chrono>
@@ -205,6 +215,8 @@ struct Options {
     PooledParameters pool;               // --bayesa0, --bayesType
     bool keepAlignments;                 // the per-base alignments come back from the device (--faster without --deviceIndelKeys; --outputRealignedBAM without --deviceCigars)
     std::set<int> injectedLateSkips;
+    int audit = 0, auditInject = -1;     // --audit N: windows audited per launch (0: off); --auditInject W (tests)
+    unsigned long long auditSeed = 0;
     bool discover;                       // --discover: the discovery stage writes varFile (= disc.windowsFile()) before the loop starts
     DiscoverOptions disc;
     std::string vcfFile, vcfRef, sampleID;   // --vcf F: PREFIX.glf.txt -> F after the loop, with the FASTA of --ref
@@ -260,6 +272,9 @@ const char *const kHelp =
     "                             also haplotypes > 574 bp) instead of skipping them; main model only: no effect with --faster\n"
     "            [--longWindowsFaster]  with --faster: compute windows with a haplotype > 766 bp or a read > 1024 bp (up to 4,094 / 4,096) instead of\n"
     "                             skipping them; no effect without --faster\n"
+    "            [--audit N [--auditSeed S]]  main model: recompute N windows of every launch with the long-window kernel and compare them on the\n"
+    "                             device with the main kernels' results (same files; differences go to stderr, exit status 3; audit_windows=,\n"
+    "                             audit_pairs=, audit_mismatches= in the timing line); refused with --faster\n"
     "            [--deviceIndelKeys]  with --faster: count every pair's indel-map keys on the device and bring 2 bytes per pair back instead of its\n"
     "                             per-base alignment (same PREFIX.glf.txt); no effect without --faster\n"
     "            [--maxRead N] [--maxReadLength N] [--minReadOverlap N] [--mapQualThreshold X] [--filterReadAux STR] [--pError X] [--pMut X] [--maxLengthIndel N]\n"
@@ -293,6 +308,8 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
         std::string a = argv[i];
         if (a.compare(0, 2, "--") != 0) { std::cerr << "Unknown argument " << a << "\n"; return false; }
         a = a.substr(2);
+        const size_t eq = a.find('=');
+        if (eq != std::string::npos && eq > 0) { opt[a.substr(0, eq)] = a.substr(eq + 1); continue; }     // --NAME=VALUE
         bool flag = false;
         for (const char *f : kFlags) flag = flag || a == f;
         if (flag) opt[a] = "1";
@@ -303,6 +320,8 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     auto num = [&](const char *k, double dflt) { return has(k) ? atof(opt[k].c_str()) : dflt; };
     exitCode = 1;
     if (has("deviceRealign") && has("doDiploid")) { std::cerr << "--deviceRealign cannot be given with --doDiploid: the realigned BAMs that stay are then the diploid step's, whose haplotype pair is computed on the host\n"; return false; }
+    if (has("audit") && has("faster")) { std::cerr << "--audit cannot be given with --faster: that model's long-window kernel shares its main kernel's text, which is no independent check\n"; return false; }
+    if ((has("auditInject") || has("auditSeed")) && !has("audit")) { std::cerr << "--auditInject and --auditSeed need --audit\n"; return false; }
     if (has("deviceRealign") && has("faster")) { std::cerr << "--deviceRealign cannot be given with --faster: realigned BAMs are written by the main model only\n"; return false; }
     if (has("deviceRealignDiploid") && has("faster")) { std::cerr << "--deviceRealignDiploid cannot be given with --faster: realigned BAMs are written by the main model only\n"; return false; }
     if (has("deviceRealignDiploid") && has("deviceRealign")) { std::cerr << "--deviceRealignDiploid cannot be given with --deviceRealign: one realigns by the diploid step's rule, the other by the pooled analysis'\n"; return false; }
@@ -438,6 +457,9 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     // making them costs a 100,000-window run more than the launches save it; with --deviceCigars a realigned-BAM run brings none back: 4 again;
     // nor does --faster with --deviceIndelKeys)
     o.mergeBatches = std::max(1, int(num("mergeBatches", o.keepAlignments ? 2 : 4)));
+    o.audit = std::max(0, int(num("audit", 0)));
+    o.auditSeed = has("auditSeed") ? strtoull(opt["auditSeed"].c_str(), NULL, 10) : 0ull;
+    o.auditInject = has("auditInject") ? int(num("auditInject", -1)) : -1;
     const std::vector<int> inject = commaInts(has("injectLateSkip") ? opt["injectLateSkip"] : std::string());
     o.injectedLateSkips.insert(inject.begin(), inject.end());
     return true;
@@ -451,6 +473,7 @@ public:
     explicit WindowLoop(const Options &options);          // set-up: throws std::string
     int run();                                            // the exit code
     const std::vector<std::string> &bamPaths() const { return opt.bamPaths; }   // the run's BAM files (--bamFile, or the files of --bamFiles)
+    long long auditMismatches() const { return n.auditMismatches.load(); }
 private:
     void prepareWindow(ReadFetcher &fetcher, WindowTask &T);
     void fillPairPrior(WindowTask &T) const;
@@ -470,6 +493,8 @@ private:
     void fail(const std::string &s);
     template <class F> void guarded(F stage);
     void configureStageEngine(LikelihoodEngine &engine) const;
+    void noteAudit(const LikelihoodEngine &engine, const std::vector<const WindowTask *> &tasks);
+    std::mutex audit_m;                  // the differences' lines on stderr, one report at a time
     WindowLikelihoods recomputeWithAlignments(const WindowTask &T);
     // the read buffer is reset behind this window: it was skipped, or (tests) its late skip was announced (DInDel.cpp:1401-1408)
     bool resetsBehind(bool skipped, int index) const { return skipped || (opt.lateSkipsKnown && opt.injectedLateSkips.count(index)); }
@@ -514,6 +539,7 @@ private:
         std::atomic<long> cigarFallbacks;      // reads redone with getCIGAR on the host (--deviceCigars)
         std::atomic<long long> hposBytes, cigarBytes, fallbackHposBytes;   // what the engines brought back from the device
         std::atomic<long long> realignBytes;   // ... of the realigned reads' arrays (--deviceRealign, --deviceRealignDiploid)
+        std::atomic<long long> auditWindows{0}, auditPairs{0}, auditMismatches{0};   // --audit: summed over the launches
         std::atomic<long long> indelKeyBytes{0};   // ... of the indel-map key counts (--deviceIndelKeys)
         std::atomic<long> pairUncertified{0}, pairFallbackReads{0}, pairDisagreements{0};   // --deviceRealignDiploid, of the windows written: done on the host, reads redone there, --checkDevicePair
         long windows, skipped, rePrepared;     // the writer's
@@ -598,6 +624,22 @@ void WindowLoop::configureStageEngine(LikelihoodEngine &engine) const
     engine.setLongWindows(opt.longWindows);
     engine.setLongWindowsFaster(opt.longWindowsFaster);
     if (opt.deviceIndelKeys) engine.setDeviceIndelKeys(true);
+    if (opt.audit > 0) engine.setAudit(opt.audit, opt.auditSeed);
+}
+
+// --audit: the report of the engine's last call into the run's counters; every difference on stderr.  tasks[j]: the window of the call's job j.
+void WindowLoop::noteAudit(const LikelihoodEngine &engine, const std::vector<const WindowTask *> &tasks)
+{
+    const LikelihoodEngine::AuditReport &A = engine.auditReport();
+    n.auditWindows += A.windows; n.auditPairs += A.pairs; n.auditMismatches += A.mismatches;
+    if (A.differences.empty()) return;
+    std::lock_guard<std::mutex> lk(audit_m);
+    for (const LikelihoodEngine::AuditDifference &d : A.differences) {
+        const WindowTask *T = d.job >= 0 && size_t(d.job) < tasks.size() ? tasks[size_t(d.job)] : NULL;
+        std::cerr << "audit mismatch: window " << (T ? T->index : -1) << " tid: " << (T ? T->tid : std::string("?")) << " pos: " << (T ? T->pos : 0u)
+                  << " pair: " << d.pair << " field: " << LikelihoodEngine::auditFieldName(d.field) << "[" << d.index << "]"
+                  << " main: 0x" << std::hex << d.primaryBits << " long-window: 0x" << d.shadowBits << std::dec << std::endl;
+    }
 }
 
 // (c) --deviceCigars: a read's CIGAR did not fit, its window is computed once more for the per-base alignments.  The engine must bring those
@@ -825,7 +867,19 @@ void WindowLoop::computeWorker(int ct)
                         for (size_t j = 0; j < group[g]->jobs.size(); j++) merged.push_back(std::move(group[g]->jobs[j]));
                     jobs = &merged;
                 }
+                if (opt.audit > 0) {                     // --auditInject: the job of that window, if this launch holds it
+                    size_t at = 0;
+                    for (size_t g = 0; g < group.size(); g++)
+                        for (size_t i = 0; i < group[g]->tasks.size(); i++)
+                            if (group[g]->jobOf[i] != size_t(-1)) { if (group[g]->tasks[i].index == opt.auditInject) engine.setAuditInject(int(at)); at++; }
+                }
                 if (opt.faster) engine.computeLikelihoodsFasterBatch(*jobs); else engine.computeLikelihoodsBatch(*jobs);
+                if (opt.audit > 0) {
+                    std::vector<const WindowTask *> taskOf;
+                    for (size_t g = 0; g < group.size(); g++)
+                        for (size_t i = 0; i < group[g]->tasks.size(); i++) if (group[g]->jobOf[i] != size_t(-1)) taskOf.push_back(&group[g]->tasks[i]);
+                    noteAudit(engine, taskOf);
+                }
                 if (group.size() > 1) {
                     size_t at = 0;
                     for (size_t g = 0; g < group.size(); g++)
@@ -997,7 +1051,9 @@ void WindowLoop::rePrepare(WindowTask &T)
             configureStageEngine(*redo.engine);
         }
         one.push_back(T.job());
+        if (opt.audit > 0 && T.index == opt.auditInject) redo.engine->setAuditInject(0);
         if (opt.faster) redo.engine->computeLikelihoodsFasterBatch(one); else redo.engine->computeLikelihoodsBatch(one);
+        if (opt.audit > 0) noteAudit(*redo.engine, std::vector<const WindowTask *>(1, &T));
         n.hposBytes += (long long)redo.engine->lastHposBytes; n.cigarBytes += (long long)redo.engine->lastCigarBytes; n.realignBytes += (long long)redo.engine->lastRealignBytes;
         n.indelKeyBytes += (long long)redo.engine->lastIndelKeyBytes;
     }
@@ -1182,6 +1238,7 @@ void WindowLoop::report()                                 // --timing: one line;
     if (opt.checkDevicePair) std::cout << " pair_disagreements=" << n.pairDisagreements.load();
     // --deviceIndelKeys: bytes of key counts brought back, and pairs over 64 keys whose window was recomputed with alignments
     if (opt.deviceIndelKeys) std::cout << " indel_key_bytes=" << n.indelKeyBytes.load() << " indel_key_fallbacks=" << LikelihoodEngine::indelKeyFallbacks();
+    if (opt.audit > 0) std::cout << " audit_windows=" << n.auditWindows.load() << " audit_pairs=" << n.auditPairs.load() << " audit_mismatches=" << n.auditMismatches.load();
     // when the first batch and the first 1 / 5 / 20 / 50 / 100 % of the windows were written (seconds since start)
     std::cout << " engines_ready_at=";
     for (size_t i = 0; i < n.readyAt.size(); i++) std::cout << (i ? "," : "") << n.readyAt[i];
@@ -1220,10 +1277,12 @@ int main(int argc, char **argv)
     try {
         if (options.discover) runDiscovery(options);
         int rc = 0;
+        long long auditMismatches = 0;
         {
             WindowLoop loop(options);
             rc = loop.run();
             options.bamPaths = loop.bamPaths();
+            auditMismatches = loop.auditMismatches();
         }
         if (rc == 0 && !options.vcfFile.empty())
             mergeOutputFiles(std::vector<std::string>(1, options.outputPrefix + ".glf.txt"), options.sampleID, options.vcfRef, 10, options.vcfFile, 20);
@@ -1234,6 +1293,10 @@ int main(int argc, char **argv)
             pooledGlfToVcf(glf, options.pooledVcf, std::cerr, options.quiet ? static_cast<std::ostream &>(notes) : std::cout);
             if (!options.pooledGlfFile.empty())
                 pooledCallsToGlf(glf, options.pooledVcfFile, options.pooledGlfFile, options.bamPaths, std::cerr, options.quiet ? static_cast<std::ostream &>(notes) : std::cout);
+        }
+        if (rc == 0 && auditMismatches > 0) {
+            std::cerr << "audit: " << auditMismatches << " difference(s) between the main kernels and the long-window kernel on the audited windows; the output files were written" << std::endl;
+            return 3;
         }
         return rc;
     } catch (std::string &s) {

@@ -857,6 +857,110 @@ int dd_indel_keys_host(const dd_batch *b, const int16_t *hpos_host, const int32_
  * stay on the device — the point of this entry.  Everything else as dd_compute_likelihoods_faster_ex. */
 int dd_compute_likelihoods_faster_keys(const dd_params *p, const dd_batch *b, dd_result *r, int16_t *keys_out, int device, uint32_t options);
 
+/* ---- audit: a sample of a launch's windows recomputed by the long-window kernel and compared on the device (opt-in) ---------- */
+/* The main model has two implementations in this library: the main kernels (hmm_kernel.hip, one build per
+ * haplotype-length class and maxLengthDel) and the long-window kernel (long_kernel.hip: one workgroup per pair, a run-time candidate loop,
+ * no speculative skip; no kernel text in common with hmm_kernel.hip, though it includes hmm_kernel.h and kernel_common.h for the table
+ * layout and the symbol codes and reads the same tables and symbol LUT), which takes any haplotype of 1..DD_LONG_MAX_HAP_LEN bp and any
+ * maxLengthDel.  An audit recomputes a seeded sample
+ * of a launch's DD_WIN_MAIN windows with the long-window kernel into shadow buffers as large as the sample and compares them, bit for bit
+ * and on the device, with what the main kernels left in HBM.  It shows that two independently compiled kernels agree on the sample; it
+ * does not prove a launch right.  Main model only (the --faster model's long kernel shares its main kernel's text).  Without these
+ * entries nothing changes.
+ *
+ * What is compared for one audited pair (csrc/audit_kernel.h is the definition, shared by the kernel and dd_audit_compare_host):
+ *   status first; if the two differ that is ONE difference (DD_AUDIT_FIELD_status) and nothing else of the pair is compared
+ *   DD_PAIR_OK, _NAN, _LLPOS   every per-pair value (ll ... lastBase), the pair's L entries of hpos, its var_covered bytes, and its
+ *                              var_fcov bytes when the batch has hap_var_flank
+ *   DD_PAIR_HAPSIZE            ll, var_covered, and var_fcov when the batch has hap_var_flank
+ *   any other status           nothing more
+ *   onHap is derived and never compared; a field whose pointer is NULL on either side is skipped; equality is equality of bits (doubles
+ *   as 64-bit integers: NaNs and signed zeros count); an element the rule does not name is never read, on either side. */
+enum {
+    DD_AUDIT_FIELD_status = 0, DD_AUDIT_FIELD_ll, DD_AUDIT_FIELD_llOn, DD_AUDIT_FIELD_llOff, DD_AUDIT_FIELD_mLogBQ, DD_AUDIT_FIELD_offHap,
+    DD_AUDIT_FIELD_offHapHMQ, DD_AUDIT_FIELD_numIndels, DD_AUDIT_FIELD_numMismatch, DD_AUDIT_FIELD_nBQT, DD_AUDIT_FIELD_nmmBQT,
+    DD_AUDIT_FIELD_nMMLeft, DD_AUDIT_FIELD_nMMRight, DD_AUDIT_FIELD_firstBase, DD_AUDIT_FIELD_lastBase, DD_AUDIT_FIELD_hpos,
+    DD_AUDIT_FIELD_var_covered, DD_AUDIT_FIELD_var_fcov, DD_AUDIT_N_FIELDS
+};
+/* One difference.  index: the element's index in the PRIMARY array (the pair for a per-pair value); the bits are zero-extended. */
+typedef struct dd_audit_record {
+    int32_t  window, field;
+    int64_t  pair, index;
+    uint64_t primary_bits, shadow_bits;
+} dd_audit_record;
+/* A report: this header, then max_records records.  n_diff counts every difference, also beyond max_records; the first
+ * min(n_diff, max_records) records are written, in any order; the other record slots are zero. */
+typedef struct dd_audit_report {
+    int64_t n_pairs;                        /* pairs compared */
+    int64_t n_diff;                         /* differences found = sum of diff[] */
+    int64_t diff[DD_AUDIT_N_FIELDS];        /* differences per field */
+    int64_t compared[DD_AUDIT_N_FIELDS];    /* elements compared per field (status: one per pair) */
+} dd_audit_report;
+#define DD_AUDIT_REPORT_BYTES(max_records) (sizeof(dd_audit_report) + (size_t)(max_records) * sizeof(dd_audit_record))
+/* The shadow of a sample: what its result arrays must hold, and what the long launch is planned for. */
+typedef struct dd_audit_sizes {
+    int32_t n_windows;                      /* chosen windows */
+    int32_t max_hap_len, max_read_len;      /* longest haplotype / read among them (0: none chosen) */
+    int32_t reserved;
+    int64_t n_pairs, hpos_len, var_cov_len; /* elements of the shadow's per-pair arrays, of its hpos, bytes of each coverage array */
+} dd_audit_sizes;
+/* Choose the sample (host arithmetic, no device).  Eligible: windows of class DD_WIN_MAIN (win_class: dd_screen_windows_ex's or
+ * dd_screen_windows' bytes; NULL = every window) with at least one pair, no empty read or haplotype and nothing beyond the long limits.
+ * The choice is a function of (seed, batch, win_class, p, n_want) alone: when n_want is at least the number of launch classes of
+ * dd_build_length_classes that hold a haplotype of an eligible window, every such class gets a chosen window that holds one of its
+ * haplotypes (one kernel build serves one class, so every build the launch selects is audited); the rest is drawn uniformly from the
+ * eligible windows not yet chosen.  n_want <= 0 chooses none, n_want at or above the eligible count all.
+ *   audit_class [n_windows]       DD_WIN_LONG for a chosen window, DD_WIN_UNSUPPORTED elsewhere
+ *   pair_off, hpos_off, varcov_off [n_windows + 1]   where window w starts in the shadow: prefix sums of dd_batch_offsets' differences over
+ *                                 the chosen windows alone (another window has width 0 there)
+ * Returns the number of eligible windows (>= 0) or a DD_ERR_* code. */
+int dd_audit_select(const dd_params *p, const dd_batch *b, const uint8_t *win_class, uint64_t seed, int32_t n_want, uint8_t *audit_class,
+                    int64_t *pair_off, int64_t *hpos_off, int64_t *varcov_off, dd_audit_sizes *sizes);
+/* dd_audit_select's outputs where the comparison runs: DEVICE copies for dd_audit_device, the host arrays for dd_audit_compare_host.
+ * n_windows and n_qual are the batch's. */
+typedef struct dd_audit_view {
+    int32_t n_windows, n_qual;
+    const uint8_t *audit_class;
+    const int64_t *pair_off, *hpos_off, *varcov_off;
+    dd_audit_sizes sizes;
+} dd_audit_view;
+/* Bytes of device workspace dd_audit_device needs: the long launch's for the sample's maxima (dd_workspace_bytes_long's layout).  0 when
+ * nothing is chosen or a shape is beyond the long limits.  Never shared by two launches that may run at the same time. */
+size_t dd_audit_workspace_bytes(const dd_params *p, const dd_audit_view *view);
+/* Enqueue the audit on `stream`, behind the likelihood launch(es) that wrote `primary` (dd_launch_device, and dd_launch_device_long when
+ * the batch has long windows): the long-window launch over the chosen windows into `shadow` (DEVICE arrays of view->sizes' lengths; ll and
+ * status required, onHap ignored), then the comparison (audit_kernel.hip) into report_dev (DD_AUDIT_REPORT_BYTES(max_records) bytes of
+ * device memory, 8-byte aligned; zeroed on the stream first).  `primary` is only read; b is the batch of the likelihood launch, as it was
+ * handed to it.  Asynchronous; no allocation, no synchronisation.  DD_ERR_NO_DEVICE without a GPU: there is no CPU fallback behind this
+ * entry. */
+int dd_audit_device(const dd_params *p, const dd_device_batch *b, const dd_result *primary, const dd_audit_view *view, const dd_result *shadow,
+                    void *report_dev, int64_t max_records, void *workspace, size_t workspace_bytes, void *stream);
+/* The audit's long launch of the last dd_audit_device / dd_compute_likelihoods_audit call on this host thread (the last window block's, for
+ * the latter): {grid of the long launch, pairs recomputed, most pairs one workgroup took, workspace bytes, K (states per thread / 256),
+ * the sample's longest haplotype, longest read, grid of the comparison}; all 0 when nothing was launched.  The two counters are read from
+ * the workspace header (or the host path's own copy): this synchronises the stream, and after dd_audit_device the workspace must still
+ * be allocated (-1 if the read fails).  dd_long_launch_log is not touched by an audit. */
+#define DD_AUDIT_LOG_FIELDS 8
+void dd_audit_last_launch(int64_t out[DD_AUDIT_LOG_FIELDS]);
+/* The same comparison on the CPU from host arrays, no device needed: `view` holds dd_audit_select's host arrays, `shadow` host arrays of
+ * view->sizes' lengths, `report` DD_AUDIT_REPORT_BYTES(max_records) bytes.  Records come in pair order, a pair's in field order. */
+int dd_audit_compare_host(const dd_batch *b, const dd_result *primary, const dd_audit_view *view, const dd_result *shadow, void *report,
+                          int64_t max_records);
+/* Host pointers: dd_compute_likelihoods_ex (options: 0 or DD_OPT_LONG_WINDOWS) with an audit of n_want windows of the batch, chosen once
+ * with `seed` (dd_audit_select over the whole batch): every window block audits its own chosen windows on its own stream, behind its
+ * likelihood launches and in front of its copy back.  report: DD_AUDIT_REPORT_BYTES(max_records) bytes of host memory; its counts are the
+ * sums over the blocks, its records the first max_records differences of all blocks, in any order.  r comes back exactly as from
+ * dd_compute_likelihoods_ex.  A batch without pairs, and n_want <= 0, give an empty report. */
+int dd_compute_likelihoods_audit(const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options, uint64_t seed,
+                                 int32_t n_want, void *report, int64_t max_records);
+
+/* TEST HOOK, not for production callers: the next dd_compute_likelihoods_audit call of this host thread inverts the lowest bit of the
+ * device copy of ll of `window`'s first pair in front of that window's audit and restores it behind it (also when the audit's launch
+ * fails), so that the caller's results are not affected; the call synchronises the window block's stream once to read the value.  A
+ * window the audit did not choose, or without pairs: nothing happens.  -1 = none.  It lets a caller's handling of a difference be tested
+ * without anything going wrong on the device (dindel_gpu --auditInject). */
+void dd_audit_inject_next(int window);
+
 /* Launch plan the library would use for the main kernel on a batch with these maxima (no device needed):
  * out = {K positions per lane, D build (6 / 11 / 12), 1 if back-pointers go to HBM scratch else 0, waves per workgroup,
  *        read split of a haplotype, LDS bytes per workgroup, scratch bytes (low 31 bits, in KiB), waves per CU the plan expects,
