@@ -50,6 +50,7 @@ AUDIT_FIELDS = ["status", "ll", "llOn", "llOff", "mLogBQ", "offHap", "offHapHMQ"
                 "nMMRight", "firstBase", "lastBase", "hpos", "var_covered", "var_fcov"]
 DD_AUDIT_N_FIELDS = len(AUDIT_FIELDS)
 AUDIT_LOG_FIELDS = ["grid", "pairs", "max_pairs_per_wg", "ws_bytes", "K", "max_hap", "max_read", "compare_grid"]
+AUDIT_FASTER_LOG_FIELDS = ["grid", "pairs", "in_lds", "ws_bytes", "lds_bytes", "max_hap", "max_read", "compare_grid"]   # dd_audit_last_launch_faster
 # alignHaplotypes on the device: per-pair status codes and the launch geometry record
 DD_ALIGN_OK, DD_ALIGN_EMPTY, DD_ALIGN_TOO_LONG, DD_ALIGN_BAD_REF = range(4)
 DD_ALIGN_WS_BUDGET = 512 << 20
@@ -290,7 +291,9 @@ EXPORTS = ["dd_params_struct_defaults", "dd_params_cli_defaults", "dd_batch_size
            "dd_diploid_pairs_device", "dd_diploid_pairs_host", "dd_compute_likelihoods_realign_diploid",
            "dd_indel_keys_device", "dd_indel_keys_host", "dd_compute_likelihoods_faster_keys",
            "dd_audit_select", "dd_audit_workspace_bytes", "dd_audit_device", "dd_audit_last_launch", "dd_audit_compare_host",
-           "dd_compute_likelihoods_audit", "dd_audit_inject_next"]
+           "dd_compute_likelihoods_audit", "dd_audit_inject_next",
+           "dd_audit_select_faster", "dd_audit_workspace_bytes_faster", "dd_audit_device_faster", "dd_audit_last_launch_faster",
+           "dd_audit_shadow_faster_host", "dd_audit_compare_host_faster", "dd_compute_likelihoods_faster_audit"]
 
 _lib = None
 
@@ -413,6 +416,17 @@ def load():
                                                  C.c_int32, C.c_void_p, C.c_int64]
     lib.dd_audit_inject_next.argtypes = [C.c_int]
     lib.dd_audit_inject_next.restype = None
+    lib.dd_audit_select_faster.argtypes = [C.POINTER(dd_params), C.POINTER(dd_batch), c_u8p, C.c_uint32, C.c_uint64, C.c_int32, c_u8p, c_i64p, c_i64p,
+                                           c_i64p, C.POINTER(dd_audit_sizes)]
+    lib.dd_audit_workspace_bytes_faster.argtypes = lib.dd_audit_workspace_bytes.argtypes
+    lib.dd_audit_workspace_bytes_faster.restype = C.c_size_t
+    lib.dd_audit_device_faster.argtypes = lib.dd_audit_device.argtypes
+    lib.dd_audit_last_launch_faster.argtypes = lib.dd_audit_last_launch.argtypes
+    lib.dd_audit_last_launch_faster.restype = None
+    lib.dd_audit_shadow_faster_host.argtypes = [C.POINTER(dd_params), C.POINTER(dd_batch), C.POINTER(dd_audit_view), C.POINTER(dd_result)]
+    lib.dd_audit_compare_host_faster.argtypes = lib.dd_audit_compare_host.argtypes
+    lib.dd_compute_likelihoods_faster_audit.argtypes = [C.POINTER(dd_params), C.POINTER(dd_batch), C.POINTER(dd_result), c_i16p, C.c_int, C.c_uint32,
+                                                        C.c_uint64, C.c_int32, C.c_void_p, C.c_int64]
     lib.dd_last_launch.argtypes = [C.POINTER(C.c_int32 * 8)]
     lib.dd_last_launch.restype = None
     lib.dd_launch_log.argtypes = [c_i32p, C.c_int]
@@ -569,9 +583,10 @@ def indel_keys_host(pb, hpos, status=None, nthreads=1):
 class AuditSample:
     """dd_audit_select on a PackedBatch: audit_class (uint8 [n_windows]), pair_off / hpos_off / varcov_off (int64 [n_windows + 1]), sizes
     (dd_audit_sizes), n_eligible, and `chosen`, the chosen windows' indices.  view() points a dd_audit_view at the host arrays (keep the
-    sample alive while it is in use)."""
+    sample alive while it is in use).  faster=True: dd_audit_select_faster, the sample of a --faster launch, with `options` (0 or
+    DD_OPT_LONG_WINDOWS_FASTER: long windows are eligible too)."""
 
-    def __init__(self, params, pb, n_want, seed=0, win_class=None):
+    def __init__(self, params, pb, n_want, seed=0, win_class=None, faster=False, options=0):
         import numpy as np
         W = pb.n_windows
         self.n_windows, self.n_qual = W, int(pb.ctypes_batch().n_qual)
@@ -580,11 +595,16 @@ class AuditSample:
         self.sizes = dd_audit_sizes()
         wc = None if win_class is None else np.ascontiguousarray(win_class, np.uint8)
         b = pb.ctypes_batch()
-        rc = load().dd_audit_select(C.byref(params), C.byref(b), wc.ctypes.data_as(c_u8p) if wc is not None else None, int(seed) & (2 ** 64 - 1),
-                                    int(n_want), self.audit_class.ctypes.data_as(c_u8p), self.pair_off.ctypes.data_as(c_i64p),
-                                    self.hpos_off.ctypes.data_as(c_i64p), self.varcov_off.ctypes.data_as(c_i64p), C.byref(self.sizes))
+        head = [C.byref(params), C.byref(b), wc.ctypes.data_as(c_u8p) if wc is not None else None]
+        tail = [int(seed) & (2 ** 64 - 1), int(n_want), self.audit_class.ctypes.data_as(c_u8p), self.pair_off.ctypes.data_as(c_i64p),
+                self.hpos_off.ctypes.data_as(c_i64p), self.varcov_off.ctypes.data_as(c_i64p), C.byref(self.sizes)]
+        self.faster = bool(faster)
+        if self.faster:
+            rc = load().dd_audit_select_faster(*head, int(options), *tail)
+        else:
+            rc = load().dd_audit_select(*head, *tail)
         if rc < 0:
-            raise RuntimeError("dd_audit_select rc=%d: %s" % (rc, last_error()))
+            raise RuntimeError("dd_audit_select%s rc=%d: %s" % ("_faster" if self.faster else "", rc, last_error()))
         self.n_eligible = rc
         self.audit_class = self.audit_class[:W]
         self.chosen = np.nonzero(self.audit_class == DD_WIN_LONG)[0]
@@ -629,6 +649,32 @@ def audit_compare_host(pb, primary, sample, shadow, max_records=64):
     if rc != 0:
         raise RuntimeError("dd_audit_compare_host rc=%d: %s" % (rc, last_error()))
     return audit_report(buf, max_records)
+
+
+def audit_shadow_faster_host(params, pb, sample, shadow):
+    """dd_audit_shadow_faster_host: the --faster model's shadow of `sample` (an AuditSample made with faster=True) on the CPU, written into
+    `shadow`, a dd_result struct over host arrays of the sample's lengths (NULL fields are not written)."""
+    b = pb.ctypes_batch()
+    v = sample.view()
+    rc = load().dd_audit_shadow_faster_host(C.byref(params), C.byref(b), C.byref(v), C.byref(shadow))
+    if rc != 0:
+        raise RuntimeError("dd_audit_shadow_faster_host rc=%d: %s" % (rc, last_error()))
+
+
+def audit_compare_host_faster(pb, primary, sample, shadow, max_records=64):
+    """dd_audit_compare_host_faster: audit_compare_host under the --faster model's rule."""
+    buf = audit_report_buffer(max_records)
+    b = pb.ctypes_batch()
+    v = sample.view()
+    rc = load().dd_audit_compare_host_faster(C.byref(b), C.byref(primary), C.byref(v), C.byref(shadow), buf.ctypes.data, int(max_records))
+    if rc != 0:
+        raise RuntimeError("dd_audit_compare_host_faster rc=%d: %s" % (rc, last_error()))
+    return audit_report(buf, max_records)
+
+
+def audit_last_launch_faster():
+    """The shadow launch of this thread's last dd_audit_device_faster call (dd_audit_last_launch_faster)."""
+    return last_launch_of("dd_audit_last_launch_faster", AUDIT_FASTER_LOG_FIELDS)
 
 
 def audit_last_launch():

@@ -7,26 +7,6 @@
 
 namespace ddh {
 namespace {
-// splitmix64: the sample's only source of randomness, so that a choice is a function of the seed and the batch alone
-struct Rng {
-    uint64_t s;
-    uint64_t next()
-    {
-        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        return z ^ (z >> 31);
-    }
-    // uniform in [0, n), n >= 1: the draw is rejected while it lies in the short last stretch of the 64-bit range
-    uint64_t below(uint64_t n)
-    {
-        const uint64_t limit = ~0ull - (~0ull % n + 1) % n;
-        uint64_t v;
-        do v = next(); while (v > limit);
-        return v % n;
-    }
-};
-
 bool window_eligible(const dd_batch *b, const uint8_t *win_class, int w)
 {
     if (win_class && win_class[w] != DD_WIN_MAIN) return false;
@@ -91,7 +71,7 @@ int dd_audit_select(const dd_params *p, const dd_batch *b, const uint8_t *win_cl
     const int E = (int)eligible.size();
     const int want = n_want <= 0 ? 0 : n_want >= E ? E : n_want;
     std::vector<uint8_t> chosen((size_t)W, 0);
-    Rng rng = {seed};
+    AuditRng rng = {seed};
     int n_chosen = 0;
     if (want == E) {
         for (int w : eligible) chosen[(size_t)w] = 1;

@@ -221,7 +221,26 @@ struct RealignInputs {
 int launch_realign_range(const dd_device_batch *b, const RealignInputs &in, const dd_realign_result *out_dev, int ops_cap, void *stream,
                          int read_begin, int read_end);
 
-// ---- audit_host.cpp, audit_capi.cpp ----
+// ---- audit_host.cpp, audit_capi.cpp, faster_shadow_host.cpp, faster_shadow_capi.cpp ----
+// splitmix64: the sample's only source of randomness, so that a choice is a function of the seed and the batch alone
+struct AuditRng {
+    uint64_t s;
+    uint64_t next()
+    {
+        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    }
+    // uniform in [0, n), n >= 1: the draw is rejected while it lies in the short last stretch of the 64-bit range
+    uint64_t below(uint64_t n)
+    {
+        const uint64_t limit = ~0ull - (~0ull % n + 1) % n;
+        uint64_t v;
+        do v = next(); while (v > limit);
+        return v % n;
+    }
+};
 // what the entries that take a dd_audit_view check about it; the comparison's geometry from a host batch (primary_off takes the primary's offsets)
 int check_audit_view(const char *who, const dd_audit_view *v, int n_windows);
 int audit_geometry_host(const dd_batch *b, const dd_audit_view *view, std::vector<int64_t> &primary_off, au_geometry &G);
@@ -232,6 +251,11 @@ int audit_geometry_host(const dd_batch *b, const dd_audit_view *view, std::vecto
 int launch_audit_range(const dd_params *p, const dd_device_batch *b, const dd_result *primary, const dd_audit_view *view, const dd_result *shadow,
                        void *report_dev, int64_t max_records, void *workspace, size_t workspace_bytes, void *stream, int w_begin, int w_end,
                        int read_begin, int read_end, int64_t j_begin, int64_t j_end, unsigned long long *stats);
+
+// The same for the --faster model (faster_shadow_capi.cpp): the shadow kernel over the sample's pairs [j_begin, j_end), then the comparison.
+int launch_audit_faster_range(const dd_params *p, const dd_device_batch *b, const dd_result *primary, const dd_audit_view *view,
+                              const dd_result *shadow, void *report_dev, int64_t max_records, void *workspace, void *stream, int64_t j_begin,
+                              int64_t j_end);
 
 static_assert(DD_LONG_LOG_FIELDS == DD_FASTER_LONG_LOG_FIELDS, "one record type serves both logs");
 struct LongRec {

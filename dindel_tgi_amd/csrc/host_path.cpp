@@ -221,7 +221,8 @@ struct ExtraRequest {
     int16_t *keys;                                                                // non-NULL: a key request, and nothing of the above
     // An audit request (dd_compute_likelihoods_audit, the main model) has nothing of the above either: a sample of the batch's windows, chosen
     // once, is recomputed per window block by the long-window kernel into a shadow as large as the sample and compared on the device with the
-    // block's results; one report for the call comes back.
+    // block's results; one report for the call comes back.  With the --faster model (dd_compute_likelihoods_faster_audit) the sample is that
+    // model's (dd_audit_select_faster), the recomputation the shadow kernel's (faster_shadow_kernel.hip), and a key request may ride along.
     bool audit; uint64_t audit_seed; int32_t audit_want; void *audit_report; int64_t audit_max_records;
 };
 
@@ -413,12 +414,17 @@ struct HostCall {
         if (x && x->audit) {
             // the sample, once for the whole batch; every window block audits its own chosen windows
             audit_class.resize((size_t)std::max(W, 1)); au_pair_off.resize(W + 1); au_hpos_off.resize(W + 1); au_vc_off.resize(W + 1);
-            rc = dd_audit_select(p, b, n_skip ? win_skip.data() : nullptr, x->audit_seed, x->audit_want, audit_class.data(), au_pair_off.data(),
-                                 au_hpos_off.data(), au_vc_off.data(), &au_view.sizes);
+            const uint8_t *cls = n_skip ? win_skip.data() : nullptr;
+            rc = model == MODEL_S ? dd_audit_select_faster(p, b, cls, options & DD_OPT_LONG_WINDOWS_FASTER, x->audit_seed, x->audit_want, audit_class.data(),
+                                                           au_pair_off.data(), au_hpos_off.data(), au_vc_off.data(), &au_view.sizes)
+                                  : dd_audit_select(p, b, cls, x->audit_seed, x->audit_want, audit_class.data(), au_pair_off.data(),
+                                                    au_hpos_off.data(), au_vc_off.data(), &au_view.sizes);
             if (rc < 0) return rc;
             au_view.n_windows = W; au_view.n_qual = b->n_qual;
             audit_on = au_view.sizes.n_pairs > 0;
-            if (audit_on) {
+            if (audit_on && model == MODEL_S) {
+                aws_bytes = std::max<size_t>(dd_audit_workspace_bytes_faster(p, &au_view), 256);    // (0: the shadow kernel's areas are in LDS)
+            } else if (audit_on) {
                 aws_bytes = dd_audit_workspace_bytes(p, &au_view);
                 if (!aws_bytes) return fail(DD_ERR_UNSUPPORTED, "audit: no long-window plan for the sample's shape");
             }
@@ -503,6 +509,10 @@ struct HostCall {
             // The comparison reads every result array on the device: arrays the caller keeps in page-locked memory are staged in HBM and copied
             // back like pageable ones, instead of being read back over the link.  An array the caller does not ask for is not compared.
             for (int i = 0; i < N_RESULT_OUTS; i++) outs[(size_t)i].in_place = false;
+            if (x->keys) {                                   // the key launch reads hpos on the device, wanted back or not: it is compared then
+                outs[OUT_hpos].device_only = !r->hpos;
+                out(x->keys, &keys_dev, SPACE_PAIR, 1, false);
+            }
         } else if (x) {
             // The request's launch reads hpos on the device: alignments the caller wants in page-locked memory are staged in HBM and copied back
             // like pageable ones, instead of being read back over the link; and they are needed there even when the caller does not want them
@@ -672,8 +682,9 @@ struct HostCall {
     int launch_extra(hipStream_t st, int c, int w0, int w1)
     {
         int rc;
+        if (x->keys && (rc = launch_indel_keys_range(&db, dr.hpos, dr.status, keys_dev, st, idx.at(SPACE_PAIR, w0), idx.at(SPACE_PAIR, w1)))) return rc;
         if (x->audit) return audit_on ? launch_audit_block(st, c, w0, w1) : DD_SUCCESS;
-        if (x->keys) return launch_indel_keys_range(&db, dr.hpos, dr.status, keys_dev, st, idx.at(SPACE_PAIR, w0), idx.at(SPACE_PAIR, w1));
+        if (x->keys) return DD_SUCCESS;
         if (x->diploid && (rc = launch_diploid_pairs_range(&db, hh_off_dev, dr.ll, dr.status, prior_dev, &ddp, st, w0, w1))) return rc;
         const ResultSpace space = x->realign ? SPACE_READ : SPACE_PAIR;
         const int64_t lo = idx.at(space, w0), hi = idx.at(space, w1);
@@ -702,8 +713,10 @@ struct HostCall {
             memcpy(&inject_ll[1], &bits, sizeof(bits));
             HIP_TRY(hipMemcpyAsync(target, &inject_ll[1], sizeof(double), hipMemcpyHostToDevice, st));
         }
-        const int rc = launch_audit_range(p, &db, &dr, &au_view, &shadow, report_dev, x->audit_max_records, aws[c & 1], aws_bytes, st, w0, w1,
-                                          b->win_read_off[w0], b->win_read_off[w1], j0, j1, audit_stats + 2 * c);
+        const int rc = model == MODEL_S
+                           ? launch_audit_faster_range(p, &db, &dr, &au_view, &shadow, report_dev, x->audit_max_records, aws[c & 1], st, j0, j1)
+                           : launch_audit_range(p, &db, &dr, &au_view, &shadow, report_dev, x->audit_max_records, aws[c & 1], aws_bytes, st, w0, w1,
+                                                b->win_read_off[w0], b->win_read_off[w1], j0, j1, audit_stats + 2 * c);
         if (inject) HIP_TRY(hipMemcpyAsync(target, &inject_ll[0], sizeof(double), hipMemcpyHostToDevice, st));     // also when the launch failed
         return rc;
     }
@@ -1087,6 +1100,20 @@ int dd_compute_likelihoods_audit(const dd_params *p, const dd_batch *b, dd_resul
     x.audit = true; x.audit_seed = seed; x.audit_want = n_want; x.audit_report = report; x.audit_max_records = max_records;
     return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device, options, &x);
 }
+int dd_compute_likelihoods_faster_audit(const dd_params *p, const dd_batch *b, dd_result *r, int16_t *keys_out, int device, uint32_t options,
+                                        uint64_t seed, int32_t n_want, void *report, int64_t max_records)
+{
+    if (options & ~DD_OPT_LONG_WINDOWS_FASTER)
+        return fail(DD_ERR_INVALID, "dd_compute_likelihoods_faster_audit: unknown option bits (0 or DD_OPT_LONG_WINDOWS_FASTER)");
+    if (!report) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_faster_audit: report is required");
+    if (max_records < 0) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_faster_audit: negative max_records");
+    memset(report, 0, DD_AUDIT_REPORT_BYTES(max_records));                // a batch without pairs, or an empty sample: an empty report
+    ExtraRequest x = {};
+    x.keys = keys_out;
+    x.audit = true; x.audit_seed = seed; x.audit_want = n_want; x.audit_report = report; x.audit_max_records = max_records;
+    return compute_likelihoods_impl(MODEL_S, p, b, r, device, options, &x);
+}
+
 // test hook, see include/dindel_hmm.h
 void dd_audit_inject_next(int window) { g_audit_inject = window; }
 int dd_compute_likelihoods_multi(const dd_params *p, const dd_batch *b, dd_result *r, const int *devices, int n_devices)

@@ -30,7 +30,7 @@ class DeviceBatch:
 
     def __init__(self, pb: PackedBatch, params: capi.dd_params, device="cuda:0", long_windows=False, long_windows_faster=False,
                  cigars=False, ops_cap=capi.DD_CIGAR_DEFAULT_OPS_CAP, hap_ref_pos=None, hap_aligned=None, realign=False, hap_n_indels=None,
-                 diploid_prior=None, indel_keys=False, audit=0, audit_seed=0, audit_max_records=256):
+                 diploid_prior=None, indel_keys=False, audit=0, audit_seed=0, audit_max_records=256, audit_faster=0):
         """long_windows: windows beyond the main kernels' limits (haplotypes up to 4,094 bp, reads up to 4,096 bp, and with maxLengthDel
         12..31 haplotypes over 574 bp) are computed by the long-window kernel after the main launch (dd_launch_device_long) instead of
         being marked DD_PAIR_UNSUPPORTED.  Off by default.
@@ -52,7 +52,12 @@ class DeviceBatch:
         audit: that many of the batch's ordinary windows (chosen once, with audit_seed: dd_audit_select) are recomputed by the long-window
         kernel into shadow tensors as large as the sample and compared bit for bit on the device with what launch() left in HBM:
         launch_audit() behind launch(), audit_results() for the counts, the first audit_max_records differences and the shadow.  Main
-        model only (ValueError with long_windows_faster).  0 = off."""
+        model only (ValueError with long_windows_faster).  0 = off.
+        audit_faster: the same for the --faster model: that many of the windows launch_faster() computes (the long ones too with
+        long_windows_faster; dd_audit_select_faster, audit_seed) are recomputed by the independent shadow kernel
+        (dd_audit_device_faster) and compared with what launch_faster() left in HBM: launch_audit_faster() behind launch_faster(),
+        audit_faster_results() in audit_results()' dict shape.  ValueError with long_windows (the batch is then screened for the main
+        model).  0 = off."""
         if long_windows and long_windows_faster:
             raise ValueError("long_windows and long_windows_faster screen the batch for different models: one resident batch, one screening")
         lib = capi.load()
@@ -212,6 +217,27 @@ class DeviceBatch:
             self.audit_report_t = torch.zeros(len(capi.audit_report_buffer(self.audit_max_records)) // 8, dtype=torch.int64, device=self.device)
             self.audit_ws_bytes = int(lib.dd_audit_workspace_bytes(C.byref(params), C.byref(self.audit_view)))
             self.audit_ws = torch.empty(max(self.audit_ws_bytes, 8), dtype=torch.uint8, device=self.device)
+        self.audit_faster = None
+        if audit_faster and int(audit_faster) > 0:
+            if self.long_windows:
+                raise ValueError("audit_faster checks what launch_faster() computes: not with long_windows (the main model's screen)")
+            smp = capi.AuditSample(params, pb, int(audit_faster), audit_seed, skip[:pb.n_windows] if self.n_skipped else None, faster=True,
+                                   options=capi.DD_OPT_LONG_WINDOWS_FASTER if self.long_windows_faster else 0)
+            self.audit_faster = smp
+            self.audit_max_records = int(audit_max_records)
+            self._audit_faster_t = [_to_dev(x, self.device) for x in (smp.audit_class, smp.pair_off, smp.hpos_off, smp.varcov_off)]
+            self.audit_faster_view = smp.view([x.data_ptr() for x in self._audit_faster_t])
+            sn = {"hpos": smp.sizes.hpos_len, "var_covered": smp.sizes.var_cov_len, "var_fcov": smp.sizes.var_cov_len, "onHap": 0}
+            self._shadow_faster_n = {k: int(sn.get(k, smp.sizes.n_pairs)) for k, _ in capi.RESULT_FIELDS}
+            self.shadow_faster = {k: torch.zeros(max(self._shadow_faster_n[k], 1), dtype=_TORCH_DT[np.dtype(RESULT_DTYPES[k])], device=self.device)
+                                  for k, _ in capi.RESULT_FIELDS if k != "onHap"}
+            self.dshadow_faster = capi.dd_device_result()
+            for k, v in self.shadow_faster.items():
+                setattr(self.dshadow_faster, k, v.data_ptr())
+            self.audit_faster_report_t = torch.zeros(len(capi.audit_report_buffer(self.audit_max_records)) // 8, dtype=torch.int64,
+                                                     device=self.device)
+            self.audit_faster_ws_bytes = int(lib.dd_audit_workspace_bytes_faster(C.byref(params), C.byref(self.audit_faster_view)))
+            self.audit_faster_ws = torch.empty(max(self.audit_faster_ws_bytes, 8), dtype=torch.uint8, device=self.device)
         if self.cigars:
             npair = max(pb.n_pairs, 1)
             self.cig = {"n_ops": torch.zeros(npair, dtype=torch.int32, device=self.device),
@@ -299,6 +325,29 @@ class DeviceBatch:
         rep = capi.audit_report(self.audit_report_t.cpu().numpy().view(np.uint8), self.audit_max_records)
         rep["shadow"] = {k: v[:self._shadow_n[k]].cpu().numpy() for k, v in self.shadow.items()}
         rep["sample"] = self.audit
+        return rep
+
+    def launch_audit_faster(self, stream=None):
+        """The audit of the --faster sample, from what the last launch_faster() left in the result tensors (same stream, behind it): the
+        shadow kernel into the shadow tensors, then the comparison into the report. Asynchronous."""
+        if self.audit_faster is None:
+            raise RuntimeError("this batch was built without audit_faster=N")
+        lib = capi.load()
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        rc = lib.dd_audit_device_faster(C.byref(self.params), C.byref(self.db), C.byref(self.dr), C.byref(self.audit_faster_view),
+                                        C.byref(self.dshadow_faster), C.c_void_p(self.audit_faster_report_t.data_ptr()), self.audit_max_records,
+                                        C.c_void_p(self.audit_faster_ws.data_ptr()), self.audit_faster_ws_bytes, C.c_void_p(stream.cuda_stream))
+        if rc != 0:
+            raise RuntimeError("dd_audit_device_faster rc=%d: %s" % (rc, capi.last_error()))
+
+    def audit_faster_results(self):
+        """Synchronise and copy back the last launch_audit_faster(): audit_results()' dict (n_pairs, n_diff, diff and compared per field,
+        records, `shadow`, `sample`)."""
+        torch.cuda.synchronize(self.device)
+        rep = capi.audit_report(self.audit_faster_report_t.cpu().numpy().view(np.uint8), self.audit_max_records)
+        rep["shadow"] = {k: v[:self._shadow_faster_n[k]].cpu().numpy() for k, v in self.shadow_faster.items()}
+        rep["sample"] = self.audit_faster
         return rep
 
     def launch_realign(self, mode, win_hap_pair=None, stream=None, on_hap=True):

@@ -937,6 +937,9 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
         const int rc = dd_compute_likelihoods_cigars(&P, &Bt, &Rz, S.hap_ref_pos.data(), S.hap_aligned.data(), &Cg, B.cig_cap, device_,
                                                      longWindows_ ? DD_OPT_LONG_WINDOWS : 0u);
         if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_cigars: ") + dd_last_error();
+    } else if (sz.n_pairs > 0 && faster && auditFaster_ > 0 && auditFasterCall_) {
+        const int rc = auditFasterCall_(*this, &P, &Bt, &Rz, B.has_keys ? B.indel_keys.reserve(np) : NULL, longWindowsFaster_ ? DD_OPT_LONG_WINDOWS_FASTER : 0u);
+        if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_faster_audit: ") + dd_last_error();
     } else if (sz.n_pairs > 0 && B.has_keys) {
         typedef int (*Entry)(const dd_params *, const dd_batch *, dd_result *, int16_t *, int, uint32_t);
         const int rc = reinterpret_cast<Entry>(indelKeysEntry_)(&P, &Bt, &Rz, B.indel_keys.reserve(np), device_,

@@ -225,8 +225,8 @@ public:
     // Audit (main model): every computeLikelihoodsBatch call that goes through the plain likelihood entry has windowsPerCall of its windows
     // (0 = off) recomputed by the long-window kernel and compared with the main kernels' results on the device
     // (dd_compute_likelihoods_audit; the sample is a function of `seed` and the batch).  The results of the call are what they are without
-    // it; auditReport() is the last such call's report.  Calls that ask for device CIGARs, realigned reads or the diploid pair, and the
-    // --faster model, take no audit: their report is empty.  Default off.
+    // it; auditReport() is the last such call's report.  Calls that ask for device CIGARs, realigned reads or the diploid pair take no
+    // audit: their report is empty (the --faster model has setAuditFaster, below).  Default off.
     // (Defined in device_audit.cpp, which binds the C ABI's entries, like setDeviceIndelKeys.)
     struct AuditDifference { int job, field; long long pair /* inside the job's window */, index; unsigned long long primaryBits, shadowBits; };
     struct AuditReport {
@@ -235,6 +235,11 @@ public:
     };
     void setAudit(int windowsPerCall, unsigned long long seed);
     int audit() const { return audit_; }
+    // Audit of the --faster model: every --faster call that goes through the plain or the key entry (setDeviceIndelKeys) has windowsPerCall of
+    // the windows it computes (its long windows too, with setLongWindowsFaster) recomputed by the independent shadow kernel and compared on the
+    // device (dd_compute_likelihoods_faster_audit).  Results, seed, auditReport() and the test hook as setAudit's.  Default off.
+    void setAuditFaster(int windowsPerCall, unsigned long long seed);
+    int auditFaster() const { return auditFaster_; }
     const AuditReport &auditReport() const { return auditReport_; }
     static const char *auditFieldName(int field);
     // test hook: the next audited call inverts one bit of the device copy of ll of job `job`'s first pair in front of the audit (of the
@@ -277,11 +282,13 @@ private:
     void (*diploidEntry_)() = nullptr;   // dd_compute_likelihoods_realign_diploid, once setDeviceRealignDiploid has been called
     bool deviceIndelKeys_ = false;
     void (*indelKeysEntry_)() = nullptr; // dd_compute_likelihoods_faster_keys, once setDeviceIndelKeys has been called
-    int audit_ = 0, auditInject_ = -1;
+    int audit_ = 0, auditFaster_ = 0, auditInject_ = -1;
     unsigned long long auditSeed_ = 0;
     AuditReport auditReport_;
     static int auditedCall(LikelihoodEngine &E, const void *params, const void *batch, void *result, unsigned options);
     int (*auditCall_)(LikelihoodEngine &, const void *, const void *, void *, unsigned) = nullptr;   // auditedCall, once setAudit has been called
+    static int auditedFasterCall(LikelihoodEngine &E, const void *params, const void *batch, void *result, short *keys, unsigned options);
+    int (*auditFasterCall_)(LikelihoodEngine &, const void *, const void *, void *, short *, unsigned) = nullptr;   // ... setAuditFaster
     int cigarOpsCap_ = 8;
     std::vector<std::shared_ptr<BatchBlock> > spare_;   // result blocks of earlier calls; one nobody references any more is reused (warm pages)
     unsigned spareNext_ = 0;

@@ -108,6 +108,11 @@
 //                     audit_mismatches=; a run with any difference ends with exit status 3.  Refused with --faster (that model's long kernel
 //                     shares its main kernel's text: no independent check); launches that ask for device CIGARs or realigned reads
 //                     (--deviceCigars, --deviceRealign, --deviceRealignDiploid) take no audit
+//   [--auditFaster N [--auditSeed S]]  --faster model, an option of its own as --longWindowsFaster is: in every launch N of the windows it
+//                     computes (the long ones too with --longWindowsFaster; a seeded sample that holds the launch's longest ordinary
+//                     haplotype and read) are recomputed by an independent shadow kernel, a second implementation of that model, and
+//                     compared on the device, bit for bit, with what the --faster kernels wrote (dd_compute_likelihoods_faster_audit).
+//                     Files, stderr lines, timing keys and exit status 3 as --audit's; also with --deviceIndelKeys.  Refused without --faster
 //   [--deviceIndelKeys]  with --faster: the one number the window loop needs of a pair's per-base alignment under that model — the size of the
 //                     record's indel map, DInDel.cpp:3529 — is counted on the device behind the likelihood launches and 2 bytes per pair come back
 //                     instead of the alignment's 2 L; a pair with more than 64 distinct keys is recomputed on the host side with alignments
@@ -215,7 +220,8 @@ struct Options {
     PooledParameters pool;               // --bayesa0, --bayesType
     bool keepAlignments;                 // the per-base alignments come back from the device (--faster without --deviceIndelKeys; --outputRealignedBAM without --deviceCigars)
     std::set<int> injectedLateSkips;
-    int audit = 0, auditInject = -1;     // --audit N: windows audited per launch (0: off); --auditInject W (tests)
+    int audit = 0, auditInject = -1;     // --audit N / --auditFaster N: windows audited per launch (0: off); --auditInject W (tests)
+    bool auditFaster = false;            // the N came with --auditFaster: the --faster model against its shadow kernel
     unsigned long long auditSeed = 0;
     bool discover;                       // --discover: the discovery stage writes varFile (= disc.windowsFile()) before the loop starts
     DiscoverOptions disc;
@@ -272,6 +278,8 @@ const char *const kHelp =
     "                             also haplotypes > 574 bp) instead of skipping them; main model only: no effect with --faster\n"
     "            [--longWindowsFaster]  with --faster: compute windows with a haplotype > 766 bp or a read > 1024 bp (up to 4,094 / 4,096) instead of\n"
     "                             skipping them; no effect without --faster\n"
+    "            [--auditFaster N [--auditSeed S]]  --faster model: recompute N windows of every launch with the independent shadow kernel and\n"
+    "                             compare them on the device with the --faster kernels' results (as --audit; needs --faster)\n"
     "            [--audit N [--auditSeed S]]  main model: recompute N windows of every launch with the long-window kernel and compare them on the\n"
     "                             device with the main kernels' results (same files; differences go to stderr, exit status 3; audit_windows=,\n"
     "                             audit_pairs=, audit_mismatches= in the timing line); refused with --faster\n"
@@ -321,7 +329,8 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     exitCode = 1;
     if (has("deviceRealign") && has("doDiploid")) { std::cerr << "--deviceRealign cannot be given with --doDiploid: the realigned BAMs that stay are then the diploid step's, whose haplotype pair is computed on the host\n"; return false; }
     if (has("audit") && has("faster")) { std::cerr << "--audit cannot be given with --faster: that model's long-window kernel shares its main kernel's text, which is no independent check\n"; return false; }
-    if ((has("auditInject") || has("auditSeed")) && !has("audit")) { std::cerr << "--auditInject and --auditSeed need --audit\n"; return false; }
+    if (has("auditFaster") && !has("faster")) { std::cerr << "--auditFaster needs --faster: it audits that model's launches (--audit is the main model's)\n"; return false; }
+    if ((has("auditInject") || has("auditSeed")) && !has("audit") && !has("auditFaster")) { std::cerr << "--auditInject and --auditSeed need --audit\n"; return false; }
     if (has("deviceRealign") && has("faster")) { std::cerr << "--deviceRealign cannot be given with --faster: realigned BAMs are written by the main model only\n"; return false; }
     if (has("deviceRealignDiploid") && has("faster")) { std::cerr << "--deviceRealignDiploid cannot be given with --faster: realigned BAMs are written by the main model only\n"; return false; }
     if (has("deviceRealignDiploid") && has("deviceRealign")) { std::cerr << "--deviceRealignDiploid cannot be given with --deviceRealign: one realigns by the diploid step's rule, the other by the pooled analysis'\n"; return false; }
@@ -457,7 +466,8 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     // making them costs a 100,000-window run more than the launches save it; with --deviceCigars a realigned-BAM run brings none back: 4 again;
     // nor does --faster with --deviceIndelKeys)
     o.mergeBatches = std::max(1, int(num("mergeBatches", o.keepAlignments ? 2 : 4)));
-    o.audit = std::max(0, int(num("audit", 0)));
+    o.auditFaster = has("auditFaster");
+    o.audit = std::max(0, int(num(o.auditFaster ? "auditFaster" : "audit", 0)));
     o.auditSeed = has("auditSeed") ? strtoull(opt["auditSeed"].c_str(), NULL, 10) : 0ull;
     o.auditInject = has("auditInject") ? int(num("auditInject", -1)) : -1;
     const std::vector<int> inject = commaInts(has("injectLateSkip") ? opt["injectLateSkip"] : std::string());
@@ -624,7 +634,8 @@ void WindowLoop::configureStageEngine(LikelihoodEngine &engine) const
     engine.setLongWindows(opt.longWindows);
     engine.setLongWindowsFaster(opt.longWindowsFaster);
     if (opt.deviceIndelKeys) engine.setDeviceIndelKeys(true);
-    if (opt.audit > 0) engine.setAudit(opt.audit, opt.auditSeed);
+    if (opt.audit > 0 && opt.auditFaster) engine.setAuditFaster(opt.audit, opt.auditSeed);
+    else if (opt.audit > 0) engine.setAudit(opt.audit, opt.auditSeed);
 }
 
 // --audit: the report of the engine's last call into the run's counters; every difference on stderr.  tasks[j]: the window of the call's job j.
@@ -638,7 +649,7 @@ void WindowLoop::noteAudit(const LikelihoodEngine &engine, const std::vector<con
         const WindowTask *T = d.job >= 0 && size_t(d.job) < tasks.size() ? tasks[size_t(d.job)] : NULL;
         std::cerr << "audit mismatch: window " << (T ? T->index : -1) << " tid: " << (T ? T->tid : std::string("?")) << " pos: " << (T ? T->pos : 0u)
                   << " pair: " << d.pair << " field: " << LikelihoodEngine::auditFieldName(d.field) << "[" << d.index << "]"
-                  << " main: 0x" << std::hex << d.primaryBits << " long-window: 0x" << d.shadowBits << std::dec << std::endl;
+                  << " main: 0x" << std::hex << d.primaryBits << (opt.auditFaster ? " shadow: 0x" : " long-window: 0x") << d.shadowBits << std::dec << std::endl;
     }
 }
 
@@ -1295,7 +1306,9 @@ int main(int argc, char **argv)
                 pooledCallsToGlf(glf, options.pooledVcfFile, options.pooledGlfFile, options.bamPaths, std::cerr, options.quiet ? static_cast<std::ostream &>(notes) : std::cout);
         }
         if (rc == 0 && auditMismatches > 0) {
-            std::cerr << "audit: " << auditMismatches << " difference(s) between the main kernels and the long-window kernel on the audited windows; the output files were written" << std::endl;
+            std::cerr << "audit: " << auditMismatches << " difference(s) between "
+                      << (options.auditFaster ? "the --faster kernels and the shadow kernel" : "the main kernels and the long-window kernel")
+                      << " on the audited windows; the output files were written" << std::endl;
             return 3;
         }
         return rc;

@@ -865,8 +865,8 @@ int dd_compute_likelihoods_faster_keys(const dd_params *p, const dd_batch *b, dd
  * maxLengthDel.  An audit recomputes a seeded sample
  * of a launch's DD_WIN_MAIN windows with the long-window kernel into shadow buffers as large as the sample and compares them, bit for bit
  * and on the device, with what the main kernels left in HBM.  It shows that two independently compiled kernels agree on the sample; it
- * does not prove a launch right.  Main model only (the --faster model's long kernel shares its main kernel's text).  Without these
- * entries nothing changes.
+ * does not prove a launch right.  Main model only (the --faster model's long kernel shares its main kernel's text: that model is audited
+ * against a shadow kernel of its own, "audit of the --faster model" below).  Without these entries nothing changes.
  *
  * What is compared for one audited pair (csrc/audit_kernel.h is the definition, shared by the kernel and dd_audit_compare_host):
  *   status first; if the two differ that is ONE difference (DD_AUDIT_FIELD_status) and nothing else of the pair is compared
@@ -954,12 +954,67 @@ int dd_audit_compare_host(const dd_batch *b, const dd_result *primary, const dd_
 int dd_compute_likelihoods_audit(const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options, uint64_t seed,
                                  int32_t n_want, void *report, int64_t max_records);
 
-/* TEST HOOK, not for production callers: the next dd_compute_likelihoods_audit call of this host thread inverts the lowest bit of the
+/* TEST HOOK, not for production callers: the next dd_compute_likelihoods_audit (or dd_compute_likelihoods_faster_audit, below) call of this
+ * host thread inverts the lowest bit of the
  * device copy of ll of `window`'s first pair in front of that window's audit and restores it behind it (also when the audit's launch
  * fails), so that the caller's results are not affected; the call synchronises the window block's stream once to read the value.  A
  * window the audit did not choose, or without pairs: nothing happens.  -1 = none.  It lets a caller's handling of a difference be tested
  * without anything going wrong on the device (dindel_gpu --auditInject). */
 void dd_audit_inject_next(int window);
+
+/* ---- audit of the --faster model: a sample of a --faster launch's windows recomputed by an independent shadow kernel (opt-in) -------- */
+/* The --faster model's two kernels (faster_kernel.hip, faster_long_kernel.hip) are one text, so neither can check the other.  These
+ * entries recompute a seeded sample of a --faster launch's windows with a second implementation of ObservationModelS, written from the
+ * reference and not from those kernels (csrc/faster_shadow.h: one function per destination state, shared by the shadow kernel
+ * faster_shadow_kernel.hip — one wavefront per pair — and the CPU evaluation below), and compare bit for bit on the device.  As above, an
+ * audit shows that two independently compiled kernels agree on the sample, not that a launch is right.  What the shadow shares with the
+ * kernels it checks, and so cannot see: dd_build_tables' block and its layout, the index arrays and the batch, and the rule itself.
+ *
+ * The rule for this model (au_compared_faster in csrc/faster_shadow.h), where it differs from the main model's:
+ *   DD_PAIR_OK                      every per-pair value, the pair's L entries of hpos, var_covered, and var_fcov with hap_var_flank
+ *   DD_PAIR_NAN, DD_PAIR_HAPSIZE    ll (0), llOn ... nMMRight (the eleven fields the model leaves at defaults; offHapHMQ = 1), var_covered,
+ *                                   var_fcov with hap_var_flank; NOT firstBase, lastBase, hpos: the kernels never write them for such a pair
+ * Records, report, field ids, views and sizes are the main model's audit's. */
+/* dd_audit_select for a --faster launch.  Eligible: windows of class DD_WIN_MAIN of the --faster screen (win_class:
+ * dd_screen_windows_ex's bytes with DD_OPT_LONG_WINDOWS_FASTER, or dd_screen_windows'; NULL = every window) with at least one pair, and,
+ * when `options` has DD_OPT_LONG_WINDOWS_FASTER, those of class DD_WIN_LONG as well (the shadow is independent of the long kernel too);
+ * never a window with an empty read or haplotype or a shape beyond the long limits.  When n_want allows (>= the number of them) the sample
+ * first takes the window holding the longest ordinary haplotype (<= DD_MAX_HAP_LEN bp), the one holding the longest ordinary read
+ * (<= DD_MAX_READ_LEN bp) — the two shapes the --faster launch sizes its LDS for; lowest window index on a tie — and one long window if any
+ * is eligible (drawn with the seed); the rest is the same seeded partial shuffle.  A pure function of its arguments.  Outputs and return
+ * value as dd_audit_select. */
+int dd_audit_select_faster(const dd_params *p, const dd_batch *b, const uint8_t *win_class, uint32_t options, uint64_t seed, int32_t n_want,
+                           uint8_t *audit_class, int64_t *pair_off, int64_t *hpos_off, int64_t *varcov_off, dd_audit_sizes *sizes);
+/* Bytes of device workspace dd_audit_device_faster needs: 0 while the sample's longest haplotype and read are ordinary (the shadow
+ * kernel's back-pointer tile and vote histogram are then in LDS), else one area per wavefront of its grid, the grid shrunk to keep the
+ * total within 256 MiB.  Never shared by two launches that may run at the same time. */
+size_t dd_audit_workspace_bytes_faster(const dd_params *p, const dd_audit_view *view);
+/* Enqueue the audit on `stream`, behind dd_launch_device_faster (and dd_launch_device_faster_long where the batch has long windows) that
+ * wrote `primary`: the shadow kernel over the sample into `shadow` (DEVICE arrays of view->sizes' lengths; ll and status required, onHap
+ * ignored), then the comparison into report_dev (as dd_audit_device's).  `primary` is only read.  workspace may be NULL when
+ * dd_audit_workspace_bytes_faster is 0.  Asynchronous; no allocation, no synchronisation.  DD_ERR_NO_DEVICE without a GPU. */
+int dd_audit_device_faster(const dd_params *p, const dd_device_batch *b, const dd_result *primary, const dd_audit_view *view,
+                           const dd_result *shadow, void *report_dev, int64_t max_records, void *workspace, size_t workspace_bytes, void *stream);
+/* The shadow launch of the last dd_audit_device_faster call on this host thread: {grid of the shadow kernel, pairs recomputed, 1 if its
+ * areas were in LDS else 0, workspace bytes, LDS bytes per workgroup, the sample's longest haplotype, longest read, grid of the
+ * comparison}; all 0 when nothing was launched.  Host-side values only: nothing is read from the device. */
+void dd_audit_last_launch_faster(int64_t out[DD_AUDIT_LOG_FIELDS]);
+/* The shadow on the CPU, no device needed: the same functions the shadow kernel calls (csrc/faster_shadow.h), looped over the sample's
+ * pairs and their destination states.  view: dd_audit_select_faster's host arrays; shadow: host arrays of view->sizes' lengths (ll and
+ * status required; NULL fields are not written).  Writes exactly the elements the rule names for each pair's status. */
+int dd_audit_shadow_faster_host(const dd_params *p, const dd_batch *b, const dd_audit_view *view, const dd_result *shadow);
+/* dd_audit_compare_host under this model's rule. */
+int dd_audit_compare_host_faster(const dd_batch *b, const dd_result *primary, const dd_audit_view *view, const dd_result *shadow, void *report,
+                                 int64_t max_records);
+/* Host pointers: dd_compute_likelihoods_faster_ex (options: 0 or DD_OPT_LONG_WINDOWS_FASTER) with an audit of n_want windows of the batch,
+ * chosen once with `seed` (dd_audit_select_faster over the whole batch, with the same options): every window block audits its own chosen
+ * windows on its own stream, behind its --faster launches and in front of its copy back.  keys_out may be NULL; when given (one int16 per
+ * pair) the key launch runs per block as in dd_compute_likelihoods_faster_keys, and hpos — then on the device whether r->hpos is given or
+ * not — is compared: the configuration --faster is run in.  report, max_records, the empty report and the caller's results: as
+ * dd_compute_likelihoods_audit; r (and keys_out) come back exactly as from the call without audit.  dd_audit_inject_next applies to this
+ * entry too.  dd_audit_last_launch_faster then describes the last window block's shadow launch. */
+int dd_compute_likelihoods_faster_audit(const dd_params *p, const dd_batch *b, dd_result *r, int16_t *keys_out, int device, uint32_t options,
+                                        uint64_t seed, int32_t n_want, void *report, int64_t max_records);
 
 /* Launch plan the library would use for the main kernel on a batch with these maxima (no device needed):
  * out = {K positions per lane, D build (6 / 11 / 12), 1 if back-pointers go to HBM scratch else 0, waves per workgroup,
