@@ -30,6 +30,10 @@ DD_MAX_HAP_LEN, DD_MAX_READ_LEN = 766, 1024
 DD_LONG_MAX_HAP_LEN, DD_LONG_MAX_READ_LEN = 4094, 4096      # the long-window path (opt-in)
 DD_OPT_LONG_WINDOWS = 1
 DD_OPT_LONG_WINDOWS_FASTER = 2     # the --faster model's own long-window option
+DD_OPT_WIDE_DELETIONS = 4          # maxLengthDel above 31: the long-window kernel's wide build (with DD_OPT_LONG_WINDOWS)
+DD_MAX_LENGTH_DEL = 31
+DD_WIDE_MAX_LENGTH_DEL = 2 ** 31 - 3
+DD_LONG_LOG_WIDE = 256             # added to a long launch record's K when the wide build ran
 DD_FASTER_LONG_WS_BUDGET = 512 << 20
 DD_WIN_MAIN, DD_WIN_UNSUPPORTED, DD_WIN_LONG = 0, 1, 2
 DD_LONG_WS_BUDGET = 512 << 20
@@ -293,7 +297,8 @@ EXPORTS = ["dd_params_struct_defaults", "dd_params_cli_defaults", "dd_batch_size
            "dd_audit_select", "dd_audit_workspace_bytes", "dd_audit_device", "dd_audit_last_launch", "dd_audit_compare_host",
            "dd_compute_likelihoods_audit", "dd_audit_inject_next",
            "dd_audit_select_faster", "dd_audit_workspace_bytes_faster", "dd_audit_device_faster", "dd_audit_last_launch_faster",
-           "dd_audit_shadow_faster_host", "dd_audit_compare_host_faster", "dd_compute_likelihoods_faster_audit"]
+           "dd_audit_shadow_faster_host", "dd_audit_compare_host_faster", "dd_compute_likelihoods_faster_audit",
+           "dd_build_tables_ex", "dd_workspace_bytes_wide", "dd_launch_device_wide", "dd_launch_device_faster_ex"]
 
 _lib = None
 
@@ -354,6 +359,11 @@ def load():
     lib.dd_launch_device_long.argtypes = [C.POINTER(dd_params), C.POINTER(dd_device_batch), C.POINTER(dd_device_result),
                                           C.c_void_p, C.c_size_t, C.c_void_p]
     lib.dd_long_launch_log.argtypes = [c_i64p, C.c_int]
+    lib.dd_build_tables_ex.argtypes = lib.dd_build_tables.argtypes + [C.c_uint32]
+    lib.dd_workspace_bytes_wide.argtypes = lib.dd_workspace_bytes_long.argtypes
+    lib.dd_workspace_bytes_wide.restype = C.c_size_t
+    lib.dd_launch_device_wide.argtypes = lib.dd_launch_device_long.argtypes
+    lib.dd_launch_device_faster_ex.argtypes = lib.dd_launch_device_faster.argtypes + [C.c_uint32]
     lib.dd_compute_likelihoods_faster_ex.argtypes = lib.dd_compute_likelihoods_ex.argtypes
     lib.dd_workspace_bytes_faster_long.argtypes = [C.POINTER(dd_params), C.POINTER(dd_device_batch)]
     lib.dd_workspace_bytes_faster_long.restype = C.c_size_t
@@ -485,8 +495,13 @@ def stream_of(stream, device):
 
 
 def long_launch_log():
-    """Every long-window launch of the last dd_launch_device_long / dd_compute_likelihoods_ex call of this thread (dd_long_launch_log)."""
-    return _launch_log(load().dd_long_launch_log, LONG_LOG_FIELDS)
+    """Every long-window launch of the last dd_launch_device_long / dd_launch_device_wide / dd_compute_likelihoods_ex call of this thread
+    (dd_long_launch_log).  `wide` says whether the wide build ran; K is the states per thread / 256 either way."""
+    recs = _launch_log(load().dd_long_launch_log, LONG_LOG_FIELDS)
+    for r in recs:
+        r["wide"] = bool(r["K"] & DD_LONG_LOG_WIDE)
+        r["K"] &= DD_LONG_LOG_WIDE - 1
+    return recs
 
 
 def faster_long_launch_log():

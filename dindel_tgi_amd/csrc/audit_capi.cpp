@@ -38,7 +38,7 @@ int launch_audit_range(const dd_params *p, const dd_device_batch *b, const dd_re
     // the launcher appends to the long path's log, which belongs to the likelihood call: the record moves to the audit's own
     std::vector<LongRec> kept;
     kept.swap(g_long.log);
-    const int rc = g_long.launch_range(p, &lb, &sh, workspace, workspace_bytes, stream, w_begin, w_end, read_begin, read_end, stats);
+    const int rc = g_long.launch_range(p, &lb, &sh, workspace, workspace_bytes, stream, w_begin, w_end, read_begin, read_end, stats, 0);
     kept.swap(g_long.log);
     if (rc) return rc;
     if (!kept.empty()) g_audit_rec.rec = kept.back();

@@ -116,6 +116,9 @@ int screen_windows_ex(const dd_params *p, const dd_batch *b, uint32_t options, u
         return class_windows(b, win_class, max_len_out, sym_lut, false, DD_MAX_HAP_LEN, DD_MAX_READ_LEN, DD_LONG_MAX_HAP_LEN, DD_LONG_MAX_READ_LEN);
     if (!(options & DD_OPT_LONG_WINDOWS))
         return class_windows(b, win_class, max_len_out, sym_lut, with_symbols, DD_MAX_HAP_LEN, DD_MAX_READ_LEN, DD_MAX_HAP_LEN, DD_MAX_READ_LEN);
+    if (wide_on(p, options))
+        // maxLengthDel > 31 (DD_OPT_WIDE_DELETIONS): no main kernel build, every window within the long limits goes to the long path
+        return class_windows(b, win_class, max_len_out, sym_lut, with_symbols, -1, -1, DD_LONG_MAX_HAP_LEN, DD_LONG_MAX_READ_LEN);
     const int main_hap_cap = pick_Dt(p->maxLengthDel + 1) > 12 ? kHapClasses[12].bound : DD_MAX_HAP_LEN;   // D = 32 build: K <= 9 (574 bp)
     return class_windows(b, win_class, max_len_out, sym_lut, with_symbols, main_hap_cap, DD_MAX_READ_LEN, DD_LONG_MAX_HAP_LEN, DD_LONG_MAX_READ_LEN);
 }
@@ -341,11 +344,13 @@ int dd_screen_windows_ex(const dd_params *p, const dd_batch *b, uint32_t options
 {
     if (!b || !win_class) return fail(DD_ERR_INVALID, "null argument");
     if (check_offset_arrays(b)) return DD_ERR_INVALID;
-    if (options & ~(DD_OPT_LONG_WINDOWS | DD_OPT_LONG_WINDOWS_FASTER)) return fail(DD_ERR_INVALID, "unknown option bits");
+    if (options & ~(DD_OPT_LONG_WINDOWS | DD_OPT_LONG_WINDOWS_FASTER | DD_OPT_WIDE_DELETIONS)) return fail(DD_ERR_INVALID, "unknown option bits");
     if ((options & DD_OPT_LONG_WINDOWS) && (options & DD_OPT_LONG_WINDOWS_FASTER))
         return fail(DD_ERR_INVALID, "DD_OPT_LONG_WINDOWS and DD_OPT_LONG_WINDOWS_FASTER class the windows for different models: one at a time");
+    if ((options & DD_OPT_WIDE_DELETIONS) && !(options & DD_OPT_LONG_WINDOWS))      // (the --faster model's classes do not depend on the parameters)
+        return fail(DD_ERR_INVALID, "DD_OPT_WIDE_DELETIONS needs DD_OPT_LONG_WINDOWS (the wide build is the long-window kernel's)");
     if (options) {
-        const int rc = check_params(p);
+        const int rc = check_params(p, options);
         if (rc) return rc;
     }
     uint8_t lut[256];
@@ -410,7 +415,18 @@ int dd_build_symbol_lut(const dd_batch *b, uint8_t *out)
 
 int dd_build_tables(const dd_params *p, const double *qual_table, int n_qual, const double *mapq_table, int n_mapq, double *out)
 {
-    int rc = check_params(p);
+    return build_tables(p, qual_table, n_qual, mapq_table, n_mapq, out, 0);
+}
+int dd_build_tables_ex(const dd_params *p, const double *qual_table, int n_qual, const double *mapq_table, int n_mapq, double *out, uint32_t options)
+{
+    if (options & ~DD_OPT_WIDE_DELETIONS) return fail(DD_ERR_INVALID, "dd_build_tables_ex: unknown option bits (0 or DD_OPT_WIDE_DELETIONS)");
+    return build_tables(p, qual_table, n_qual, mapq_table, n_mapq, out, options);
+}
+} // extern "C"
+// the tables do not depend on maxLengthDel: options only decide which values of it pass the parameter check
+int ddh::build_tables(const dd_params *p, const double *qual_table, int n_qual, const double *mapq_table, int n_mapq, double *out, uint32_t options)
+{
+    int rc = check_params(p, options);
     if (rc) return rc;
     if (n_qual < 0 || n_qual > DD_MAX_QUAL_TABLE || n_mapq < 0 || n_mapq > DD_MAX_QUAL_TABLE)
         return fail(DD_ERR_INVALID, "quality table larger than 256 entries");
@@ -480,6 +496,7 @@ int dd_build_tables(const dd_params *p, const double *qual_table, int n_qual, co
     }
     return T_END;
 }
+extern "C" {
 
 int dd_build_length_classes(const dd_batch *b, const uint8_t *win_skip, const dd_params *p, int32_t *hap_class_list, dd_length_classes *out)
 {

@@ -38,11 +38,14 @@ inline int fail(int code, const std::string &msg) { g_err = msg; return code; }
             return fail(DD_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));        \
     } while (0)
 
-inline int check_params(const dd_params *p)
+// options: the entry's option bits; DD_OPT_WIDE_DELETIONS lets maxLengthDel above 31 pass (an entry without options answers as ever)
+inline int check_params(const dd_params *p, uint32_t options = 0)
 {
     if (!p) return fail(DD_ERR_INVALID, "null params");
     if (p->forceReadOnHaplotype) return fail(DD_ERR_UNSUPPORTED, "forceReadOnHaplotype is not on the production path (DInDel.cpp:1446 only)");
-    if (p->maxLengthDel < 0 || p->maxLengthDel > DD_MAX_LENGTH_DEL) return fail(DD_ERR_UNSUPPORTED, "maxLengthDel outside [0,31]");
+    if ((options & DD_OPT_WIDE_DELETIONS) && p->maxLengthDel > DD_MAX_LENGTH_DEL) {
+        if (p->maxLengthDel > DD_WIDE_MAX_LENGTH_DEL) return fail(DD_ERR_INVALID, "maxLengthDel above INT32_MAX - 2 (D = maxLengthDel + 1 is a 32-bit count)");
+    } else if (p->maxLengthDel < 0 || p->maxLengthDel > DD_MAX_LENGTH_DEL) return fail(DD_ERR_UNSUPPORTED, "maxLengthDel outside [0,31]");
     if (!(p->pError > 0.0 && p->pError < 1.0)) return fail(DD_ERR_INVALID, "pError outside (0,1)");
     // each of these would put a NaN into dd_build_tables' output (log of a negative number, pow of a NaN), and the kernels' dmax() is
     // defined for non-NaN doubles only; the negated compares refuse a NaN field too
@@ -177,13 +180,16 @@ void shape_log_record(const LaunchShape &s, int32_t v[DD_LAUNCH_LOG_FIELDS]);
 
 // ---- long_plan.cpp ----
 struct LongPlan { int K; size_t lds; unsigned grid; uint64_t off_lpoff, off_tiles, stash_off, tile_bytes, ws_bytes; };
-int long_plan(int n_windows, int max_hap_len, int max_read_len, int n_qual, LongPlan &lp, ddl::LongArgs &A);
+int long_plan(int n_windows, int max_hap_len, int max_read_len, int n_qual, LongPlan &lp, ddl::LongArgs &A, bool wide = false);
+// the wide build is asked for (DD_OPT_WIDE_DELETIONS) and needed (maxLengthDel > 31)
+inline bool wide_on(const dd_params *p, uint32_t options) { return (options & DD_OPT_WIDE_DELETIONS) && p && p->maxLengthDel > DD_MAX_LENGTH_DEL; }
 struct FLPlan { size_t lds; unsigned grid; uint64_t off_ioff, off_tiles, ws_bytes; };
 int fl_plan(const dd_device_batch *b, FLPlan &fp, ddf::FLArgs &A);
 
 // ---- batch_host.cpp ----
 int assign_symbols(const dd_batch *b, uint8_t *out);
 int screen_windows(const dd_batch *b, uint8_t *win_skip, int32_t max_len_out[2], const uint8_t *sym_lut, bool with_symbols);
+int build_tables(const dd_params *p, const double *qual_table, int n_qual, const double *mapq_table, int n_mapq, double *out, uint32_t options);
 int screen_windows_ex(const dd_params *p, const dd_batch *b, uint32_t options, uint8_t *win_class, int32_t max_len_out[4],
                       const uint8_t *sym_lut, bool with_symbols);
 int build_launch_classes(const dd_batch *b, const uint8_t *win_skip, const dd_params *p, int32_t *list, dd_length_classes *out);
@@ -200,7 +206,8 @@ LenClass len_class_of(const dd_launch_class &L, const int32_t *class_list, bool 
 // contiguous block of windows); hap_end < 0 means the whole batch.
 // overlapping_chunks: the caller alternates chunk launches between two streams (the host-pointer path)
 int launch_range(Model model, const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes,
-                 void *stream, int hap_begin, int hap_end, int read_begin, int read_end, bool overlapping_chunks, const LenClass *lc = nullptr);
+                 void *stream, int hap_begin, int hap_end, int read_begin, int read_end, bool overlapping_chunks, const LenClass *lc = nullptr,
+                 uint32_t options = 0);
 void launch_log_clear();
 // the CIGAR launch (cigar_kernel.hip) over the pairs [pair_begin, pair_end) of the batch; pair_end < 0 = all of them (win_pair_off is a
 // device array: a caller that wants a range knows its bounds)
@@ -267,7 +274,8 @@ struct LongRec {
 struct LongPath {
     const char *name, *ws_fn;
     int n_stats, stat_field[4];          // stats word i -> log field stat_field[i] (-1: none); also the stride of compute_likelihoods' stats words per window block
-    int (*launch_range)(const dd_params *, const dd_device_batch *, const dd_result *, void *, size_t, void *, int, int, int, int, unsigned long long *);
+    // (the last argument: the call's option bits, of which DD_OPT_WIDE_DELETIONS matters here)
+    int (*launch_range)(const dd_params *, const dd_device_batch *, const dd_result *, void *, size_t, void *, int, int, int, int, unsigned long long *, uint32_t);
     size_t (*workspace_bytes)(const dd_params *, const dd_device_batch *);
     std::vector<LongRec> log;
 };

@@ -139,9 +139,9 @@ struct ResultIndex {
 };
 
 // What a host-pointer call checks first; sz: the batch's sizes.  A batch without pairs (sz.n_pairs == 0) is finished here.
-int front_checks(const dd_params *p, const dd_batch *b, dd_result *r, dd_sizes &sz)
+int front_checks(const dd_params *p, const dd_batch *b, dd_result *r, dd_sizes &sz, uint32_t options = 0)
 {
-    int rc = check_params(p);
+    int rc = check_params(p, options);
     if (rc) return rc;
     if (!r || !r->ll || !r->status) return fail(DD_ERR_INVALID, "ll and status outputs are required");
     if ((rc = dd_batch_sizes(b, &sz))) return rc;
@@ -240,6 +240,7 @@ struct HostCall {
     uint8_t sym_lut[256];
     int n_skip = 0;
     bool long_on = false;
+    bool wide_main = false;                              // main model, DD_OPT_WIDE_DELETIONS and maxLengthDel > 31: the long path's wide launch is the only one
     LongPath *long_path = nullptr;                       // the model's long path (used only if long_on)
     int32_t long_max[4] = {0, 0, 0, 0};
     std::vector<double> lib_logprob, lib_log95;
@@ -293,7 +294,7 @@ struct HostCall {
         launch_log_clear();
         g_long.log.clear();
         g_flong.log.clear();
-        int rc = front_checks(p, b, r, sz);
+        int rc = front_checks(p, b, r, sz, options);
         if (!rc && sz.n_pairs == 0 && x && x->realign)       // reads without haplotypes: no pair, nothing to launch, every read marked
             for (int64_t q = 0; q < sz.n_reads; q++) {
                 const dd_realign_result &o = x->reads;
@@ -345,6 +346,7 @@ struct HostCall {
         const bool fl_on = model == MODEL_S && (options & DD_OPT_LONG_WINDOWS_FASTER);
         long_on = (model == MODEL_FBMAXERR && (options & DD_OPT_LONG_WINDOWS)) || fl_on;
         long_path = fl_on ? &g_flong : &g_long;
+        wide_main = model == MODEL_FBMAXERR && long_on && wide_on(p, options);
         if (long_on) {
             n_skip = screen_windows_ex(p, b, options, win_skip.data(), long_max, sym_lut, sym_left > 0);
             ok_max[0] = long_max[0]; ok_max[1] = long_max[1];
@@ -389,11 +391,11 @@ struct HostCall {
             if ((rc = dd_pair_sum_offsets(b, hh_off.data()))) return rc;
         }
         tables.resize(DD_TABLE_DOUBLES);
-        rc = dd_build_tables(p, b->qual_table, b->n_qual, b->mapq_table, b->n_mapq, tables.data());
+        rc = build_tables(p, b->qual_table, b->n_qual, b->mapq_table, b->n_mapq, tables.data(), options);
         if (rc < 0) return rc;
         // Ragged batches: one launch per (lane tiling of the haplotypes, read-length interval) that has work (build_launch_classes) — a single
         // 170-bp haplotype or 250-bp read does not drag every pair of the batch onto the K = 3 / long-read build.
-        if (model == MODEL_FBMAXERR && !getenv("DD_NO_LENGTH_CLASSES")) {                      // env: A/B only
+        if (model == MODEL_FBMAXERR && !wide_main && !getenv("DD_NO_LENGTH_CLASSES")) {          // env: A/B only
             class_list.resize((size_t)sz.n_haps * DD_N_READ_CLASSES + 1);
             if ((rc = build_launch_classes(b, n_skip ? win_skip.data() : nullptr, p, class_list.data(), &lcls))) return rc;
         }
@@ -402,7 +404,7 @@ struct HostCall {
         db.n_qual = b->n_qual; db.n_mapq = b->n_mapq;
         for (int w = 0; w < W; w++)
             if (!win_skip[(size_t)w] && b->win_read_off[w + 1] - b->win_read_off[w] > db.max_window_reads) db.max_window_reads = b->win_read_off[w + 1] - b->win_read_off[w];
-        ws_bytes = model == MODEL_S ? 0 : dd_workspace_bytes(p, &db);
+        ws_bytes = (model == MODEL_S || wide_main) ? 0 : dd_workspace_bytes(p, &db);
         single_class = lcls.n_launches <= 1;
         if (!single_class) {
             db.classes = &lcls;
@@ -433,7 +435,7 @@ struct HostCall {
         }
         if (long_on && long_max[2] > 0) {
             db.long_max_hap_len = long_max[2]; db.long_max_read_len = long_max[3];
-            lws_bytes = long_path->workspace_bytes(p, &db);
+            lws_bytes = wide_main ? dd_workspace_bytes_wide(p, &db) : long_path->workspace_bytes(p, &db);   // (the --faster long workspace does not depend on the parameters)
             if (!lws_bytes) return fail(DD_ERR_UNSUPPORTED, "long path: no plan for this shape");
         }
         clk.mark("plan");
@@ -737,8 +739,10 @@ struct HostCall {
                 HIP_TRY(hipMemcpyAsync(const_cast<char *>(db.read_seq) + s0, b->read_seq + s0, sn, hipMemcpyHostToDevice, st));
                 HIP_TRY(hipMemcpyAsync(const_cast<uint8_t *>(db.read_qidx) + s0, b->read_qidx + s0, sn, hipMemcpyHostToDevice, st));
             }
-            if (single_class) {
-                if ((rc = launch_range(model, p, &db, &dr, ws[c & 1], ws_bytes, st, g0, g1, q0, q1, n_chunks > 1))) return rc;
+            if (wide_main) {
+                // no main-kernel build for these parameters: the wide launch below writes every pair of the block, placeholders included
+            } else if (single_class) {
+                if ((rc = launch_range(model, p, &db, &dr, ws[c & 1], ws_bytes, st, g0, g1, q0, q1, n_chunks > 1, nullptr, options))) return rc;
             } else {
                 // every launch class of this window block, then onHap once
                 for (int i = 0; i < lcls.n_launches; i++) {
@@ -750,10 +754,11 @@ struct HostCall {
                     if ((rc = launch_range(model, p, &db, &dr, ws[c & 1], ws_bytes, st, g0, g1, q0, q1, n_chunks > 1, &lc))) return rc;
                 }
             }
-            if (lws_bytes) {
-                bool any = false;
+            if (lws_bytes || wide_main) {
+                bool any = wide_main;
                 for (int w = w0; w < w1 && !any; w++) any = win_skip[(size_t)w] == DD_WIN_LONG;
-                if (any && (rc = long_path->launch_range(p, &db, &dr, lws[c & 1], lws_bytes, st, w0, w1, q0, q1, long_stats + long_path->n_stats * c))) return rc;
+                if (any && (rc = long_path->launch_range(p, &db, &dr, lws[c & 1], lws_bytes, st, w0, w1, q0, q1,
+                                                         long_stats ? long_stats + long_path->n_stats * c : nullptr, options))) return rc;
             }
             if (x && (rc = launch_extra(st, c, w0, w1))) return rc;
             if (!staged && c > 0 && (rc = download(c - 1))) return rc;
@@ -1022,15 +1027,23 @@ int dd_compute_likelihoods(const dd_params *p, const dd_batch *b, dd_result *r, 
 {
     return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device);
 }
+// the options of the main model's host-pointer entries: long windows, and with them wide deletions
+static int check_main_options(uint32_t options)
+{
+    if (options & ~(DD_OPT_LONG_WINDOWS | DD_OPT_WIDE_DELETIONS)) return fail(DD_ERR_INVALID, "unknown option bits");
+    if ((options & DD_OPT_WIDE_DELETIONS) && !(options & DD_OPT_LONG_WINDOWS))
+        return fail(DD_ERR_INVALID, "DD_OPT_WIDE_DELETIONS needs DD_OPT_LONG_WINDOWS (the wide build is the long-window kernel's)");
+    return DD_SUCCESS;
+}
 int dd_compute_likelihoods_ex(const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options)
 {
-    if (options & ~DD_OPT_LONG_WINDOWS) return fail(DD_ERR_INVALID, "unknown option bits");
+    if (check_main_options(options)) return DD_ERR_INVALID;
     return compute_likelihoods_impl(MODEL_FBMAXERR, p, b, r, device, options);
 }
 int dd_compute_likelihoods_cigars(const dd_params *p, const dd_batch *b, dd_result *r, const int32_t *hap_ref_pos, const uint8_t *hap_aligned,
                                   const dd_cigar_result *cig, int ops_cap, int device, uint32_t options)
 {
-    if (options & ~DD_OPT_LONG_WINDOWS) return fail(DD_ERR_INVALID, "unknown option bits");
+    if (check_main_options(options)) return DD_ERR_INVALID;
     if (!hap_ref_pos) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_cigars: hap_ref_pos is required (Haplotype::refHpos per haplotype base)");
     if (ops_cap < 1) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_cigars: ops_cap must be at least 1");
     if (!cig || !cig->n_ops || !cig->ops || !cig->ref_off || !cig->status)
@@ -1043,7 +1056,7 @@ int dd_compute_likelihoods_realign(const dd_params *p, const dd_batch *b, dd_res
                                    const int32_t *hap_n_indels, const int32_t *hap_ref_pos, const uint8_t *hap_aligned,
                                    const dd_realign_result *out, int ops_cap, int device, uint32_t options)
 {
-    if (options & ~DD_OPT_LONG_WINDOWS) return fail(DD_ERR_INVALID, "unknown option bits");
+    if (check_main_options(options)) return DD_ERR_INVALID;
     if (mode != DD_REALIGN_FIRST_MAX && mode != DD_REALIGN_PAIR) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign: unknown mode");
     if (mode == DD_REALIGN_PAIR && (!win_hap_pair || !hap_n_indels))
         return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign: DD_REALIGN_PAIR needs win_hap_pair and hap_n_indels");
@@ -1059,7 +1072,7 @@ int dd_compute_likelihoods_realign_diploid(const dd_params *p, const dd_batch *b
                                            const int32_t *hap_ref_pos, const uint8_t *hap_aligned, const dd_diploid_pair_result *pair_out,
                                            const dd_realign_result *realign_out, int ops_cap, int device, uint32_t options)
 {
-    if (options & ~DD_OPT_LONG_WINDOWS) return fail(DD_ERR_INVALID, "unknown option bits");
+    if (check_main_options(options)) return DD_ERR_INVALID;
     if (!prior || !hap_n_indels) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign_diploid: prior and hap_n_indels are required");
     if (!hap_ref_pos) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign_diploid: hap_ref_pos is required (Haplotype::refHpos per haplotype base)");
     if (ops_cap < 1) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_realign_diploid: ops_cap must be at least 1");
@@ -1078,12 +1091,13 @@ int dd_compute_likelihoods_faster(const dd_params *p, const dd_batch *b, dd_resu
 }
 int dd_compute_likelihoods_faster_ex(const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options)
 {
-    if (options & ~DD_OPT_LONG_WINDOWS_FASTER) return fail(DD_ERR_INVALID, "unknown option bits");
+    if (options & ~(DD_OPT_LONG_WINDOWS_FASTER | DD_OPT_WIDE_DELETIONS)) return fail(DD_ERR_INVALID, "unknown option bits");
     return compute_likelihoods_impl(MODEL_S, p, b, r, device, options);
 }
 int dd_compute_likelihoods_faster_keys(const dd_params *p, const dd_batch *b, dd_result *r, int16_t *keys_out, int device, uint32_t options)
 {
-    if (options & ~DD_OPT_LONG_WINDOWS_FASTER) return fail(DD_ERR_INVALID, "unknown option bits");
+    // DD_OPT_WIDE_DELETIONS is taken where it is needed (maxLengthDel above 31); beside a smaller value it stays an unknown bit of this entry
+    if (options & ~(DD_OPT_LONG_WINDOWS_FASTER | (wide_on(p, options) ? DD_OPT_WIDE_DELETIONS : 0u))) return fail(DD_ERR_INVALID, "unknown option bits");
     if (!keys_out) return fail(DD_ERR_INVALID, "dd_compute_likelihoods_faster_keys: keys_out is required");
     ExtraRequest x = {};
     x.keys = keys_out;

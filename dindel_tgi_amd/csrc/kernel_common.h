@@ -79,9 +79,9 @@ __device__ __forceinline__ long long long_prepass(const Args &P, uint64_t off_pr
 
 // onHap[r] of one read of a long window: 1 iff any haplotype of its window has a computed pair with !offHapHMQ (DInDel.cpp:1710, 1720).
 // Runs after the long kernel, so that it sees that kernel's outputs; reads of windows outside [w_begin, w_end) or of another class are
-// not touched.  (Both callers pass [read_begin, read_end) = the reads of the windows [w_begin, w_end), so the range test on w never
+// not touched — EVERY_CLASS (the wide launch, which has no main launch in front of it): reads of every class' windows are written.  (Both callers pass [read_begin, read_end) = the reads of the windows [w_begin, w_end), so the range test on w never
 // decides anything; it only keeps a wrong caller from writing reads of a window the launch did not compute.)
-template <class Args>
+template <bool EVERY_CLASS = false, class Args>
 __device__ __forceinline__ void onhap_of_read(const Args &P)
 {
     const int r = P.read_begin + blockIdx.x * blockDim.x + threadIdx.x;
@@ -92,7 +92,7 @@ __device__ __forceinline__ void onhap_of_read(const Args &P)
         if (P.win_read_off[mid] <= r) lo = mid; else hi = mid;
     }
     const int w = lo;
-    if (w < P.w_begin || w >= P.w_end || P.win_class[w] != DD_WIN_LONG) return;
+    if (w < P.w_begin || w >= P.w_end || (!EVERY_CLASS && P.win_class[w] != DD_WIN_LONG)) return;
     const int H = P.win_hap_off[w + 1] - P.win_hap_off[w];
     const int r0 = P.win_read_off[w];
     const int R = P.win_read_off[w + 1] - r0;

@@ -59,9 +59,10 @@ template <class Args> static int fill_mate_args(Args &A, const dd_device_batch *
 // Check, fill the arguments from the batch, shape the launch (plan.cpp: every decision is shape_launch's / shape_fast's), copy the shape
 // into the arguments, enqueue.
 int launch_range(Model model, const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes,
-                 void *stream, int hap_begin, int hap_end, int read_begin, int read_end, bool overlapping_chunks, const LenClass *lc)
+                 void *stream, int hap_begin, int hap_end, int read_begin, int read_end, bool overlapping_chunks, const LenClass *lc, uint32_t options)
 {
-    int rc = check_params(p);
+    // DD_OPT_WIDE_DELETIONS lifts the parameter check for the --faster model alone: maxLengthDel is only a size check there
+    int rc = check_params(p, model == MODEL_S ? options : 0);
     if (rc) return rc;
     if (!b || !r || !r->ll || !r->status) return fail(DD_ERR_INVALID, "ll and status outputs are required");
     if (b->n_haps <= 0 || b->n_reads <= 0) return DD_SUCCESS;
@@ -209,9 +210,10 @@ int launch_realign_range(const dd_device_batch *b, const RealignInputs &in, cons
 
 // ---------------- long windows: what the two long paths share (long_kernel.hip for the main model, faster_long_kernel.hip for --faster) ----------------
 // The front checks of a long launch.  1: nothing to do (empty batch or range), 0: go on, < 0: error.
-static int long_front_checks(const LongPath &lp, const dd_params *p, const dd_device_batch *b, const dd_result *r, int w_begin, int w_end)
+static int long_front_checks(const LongPath &lp, const dd_params *p, const dd_device_batch *b, const dd_result *r, int w_begin, int w_end,
+                             uint32_t options = 0)
 {
-    int rc = check_params(p);
+    int rc = check_params(p, options);
     if (rc) return rc;
     if (!b || !r || !r->ll || !r->status) return fail(DD_ERR_INVALID, "ll and status outputs are required");
     if (b->long_max_hap_len <= 0 || b->long_max_read_len <= 0 || b->n_haps <= 0 || b->n_reads <= 0 || w_end <= w_begin) return 1;
@@ -220,13 +222,15 @@ static int long_front_checks(const LongPath &lp, const dd_params *p, const dd_de
 }
 
 // The workspace check and the fields LongArgs and FLArgs name alike; the model's own (read_flags, sym_lut, mate / library arrays, D, bMid) stay with the caller.
-// ws_bytes: what the plan needs.  stats: the caller's device words, or NULL for the ones in the workspace header.
+// ws_bytes: what the plan needs; ws_fn: the function that says so (NULL: the path's).  stats: the caller's device words, or NULL for the
+// ones in the workspace header.
 template <class Args>
 static int long_fill_args(const LongPath &lp, Args &A, const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace,
-                          size_t workspace_bytes, uint64_t ws_bytes, int w_begin, int w_end, int read_begin, int read_end, unsigned long long *stats)
+                          size_t workspace_bytes, uint64_t ws_bytes, int w_begin, int w_end, int read_begin, int read_end, unsigned long long *stats,
+                          const char *ws_fn = nullptr)
 {
     if (!workspace || workspace_bytes < ws_bytes)
-        return fail(DD_ERR_INVALID, std::string("workspace too small for the ") + lp.name + ": allocate " + lp.ws_fn + "() bytes");
+        return fail(DD_ERR_INVALID, std::string("workspace too small for the ") + lp.name + ": allocate " + (ws_fn ? ws_fn : lp.ws_fn) + "() bytes");
     fill_batch_args(A, p, b, r);
     A.w_begin = w_begin; A.w_end = w_end; A.read_begin = read_begin; A.read_end = read_end;
     A.win_class = b->win_skip;
@@ -266,17 +270,31 @@ static int long_read_log(LongPath &lp, int64_t *out, int max_records)
 }
 
 // ---------------- long windows of the main model (long_kernel.hip) ----------------
-// one long launch over the windows [w_begin, w_end) (their reads: [read_begin, read_end)); stats: device words the kernel counts into
+// one long launch over the windows [w_begin, w_end) (their reads: [read_begin, read_end)); stats: device words the kernel counts into.
+// options with DD_OPT_WIDE_DELETIONS and maxLengthDel > 31: the wide build, which also writes the placeholders of the other windows of the
+// range and onHap of all its reads (there is no main launch for these parameters).
 static int launch_long_range(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes,
-                             void *stream, int w_begin, int w_end, int read_begin, int read_end, unsigned long long *stats)
+                             void *stream, int w_begin, int w_end, int read_begin, int read_end, unsigned long long *stats, uint32_t options)
 {
-    int rc = long_front_checks(g_long, p, b, r, w_begin, w_end);
-    if (rc) return rc < 0 ? rc : DD_SUCCESS;
+    int rc = long_front_checks(g_long, p, b, r, w_begin, w_end, options);
+    if (rc < 0) return rc;
+    const bool wide = wide_on(p, options);
     ddl::LongArgs A;
     memset(&A, 0, sizeof(A));
+    if (rc && wide && b->n_haps > 0 && b->n_reads > 0 && w_end > w_begin) {
+        // no long window in the batch: placeholders and onHap are still this launch's to write
+        if (!b->win_skip) return fail(DD_ERR_INVALID, "long path: win_skip must hold dd_screen_windows_ex's classes");
+        fill_batch_args(A, p, b, r);
+        A.w_begin = w_begin; A.w_end = w_end; A.read_begin = read_begin; A.read_end = read_end;
+        A.win_class = b->win_skip;
+        HIP_TRY(ddl::launch_wide_tail(A, r->onHap && r->offHapHMQ, static_cast<hipStream_t>(stream)));
+        return DD_SUCCESS;
+    }
+    if (rc) return DD_SUCCESS;
     LongPlan lp;
-    if ((rc = long_plan(b->n_windows, b->long_max_hap_len, b->long_max_read_len, b->n_qual, lp, A))) return rc;
-    if ((rc = long_fill_args(g_long, A, p, b, r, workspace, workspace_bytes, lp.ws_bytes, w_begin, w_end, read_begin, read_end, stats))) return rc;
+    if ((rc = long_plan(b->n_windows, b->long_max_hap_len, b->long_max_read_len, b->n_qual, lp, A, wide))) return rc;
+    if ((rc = long_fill_args(g_long, A, p, b, r, workspace, workspace_bytes, lp.ws_bytes, w_begin, w_end, read_begin, read_end, stats,
+                             wide ? "dd_workspace_bytes_wide" : nullptr))) return rc;
     A.read_flags = b->read_flags; A.sym_lut = b->sym_lut;
     if (p->mapUnmappedReads && (rc = fill_mate_args(A, b))) return rc;
     A.D = p->maxLengthDel + 1; A.bMid = p->bMid;
@@ -284,18 +302,20 @@ static int launch_long_range(const dd_params *p, const dd_device_batch *b, const
     A.off_lpoff = lp.off_lpoff; A.off_tiles = lp.off_tiles; A.tile_bytes = lp.tile_bytes; A.stash_off = lp.stash_off;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool onhap = r->onHap && r->offHapHMQ;
-    HIP_TRY(ddl::launch_long(lp.K, A, lp.grid, lp.lds, onhap, st));
-    const int64_t v[DD_LONG_LOG_FIELDS] = {(int64_t)lp.grid, -1, -1, (int64_t)lp.ws_bytes, lp.K, b->long_max_hap_len, b->long_max_read_len, (int64_t)lp.lds};
+    HIP_TRY(ddl::launch_long(lp.K, wide, A, lp.grid, lp.lds, onhap, st));
+    const int64_t v[DD_LONG_LOG_FIELDS] = {(int64_t)lp.grid, -1, -1, (int64_t)lp.ws_bytes, lp.K | (wide ? DD_LONG_LOG_WIDE : 0), b->long_max_hap_len,
+                                           b->long_max_read_len, (int64_t)lp.lds};
     long_log_push(g_long, v, A.stats, st);
     return DD_SUCCESS;
 }
 
 // ---------------- long windows of the --faster model (faster_long_kernel.hip) ----------------
-// one launch over the windows [w_begin, w_end) (their reads: [read_begin, read_end)); stats: 4 device words the kernel counts into
+// one launch over the windows [w_begin, w_end) (their reads: [read_begin, read_end)); stats: 4 device words the kernel counts into;
+// options: DD_OPT_WIDE_DELETIONS lifts the parameter check (maxLengthDel is only a size check in this model)
 static int launch_faster_long_range(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes,
-                                    void *stream, int w_begin, int w_end, int read_begin, int read_end, unsigned long long *stats)
+                                        void *stream, int w_begin, int w_end, int read_begin, int read_end, unsigned long long *stats, uint32_t options)
 {
-    int rc = long_front_checks(g_flong, p, b, r, w_begin, w_end);
+    int rc = long_front_checks(g_flong, p, b, r, w_begin, w_end, options);
     if (rc) return rc < 0 ? rc : DD_SUCCESS;
     ddf::FLArgs A;
     memset(&A, 0, sizeof(A));
@@ -343,7 +363,13 @@ int dd_launch_device_long(const dd_params *p, const dd_device_batch *b, const dd
 {
     g_long.log.clear();
     if (!b) return fail(DD_ERR_INVALID, "null batch");
-    return launch_long_range(p, b, r, workspace, workspace_bytes, stream, 0, b->n_windows, 0, b->n_reads, nullptr);
+    return launch_long_range(p, b, r, workspace, workspace_bytes, stream, 0, b->n_windows, 0, b->n_reads, nullptr, 0);
+}
+int dd_launch_device_wide(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes, void *stream)
+{
+    g_long.log.clear();
+    if (!b) return fail(DD_ERR_INVALID, "null batch");
+    return launch_long_range(p, b, r, workspace, workspace_bytes, stream, 0, b->n_windows, 0, b->n_reads, nullptr, DD_OPT_WIDE_DELETIONS);
 }
 int dd_long_launch_log(int64_t *out, int max_records) { return long_read_log(g_long, out, max_records); }   // see include/dindel_hmm.h
 
@@ -351,7 +377,7 @@ int dd_launch_device_faster_long(const dd_params *p, const dd_device_batch *b, c
 {
     g_flong.log.clear();
     if (!b) return fail(DD_ERR_INVALID, "null batch");
-    return launch_faster_long_range(p, b, r, workspace, workspace_bytes, stream, 0, b->n_windows, 0, b->n_reads, nullptr);
+    return launch_faster_long_range(p, b, r, workspace, workspace_bytes, stream, 0, b->n_windows, 0, b->n_reads, nullptr, 0);
 }
 int dd_faster_long_launch_log(int64_t *out, int max_records) { return long_read_log(g_flong, out, max_records); }   // see include/dindel_hmm.h
 
@@ -373,6 +399,11 @@ int dd_launch_device(const dd_params *p, const dd_device_batch *b, const dd_resu
 int dd_launch_device_faster(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *stream)
 {
     return launch_range(MODEL_S, p, b, r, nullptr, 0, stream, 0, -1, 0, 0, false);
+}
+int dd_launch_device_faster_ex(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *stream, uint32_t options)
+{
+    if (options & ~DD_OPT_WIDE_DELETIONS) return fail(DD_ERR_INVALID, "dd_launch_device_faster_ex: unknown option bits (0 or DD_OPT_WIDE_DELETIONS)");
+    return launch_range(MODEL_S, p, b, r, nullptr, 0, stream, 0, -1, 0, 0, false, nullptr, options);
 }
 
 int dd_cigars_device(const dd_device_batch *b, const int16_t *hpos_dev, const int32_t *status_dev, const int32_t *hap_ref_pos_dev,

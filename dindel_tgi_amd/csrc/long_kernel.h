@@ -7,7 +7,7 @@
 #include "kernel_common.h"   /* the header words and lists both long paths share: DD_LWS_* */
 
 #define DD_LONG_THREADS 256   /* one workgroup (four wavefronts) per pair */
-#define DD_LONG_PAD 32        /* pad states either side of the LDS row: jumps reach D <= 32 states */
+#define DD_LONG_PAD 32        /* pad states either side of the LDS row: jumps reach D <= 32 states (the wide build clips its loops instead) */
 
 namespace ddl {
 
@@ -15,7 +15,8 @@ namespace ddl {
  *   [0, 256)        header: u64 item counter, i32 long windows, pad, i64 long pairs, u64 stats[2] (pairs computed, most pairs of one workgroup)
  *   [256, ...)      i32 long_win[n_windows]           windows of class DD_WIN_LONG, ascending
  *   [off_lpoff ...) i64 long_pair_off[n_windows + 1]  prefix sums of their pair counts
- *   [off_tiles ...) grid x tile_bytes                 per workgroup: max_read_len rows x 256 K bytes of back-pointers, 2 x 256 K doubles */
+ *   [off_tiles ...) grid x tile_bytes                 per workgroup: max_read_len rows x 256 K bytes of back-pointers (the wide build: x 2),
+ *                                                      2 x 256 K doubles */
 #define DD_LONG_HDR_TOTAL 16
 
 struct LongArgs {
@@ -48,8 +49,12 @@ struct LongArgs {
 
 /* LDS bytes of the long kernel for K positions per thread and reads up to max_read_len; fills the offsets of A */
 size_t long_lds_layout(int K, int max_read_len, LongArgs &A);
-/* prepass (one workgroup: class-2 windows, pair prefix sums, counter and stats zeroed), the kernel, then onHap of the long windows' reads */
-hipError_t launch_long(int K, const LongArgs &A, unsigned grid, size_t lds, bool onhap, hipStream_t st);
+/* what a wide launch does behind its kernel, and all it does for a range without a long window (needs no workspace): the placeholders of
+ * the windows of [w_begin, w_end) that are not DD_WIN_LONG, then onHap of every read of [read_begin, read_end) */
+hipError_t launch_wide_tail(const LongArgs &A, bool onhap, hipStream_t st);
+/* prepass (one workgroup: class-2 windows, pair prefix sums, counter and stats zeroed), the kernel, then onHap of the long windows' reads.
+ * wide: the build for maxLengthDel > 31 (two-byte back-pointers), then launch_wide_tail: that launch has no main launch in front of it */
+hipError_t launch_long(int K, bool wide, const LongArgs &A, unsigned grid, size_t lds, bool onhap, hipStream_t st);
 
 } // namespace ddl
 #endif

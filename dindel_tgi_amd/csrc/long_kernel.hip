@@ -18,6 +18,9 @@
 //   * the join's arg max is a workgroup max + count of near-ties; with more than one state within 3e-10 the reference's scan is replayed
 //     serially (hmm_kernel.hip slice_argmax);
 //   * traceback, hpos, QC counters and coverage flags run on wavefront 0 from the tile and LDS, with the main kernel's run detection.
+// The wide build (maxLengthDel above 31, opt-in: DD_OPT_WIDE_DELETIONS) is the same kernel with two bytes per back-pointer
+// (12 bits of choice: jump lengths up to 4,095) and its candidate loops clipped to the haplotype; it runs without a main launch in front,
+// so its launch writes the placeholders of the screened windows and onHap of every read itself.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
@@ -32,9 +35,13 @@ using ddc::up16;
 #define L_EPS 1e-10
 constexpr int NT = DD_LONG_THREADS;
 constexpr int PAD = DD_LONG_PAD;
-constexpr int CB = 6;                                  // choice bits: jump lengths 0..32
-constexpr unsigned INS_BIT = 1u << CB;
-constexpr unsigned CHMASK = INS_BIT - 1u, FMASK = (INS_BIT << 1) - 1u;
+// a back-pointer field: choice bits (jump lengths 0..32; the wide build's 0..4095), then one bit for the inserted state
+constexpr int choice_bits(bool wide) { return wide ? 12 : 6; }
+constexpr unsigned ins_bit(bool wide) { return 1u << choice_bits(wide); }
+constexpr unsigned choice_mask(bool wide) { return ins_bit(wide) - 1u; }
+constexpr unsigned field_mask(bool wide) { return (ins_bit(wide) << 1) - 1u; }
+template <bool WIDE> struct BtField { typedef unsigned char type; };      // the field as it lies in the tile
+template <> struct BtField<true> { typedef uint16_t type; };
 constexpr int HP_DEF = 64;                             // E/N code of a state without a homopolymer entry: log(1e-5), log(1-1e-5)
 constexpr int SYM_N = 4, SYM_PAD = 255;
 
@@ -148,11 +155,16 @@ __global__ void __launch_bounds__(1024) dd_long_prepass(const LongArgs P)
     if (threadIdx.x == 1023) *reinterpret_cast<int64_t *>(P.ws + DD_LONG_HDR_TOTAL) = total;
 }
 
-template <int K>
+// WIDE (maxLengthDel > 31, DD_OPT_WIDE_DELETIONS): 16-bit back-pointer fields, and candidate loops clipped to the haplotype instead of
+// running into the row pads (the clipped-away candidates are the reference's clamped sources, which never win)
+template <int K, bool WIDE>
 __global__ void __launch_bounds__(NT, K >= 16 ? 1 : 2) dd_long_kernel(const LongArgs P)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NP = NT * K;
+    constexpr int CB = choice_bits(WIDE);
+    constexpr unsigned INS_BIT = ins_bit(WIDE), CHMASK = choice_mask(WIDE), FMASK = field_mask(WIDE);
+    typedef typename BtField<WIDE>::type bt_t;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     double2 *rowA = reinterpret_cast<double2 *>(smem);                        // [PAD + NP + PAD] state s at PAD + s: {alpha / beta, emission}
     double *rowI = reinterpret_cast<double *>(smem + P.lds_off_rowI);          // [1 + NP]  inserted state s at 1 + s
@@ -312,7 +324,7 @@ __global__ void __launch_bounds__(NT, K >= 16 ? 1 : 2) dd_long_kernel(const Long
                 rowA[PAD + x] = make_double2(a[k], ((sym_mask(sc[x]) >> col) & 1u) ? eq : uq);
             }
             __syncthreads();
-            unsigned char *trow = tile + (size_t)b * NP;
+            bt_t *trow = reinterpret_cast<bt_t *>(tile) + (size_t)b * NP;
 #pragma unroll
             for (int k = 0; k < K; k++) {
                 const int x = k * NT + t;
@@ -324,8 +336,9 @@ __global__ void __launch_bounds__(NT, K >= 16 ? 1 : 2) dd_long_kernel(const Long
                     best = (c + s1.x) + s1.y;
                 }
                 unsigned ch = 1;
+                const int yEnd = WIDE ? min(Dr, RO - x) : Dr;  // wide: sources up to RO only
 #pragma unroll 1
-                for (int y = 2; y <= Dr; y++) {
+                for (int y = 2; y <= yEnd; y++) {
                     const int src = x + y;
                     const double yII = (double)(y - 1) * II;
                     const double2 tv = rowA[PAD + src];
@@ -371,7 +384,7 @@ __global__ void __launch_bounds__(NT, K >= 16 ? 1 : 2) dd_long_kernel(const Long
                     in[k] = ni;
                 }
                 a[k] = na;
-                trow[x] = (unsigned char)code;                // btb[b-1] stored at row b
+                trow[x] = (bt_t)code;                // btb[b-1] stored at row b
             }
             __syncthreads();
         }
@@ -401,7 +414,7 @@ __global__ void __launch_bounds__(NT, K >= 16 ? 1 : 2) dd_long_kernel(const Long
                 rowI[1 + x] = in[k];
             }
             __syncthreads();
-            unsigned char *trow = tile + (size_t)b * NP;
+            bt_t *trow = reinterpret_cast<bt_t *>(tile) + (size_t)b * NP;
 #pragma unroll
             for (int k = 0; k < K; k++) {
                 const int x = k * NT + t;
@@ -413,8 +426,9 @@ __global__ void __launch_bounds__(NT, K >= 16 ? 1 : 2) dd_long_kernel(const Long
                 const double2 s1 = rowA[PAD + x - 1];          // state x-1 (the left pad below state 0)
                 double best = ((s1.y + lpn) + s1.x) + lpn;     // (:1793), y = 1
                 unsigned ch = 1;
+                const int yEnd = WIDE ? min(Dr, x) : Dr;       // wide: sources down to LO only
 #pragma unroll 1
-                for (int y = 2; y <= Dr; y++) {
+                for (int y = 2; y <= yEnd; y++) {
                     const double2 tv = rowA[PAD + x - y];
                     const double lp = eIn + (double)(y - 1) * II;
                     const double val = ((tv.y + lp) + tv.x) + lpn;
@@ -457,7 +471,7 @@ __global__ void __launch_bounds__(NT, K >= 16 ? 1 : 2) dd_long_kernel(const Long
                 }
                 a[k] = na;
                 in[k] = ni;
-                trow[x] = (unsigned char)code;
+                trow[x] = (bt_t)code;
             }
             __syncthreads();
         }
@@ -550,7 +564,7 @@ __global__ void __launch_bounds__(NT, K >= 16 ? 1 : 2) dd_long_kernel(const Long
         const bool offHapHMQ = (xH == 0 || xH == RO);
         // ================= traceback: computeMAPState (:1148-1165), the main kernel's run detection (64 rows at a time)
         {
-            auto fieldAt = [&](int row, int x) -> unsigned { return (unsigned)tile[(size_t)row * NP + x] & FMASK; };
+            auto fieldAt = [&](int row, int x) -> unsigned { return (unsigned)reinterpret_cast<const bt_t *>(tile)[(size_t)row * NP + x] & FMASK; };
             const int s0 = __builtin_amdgcn_readfirstlane(mapHMQ);
             if (lane == 0) ms[bMid] = (int16_t)s0;
             {   // towards base 0: mapState[b-1] = btf[b][mapState[b]]
@@ -767,6 +781,25 @@ __global__ void __launch_bounds__(NT, K >= 16 ? 1 : 2) dd_long_kernel(const Long
 // onHap[r] of the long windows' reads, after the long kernel (kernel_common.h)
 __global__ void dd_long_onhap_kernel(const LongArgs P) { ddc::onhap_of_read(P); }
 
+// A wide launch has no main launch in front of it: the pairs of the windows of [w_begin, w_end) that are not DD_WIN_LONG get here the
+// placeholder the main kernels give a screened window (hmm_kernel.hip mark_unsupported).  One workgroup per window.
+__global__ void __launch_bounds__(256) dd_wide_placeholder_kernel(const LongArgs P)
+{
+    const int w = P.w_begin + (int)blockIdx.x;
+    if (w >= P.w_end || P.win_class[w] == DD_WIN_LONG) return;
+    const int64_t p0 = P.win_pair_off[w], p1 = P.win_pair_off[w + 1];
+    for (int64_t pair = p0 + threadIdx.x; pair < p1; pair += blockDim.x) {
+        P.out.status[pair] = DD_PAIR_UNSUPPORTED;
+        P.out.ll[pair] = 0.0;
+        if (P.out.offHap) P.out.offHap[pair] = 1;
+        if (P.out.offHapHMQ) P.out.offHapHMQ[pair] = 1;
+    }
+}
+
+// ... and onHap[r] of every read of [read_begin, read_end), after the kernels above (a placeholder window's pairs are all
+// DD_PAIR_UNSUPPORTED: its reads get 0, as from the main launch's pass)
+__global__ void dd_wide_onhap_kernel(const LongArgs P) { ddc::onhap_of_read<true>(P); }
+
 size_t long_lds_layout(int K, int max_read_len, LongArgs &A)
 {
     const size_t NP = (size_t)NT * K;
@@ -784,33 +817,54 @@ size_t long_lds_layout(int K, int max_read_len, LongArgs &A)
     return up16(o);
 }
 
-template <int K>
+template <int K, bool WIDE>
 static hipError_t launch_k(const LongArgs &A, unsigned grid, size_t lds, hipStream_t st)
 {
     // the dynamic-LDS cap is raised once per instance and device
     static std::atomic<unsigned> raised(0u);
-    const hipError_t e = ddc::raise_lds_cap_once(reinterpret_cast<const void *>(&dd_long_kernel<K>), raised);
+    const hipError_t e = ddc::raise_lds_cap_once(reinterpret_cast<const void *>(&dd_long_kernel<K, WIDE>), raised);
     if (e != hipSuccess) return e;
     if (lds > 160u * 1024u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dd_long_kernel<K>, dim3(grid), dim3(NT), lds, st, A);
+    hipLaunchKernelGGL((dd_long_kernel<K, WIDE>), dim3(grid), dim3(NT), lds, st, A);
     return hipGetLastError();
 }
 
-hipError_t launch_long(int K, const LongArgs &A, unsigned grid, size_t lds, bool onhap, hipStream_t st)
+hipError_t launch_wide_tail(const LongArgs &A, bool onhap, hipStream_t st)
+{
+    hipError_t e = hipSuccess;
+    if (A.w_end > A.w_begin) {
+        hipLaunchKernelGGL(dd_wide_placeholder_kernel, dim3(A.w_end - A.w_begin), dim3(256), 0, st, A);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if (onhap && A.read_end > A.read_begin) {
+        hipLaunchKernelGGL(dd_wide_onhap_kernel, dim3((A.read_end - A.read_begin + 255) / 256), dim3(256), 0, st, A);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
+template <bool WIDE>
+static hipError_t launch_build(int K, const LongArgs &A, unsigned grid, size_t lds, hipStream_t st)
+{
+    switch (K) {
+    case 1: return launch_k<1, WIDE>(A, grid, lds, st);
+    case 2: return launch_k<2, WIDE>(A, grid, lds, st);
+    case 4: return launch_k<4, WIDE>(A, grid, lds, st);
+    case 8: return launch_k<8, WIDE>(A, grid, lds, st);
+    case 16: return launch_k<16, WIDE>(A, grid, lds, st);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_long(int K, bool wide, const LongArgs &A, unsigned grid, size_t lds, bool onhap, hipStream_t st)
 {
     if (grid < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(dd_long_prepass, dim3(1), dim3(1024), 0, st, A);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    switch (K) {
-    case 1: e = launch_k<1>(A, grid, lds, st); break;
-    case 2: e = launch_k<2>(A, grid, lds, st); break;
-    case 4: e = launch_k<4>(A, grid, lds, st); break;
-    case 8: e = launch_k<8>(A, grid, lds, st); break;
-    case 16: e = launch_k<16>(A, grid, lds, st); break;
-    default: return hipErrorInvalidValue;
-    }
+    e = wide ? launch_build<true>(K, A, grid, lds, st) : launch_build<false>(K, A, grid, lds, st);
     if (e != hipSuccess) return e;
+    if (wide) return launch_wide_tail(A, onhap, st);
     if (onhap && A.read_end > A.read_begin) {
         hipLaunchKernelGGL(dd_long_onhap_kernel, dim3((A.read_end - A.read_begin + 255) / 256), dim3(256), 0, st, A);
         e = hipGetLastError();

@@ -14,8 +14,8 @@ static void long_list_layout(int n_windows, uint64_t &off_prefix, uint64_t &off_
 // ---------------- long windows of the main model (long_kernel.hip) ----------------
 // Plan of a long launch: K states per thread (numS <= 256 K, K = 1, 2, 4, 8, 16), LDS, and the persistent grid: the chip's resident
 // workgroups (LDS- and register-limited: 2 per CU, 1 at K = 16), shrunk so that header + lists + one back-pointer tile per workgroup stay
-// within DD_LONG_WS_BUDGET.
-int long_plan(int n_windows, int max_hap_len, int max_read_len, int n_qual, LongPlan &lp, ddl::LongArgs &A)
+// within DD_LONG_WS_BUDGET.  wide: the build for maxLengthDel > 31, whose back-pointer fields take two bytes (32 MiB + stash at the maximum shape).
+int long_plan(int n_windows, int max_hap_len, int max_read_len, int n_qual, LongPlan &lp, ddl::LongArgs &A, bool wide)
 {
     if (max_hap_len < 1 || max_hap_len > DD_LONG_MAX_HAP_LEN) return fail(DD_ERR_UNSUPPORTED, "long path: haplotype length outside [1,4094]");
     if (max_read_len < 1 || max_read_len > DD_LONG_MAX_READ_LEN) return fail(DD_ERR_UNSUPPORTED, "long path: read length outside [1,4096]");
@@ -27,7 +27,7 @@ int long_plan(int n_windows, int max_hap_len, int max_read_len, int n_qual, Long
     if (lp.lds + 64 > kCuLdsBytes) return fail(DD_ERR_UNSUPPORTED, "long path: LDS layout too large");
     const unsigned per_cu = std::max(1u, std::min(lp.K >= 16 ? 1u : 2u, (unsigned)((kCuLdsBytes) / (lp.lds + 64))));
     long_list_layout(n_windows, lp.off_lpoff, lp.off_tiles);
-    lp.stash_off = al256((uint64_t)max_read_len * DD_LONG_THREADS * lp.K);
+    lp.stash_off = al256((uint64_t)max_read_len * DD_LONG_THREADS * lp.K * (wide ? 2 : 1));
     lp.tile_bytes = lp.stash_off + 16 * (uint64_t)DD_LONG_THREADS * lp.K;
     uint64_t grid = (uint64_t)kCUs * per_cu;
     const uint64_t fit = DD_LONG_WS_BUDGET > lp.off_tiles ? (DD_LONG_WS_BUDGET - lp.off_tiles) / lp.tile_bytes : 0;
@@ -76,6 +76,18 @@ size_t dd_workspace_bytes_long(const dd_params *p, const dd_device_batch *b)
     memset(&A, 0, sizeof(A));
     LongPlan lp;
     if (long_plan(b->n_windows, b->long_max_hap_len, b->long_max_read_len, b->n_qual, lp, A)) return 0;
+    return (size_t)lp.ws_bytes;
+}
+
+size_t dd_workspace_bytes_wide(const dd_params *p, const dd_device_batch *b)
+{
+    if (!p || check_params(p, DD_OPT_WIDE_DELETIONS) != DD_SUCCESS) return 0;
+    if (p->maxLengthDel <= DD_MAX_LENGTH_DEL) return dd_workspace_bytes_long(p, b);
+    if (!b || b->long_max_hap_len <= 0 || b->long_max_read_len <= 0) return 0;
+    ddl::LongArgs A;
+    memset(&A, 0, sizeof(A));
+    LongPlan lp;
+    if (long_plan(b->n_windows, b->long_max_hap_len, b->long_max_read_len, b->n_qual, lp, A, true)) return 0;
     return (size_t)lp.ws_bytes;
 }
 

@@ -30,7 +30,8 @@ class DeviceBatch:
 
     def __init__(self, pb: PackedBatch, params: capi.dd_params, device="cuda:0", long_windows=False, long_windows_faster=False,
                  cigars=False, ops_cap=capi.DD_CIGAR_DEFAULT_OPS_CAP, hap_ref_pos=None, hap_aligned=None, realign=False, hap_n_indels=None,
-                 diploid_prior=None, indel_keys=False, audit=0, audit_seed=0, audit_max_records=256, audit_faster=0):
+                 diploid_prior=None, indel_keys=False, audit=0, audit_seed=0, audit_max_records=256, audit_faster=0,
+                 wide_deletions=False, wide_deletions_faster=False):
         """long_windows: windows beyond the main kernels' limits (haplotypes up to 4,094 bp, reads up to 4,096 bp, and with maxLengthDel
         12..31 haplotypes over 574 bp) are computed by the long-window kernel after the main launch (dd_launch_device_long) instead of
         being marked DD_PAIR_UNSUPPORTED.  Off by default.
@@ -57,7 +58,19 @@ class DeviceBatch:
         long_windows_faster; dd_audit_select_faster, audit_seed) are recomputed by the independent shadow kernel
         (dd_audit_device_faster) and compared with what launch_faster() left in HBM: launch_audit_faster() behind launch_faster(),
         audit_faster_results() in audit_results()' dict shape.  ValueError with long_windows (the batch is then screened for the main
-        model).  0 = off."""
+        model).  0 = off.
+        wide_deletions: params.maxLengthDel above 31 is accepted (DD_OPT_WIDE_DELETIONS): launch() then sends every window through the
+        long-window kernel's wide build (dd_launch_device_wide, no main launch; windows beyond the long limits get their placeholders from
+        it).  Needs long_windows (ValueError without); with maxLengthDel <= 31 it changes nothing.  No audit with maxLengthDel above 31.
+        wide_deletions_faster: the same value lifted for launch_faster() (dd_launch_device_faster_ex; the --faster model only compares it
+        with the haplotype length).  Not with long_windows; the long windows of the --faster model take such a value through the
+        host-pointer entries only (dd_compute_likelihoods_faster_ex)."""
+        if wide_deletions and not long_windows:
+            raise ValueError("wide_deletions needs long_windows=True: the wide build is the long-window kernel's")
+        if wide_deletions_faster and (long_windows or long_windows_faster):
+            raise ValueError("wide_deletions_faster lifts the check for launch_faster()'s main launch: not with long_windows / long_windows_faster")
+        self.opt_wide = capi.DD_OPT_WIDE_DELETIONS if (wide_deletions or wide_deletions_faster) else 0
+        self.wide = bool(wide_deletions) and params.maxLengthDel > capi.DD_MAX_LENGTH_DEL
         if long_windows and long_windows_faster:
             raise ValueError("long_windows and long_windows_faster screen the batch for different models: one resident batch, one screening")
         lib = capi.load()
@@ -77,10 +90,10 @@ class DeviceBatch:
         if rc != 0:
             raise RuntimeError("dd_build_index: " + capi.last_error())
         tables = np.zeros(capi.DD_TABLE_DOUBLES, np.float64)
-        rc = lib.dd_build_tables(C.byref(params), hb.qual_table, hb.n_qual, hb.mapq_table, hb.n_mapq,
-                                 tables.ctypes.data_as(capi.c_f64p))
+        rc = lib.dd_build_tables_ex(C.byref(params), hb.qual_table, hb.n_qual, hb.mapq_table, hb.n_mapq,
+                                    tables.ctypes.data_as(capi.c_f64p), self.opt_wide)
         if rc < 0:
-            raise RuntimeError("dd_build_tables: " + capi.last_error())
+            raise RuntimeError("dd_build_tables_ex: " + capi.last_error())
         t["hap_window"] = _to_dev(hap_window, self.device)
         t["win_pair_off"] = _to_dev(po, self.device)
         t["win_hpos_off"] = _to_dev(ho, self.device)
@@ -106,7 +119,7 @@ class DeviceBatch:
         self.n_long = 0
         if self.long_windows or self.long_windows_faster:   # classes: 0 main kernels, 1 unsupported, 2 long path (the main kernels skip every non-zero value)
             ok_max = (C.c_int32 * 4)()
-            opt = capi.DD_OPT_LONG_WINDOWS_FASTER if self.long_windows_faster else capi.DD_OPT_LONG_WINDOWS
+            opt = (capi.DD_OPT_LONG_WINDOWS_FASTER if self.long_windows_faster else capi.DD_OPT_LONG_WINDOWS) | self.opt_wide
             n_bad = lib.dd_screen_windows_ex(C.byref(params), C.byref(hb), opt, skip.ctypes.data_as(capi.c_u8p),
                                              C.byref(ok_max))
             if n_bad < 0:
@@ -122,7 +135,9 @@ class DeviceBatch:
             t["win_skip"] = _to_dev(skip, self.device)
         self.classes = capi.dd_length_classes()
         hcl = np.zeros(max(pb.n_haps, 1) * capi.N_READ_CLASSES, np.int32)
-        if lib.dd_build_length_classes(C.byref(hb), skip.ctypes.data_as(capi.c_u8p) if self.n_skipped else None, C.byref(params),
+        # (launch classes are the main kernels': none where maxLengthDel is beyond every main build)
+        if params.maxLengthDel <= capi.DD_MAX_LENGTH_DEL and \
+           lib.dd_build_length_classes(C.byref(hb), skip.ctypes.data_as(capi.c_u8p) if self.n_skipped else None, C.byref(params),
                                        hcl.ctypes.data_as(capi.c_i32p), C.byref(self.classes)) != 0:
             raise RuntimeError("dd_build_length_classes: " + capi.last_error())
         t["hap_class_list"] = _to_dev(hcl[:max(self.classes.list_len, 1)], self.device)
@@ -151,9 +166,9 @@ class DeviceBatch:
         # device scratch the launch needs for this shape (back-pointer tiles in HBM for long reads); 0 if none
         self.ws_bytes = int(lib.dd_workspace_bytes(C.byref(params), C.byref(db)))
         self.ws = torch.empty(max(self.ws_bytes, 8), dtype=torch.uint8, device=self.device)
-        ws_long = lib.dd_workspace_bytes_faster_long if self.long_windows_faster else lib.dd_workspace_bytes_long
+        ws_long = lib.dd_workspace_bytes_faster_long if self.long_windows_faster else lib.dd_workspace_bytes_wide if self.wide else lib.dd_workspace_bytes_long
         self.long_ws_bytes = int(ws_long(C.byref(params), C.byref(db))) if self.n_long else 0
-        self.long_ws = torch.empty(max(self.long_ws_bytes, 8), dtype=torch.uint8, device=self.device) if self.n_long else None
+        self.long_ws = torch.empty(max(self.long_ws_bytes, 8), dtype=torch.uint8, device=self.device) if (self.n_long or self.wide) else None
         self.cigars = bool(cigars)
         self.realign = bool(realign)
         if self.cigars or self.realign:
@@ -199,6 +214,8 @@ class DeviceBatch:
             self.keys = torch.zeros(max(pb.n_pairs, 1), dtype=torch.int16, device=self.device)
         self.audit = None
         if audit and int(audit) > 0:
+            if self.wide:
+                raise ValueError("no audit with maxLengthDel above 31: the shadow would be the same kernel")
             if self.long_windows_faster:
                 raise ValueError("audit checks the main model against its long-window kernel: not with long_windows_faster")
             smp = capi.AuditSample(params, pb, int(audit), audit_seed, skip[:pb.n_windows] if self.n_skipped else None)
@@ -253,6 +270,12 @@ class DeviceBatch:
         lib = capi.load()
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
+        if self.wide:                  # no main launch for these parameters: the wide launch writes every pair and every read's onHap
+            rc = lib.dd_launch_device_wide(C.byref(self.params), C.byref(self.db), C.byref(self.dr), C.c_void_p(self.long_ws.data_ptr()),
+                                           self.long_ws_bytes, C.c_void_p(stream.cuda_stream))
+            if rc != 0:
+                raise RuntimeError("dd_launch_device_wide rc=%d: %s" % (rc, capi.last_error()))
+            return
         rc = lib.dd_launch_device(C.byref(self.params), C.byref(self.db), C.byref(self.dr),
                                   C.c_void_p(self.ws.data_ptr()), self.ws_bytes, C.c_void_p(stream.cuda_stream))
         if rc != 0:
@@ -268,9 +291,9 @@ class DeviceBatch:
         lib = capi.load()
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
-        rc = lib.dd_launch_device_faster(C.byref(self.params), C.byref(self.db), C.byref(self.dr), C.c_void_p(stream.cuda_stream))
+        rc = lib.dd_launch_device_faster_ex(C.byref(self.params), C.byref(self.db), C.byref(self.dr), C.c_void_p(stream.cuda_stream), self.opt_wide)
         if rc != 0:
-            raise RuntimeError("dd_launch_device_faster rc=%d: %s" % (rc, capi.last_error()))
+            raise RuntimeError("dd_launch_device_faster_ex rc=%d: %s" % (rc, capi.last_error()))
         if self.long_windows_faster and self.n_long:   # after the main launch and its onHap pass, on the same stream
             rc = lib.dd_launch_device_faster_long(C.byref(self.params), C.byref(self.db), C.byref(self.dr), C.c_void_p(self.long_ws.data_ptr()),
                                                   self.long_ws_bytes, C.c_void_p(stream.cuda_stream))

@@ -235,9 +235,9 @@ struct BatchBlock {
     RawBuf<double> dp_best, dp_gap, dp_margin;
     bool has_keys;                                       // device indel keys (setDeviceIndelKeys): per pair, the --faster model
     RawBuf<int16_t> indel_keys;
-    int device; bool long_faster;                        // ... and what a recomputation of one of its windows needs of the engine that made it
+    int device; bool long_faster, wide;                  // ... and what a recomputation of one of its windows needs of the engine that made it
     BatchBlock() : W(0), faster(false), has_hpos(false), has_cigars(false), cig_cap(0), has_realign(false), has_pairs(false), has_keys(false),
-                   device(0), long_faster(false) {}
+                   device(0), long_faster(false), wide(false) {}
 };
 
 struct PackScratch {
@@ -446,7 +446,7 @@ WindowLikelihoods WindowLikelihoods::handMadeFaster(const std::vector<Haplotype>
     WindowLikelihoods v = handMadeRealign(haps, reads, 1, NULL, NULL, NULL, NULL, NULL, hpos);
     BatchBlock &B = const_cast<BatchBlock &>(*v.blk_);     // (just made, nobody else refers to it)
     B.faster = true;
-    if (eng) { B.params = eng->params; B.device = eng->device_; B.long_faster = eng->longWindowsFaster_; }
+    if (eng) { B.params = eng->params; B.device = eng->device_; B.long_faster = eng->longWindowsFaster_; B.wide = eng->wideDeletions_; }
     if (keys) {
         const size_t np = haps.size() * reads.size();
         B.has_keys = true;
@@ -475,6 +475,7 @@ int WindowLikelihoods::indelCount(size_t h, size_t r) const
         if (!full_) {
             LikelihoodEngine own(B.params, B.device);
             own.setLongWindowsFaster(B.long_faster);
+            own.setWideDeletions(B.wide);
             std::vector<WindowJob> one(1);
             one[0].haps = haps_; one[0].reads = reads_; one[0].leftPos = leftPos_; one[0].rightPos = leftPos_ + 1;
             own.runBatch(one, true);
@@ -678,7 +679,7 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
     if (!scratch_) scratch_ = std::make_shared<PackScratch>();
     BatchBlock &B = *blk;
     PackScratch &S = *scratch_;
-    B.W = W; B.faster = faster; B.params = params; B.device = device_; B.long_faster = longWindowsFaster_;
+    B.W = W; B.faster = faster; B.params = params; B.device = device_; B.long_faster = longWindowsFaster_; B.wide = wideDeletions_;
     bool any_eager = false;
     for (int w = 0; w < W; w++) if (jobs[w].liks) any_eager = true;
     // device CIGARs: the pairs' CIGARs come back instead of their alignments (main model, lazy jobs only)
@@ -919,6 +920,9 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
     auditReport_ = AuditReport();
     dd_params P = to_abi(params);
     if (faster) P.mapUnmappedReads = 0;                 // ObservationModelS has no insert-size prior
+    // the entries' option bits (the audits take the long-window bit alone; the wide bit goes along only where it is needed)
+    const uint32_t wideOpt = wideDeletions_ && P.maxLengthDel > DD_MAX_LENGTH_DEL ? DD_OPT_WIDE_DELETIONS : 0u;
+    const uint32_t mainOpt = (longWindows_ ? DD_OPT_LONG_WINDOWS : 0u) | wideOpt, fasterOpt = (longWindowsFaster_ ? DD_OPT_LONG_WINDOWS_FASTER : 0u) | wideOpt;
     const std::chrono::steady_clock::time_point t_packed = std::chrono::steady_clock::now();
     if (getenv("DD_TIMING"))
         fprintf(stderr, "pack_timing: windows=%d pass1=%.2fms pass2+alloc=%.2fms\n", W, std::chrono::duration<double, std::milli>(t_pass1 - t_start).count(),
@@ -927,32 +931,29 @@ void LikelihoodEngine::runBatch(std::vector<WindowJob> &jobs, bool faster)
         typedef int (*Entry)(const dd_params *, const dd_batch *, dd_result *, const double *, const int32_t *, const int32_t *, const uint8_t *,
                              const dd_diploid_pair_result *, const dd_realign_result *, int, int, uint32_t);
         const int rc = reinterpret_cast<Entry>(diploidEntry_)(&P, &Bt, &Rz, S.pair_prior.data(), S.hap_n_indels.data(), S.hap_ref_pos.data(),
-                                                              S.hap_aligned.data(), &Dp, &Rl, B.cig_cap, device_, longWindows_ ? DD_OPT_LONG_WINDOWS : 0u);
+                                                              S.hap_aligned.data(), &Dp, &Rl, B.cig_cap, device_, mainOpt);
         if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_realign_diploid: ") + dd_last_error();
     } else if (B.has_realign) {                          // (also without pairs: reads of windows without haplotypes are marked)
         const int rc = dd_compute_likelihoods_realign(&P, &Bt, &Rz, DD_REALIGN_FIRST_MAX, NULL, NULL, S.hap_ref_pos.data(), S.hap_aligned.data(), &Rl,
-                                                      B.cig_cap, device_, longWindows_ ? DD_OPT_LONG_WINDOWS : 0u);
+                                                      B.cig_cap, device_, mainOpt);
         if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_realign: ") + dd_last_error();
     } else if (sz.n_pairs > 0 && B.has_cigars) {
-        const int rc = dd_compute_likelihoods_cigars(&P, &Bt, &Rz, S.hap_ref_pos.data(), S.hap_aligned.data(), &Cg, B.cig_cap, device_,
-                                                     longWindows_ ? DD_OPT_LONG_WINDOWS : 0u);
+        const int rc = dd_compute_likelihoods_cigars(&P, &Bt, &Rz, S.hap_ref_pos.data(), S.hap_aligned.data(), &Cg, B.cig_cap, device_, mainOpt);
         if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_cigars: ") + dd_last_error();
     } else if (sz.n_pairs > 0 && faster && auditFaster_ > 0 && auditFasterCall_) {
         const int rc = auditFasterCall_(*this, &P, &Bt, &Rz, B.has_keys ? B.indel_keys.reserve(np) : NULL, longWindowsFaster_ ? DD_OPT_LONG_WINDOWS_FASTER : 0u);
         if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_faster_audit: ") + dd_last_error();
     } else if (sz.n_pairs > 0 && B.has_keys) {
         typedef int (*Entry)(const dd_params *, const dd_batch *, dd_result *, int16_t *, int, uint32_t);
-        const int rc = reinterpret_cast<Entry>(indelKeysEntry_)(&P, &Bt, &Rz, B.indel_keys.reserve(np), device_,
-                                                                longWindowsFaster_ ? DD_OPT_LONG_WINDOWS_FASTER : 0u);
+        const int rc = reinterpret_cast<Entry>(indelKeysEntry_)(&P, &Bt, &Rz, B.indel_keys.reserve(np), device_, fasterOpt);
         if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_faster_keys: ") + dd_last_error();
     } else if (sz.n_pairs > 0 && !faster && audit_ > 0 && auditCall_) {
         const int rc = auditCall_(*this, &P, &Bt, &Rz, longWindows_ ? DD_OPT_LONG_WINDOWS : 0u);
         if (rc != DD_SUCCESS) throw std::string("dd_compute_likelihoods_audit: ") + dd_last_error();
     } else if (sz.n_pairs > 0) {
-        const int rc = faster ? (longWindowsFaster_ ? dd_compute_likelihoods_faster_ex(&P, &Bt, &Rz, device_, DD_OPT_LONG_WINDOWS_FASTER)
-                                                    : dd_compute_likelihoods_faster(&P, &Bt, &Rz, device_))
-                     : longWindows_ ? dd_compute_likelihoods_ex(&P, &Bt, &Rz, device_, DD_OPT_LONG_WINDOWS) : dd_compute_likelihoods(&P, &Bt, &Rz, device_);
-        if (rc != DD_SUCCESS) throw std::string(faster ? (longWindowsFaster_ ? "dd_compute_likelihoods_faster_ex: " : "dd_compute_likelihoods_faster: ") : longWindows_ ? "dd_compute_likelihoods_ex: " : "dd_compute_likelihoods: ") + dd_last_error();
+        const int rc = faster ? (fasterOpt ? dd_compute_likelihoods_faster_ex(&P, &Bt, &Rz, device_, fasterOpt) : dd_compute_likelihoods_faster(&P, &Bt, &Rz, device_))
+                     : mainOpt ? dd_compute_likelihoods_ex(&P, &Bt, &Rz, device_, mainOpt) : dd_compute_likelihoods(&P, &Bt, &Rz, device_);
+        if (rc != DD_SUCCESS) throw std::string(faster ? (fasterOpt ? "dd_compute_likelihoods_faster_ex: " : "dd_compute_likelihoods_faster: ") : mainOpt ? "dd_compute_likelihoods_ex: " : "dd_compute_likelihoods: ") + dd_last_error();
     }
 
     const std::chrono::steady_clock::time_point t_device = std::chrono::steady_clock::now();

@@ -194,6 +194,12 @@ public:
     // No effect on the main model; default off.
     void setLongWindowsFaster(bool v) { longWindowsFaster_ = v; }
     bool longWindowsFaster() const { return longWindowsFaster_; }
+    // true: maxLengthDel above 31 is accepted (DD_OPT_WIDE_DELETIONS).  Main model: with setLongWindows(true) (the library refuses the
+    // option without it) every window within the long limits is then computed by the long-window kernel's wide build.  --faster model: the
+    // value is only compared with the haplotype length, the kernels run unchanged.  With maxLengthDel <= 31 it changes nothing; audits
+    // (setAudit, setAuditFaster) are not given the option and keep refusing such a value.  Default off.
+    void setWideDeletions(bool v) { wideDeletions_ = v; }
+    bool wideDeletions() const { return wideDeletions_; }
     // true: computeLikelihoodsBatch packs every haplotype's refHpos and asks for the pairs' CIGARs (dd_compute_likelihoods_cigars) INSTEAD of
     // their per-base alignments: 4 opsCap + 12 bytes per pair come back instead of 2 L, and the lazy views expose them (hasDeviceCigars()).
     // get() on such a view recomputes the window with alignments, as for setKeepAlignments(false).  Main model, lazy jobs only: a batch with an
@@ -276,6 +282,7 @@ private:
     bool keepAlignments_;
     bool longWindows_ = false;
     bool longWindowsFaster_ = false;
+    bool wideDeletions_ = false;
     bool deviceCigars_ = false;
     bool deviceRealign_ = false;
     bool deviceRealignDiploid_ = false;

@@ -101,6 +101,13 @@
 //                     of being written as skipped windows; no effect with --faster
 //   [--longWindowsFaster]  the same for the --faster model (its own kernel): windows with a haplotype of 767..4,094 bp or a read of
 //                     1,025..4,096 bp are computed instead of being written as skipped windows; effective only with --faster
+//   [--wideDeletions]  --maxLengthIndel 32 and above (the reference takes any value): implies --longWindows, and every window within the
+//                     long-window limits is then computed by that kernel's wide build (two bytes per back-pointer).  Required for such a value:
+//                     without it the command is refused.  With --faster it only lifts the parameter check (that model compares the value
+//                     with the haplotype length and does nothing else with it).  With --maxLengthIndel up to 31 it changes nothing but the
+//                     implied --longWindows.  Refused with --audit / --auditFaster when --maxLengthIndel is 32 or more (the audit's shadow
+//                     would be the same kernel).  At the default parameters such deletions are not on a read's most likely path anyway
+//                     (DESIGN §27): the flag then changes which windows end with "hapSize error." and nothing else
 //   [--audit N [--auditSeed S]]  main model: in every launch N of its ordinary windows (a seeded sample with every kernel build of the launch in
 //                     it) are recomputed by the long-window kernel and compared on the device, bit for bit, with what the main kernels wrote
 //                     (dd_compute_likelihoods_audit).  The output files are written as without the flag.  Every difference is printed to
@@ -213,7 +220,7 @@ struct Options {
     int batchWindows, mergeBatches, cigarOpsCap, prepareThreads, computeThreads, packThreads, reduceThreads;
     long computeAhead;
     std::vector<int> devices;            // --devices 0,1,...: the engines are dealt out over these GPUs (batches are independent: no exchange between devices)
-    bool faster, oneBased, prepareOnly, quiet, timing, longWindows, longWindowsFaster, noLookBack, lateSkipsKnown, windowByWindow;
+    bool faster, oneBased, prepareOnly, quiet, timing, longWindows, longWindowsFaster, wideDeletions, noLookBack, lateSkipsKnown, windowByWindow;
     bool realignedBAM, deviceCigars, deviceRealign, deviceRealignDiploid, checkDevicePair;
     bool deviceIndelKeys;                // --faster --deviceIndelKeys: the pairs' indel-map key counts come back instead of their alignments
     bool doPooled, doDiploid, hostEM;    // --doPooled: the pooled lines; the diploid lines too with --doDiploid, or when --doPooled is not given
@@ -278,6 +285,9 @@ const char *const kHelp =
     "                             also haplotypes > 574 bp) instead of skipping them; main model only: no effect with --faster\n"
     "            [--longWindowsFaster]  with --faster: compute windows with a haplotype > 766 bp or a read > 1024 bp (up to 4,094 / 4,096) instead of\n"
     "                             skipping them; no effect without --faster\n"
+    "            [--wideDeletions]  accept --maxLengthIndel 32 and above (refused without it): implies --longWindows, every window then runs on the\n"
+    "                             long-window kernel's wide build; with --faster it only lifts the parameter check; refused with --audit /\n"
+    "                             --auditFaster at such a value\n"
     "            [--auditFaster N [--auditSeed S]]  --faster model: recompute N windows of every launch with the independent shadow kernel and\n"
     "                             compare them on the device with the --faster kernels' results (as --audit; needs --faster)\n"
     "            [--audit N [--auditSeed S]]  main model: recompute N windows of every launch with the long-window kernel and compare them on the\n"
@@ -292,7 +302,7 @@ const char *const kHelp =
     "  files:    --varFile: the reference's window file; --hapFile: W / H / V / A records (host/window_io.hpp)\n";
 // the options without a value; any other --NAME takes the next argument as its value, whatever its name
 const char *const kFlags[] = {"varFileIsOneBased", "faster", "filterHaplotypes", "quiet", "doDiploid", "timing", "outputRealignedBAM", "prepareOnly", "noLookBack",
-                              "lateSkipsKnown", "windowByWindow", "doPooled", "hostEM", "longWindows", "longWindowsFaster", "deviceCigars", "deviceRealign", "deviceRealignDiploid", "checkDevicePair", "deviceIndelKeys", "changeINStoN", "hostDistribution", "hostConvert", "discover", "useLibraries", "vcfCandidatesOnly"};
+                              "lateSkipsKnown", "windowByWindow", "doPooled", "hostEM", "longWindows", "longWindowsFaster", "wideDeletions", "deviceCigars", "deviceRealign", "deviceRealignDiploid", "checkDevicePair", "deviceIndelKeys", "changeINStoN", "hostDistribution", "hostConvert", "discover", "useLibraries", "vcfCandidatesOnly"};
 
 std::vector<int> commaInts(const std::string &list)      // "3,5,,8" -> 3 5 8
 {
@@ -385,7 +395,8 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     if (has("bamFile")) o.bamPaths.push_back(opt["bamFile"]);        // --bamFile wins when both are given (DInDel.cpp:4220-4226)
     else o.bamList = opt["bamFiles"];
     o.faster = has("faster"); o.oneBased = has("varFileIsOneBased") && !o.discover; o.prepareOnly = has("prepareOnly"); o.quiet = has("quiet"); o.timing = has("timing");
-    o.longWindows = has("longWindows"); o.longWindowsFaster = has("longWindowsFaster");
+    o.wideDeletions = has("wideDeletions");
+    o.longWindows = has("longWindows") || o.wideDeletions; o.longWindowsFaster = has("longWindowsFaster");
     o.noLookBack = has("noLookBack"); o.lateSkipsKnown = has("lateSkipsKnown"); o.windowByWindow = has("windowByWindow");
     o.realignedBAM = has("outputRealignedBAM") && !o.faster;                      // `params.outputRealignedBAM && params.slower`, :589
     o.deviceCigars = o.realignedBAM && has("deviceCigars");                       // modifies --outputRealignedBAM only
@@ -420,6 +431,14 @@ bool parseOptions(int argc, char **argv, Options &o, int &exitCode)
     obs.setCLIDefaultValues();
     obs.pError = num("pError", obs.pError); obs.pMut = num("pMut", obs.pMut);
     obs.maxLengthIndel = obs.maxLengthDel = int(num("maxLengthIndel", obs.maxLengthIndel));
+    if (obs.maxLengthDel > DD_MAX_LENGTH_DEL && !o.wideDeletions) {
+        std::cerr << "--maxLengthIndel " << obs.maxLengthDel << " needs --wideDeletions: the main kernels hold deletions up to " << DD_MAX_LENGTH_DEL << " bp\n";
+        return false;
+    }
+    if (obs.maxLengthDel > DD_MAX_LENGTH_DEL && (has("audit") || has("auditFaster"))) {
+        std::cerr << "--wideDeletions with --maxLengthIndel " << obs.maxLengthDel << " cannot be given with --audit / --auditFaster: the audit's shadow would be the same kernel\n";
+        return false;
+    }
     obs.padCover = int(num("flankRefSeq", obs.padCover)); obs.maxMismatch = int(num("flankMaxMismatch", obs.maxMismatch));
     obs.mapQualThreshold = num("capMapQualThreshold", obs.mapQualThreshold); obs.capMapQualFast = num("capMapQualFast", obs.capMapQualFast);
     ReadSelectionParameters &rsp = o.rsp;
@@ -633,6 +652,7 @@ void WindowLoop::configureStageEngine(LikelihoodEngine &engine) const
     engine.setDeviceRealignDiploid(opt.deviceRealignDiploid, opt.cigarOpsCap);
     engine.setLongWindows(opt.longWindows);
     engine.setLongWindowsFaster(opt.longWindowsFaster);
+    engine.setWideDeletions(opt.wideDeletions);
     if (opt.deviceIndelKeys) engine.setDeviceIndelKeys(true);
     if (opt.audit > 0 && opt.auditFaster) engine.setAuditFaster(opt.audit, opt.auditSeed);
     else if (opt.audit > 0) engine.setAudit(opt.audit, opt.auditSeed);
@@ -663,6 +683,7 @@ WindowLikelihoods WindowLoop::recomputeWithAlignments(const WindowTask &T)
         fallbackEngine.reset(new LikelihoodEngine(opt.obs, opt.devices[0]));
         fallbackEngine->setThrowOnPositiveLikelihood(false);
         fallbackEngine->setLongWindows(opt.longWindows);
+        fallbackEngine->setWideDeletions(opt.wideDeletions);
     }
     std::vector<WindowJob> one(1, T.job());
     fallbackEngine->computeLikelihoodsBatch(one);

@@ -74,7 +74,8 @@ extern "C" {
 #define DD_MAX_HAP_LEN      766   /* numS = Hs+2 <= 64 lanes x 12 positions                         */
 #define DD_MAX_READ_LEN    1024
 #define DD_MAX_LENGTH_DEL    31   /* D = maxLengthDel + 1 <= 32.  0..11 run the specialised D = 6 / 11 / 12 builds; 12..31 one D = 32 build (correct, not tuned;
-                                     haplotypes up to 574 bp there) */
+                                     haplotypes up to 574 bp there).  Above 31: opt-in, DD_OPT_WIDE_DELETIONS (the long-window kernel's wide build) */
+#define DD_WIDE_MAX_LENGTH_DEL 2147483645   /* INT32_MAX - 2: D = maxLengthDel + 1 and numT = maxLengthDel + 2 stay 32-bit counts */
 /* limits of the long-window path (opt-in: DD_OPT_LONG_WINDOWS); numS = Hs+2 <= 4,096 states */
 #define DD_LONG_MAX_HAP_LEN  4094
 #define DD_LONG_MAX_READ_LEN 4096
@@ -84,7 +85,10 @@ extern "C" {
 /* Mirrors the fields of ObservationModelParameters the path reads — ObservationModel.hpp:28-99.
  * Every entry point that takes a dd_params refuses, with DD_ERR_INVALID and a dd_last_error() that names the field, a value that would put
  * a NaN into the tables of dd_build_tables: pError outside (0,1); pMut or pFirstgLO outside [0,1]; mapQualThreshold or capMapQualFast
- * negative; a NaN in any of these or in checkBaseQualThreshold.  (maxLengthDel outside [0,31] and forceReadOnHaplotype: DD_ERR_UNSUPPORTED.) */
+ * negative; a NaN in any of these or in checkBaseQualThreshold.  (maxLengthDel outside [0,31] and forceReadOnHaplotype: DD_ERR_UNSUPPORTED.
+ * An entry that takes option bits lets maxLengthDel 32..DD_WIDE_MAX_LENGTH_DEL pass when DD_OPT_WIDE_DELETIONS is among them — see "wide
+ * deletions" below; a larger value is then DD_ERR_INVALID.  The reference takes any value: its only check is maxLengthDel > hapSize,
+ * DD_PAIR_HAPSIZE for that pair.) */
 typedef struct dd_params {
     double  pError;                  /* probability of a read indel                                  */
     double  pMut;                    /* probability of a mutation in the read                        */
@@ -242,6 +246,10 @@ void dd_host_free(void *p);
 #define DD_TABLE_DOUBLES (32 + 4*DD_MAX_QUAL_TABLE + 4*DD_MAX_QUAL_TABLE + 2*DD_HP_TABLE + 2*DD_MAX_QUAL_TABLE + 2*DD_MAX_QUAL_TABLE + 64)
 int dd_build_tables(const dd_params *p, const double *qual_table, int n_qual,
                     const double *mapq_table, int n_mapq, double *out);
+/* The same with option bits (0 or DD_OPT_WIDE_DELETIONS, below): the tables do not depend on maxLengthDel, the bit only lets a value
+ * above 31 pass the parameter check. */
+int dd_build_tables_ex(const dd_params *p, const double *qual_table, int n_qual,
+                       const double *mapq_table, int n_mapq, double *out, uint32_t options);
 
 /* Bases are compared as characters, as in the reference (hap[y]==nuc || hap[y]=='N', ObservationModelFB.cpp:246): any
  * byte may occur in reads and haplotypes (IUPAC codes, soft-masked lower case).  This builds the byte -> symbol-id table
@@ -325,7 +333,7 @@ int dd_launch_device(const dd_params *p, const dd_device_batch *b, const dd_resu
 
 /* ---- long windows (opt-in) ----------------------------------------------------------------- */
 /* The main kernels cover haplotypes up to DD_MAX_HAP_LEN, reads up to DD_MAX_READ_LEN, and with maxLengthDel >= 12 haplotypes up to 574 bp.
- * With DD_OPT_LONG_WINDOWS a window outside those limits but inside DD_LONG_MAX_HAP_LEN / DD_LONG_MAX_READ_LEN (any maxLengthDel 0..31) is
+ * With DD_OPT_LONG_WINDOWS a window outside those limits but inside DD_LONG_MAX_HAP_LEN / DD_LONG_MAX_READ_LEN (any maxLengthDel 0..31; above 31 see "wide deletions" below) is
  * computed by a kernel of its own (one workgroup per pair), launched after the main launch: the same outputs, bit for bit, as the main
  * kernels would give (main model only; the --faster model has an option of its own, DD_OPT_LONG_WINDOWS_FASTER below).  Without the option
  * nothing changes. */
@@ -357,7 +365,35 @@ int dd_launch_device_long(const dd_params *p, const dd_device_batch *b, const dd
  * host path's own copy): this synchronises the launch's stream, and for dd_launch_device_long the workspace must still be allocated.
  * Returns the number of launches. */
 #define DD_LONG_LOG_FIELDS 8
+#define DD_LONG_LOG_WIDE 256   /* added to the K field of a record when the wide build ran (below) */
 int dd_long_launch_log(int64_t *out, int max_records);
+
+/* ---- wide deletions (opt-in): maxLengthDel above 31 ---------------------------------------- */
+/* No main-kernel build holds a jump of more than 32 states.  With DD_OPT_WIDE_DELETIONS — beside DD_OPT_LONG_WINDOWS, whose kernel it uses —
+ * and p->maxLengthDel in 32..DD_WIDE_MAX_LENGTH_DEL, every window within the long limits is DD_WIN_LONG (dd_screen_windows_ex) and is computed
+ * by the wide build of the long-window kernel: two bytes per back-pointer (12 bits of jump length), candidate loops clipped to the haplotype.
+ * The same outputs, bit for bit, as the reference's model gives (oracle: ddo_batch); a pair with maxLengthDel > hapSize is DD_PAIR_HAPSIZE.
+ * With maxLengthDel <= 31 the bit changes nothing anywhere.  Without the bit every entry answers as ever (DD_ERR_UNSUPPORTED above 31).
+ * The bit alone, without DD_OPT_LONG_WINDOWS, is DD_ERR_INVALID for the main model's entries.  Out of scope: the audits (dd_audit_select and
+ * dd_audit_select_faster refuse maxLengthDel > 31: the shadow would be the same kernel), the _multi entries, forceReadOnHaplotype.
+ *
+ * Host pointers: dd_compute_likelihoods_ex (and the _cigars / _realign / _realign_diploid entries) with
+ * DD_OPT_LONG_WINDOWS | DD_OPT_WIDE_DELETIONS.
+ * Device pointers: tables from dd_build_tables_ex, classes from dd_screen_windows_ex with both bits, then ONE launch, dd_launch_device_wide,
+ * in place of dd_launch_device + dd_launch_device_long: there is no main launch for these parameters, so it also writes the placeholder of
+ * every DD_WIN_UNSUPPORTED window's pairs (DD_PAIR_UNSUPPORTED, ll = 0, off the haplotype) and onHap of every read.  With
+ * maxLengthDel <= 31 it is dd_launch_device_long (and dd_workspace_bytes_wide is dd_workspace_bytes_long).  A tile of the wide build is
+ * long_max_read_len x 256 K x 2 bytes (the maximum shape: 32 MiB + stash per workgroup, the grid stays >= 1 within DD_LONG_WS_BUDGET).
+ * dd_long_launch_log records the launch; its K field is K + DD_LONG_LOG_WIDE when the wide build ran.
+ * The consumers behind a launch (dd_cigars_device, dd_realign_device, dd_diploid_pairs_device, dd_indel_keys_device, dd_pooled_em_device)
+ * read outputs only and work behind it unchanged.
+ * The --faster model compares maxLengthDel with the haplotype length and does nothing else with it: dd_compute_likelihoods_faster_ex,
+ * dd_compute_likelihoods_faster_keys (where the bit is needed, maxLengthDel above 31; beside a smaller value it stays an unknown bit of
+ * that entry, as ever) and dd_launch_device_faster_ex accept the bit, which only lifts the parameter check (both kernels run
+ * unchanged; DD_OPT_LONG_WINDOWS_FASTER composes with it on the host-pointer entries). */
+#define DD_OPT_WIDE_DELETIONS 4u
+size_t dd_workspace_bytes_wide(const dd_params *p, const dd_device_batch *b);
+int dd_launch_device_wide(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- row A13: the --faster model ---------------------------------------------------------- */
 /* Same batch in, same result layout out, but each pair is scored by ObservationModelS(hap, read, hapStart,
@@ -371,6 +407,8 @@ int dd_long_launch_log(int64_t *out, int max_records);
 int dd_compute_likelihoods_faster(const dd_params *p, const dd_batch *b, dd_result *r, int device);
 int dd_compute_likelihoods_faster_multi(const dd_params *p, const dd_batch *b, dd_result *r, const int *devices, int n_devices);
 int dd_launch_device_faster(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *stream);
+/* with options: 0 is dd_launch_device_faster; DD_OPT_WIDE_DELETIONS (above) lets maxLengthDel above 31 pass; any other bit is DD_ERR_INVALID */
+int dd_launch_device_faster_ex(const dd_params *p, const dd_device_batch *b, const dd_result *r, void *stream, uint32_t options);
 
 /* ---- long windows of the --faster model (opt-in, separate from DD_OPT_LONG_WINDOWS) ------- */
 /* dd_faster_kernel covers haplotypes up to DD_MAX_HAP_LEN and reads up to DD_MAX_READ_LEN (its per-pair LDS area); the reference's model has
@@ -385,7 +423,7 @@ int dd_launch_device_faster(const dd_params *p, const dd_device_batch *b, const 
  * Out of scope: dd_compute_likelihoods_faster_multi (long windows stay skipped there); mapUnmappedReads (this model has no insert-size prior). */
 #define DD_OPT_LONG_WINDOWS_FASTER 2u
 /* dd_compute_likelihoods_faster with options: 0 is dd_compute_likelihoods_faster; DD_OPT_LONG_WINDOWS_FASTER computes the long windows
- * too; any other bit is DD_ERR_INVALID. */
+ * too; DD_OPT_WIDE_DELETIONS lets maxLengthDel above 31 pass; any other bit is DD_ERR_INVALID. */
 int dd_compute_likelihoods_faster_ex(const dd_params *p, const dd_batch *b, dd_result *r, int device, uint32_t options);
 /* Device-pointer path: b->win_skip = DEVICE copy of the classes dd_screen_windows_ex gave with DD_OPT_LONG_WINDOWS_FASTER,
  * b->long_max_hap_len / long_max_read_len its max_len_out[2..3] (a dd_device_batch is screened for one model at a time).
